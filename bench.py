@@ -13,9 +13,12 @@ sweeps (RCCL over xGMI, issued by the library); a weak-scaling figure (one 1415 
 measured afterwards and printed as the `weak_scaling` field.  value = owned message updates of all ranks /
 max-over-ranks time.  Inputs are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line carrying `roofline` (dominant kernel: device time of the timed region on the
-library's stream / launches; counter traffic from profiles/) and, at N = 1, `cpu_baseline` (the CPU restatement
-of the reference scheduler on a bounded sample).
+A plain run sets up, runs W warm-up sweeps, times ONE region of exactly K sweeps and prints ONE JSON line (`value`,
+`ms_per_step` = the region's wall time / K, ...).  `--dump-outputs DIR` writes what the last timed sweep computed
+(dump_outputs).  With `--full`, five regions are timed (the median is reported) and the line also carries `roofline`
+(dominant kernel: device time of the timed region on the library's stream / launches; counter traffic from profiles/)
+and, at N = 1, `cpu_baseline` (the CPU restatement of the reference scheduler on a bounded sample), `parity` and a
+digest of the other configs; everything else goes to a side file.
 """
 from __future__ import annotations
 
@@ -45,10 +48,17 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of exactly --steps steps each (barrier + synchronize on both sides); the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: five timed regions (median), the per-launch "
+                         "sampling region and the roofline, the halo audit and the weak-scaling figure (N > 1), the CPU baselines, the "
+                         "parity checks and the other configs (N = 1), and the side file.  Off: ONE timed region of --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, see dump_outputs)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps steps each (barrier + synchronize on both sides); the median is reported "
+                         "(default: 1, and 5 with --full)")
     ap.add_argument("--event-stride", type=int, default=1,
-                    help="per-launch hipEvent pairs in the extra, untimed sampling region (every n-th launch)")
+                    help="--full: per-launch hipEvent pairs in the extra, untimed sampling region (every n-th launch)")
     ap.add_argument("--grid", type=int, default=1415, help="N: the N x N grid (1415 -> 10,005,465 edges)")
     ap.add_argument("--schedule", choices=["flooding", "fused"], default=os.environ.get("CX_BENCH_SCHEDULE", "fused"))
     ap.add_argument("--materialize", action="store_true", help="also store every variable→factor message each sweep")
@@ -68,7 +78,7 @@ def parse(argv=None):
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="strong (default, BASELINE config 4): the ONE N x N grid is cut into row blocks over the ranks; "
                          "weak: every rank owns an N x N strip of an (N*ranks) x N grid")
-    ap.add_argument("--no-weak-figure", action="store_true", help="N > 1, strong scaling: skip the second (weak-scaling) measurement")
+    ap.add_argument("--no-weak-figure", action="store_true", help="--full, N > 1, strong scaling: skip the second (weak-scaling) measurement")
     ap.add_argument("--halo-depth", default=os.environ.get("CX_HALO_DEPTH", "auto"),
                     help="deep halo: each rank keeps this many redundant rows of its neighbours and exchanges their state once "
                          "per that many sweeps (bit-identical to the un-partitioned sweep); 0 = one message halo per sweep; "
@@ -78,8 +88,9 @@ def parse(argv=None):
     ap.add_argument("--cpu-configs", action="store_true", help="CPU baselines of configs C1, C2 and the C4 sample only (no GPU needed)")
     ap.add_argument("--self-halo", action="store_true",
                     help="N = 1 experiment: a cylinder whose wrap-around cut makes rank 0 its own halo neighbour")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1: skip the other BASELINE configs (C2, C3, C5, variational families)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the CPU baselines and the parity checks")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="--full, N = 1: skip the other BASELINE configs (C2, C3, C5, variational families)")
     ap.add_argument("--parity-sweeps", type=int, default=8, help="sweeps of the in-run parity check on the CPU sample grid")
     ap.add_argument("--cpu-sample-grid", type=int, default=768, help="grid side of the bounded CPU sample")
     ap.add_argument("--seed", type=int, default=1234)
@@ -576,6 +587,8 @@ def headline_line(full: dict, details_path=None) -> str:
     line["roofline"] = {k: ro.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "basis", "avg_kernel_ms",
                                                  "payload_bytes_per_launch", "frac_payload", "survey_convention_bytes_per_launch",
                                                  "frac_survey_convention") if k in ro}
+    if not ro:                                            # a plain run measures no roofline: no empty object for it
+        del line["roofline"]
     if cb is not None:
         line["cpu_baseline"] = {k: cb.get(k) for k in ("value", "unit", "cores", "kind", "sample")}
         fa = cb.get("flooding_all_cores")
@@ -606,7 +619,7 @@ def headline_line(full: dict, details_path=None) -> str:
     text = dump()
     if len(text.encode()) >= HEADLINE_MAX_BYTES:          # long free-text fields are the only thing that can grow: cut them, in this order
         for d, key, n in ((line["config"], "schedule", 200), (line.get("parity") or {}, "checker", 120), (line.get("cpu_baseline") or {}, "sample", 160),
-                          (line["config"], "workload", 240), (line["roofline"], "basis", 120), (line.get("parity") or {}, "sample", 100)):
+                          (line["config"], "workload", 240), (line.get("roofline") or {}, "basis", 120), (line.get("parity") or {}, "sample", 100)):
             clip(d, key, n)
             text = dump()
             if len(text.encode()) < HEADLINE_MAX_BYTES:
@@ -678,7 +691,7 @@ class Workload:
         self.halo_kind, self.halo_tensors, self.part, self.exchange, self.ipc = None, None, None, None, None
         red_dev = "cuda" if backend == "nccl" else "cpu"
         if world == 1 and not args.self_halo:
-            model = cx.synth.gaussian_grid(N, N, seed=args.seed)
+            model = self.model = cx.synth.gaussian_grid(N, N, seed=args.seed)
             cx.synth.load_into_device(model, dev, seed_variance=1e6)
         else:
             rows_min = N if scaling == "weak" else N // world
@@ -692,7 +705,7 @@ class Workload:
                 part = partition.grid_strip_deep(N, N, rank, world, depth, seed=args.seed)
             else:
                 part = partition.grid_strip(N, N, rank, world, seed=args.seed)
-            self.part = part
+            self.part, self.model = part, part.model
             cx.synth.load_into_device(part.model, dev, seed_variance=1e6)
             exchange = None
             tdev = torch.device("cuda", local_rank)
@@ -822,7 +835,7 @@ class Workload:
             self.exchange.sweep(n)
 
     def close(self):
-        self.exchange = None
+        self.exchange, self.model = None, None
         self.dev.close()
 
 
@@ -837,6 +850,8 @@ def timed_regions(w: Workload, steps: int, repeats: int, dist, torch, red_dev):
     walls, devs = [], []
     for _ in range(max(1, repeats)):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()                 # torch creates an event at its first record: not inside the clock (a plain run times one region)
+        e1.record()
         barrier()
         t0 = time.perf_counter()
         e0.record()
@@ -852,6 +867,103 @@ def timed_regions(w: Workload, steps: int, repeats: int, dist, torch, red_dev):
         walls.append(elapsed)
         devs.append(dev_ms)
     return walls, devs
+
+
+DUMP_MAX_MARGINALS = 2_500_000      # 40 MB of (mean, variance) pairs: every marginal of the 1415 x 1415 grid
+DUMP_MAX_MESSAGES = 1_000_000       # 16 MB
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir: str, w: Workload) -> dict:
+    """--dump-outputs: what a caller of the timed path reads back after its last sweep, float64, at most 56 MB in all.
+    marginals.npy: (mean, variance) of the latent variables this rank owns, in id order; messages_to_variable.npy:
+    (mean, variance) of the stored factor→variable messages on the edges into those variables.  Above DUMP_MAX_* rows a
+    fixed sample is written, drawn with a generator of its own seed: the same arguments read the same entries in every run."""
+    from cortex.jl_amd import _lib as L
+
+    model, part = w.model, w.part
+    owned = np.asarray(model.x_ids if part is None or part.owned_x is None else part.owned_x, dtype=np.int64)
+    ev, ef = np.asarray(model.edge_var, dtype=np.int64), np.asarray(model.edge_fac, dtype=np.int64)
+    into = np.arange(len(ev)) if part is None else np.flatnonzero(np.isin(ev, owned))
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+
+    def sample(a, n):
+        return a if len(a) <= n else np.sort(rng.choice(a, n, replace=False))
+
+    owned, into = sample(owned, DUMP_MAX_MARGINALS), sample(into, DUMP_MAX_MESSAGES)
+    arrays = {"marginals": w.dev.get_marginals(owned), "messages_to_variable": w.dev.get_messages(ev[into], ef[into], L.TO_VARIABLE)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def roofline(args, w: Workload, kern: dict, dev_ms: float) -> dict:
+    """--full: the dominant kernel of the median timed region against the HBM roofline (`kern`: the sampling region's
+    per-kernel event times; `dev_ms`: the region's device time)"""
+    from cortex.jl_amd import _lib as L
+
+    st = w.st
+    if kern:
+        dom_name, (dom_ms, dom_n, dom_id) = max(kern.items(), key=lambda kv: kv[1][0])
+    else:
+        dom_name, (dom_ms, dom_n, dom_id) = "k_sweep<fused>", (0.0, 0, L.KERNEL_FUSED)
+    # launches per step: the flooding schedule needs two launches per step
+    steps_per_launch = 1.0 if args.schedule == "fused" else 0.5
+    # algorithmic bytes per launch: §8d's 32 B per directed message update x the updates one launch performs
+    upd_per_launch = w.local_updates_per_step * steps_per_launch
+    alg_bytes = upd_per_launch * BYTES_PER_UPDATE
+    # average launch duration: device time of the median timed region (events on the library's stream around the whole
+    # region, launches back to back) / launches.  It contains the inter-launch gaps, so it can only over-state the
+    # kernel; the per-launch event pairs of the sampling region are printed beside it.
+    region_ms_per_launch = dev_ms / args.steps * steps_per_launch if args.schedule == "fused" else None
+    sampled_ms = dom_ms / dom_n if dom_n else None
+    avg_ms = region_ms_per_launch if region_ms_per_launch is not None else sampled_ms
+    # counter traffic (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, gfx950 corrections: profiles/): measured on
+    # the full 1415 x 1415 launch, carried to other launch sizes per message update
+    traffic, traffic_src = None, None
+    traffic_file = os.path.join(ROOT, "profiles", "traffic_latest.json")
+    if os.path.exists(traffic_file) and args.schedule == "fused" and not args.materialize:
+        try:
+            tr = json.load(open(traffic_file))
+            from cortex.jl_amd.build import sources_sha16
+            if tr.get("kernel") == dom_name and tr.get("sources_sha16") == sources_sha16("k_sweep"):
+                per_update = tr["hbm_bytes_per_launch"] / tr.get("updates_per_launch", 16006480)
+                traffic = per_update * upd_per_launch
+                traffic_src = tr.get("source")
+            elif tr.get("kernel") == dom_name:
+                traffic_src = "REFUSED: profiles/traffic_latest.json was measured on another version of the kernel's sources (tools/profile_round.sh)"
+                print("[bench] STALE PROFILE: profiles/traffic_latest.json was measured on another version of cx_kernels.hip — the headline's roofline falls back "
+                      "to algorithmic bytes until tools/profile_round.sh is re-run and its summary copied into profiles/", file=sys.stderr, flush=True)
+        except Exception:
+            pass
+    achieved_alg = alg_bytes / (avg_ms * 1e-3) / 1e9
+    # payload: stored factor→variable messages read (one per edge), those written (one per directed pairwise update pair) and the
+    # marginals, 16 B each; the flooding schedule also stores variable→factor messages
+    payload_bytes = 16.0 * (st["n_edges"] + w.local_updates_per_step / 2 + st["n_variables"]) * max(steps_per_launch, 1.0)
+    if args.schedule != "fused" or args.materialize:
+        payload_bytes = 16.0 * (st["n_edges"] + w.local_updates_per_step + st["n_variables"]) * steps_per_launch
+    achieved = (traffic / (avg_ms * 1e-3) / 1e9) if traffic else payload_bytes / (avg_ms * 1e-3) / 1e9
+    return {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            # what the number is: bytes that crossed the L2 <-> fabric boundary (FETCH_SIZE x2 + WRITE_SIZE), i.e. HBM traffic
+            # PLUS hits in the 256 MiB Infinity Cache (the index arrays stay resident there) — which is how it can exceed the
+            # 6.29 TB/s a pure HBM copy reaches; `frac` prices it against the 8 TB/s spec, `frac_of_measured_copy` against that copy
+            "bound_detail": "L2-fabric traffic incl. Infinity-Cache hits (memory system, not HBM alone)",
+            "frac_of_measured_copy": achieved / HBM_COPY_GBS, "measured_copy_peak": HBM_COPY_GBS,
+            "basis": ("counter bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, profiles/) / avg launch duration (events on the library's stream)"
+                      if traffic else "payload bytes / avg launch duration (no counter traffic on file for this kernel)"),
+            "traffic_source": traffic_src,
+            "avg_kernel_ms": avg_ms,
+            "avg_kernel_basis": "device time of the median timed region (events on the library's stream) / launches",
+            "sampled_kernel_ms": sampled_ms, "sampled_launches": dom_n,
+            # what the fused schedule MUST move per launch: every stored message read once (16 B), every message out of a
+            # pairwise factor and every marginal written once; index and parameter arrays are not payload
+            "payload_bytes_per_launch": payload_bytes, "frac_payload": payload_bytes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            # SURVEY §8d's convention (32 B per directed update: payload read + written, variable→factor messages included);
+            # the fused kernel keeps those in registers, so this convention counts bytes that never move and can exceed 1
+            "survey_convention_bytes_per_launch": alg_bytes, "frac_survey_convention": achieved_alg / HBM_PEAK_GBS,
+            "all_kernels_sampled_ms": {k: v[0] / v[1] for k, v in kern.items()}}
 
 
 def run_rank(args):
@@ -953,25 +1065,31 @@ def run_rank(args):
     w = Workload(args, args.scaling, rank, world, local_rank, backend, dist, torch, cx, L)
     dev = w.dev
 
+    repeats = args.repeats if args.repeats is not None else (5 if args.full else 1)
     w.run(args.warmup)
-    dev.residual()   # snapshot: the residual reported below is the change over the timed regions
-    walls, devs = timed_regions(w, args.steps, args.repeats, dist, torch, red_dev)
+    # snapshot: the residual reported with --full is the change over the timed regions.  Taken in a plain run too: the sweeps
+    # timed after it run ~2.5 % faster than without it (measured at 5000 steps; cause not known), and every earlier figure had it
+    dev.residual()
+    walls, devs = timed_regions(w, args.steps, repeats, dist, torch, red_dev)
     order = sorted(range(len(walls)), key=lambda i: walls[i])
     mid = order[len(order) // 2]
     elapsed, dev_ms = walls[mid], devs[mid]
-    res = dev.residual()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w)
 
-    # one more, UNTIMED region with a hipEvent pair around every launch (each pair is a barrier packet on the queue, which
-    # is why it stays out of the timed regions): per-launch durations of every kernel
-    dev.profile_enable(max(1, args.event_stride))
-    w.run(min(args.steps, 400))
-    dev.sync()
-    dev.profile_enable(False)
-    kern = {}
-    for k in (L.KERNEL_FUSED, L.KERNEL_VAR_TO_FACTOR, L.KERNEL_FACTOR_TO_VAR, L.KERNEL_HALO_BEGIN, L.KERNEL_HALO_END):
-        ms, n = dev.profile_read(k)
-        if n:
-            kern[dev.kernel_name(k)] = (ms, n, k)
+    res, kern = None, {}
+    if args.full:
+        res = dev.residual()
+        # one more, UNTIMED region with a hipEvent pair around every launch (each pair is a barrier packet on the queue, which
+        # is why it stays out of the timed regions): per-launch durations of every kernel
+        dev.profile_enable(max(1, args.event_stride))
+        w.run(min(args.steps, 400))
+        dev.sync()
+        dev.profile_enable(False)
+        for k in (L.KERNEL_FUSED, L.KERNEL_VAR_TO_FACTOR, L.KERNEL_FACTOR_TO_VAR, L.KERNEL_HALO_BEGIN, L.KERNEL_HALO_END):
+            ms, n = dev.profile_read(k)
+            if n:
+                kern[dev.kernel_name(k)] = (ms, n, k)
 
     if dist is not None:
         u = torch.tensor([w.updates_per_step, w.owned_variables], dtype=torch.float64, device=red_dev)
@@ -982,12 +1100,12 @@ def run_rank(args):
 
     # audit of the last exchange of the run (outside the timed region): what each rank imported == what its neighbour packed
     halo_check = None
-    if w.halo_tensors is not None:
+    if args.full and w.halo_tensors is not None:
         from cortex.jl_amd import partition
         dev.sync()
         torch.cuda.synchronize()
         halo_check = partition.verify_last_exchange(w.part, w.halo_tensors[0], w.halo_tensors[1], dist, torch)
-    elif w.ipc is not None:
+    elif args.full and w.ipc is not None:
         # one more exchange, audited (the run ends between batches only when its sweeps are a multiple of the depth: top up)
         w.ipc.check()
         if w.ipc.k % w.ipc.depth:
@@ -996,11 +1114,11 @@ def run_rank(args):
 
     # second figure at N > 1: weak scaling (every rank one N x N strip of an (N * ranks) x N grid)
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak_figure:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak_figure:
         st_strong, halo_kind_strong = dict(w.st), w.halo_kind
         w2 = Workload(args, "weak", rank, world, local_rank, backend, dist, torch, cx, L)
         w2.run(args.warmup)
-        wl, _ = timed_regions(w2, args.steps, min(args.repeats, 3), dist, torch, red_dev)
+        wl, _ = timed_regions(w2, args.steps, min(repeats, 3), dist, torch, red_dev)
         wl.sort()
         u = torch.tensor([w2.updates_per_step], dtype=torch.float64, device=red_dev)
         dist.all_reduce(u, op=dist.ReduceOp.SUM)
@@ -1013,46 +1131,6 @@ def run_rank(args):
     if rank == 0:
         st = w.st
         value = total_updates_per_step * args.steps / elapsed
-        if kern:
-            dom_name, (dom_ms, dom_n, dom_id) = max(kern.items(), key=lambda kv: kv[1][0])
-        else:
-            dom_name, (dom_ms, dom_n, dom_id) = "k_sweep<fused>", (0.0, 0, L.KERNEL_FUSED)
-        # launches per step: the flooding schedule needs two launches per step
-        steps_per_launch = 1.0 if args.schedule == "fused" else 0.5
-        # algorithmic bytes per launch: §8d's 32 B per directed message update x the updates one launch performs
-        upd_per_launch = w.local_updates_per_step * steps_per_launch
-        alg_bytes = upd_per_launch * BYTES_PER_UPDATE
-        # average launch duration: device time of the median timed region (events on the library's stream around the whole
-        # region, launches back to back) / launches.  It contains the inter-launch gaps, so it can only over-state the
-        # kernel; the per-launch event pairs of the sampling region are printed beside it.
-        region_ms_per_launch = dev_ms / args.steps * steps_per_launch if args.schedule == "fused" else None
-        sampled_ms = dom_ms / dom_n if dom_n else None
-        avg_ms = region_ms_per_launch if region_ms_per_launch is not None else sampled_ms
-        # counter traffic (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, gfx950 corrections: profiles/): measured on
-        # the full 1415 x 1415 launch, carried to other launch sizes per message update
-        traffic, traffic_src = None, None
-        traffic_file = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(traffic_file) and args.schedule == "fused" and not args.materialize:
-            try:
-                tr = json.load(open(traffic_file))
-                from cortex.jl_amd.build import sources_sha16
-                if tr.get("kernel") == dom_name and tr.get("sources_sha16") == sources_sha16("k_sweep"):
-                    per_update = tr["hbm_bytes_per_launch"] / tr.get("updates_per_launch", 16006480)
-                    traffic = per_update * upd_per_launch
-                    traffic_src = tr.get("source")
-                elif tr.get("kernel") == dom_name:
-                    traffic_src = "REFUSED: profiles/traffic_latest.json was measured on another version of the kernel's sources (tools/profile_round.sh)"
-                    print("[bench] STALE PROFILE: profiles/traffic_latest.json was measured on another version of cx_kernels.hip — the headline's roofline falls back "
-                          "to algorithmic bytes until tools/profile_round.sh is re-run and its summary copied into profiles/", file=sys.stderr, flush=True)
-            except Exception:
-                pass
-        achieved_alg = alg_bytes / (avg_ms * 1e-3) / 1e9
-        # payload: stored factor→variable messages read (one per edge), those written (one per directed pairwise update pair) and the
-        # marginals, 16 B each; the flooding schedule also stores variable→factor messages
-        payload_bytes = 16.0 * (st["n_edges"] + w.local_updates_per_step / 2 + st["n_variables"]) * max(steps_per_launch, 1.0)
-        if args.schedule != "fused" or args.materialize:
-            payload_bytes = 16.0 * (st["n_edges"] + w.local_updates_per_step + st["n_variables"]) * steps_per_launch
-        achieved = (traffic / (avg_ms * 1e-3) / 1e9) if traffic else payload_bytes / (avg_ms * 1e-3) / 1e9
         strong = args.scaling == "strong"
         out = {
             "metric": "edge-message updates/sec per sweep, 10M-edge Gaussian grid",
@@ -1070,43 +1148,25 @@ def run_rank(args):
                        **({"halo_depth": args.halo_depth, "halo_depth_trials_ms_per_sweep": depth_trials} if depth_trials else {})},
             "timed_regions": {"count": len(walls), "reported": "median", "ms_per_step_each": [x / args.steps * 1e3 for x in walls],
                               "device_ms_per_step_each": [x / args.steps for x in devs]},
-            "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         # what the number is: bytes that crossed the L2 <-> fabric boundary (FETCH_SIZE x2 + WRITE_SIZE), i.e. HBM traffic
-                         # PLUS hits in the 256 MiB Infinity Cache (the index arrays stay resident there) — which is how it can exceed the
-                         # 6.29 TB/s a pure HBM copy reaches; `frac` prices it against the 8 TB/s spec, `frac_of_measured_copy` against that copy
-                         "bound_detail": "L2-fabric traffic incl. Infinity-Cache hits (memory system, not HBM alone)",
-                         "frac_of_measured_copy": achieved / HBM_COPY_GBS, "measured_copy_peak": HBM_COPY_GBS,
-                         "basis": ("counter bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, profiles/) / avg launch duration (events on the library's stream)"
-                                   if traffic else "payload bytes / avg launch duration (no counter traffic on file for this kernel)"),
-                         "traffic_source": traffic_src,
-                         "avg_kernel_ms": avg_ms,
-                         "avg_kernel_basis": "device time of the median timed region (events on the library's stream) / launches",
-                         "sampled_kernel_ms": sampled_ms, "sampled_launches": dom_n,
-                         # what the fused schedule MUST move per launch: every stored message read once (16 B), every message out of a
-                         # pairwise factor and every marginal written once; index and parameter arrays are not payload
-                         "payload_bytes_per_launch": payload_bytes, "frac_payload": payload_bytes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         # SURVEY §8d's convention (32 B per directed update: payload read + written, variable→factor messages included);
-                         # the fused kernel keeps those in registers, so this convention counts bytes that never move and can exceed 1
-                         "survey_convention_bytes_per_launch": alg_bytes, "frac_survey_convention": achieved_alg / HBM_PEAK_GBS,
-                         "all_kernels_sampled_ms": {k: v[0] / v[1] for k, v in kern.items()}},
             # computed inside the same kernel, not counted in `value`
             "marginals_per_s": total_variables * args.steps / elapsed,
-            "max_message_change_over_run": res,
         }
+        if args.full:
+            out["roofline"] = roofline(args, w, kern, dev_ms)
+            out["max_message_change_over_run"] = res
         if halo_check is not None:
             out["halo_check"] = "ok: last imported halo == neighbours' packed messages, bit for bit" if halo_check else "FAILED"
         if weak is not None:
             out["weak_scaling"] = weak
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample_grid, args.seed)
             out["parity"] = parity_check(args.cpu_sample_grid, args.seed, args.parity_sweeps, local_rank)
-        if world == 1 and not args.no_other_configs and not args.self_halo:
+        if args.full and world == 1 and not args.no_other_configs and not args.self_halo:
             w.close()                                  # free the headline grid before the other configs allocate theirs
             out["other_configs"] = other_configs(config_parity(local_rank) if not args.no_cpu_baseline else None)
-        # ONE compact line on stdout, printed last; everything else to the side file and to stderr
+        # ONE compact line on stdout, printed last; with --full everything else to the side file and to stderr
         sys.stderr.flush()
-        print(headline_line(out, write_details(out, world)), flush=True)
+        print(headline_line(out, write_details(out, world) if args.full else None), flush=True)
     dog.cancel()
     if dist is not None:
         dist.barrier()

@@ -118,7 +118,9 @@ def test_oracle_under_address_and_ub_sanitizers(tmp_path):
 
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "asan"])
     asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
-    env = dict(os.environ, LD_PRELOAD=asan, CXO_LIB=os.path.join(ROOT, "oracle", "libcortex_oracle_asan.so"),
+    # the ASan runtime first, whatever the environment already preloads kept behind it
+    preload = " ".join(p for p in (asan, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, CXO_LIB=os.path.join(ROOT, "oracle", "libcortex_oracle_asan.so"),
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
     code = ("import sys; sys.path.insert(0, %r); import pytest; "
             "sys.exit(pytest.main(['-x', '-q', '-p', 'no:cacheprovider', %r, '-k', "

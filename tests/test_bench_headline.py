@@ -3,8 +3,10 @@
 came back `parsed: null`.)  The emitter is run here on canned numbers — no GPU."""
 import json
 import os
+import re
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,3 +94,62 @@ def test_bench_prints_the_headline_last_and_only_once():
     body = src[src.index("def run_rank"):src.index("def main")]
     assert body.count("print(headline_line(") == 1
     assert "print(json.dumps(out)" not in body
+
+
+def test_a_plain_run_line_holds_the_contract_keys_and_no_roofline():
+    full = _canned(0, 10)
+    for k in ("roofline", "cpu_baseline", "parity", "other_configs"):
+        del full[k]
+    d = json.loads(bench.headline_line(full, None))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["details"] is None and not {"roofline", "cpu_baseline", "parity", "other_configs_digest"} & set(d)
+
+
+def test_the_extras_are_behind_full_and_steps_is_one_region():
+    a = bench.parse(["--gpus", "1", "--steps", "30", "--warmup", "4"])
+    assert a.full is False and a.repeats is None and a.dump_outputs is None and a.steps == 30
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    body = open(os.path.join(ROOT, "bench.py")).read()
+    body = body[body.index("def run_rank"):body.index("def main")]
+    assert "(5 if args.full else 1)" in body
+    lines = body.splitlines()
+    for call in ("cpu_baseline(", "parity_check(", "other_configs(", "write_details(", "roofline(", "dev.profile_enable(", "timed_regions(w2"):
+        n = next(i for i, l in enumerate(lines) if call in l and not l.lstrip().startswith("#"))
+        guard = next(l for l in reversed(lines[:n + 1]) if re.match(r"\s*(el)?if ", l) or " if args.full else " in l)
+        assert "args.full" in guard, (call, guard)
+
+
+class _FakeDev:
+    """what dump_outputs reads: marginals and messages as functions of the ids, so that a sample is recognisable"""
+    def get_marginals(self, ids):
+        ids = np.asarray(ids, dtype=np.float64)
+        return np.stack([ids, -ids], axis=1)
+
+    def get_messages(self, v, f, direction):
+        return np.stack([np.asarray(v, dtype=np.float64), np.asarray(f, dtype=np.float64)], axis=1)
+
+
+def test_dump_outputs_writes_float64_and_samples_the_same_entries_every_time(tmp_path, monkeypatch):
+    import types
+
+    import cortex.jl_amd as cx
+
+    model = cx.synth.gaussian_grid(20, 20, seed=3)
+    w = types.SimpleNamespace(model=model, part=None, dev=_FakeDev())
+    budget = (bench.DUMP_MAX_MARGINALS + bench.DUMP_MAX_MESSAGES) * 2 * 8     # (mean, variance) pairs of float64
+    assert budget <= 64 * 2**20
+    shapes = bench.dump_outputs(str(tmp_path / "all"), w)
+    assert shapes == {"marginals": [400, 2], "messages_to_variable": [len(model.edge_var), 2]}
+    m = np.load(tmp_path / "all" / "marginals.npy")
+    assert m.dtype == np.float64 and np.array_equal(m[:, 0], model.x_ids)
+    monkeypatch.setattr(bench, "DUMP_MAX_MARGINALS", 50)
+    monkeypatch.setattr(bench, "DUMP_MAX_MESSAGES", 70)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), w) == {"marginals": [50, 2], "messages_to_variable": [70, 2]}
+    for name in ("marginals", "messages_to_variable"):
+        a, b = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    s = np.load(tmp_path / "s1" / "marginals.npy")[:, 0]
+    assert np.all(np.diff(s) > 0) and np.all(np.isin(s, model.x_ids))

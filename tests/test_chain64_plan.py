@@ -262,6 +262,7 @@ def test_plan_builder_under_address_and_ub_sanitizers():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # libstdc++ beside libasan: the interceptor of __cxa_throw needs the real one loaded before it (python itself is plain C)
     pre = " ".join(subprocess.check_output(["gcc", "-print-file-name=" + n], text=True).strip() for n in ("libasan.so", "libstdc++.so.6"))
+    pre = " ".join(p for p in (pre, os.environ.get("LD_PRELOAD", "")) if p)      # whatever the environment preloads stays, behind them
     env = dict(os.environ, LD_PRELOAD=pre, CXH_LIB=B.build_hostlogic(asan=True), ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1")
     code = ("import sys; sys.path.insert(0, %r); import pytest; sys.exit(pytest.main(['-x', '-q', '-p', 'no:cacheprovider', %r, '-k', "

@@ -246,6 +246,7 @@ def test_error_paths_leave_nothing_out_of_bounds():
 
 def _run_under_asan(lib, select, files=None):
     pre = " ".join(subprocess.check_output(["gcc", "-print-file-name=" + n], text=True).strip() for n in ("libasan.so", "libstdc++.so.6"))
+    pre = " ".join(p for p in (pre, os.environ.get("LD_PRELOAD", "")) if p)      # whatever the environment preloads stays, behind them
     env = dict(os.environ, LD_PRELOAD=pre, CXH_LIB=lib, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
     files = files or [os.path.abspath(__file__)]
     code = ("import sys; sys.path.insert(0, %r); import pytest; sys.exit(pytest.main(['-x', '-q', '-s', '-p', 'no:cacheprovider'] + %r + ['-k', %r]))"
