@@ -37,6 +37,7 @@ void dev_free_all(cx_handle *h) {
     h->d_marg64_sums = h->d_marg64_tab = nullptr; h->d_marg64_rec = nullptr; h->marg64_cap = 0;
     cx::chain64_tree_free(h);
     cx::kary_free(h);
+    cx::evidence_free(h);
     if (h->d_prod) (void)hipFree(h->d_prod);
     if (h->d_joint) (void)hipFree(h->d_joint);
     h->d_prod = nullptr; h->d_joint = nullptr; h->prod_cap = h->joint_cap = 0; h->prod_index.clear(); h->joint_index.clear();
@@ -230,6 +231,7 @@ int32_t cx_set_factor_matrices(cx_handle *h, int64_t parameter_set, const double
         }
         if ((int64_t)h->psets.size() <= parameter_set) h->psets.resize(parameter_set + 1);
         auto &ps = h->psets[parameter_set];
+        h->param_epoch++;
         ps.assign(A, A + d * d);
         ps.insert(ps.end(), Q, Q + d * d);
         std::vector<double> chk((size_t)6 * d * d);

@@ -1,0 +1,851 @@
+// cx_evidence.hip — cx_log_evidence: log p(data) of a Gaussian model (dim 1 .. 4) from the stored factor→variable messages, on the
+// device.  No counterpart in the reference (Cortex.jl computes no numbers); the derivation is DESIGN.md §4e.
+//
+//   log Z = Σ_o c_o + Σ_a log z_a + Σ_i (1 - d_i) log z_i
+//
+// M_i = the product of variable i's stored factor→variable messages (natural parameters), d_i = its factors that carry a rule,
+// z_a = ∫ f_a Π m_{i→a} with m_{i→a} = M_i / m_{a→i}, z_i = ∫ M_i, c_o = the log-normaliser of a caller-set (opaque) message.
+// Every term is evaluated in coordinates centred on the belief mean μ_i of each variable (x_i = μ_i + u_i): the constants that the
+// shift pulls out of the terms of one variable sum to those of its opaque messages alone (the leave-one-out messages add up to
+// d_i M_i minus the rule messages), so nothing of size ½ η'Λ⁻¹η — 10^12 for data of size 10^6 — is formed and cancelled.
+//
+//   pass 1 (k_ev_var)   one thread per variable: M_i over its SELL slots, μ_i, the variable term (Cholesky log-det) and the centred
+//                       opaque terms log N(μ_i; μ_o, Λ_o⁻¹); writes (μ_i | η_i, Λ_i, positive-definite flag) to a per-variable scratch
+//   pass 2 (k_ev_pair)  one thread per two-variable factor: the factor belief's joint precision (2d x 2d, registers), its log-det and
+//                       quadratic form — a flat leaf message is a zero block of a matrix that stays positive definite
+//          (k_ev_kary)  one thread per factor of 3 .. 7 variables, its joint precision (up to 28 x 28) packed in LDS
+//   k_ev_final          the per-block partial sums (compensated, f64) in a fixed order: two calls on one state are bit-identical
+// The counters travel with the partial sums (per block, then in index order): no atomics at all.
+#include "cx_host.h"
+#include "cx_mv_core.h"
+
+namespace cx {
+namespace ev {
+
+constexpr int kB = 256;        // threads per block of the variable, pairwise and final passes
+constexpr int kKB = 16;        // threads per block of the k-ary pass: each thread's joint precision lives in LDS
+constexpr int kFB = 1024;      // threads of the one block of the final sum (C4: 23 k block partials)
+constexpr double kLog2Pi = 1.83787706640934548356;
+
+// counters read back: 0 variable terms, 1 terms with an undefined input, 2 terms whose belief is not positive definite, 3 stand-in
+// variables met (a halo handle: refused); the factor terms are known on the host
+constexpr int kNCnt = 4;
+
+template <int D>
+struct Lay {
+    static constexpr int NT = D * (D + 1) / 2;
+    static constexpr int K = D == 1 ? 2 : ((D + NT + 1) + 1) / 2 * 2;      // doubles per variable of the scratch: a[D] | Λ[NT] | flag
+};
+// a = μ_i when Λ_i is positive definite (flag 1; D = 1: Λ > 0), η_i otherwise (flag 0, centre 0)
+
+// ---- compensated sums -----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void neu(double &s, double &c, double x) {
+    const double t = s + x;
+    c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
+    s = t;
+}
+
+// per block: the compensated sum and the counters of its terms (variable terms, undefined input, not positive definite, stand-ins);
+// k_ev_final adds the blocks up in index order: no floating-point atomic, no atomic at all
+struct Part {
+    double s, c;
+    unsigned n[4];
+};
+
+// fixed-order tree over the block's threads; thread 0 writes the block's Part
+template <int NB>
+__device__ __forceinline__ void block_part(double s, double c, unsigned n0, unsigned n1, unsigned n2, unsigned n3, Part *__restrict__ out) {
+    __shared__ double ss[NB], cs[NB];
+    __shared__ unsigned ns[4][NB];
+    const int t = threadIdx.x;
+    ss[t] = s; cs[t] = c; ns[0][t] = n0; ns[1][t] = n1; ns[2][t] = n2; ns[3][t] = n3;
+    __syncthreads();
+#pragma unroll
+    for (int w = NB / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            double a = ss[t], ac = cs[t];
+            neu(a, ac, ss[t + w]);
+            ss[t] = a; cs[t] = ac + cs[t + w];
+#pragma unroll
+            for (int k = 0; k < 4; k++) ns[k][t] += ns[k][t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        Part p;
+        p.s = ss[0]; p.c = cs[0];
+#pragma unroll
+        for (int k = 0; k < 4; k++) p.n[k] = ns[k][0];
+        out[blockIdx.x] = p;
+    }
+}
+
+// ---- messages -------------------------------------------------------------------------------------------------------------------
+template <int D>
+__device__ __forceinline__ void ld_msg(const double *__restrict__ buf, int slot, double (&eta)[D], double (&lam)[Lay<D>::NT]) {
+    if constexpr (D == 1) {
+        const double2 m = reinterpret_cast<const double2 *>(buf)[slot];
+        eta[0] = m.x; lam[0] = m.y;
+    } else {
+        const Msg<D> m = slot_load<D, false>(buf, slot);
+#pragma unroll
+        for (int k = 0; k < D; k++) eta[k] = m.eta[k];
+#pragma unroll
+        for (int k = 0; k < Lay<D>::NT; k++) lam[k] = m.lam[k];
+    }
+}
+
+template <int D>
+__device__ __forceinline__ double lam_at(const double (&lam)[Lay<D>::NT], int i, int j) { return i <= j ? lam[tri<D>(i, j)] : lam[tri<D>(j, i)]; }
+
+// in-place lower Cholesky of the full symmetric J (lower triangle read), then h <- L⁻¹ h: log det J and h'J⁻¹h.  false: not positive definite
+template <int N>
+__device__ __forceinline__ bool chol_quad(double (&J)[N][N], double (&h)[N], double &logdet, double &quad) {
+    logdet = 0.0; quad = 0.0;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        double d = J[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) d -= J[j][k] * J[j][k];
+        if (!(d > 0.0)) return false;
+        logdet += log(d);
+        const double l = sqrt(d), il = 1.0 / l;
+        J[j][j] = l;
+#pragma unroll
+        for (int i = j + 1; i < N; i++) {
+            double s = J[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) s -= J[i][k] * J[j][k];
+            J[i][j] = s * il;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        double s = h[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) s -= J[i][k] * h[k];
+        h[i] = s / J[i][i];
+        quad += h[i] * h[i];
+    }
+    return true;
+}
+
+// Λ μ = η by the factor chol_quad left in L (h = L⁻¹ η on entry): back substitution
+template <int N>
+__device__ __forceinline__ void back_solve(const double (&L)[N][N], const double (&y)[N], double (&x)[N]) {
+#pragma unroll
+    for (int i = N - 1; i >= 0; i--) {
+        double s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < N; k++) s -= L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+}
+
+// ---- pass 1: variables ----------------------------------------------------------------------------------------------------------
+// vrec[v] = d_v (low 24 bits) | opaque mask of the SELL slots (bits 24..31); variables of the CSR tail read tail_opq[slot - tail0]
+template <int D>
+__global__ __launch_bounds__(kB) void k_ev_var(int64_t nv, const int32_t *__restrict__ vbase, const int32_t *__restrict__ vdeg,
+                                               const uint8_t *__restrict__ vinfo, const int32_t *__restrict__ vrec,
+                                               const uint8_t *__restrict__ tail_opq, int32_t tail0, const double *__restrict__ f2v,
+                                               double *__restrict__ W, Part *__restrict__ partial) {
+    constexpr int NT = Lay<D>::NT, K = Lay<D>::K;
+    const int64_t v = (int64_t)blockIdx.x * kB + threadIdx.x;
+    double s = 0.0, c = 0.0;
+    bool ghost = false, vterm = false, undef_t = false, npd_t = false;
+    if (v < nv) {
+        const int info = vinfo[v];
+        ghost = (info & kGhost) != 0;
+        if (!ghost && !(info & kClamped)) {
+            const int deg = vdeg[v], b = vbase[v], rec = vrec[v];
+            const bool big = (info & kDegMask) == kBigDeg;
+            const int stride = big ? 1 : kBlock, di = rec & 0xffffff, mask = (rec >> 24) & 0xff;
+            double eta[D], lam[NT];
+#pragma unroll
+            for (int k = 0; k < D; k++) eta[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < NT; k++) lam[k] = 0.0;
+            for (int k = 0; k < deg; k++) {
+                double e[D], l[NT];
+                ld_msg<D>(f2v, b + k * stride, e, l);
+#pragma unroll
+                for (int q = 0; q < D; q++) eta[q] += e[q];
+#pragma unroll
+                for (int q = 0; q < NT; q++) lam[q] += l[q];
+            }
+            bool undef = false;
+#pragma unroll
+            for (int q = 0; q < D; q++) undef = undef || __builtin_isnan(eta[q]);
+#pragma unroll
+            for (int q = 0; q < NT; q++) undef = undef || __builtin_isnan(lam[q]);
+            double L[D][D], y[D], mu[D], logdet, quad;
+#pragma unroll
+            for (int i = 0; i < D; i++) {
+                y[i] = eta[i]; mu[i] = 0.0;
+#pragma unroll
+                for (int j = 0; j < D; j++) L[i][j] = lam_at<D>(lam, i, j);
+            }
+            const bool pd = !undef && chol_quad<D>(L, y, logdet, quad);
+            if (pd) back_solve<D>(L, y, mu);
+            double *w = W + v * K;
+#pragma unroll
+            for (int i = 0; i < D; i++) w[i] = pd ? mu[i] : eta[i];
+#pragma unroll
+            for (int i = 0; i < NT; i++) w[D + i] = lam[i];
+            if constexpr (D > 1) {
+                w[D + NT] = pd ? 1.0 : 0.0;
+                if (K > D + NT + 1) w[K - 1] = 0.0;
+            }
+            if (di != 1) {
+                vterm = true;
+                undef_t = undef;
+                npd_t = !undef && !pd;
+                if (pd) neu(s, c, (double)(1 - di) * 0.5 * (D * kLog2Pi - logdet));
+            }
+            // the opaque messages, centred on μ_i: c_o + η_o'μ - ½ μ'Λ_o μ = log N(μ_i; μ_o, Λ_o⁻¹) when Λ_o is positive definite,
+            // η_o'μ - ½ μ'Λ_o μ otherwise (c_o = 0); an undefined one is skipped
+            for (int k = 0; k < deg; k++) {
+                const bool opq = big ? tail_opq[b + k - tail0] != 0 : ((mask >> k) & 1) != 0;
+                if (!opq) continue;
+                double e[D], l[NT];
+                ld_msg<D>(f2v, b + k * stride, e, l);
+                bool u = false;
+#pragma unroll
+                for (int q = 0; q < D; q++) u = u || __builtin_isnan(e[q]);
+#pragma unroll
+                for (int q = 0; q < NT; q++) u = u || __builtin_isnan(l[q]);
+                if (u) continue;
+                double Lo[D][D], r[D], ld, qd;
+#pragma unroll
+                for (int i = 0; i < D; i++) {
+                    double t = e[i];
+#pragma unroll
+                    for (int j = 0; j < D; j++) { Lo[i][j] = lam_at<D>(l, i, j); t -= Lo[i][j] * mu[j]; }
+                    r[i] = t;
+                }
+                if (chol_quad<D>(Lo, r, ld, qd)) {
+                    neu(s, c, -0.5 * qd + 0.5 * ld - 0.5 * D * kLog2Pi);
+                } else {
+                    double t = 0.0;
+#pragma unroll
+                    for (int i = 0; i < D; i++) {
+                        double lm = 0.0;
+#pragma unroll
+                        for (int j = 0; j < D; j++) lm += lam_at<D>(l, i, j) * mu[j];
+                        t += mu[i] * (e[i] - 0.5 * lm);
+                    }
+                    neu(s, c, t);
+                }
+            }
+        }
+    }
+    block_part<kB>(s, c, vterm, undef_t, npd_t, ghost, partial);
+}
+
+// ---- pass 2 helpers -------------------------------------------------------------------------------------------------------------
+// one non-observed edge of a factor: the centred leave-one-out message m~_{i→a} (η~, Λ~) and the centre μ_i
+template <int D>
+__device__ __forceinline__ bool free_edge(const double *__restrict__ f2v, const double *__restrict__ W, int slot, int var, double (&mu)[D],
+                                          double (&et)[D], double (&lm)[Lay<D>::NT]) {
+    constexpr int NT = Lay<D>::NT, K = Lay<D>::K;
+    double e[D], l[NT];
+    ld_msg<D>(f2v, slot, e, l);
+    const double *w = W + (int64_t)var * K;
+    double a[D], L[NT];
+#pragma unroll
+    for (int i = 0; i < D; i++) a[i] = w[i];
+#pragma unroll
+    for (int i = 0; i < NT; i++) L[i] = w[D + i];
+    const bool pd = D == 1 ? L[0] > 0.0 : w[D + NT] != 0.0;
+    bool undef = false;
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+        mu[i] = pd ? a[i] : 0.0;
+        undef = undef || __builtin_isnan(a[i]) || __builtin_isnan(e[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < NT; i++) { lm[i] = L[i] - l[i]; undef = undef || __builtin_isnan(L[i]) || __builtin_isnan(l[i]); }
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+        double t = e[i];
+#pragma unroll
+        for (int j = 0; j < D; j++) t -= lam_at<D>(l, i, j) * mu[j];
+        et[i] = (pd ? 0.0 : a[i]) - t;
+    }
+    return !undef;
+}
+
+template <int D>
+__device__ __forceinline__ void datum(const double *__restrict__ v2f, int slot, double (&y)[D]) {
+    double l[Lay<D>::NT];
+    ld_msg<D>(v2f, slot, y, l);
+}
+
+// ---- pass 2: factors of two variables -------------------------------------------------------------------------------------------
+// x_out = A x_in + b + N(0, Q): the residual C x - b with C_out = I, C_in = -A is N(0, Q).  rec = (slot out, slot in, var out, var in).
+// dim 1: (q, a, b) per factor (pa, pb may be null: a = 1, b = 0); dim > 1: the factor's parameter set in ptab = [set][A | Q⁻¹ | log det 2πQ, 0]
+template <int D>
+__global__ __launch_bounds__(kB) void k_ev_pair(int64_t n, const int4 *__restrict__ rec, const int32_t *__restrict__ pset, const double *__restrict__ pq,
+                                                const double *__restrict__ pa, const double *__restrict__ pb, const double *__restrict__ ptab,
+                                                const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v, const double *__restrict__ v2f,
+                                                const double *__restrict__ W, Part *__restrict__ partial) {
+    constexpr int NT = Lay<D>::NT;
+    const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+    double s = 0.0, c = 0.0;
+    bool undef_t = false, npd_t = false;
+    if (i < n) {
+        const int4 r = rec[i];
+        double A[D][D], Qi[D][D], ldq, bb[D];
+        if constexpr (D == 1) {
+            const double q = pq[i];
+            A[0][0] = pa ? pa[i] : 1.0; Qi[0][0] = 1.0 / q; ldq = log(q) + kLog2Pi; bb[0] = pb ? pb[i] : 0.0;
+        } else {
+            const double *t = ptab + (int64_t)pset[i] * (2 * D * D + 2);
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+                bb[p] = 0.0;
+#pragma unroll
+                for (int q = 0; q < D; q++) { A[p][q] = t[p * D + q]; Qi[p][q] = t[D * D + p * D + q]; }
+            }
+            ldq = t[2 * D * D];
+        }
+        const bool fo = !(vinfo[r.z] & kClamped), fi = !(vinfo[r.w] & kClamped);
+        double mo[D], eo[D], lo[NT], mi[D], ei[D], li[NT];
+        bool ok = true;
+        if (fo) ok = free_edge<D>(f2v, W, r.x, r.z, mo, eo, lo) && ok;
+        else datum<D>(v2f, r.x, mo);
+        if (fi) ok = free_edge<D>(f2v, W, r.y, r.w, mi, ei, li) && ok;
+        else datum<D>(v2f, r.y, mi);
+        // b'' = b - C_out x_out - C_in x_in at the data / the centres
+        double bp[D];
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            double t = bb[p] - mo[p];
+#pragma unroll
+            for (int q = 0; q < D; q++) t += A[p][q] * mi[q];
+            bp[p] = t;
+        }
+        double g[D], cq = 0.0;      // g = Q⁻¹ b''
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            double t = 0.0;
+#pragma unroll
+            for (int q = 0; q < D; q++) t += Qi[p][q] * bp[q];
+            g[p] = t; cq += bp[p] * t;
+        }
+        double lz = -0.5 * cq - 0.5 * ldq, logdet = 0.0, quad = 0.0;
+        bool pd = true;
+        double T[D][D];             // T = Q⁻¹ A
+#pragma unroll
+        for (int p = 0; p < D; p++)
+#pragma unroll
+            for (int q = 0; q < D; q++) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; k++) t += Qi[p][k] * A[k][q];
+                T[p][q] = t;
+            }
+        if (fo && fi) {
+            double J[2 * D][2 * D], h[2 * D];
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+                h[p] = g[p] + eo[p];
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; k++) t += A[k][p] * g[k];
+                h[D + p] = -t + ei[p];
+#pragma unroll
+                for (int q = 0; q < D; q++) {
+                    J[p][q] = Qi[p][q] + lam_at<D>(lo, p, q);
+                    J[D + p][q] = -T[q][p];          // (-Q⁻¹A)' below the diagonal
+                    J[q][D + p] = -T[q][p];
+                    double u = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; k++) u += A[k][p] * T[k][q];
+                    J[D + p][D + q] = u + lam_at<D>(li, p, q);
+                }
+            }
+            pd = chol_quad<2 * D>(J, h, logdet, quad);
+            lz += 0.5 * quad - 0.5 * logdet + D * kLog2Pi;
+        } else if (fo || fi) {
+            double J[D][D], h[D];
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+                double t = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; k++) t += A[k][p] * g[k];
+                h[p] = fo ? g[p] + eo[p] : -t + ei[p];
+#pragma unroll
+                for (int q = 0; q < D; q++) {
+                    double u = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; k++) u += A[k][p] * T[k][q];
+                    J[p][q] = fo ? Qi[p][q] + lam_at<D>(lo, p, q) : u + lam_at<D>(li, p, q);
+                }
+            }
+            pd = chol_quad<D>(J, h, logdet, quad);
+            lz += 0.5 * quad - 0.5 * logdet + 0.5 * D * kLog2Pi;
+        }
+        undef_t = !ok;
+        npd_t = ok && !pd;
+        if (ok && pd) neu(s, c, lz);
+    }
+    block_part<kB>(s, c, 0, undef_t, npd_t, 0, partial);
+}
+
+// ---- pass 2: factors of 3 .. 7 variables ----------------------------------------------------------------------------------------
+// x_out = Σ A_k x_k + b + N(0, Q), entries in the k-ary table's order (OUT first).  krec[f] = slots[8] | vars[8] (-1: none).
+// dim 1: kc[f] = C_e[8] (+1 OUT, -a_i IN) | q | b.  dim > 1: kps[f] = parameter set per entry (IN: its A; OUT: Q); ptab as k_ev_pair's.
+// The joint precision over the free entries (packed lower triangle, up to 28 x 28) and its right-hand side live in LDS, thread-interleaved.
+template <int D>
+struct KLay {
+    static constexpr int NM = 7 * D, NP = NM * (NM + 1) / 2;
+};
+__device__ __forceinline__ int pk(int i, int j) { return i * (i + 1) / 2 + j; }      // i >= j
+
+template <int D>
+__device__ __forceinline__ double cel(const double *__restrict__ Ae, double ce, int p, int q) {      // C_e[p][q]
+    if constexpr (D == 1) return ce;
+    else return Ae ? -Ae[p * D + q] : (p == q ? 1.0 : 0.0);
+}
+
+template <int D>
+__global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, const int32_t *__restrict__ krec, const double *__restrict__ kc, const int32_t *__restrict__ kps,
+                                                 const double *__restrict__ ptab, const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v,
+                                                 const double *__restrict__ v2f, const double *__restrict__ W, Part *__restrict__ partial) {
+    constexpr int NT = Lay<D>::NT, NP = KLay<D>::NP, NM = KLay<D>::NM, PS = 2 * D * D + 2;
+    __shared__ double sJ[NP * kKB], sh[NM * kKB];
+    const int t = threadIdx.x;
+    double *J = sJ + t, *hv = sh + t;      // element k at [k * kKB]
+    const int64_t f = (int64_t)blockIdx.x * kKB + t;
+    double s = 0.0, c = 0.0;
+    bool undef_t = false, npd_t = false;
+    if (f < n) {
+        const int32_t *sl = krec + f * 16, *vr = sl + 8;
+        double Qi[D][D], ldq, bp[D];
+        // C_e of entry e: dim 1 the coefficient, dim > 1 I (OUT) or -A of the entry's set (read where used: no per-thread arrays)
+        auto Aof = [&](int e) -> const double * {
+            if constexpr (D == 1) return nullptr;
+            else return e == 0 ? nullptr : ptab + (int64_t)kps[f * 8 + e] * PS;
+        };
+        auto Cof = [&](int e) -> double {
+            if constexpr (D == 1) return kc[f * 10 + e];
+            else return 0.0;
+        };
+        if constexpr (D == 1) {
+            const double *k = kc + f * 10;
+            Qi[0][0] = 1.0 / k[8]; ldq = log(k[8]) + kLog2Pi; bp[0] = k[9];
+        } else {
+            const double *tq = ptab + (int64_t)kps[f * 8] * PS;
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+                bp[p] = 0.0;
+#pragma unroll
+                for (int q = 0; q < D; q++) Qi[p][q] = tq[D * D + p * D + q];
+            }
+            ldq = tq[2 * D * D];
+        }
+        unsigned freemask = 0;
+        int nfree = 0;
+        bool ok = true;
+        for (int e = 0; e < 8; e++) {
+            if (sl[e] < 0) continue;
+            double x[D];
+            if (vinfo[vr[e]] & kClamped) datum<D>(v2f, sl[e], x);
+            else {
+                double et[D], lm[NT];
+                ok = free_edge<D>(f2v, W, sl[e], vr[e], x, et, lm) && ok;
+                const int o = nfree * D;
+                for (int r = 0; r < D; r++) {
+                    hv[(o + r) * kKB] = et[r];
+                    for (int q = 0; q <= r; q++) J[pk(o + r, o + q) * kKB] = lam_at<D>(lm, r, q);
+                    for (int j = 0; j < o; j++) J[pk(o + r, j) * kKB] = 0.0;
+                }
+                freemask |= 1u << e;
+                nfree++;
+            }
+            // b'' -= C_e x
+#pragma unroll
+            for (int p = 0; p < D; p++) {
+                double u = 0.0;
+#pragma unroll
+                for (int q = 0; q < D; q++) u += cel<D>(Aof(e), Cof(e), p, q) * x[q];
+                bp[p] -= u;
+            }
+        }
+        double g[D], cq = 0.0;
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            double u = 0.0;
+#pragma unroll
+            for (int q = 0; q < D; q++) u += Qi[p][q] * bp[q];
+            g[p] = u; cq += bp[p] * u;
+        }
+        double lz = -0.5 * cq - 0.5 * ldq;
+        // J += C_u' Q⁻¹ C_u, h += C_u' Q⁻¹ b''
+        int jk = 0;
+        for (int k = 0; k < 8; k++) {
+            if (!((freemask >> k) & 1)) continue;
+            double G[D][D];          // Q⁻¹ C_k
+#pragma unroll
+            for (int p = 0; p < D; p++)
+#pragma unroll
+                for (int q = 0; q < D; q++) {
+                    double u = 0.0;
+#pragma unroll
+                    for (int m = 0; m < D; m++) u += Qi[p][m] * cel<D>(Aof(k), Cof(k), m, q);
+                    G[p][q] = u;
+                }
+#pragma unroll
+            for (int r = 0; r < D; r++) {
+                double u = 0.0;
+#pragma unroll
+                for (int p = 0; p < D; p++) u += cel<D>(Aof(k), Cof(k), p, r) * g[p];
+                hv[(jk * D + r) * kKB] += u;
+            }
+            int jj = 0;
+            for (int j = 0; j <= k; j++) {
+                if (!((freemask >> j) & 1)) continue;
+                // block (k, j) of the lower triangle: C_k' Q⁻¹ C_j = G_k'... written as rows of k, columns of j
+                for (int r = 0; r < D; r++)
+                    for (int q = 0; q < D; q++) {
+                        if (jj == jk && q > r) continue;
+                        double u = 0.0;
+#pragma unroll
+                        for (int p = 0; p < D; p++) u += cel<D>(Aof(j), Cof(j), p, q) * G[p][r];      // (C_j' Q⁻¹ C_k)[q][r] = (C_k' Q⁻¹ C_j)[r][q]
+                        J[pk(jk * D + r, jj * D + q) * kKB] += u;
+                    }
+                jj++;
+            }
+            jk++;
+        }
+        // Cholesky in place, then the forward solve
+        const int N = nfree * D;
+        bool pd = true;
+        double logdet = 0.0, quad = 0.0;
+        for (int j = 0; j < N && pd; j++) {
+            double d = J[pk(j, j) * kKB];
+            for (int k = 0; k < j; k++) { const double l = J[pk(j, k) * kKB]; d -= l * l; }
+            if (!(d > 0.0)) { pd = false; break; }
+            logdet += log(d);
+            const double l = sqrt(d), il = 1.0 / l;
+            J[pk(j, j) * kKB] = l;
+            for (int i = j + 1; i < N; i++) {
+                double u = J[pk(i, j) * kKB];
+                for (int k = 0; k < j; k++) u -= J[pk(i, k) * kKB] * J[pk(j, k) * kKB];
+                J[pk(i, j) * kKB] = u * il;
+            }
+        }
+        if (pd)
+            for (int i = 0; i < N; i++) {
+                double u = hv[i * kKB];
+                for (int k = 0; k < i; k++) u -= J[pk(i, k) * kKB] * hv[k * kKB];
+                u /= J[pk(i, i) * kKB];
+                hv[i * kKB] = u;
+                quad += u * u;
+            }
+        lz += 0.5 * quad - 0.5 * logdet + 0.5 * N * kLog2Pi;
+        undef_t = !ok;
+        npd_t = ok && !pd;
+        if (ok && pd) neu(s, c, lz);
+    }
+    block_part<kKB>(s, c, 0, undef_t, npd_t, 0, partial);
+}
+
+// ---- the partial sums and counters in index order; out = value | counters[kNCnt] (u64) ------------------------------------------
+__global__ __launch_bounds__(kFB) void k_ev_final(int64_t n, const Part *__restrict__ partial, double *__restrict__ out) {
+    __shared__ double ss[kFB], cs[kFB];
+    __shared__ unsigned long long ns[kNCnt][kFB];
+    const int t = threadIdx.x;
+    double s = 0.0, c = 0.0;
+    unsigned long long m[kNCnt] = {0, 0, 0, 0};
+    for (int64_t i = t; i < n; i += kFB) {
+        const Part p = partial[i];
+        neu(s, c, p.s);
+        c += p.c;
+#pragma unroll
+        for (int k = 0; k < kNCnt; k++) m[k] += p.n[k];
+    }
+    ss[t] = s; cs[t] = c;
+#pragma unroll
+    for (int k = 0; k < kNCnt; k++) ns[k][t] = m[k];
+    __syncthreads();
+    for (int w = kFB / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            double a = ss[t], ac = cs[t];
+            neu(a, ac, ss[t + w]);
+            ss[t] = a; cs[t] = ac + cs[t + w];
+#pragma unroll
+            for (int k = 0; k < kNCnt; k++) ns[k][t] += ns[k][t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) out[0] = ss[0] + cs[0];
+    if (t < kNCnt) reinterpret_cast<unsigned long long *>(out)[1 + t] = ns[t][0];
+}
+
+// ---- host: the work lists -------------------------------------------------------------------------------------------------------
+struct Cache {
+    bool built = false;
+    uint64_t epoch = ~0ull;
+    int64_t zero_noise_fac = -1;          // a factor with q = 0 (dim 1): refused
+    int64_t unsupported_fac = -1;         // a factor of a kind without a sum-product rule
+    int64_t n_pair = 0, n_kary = 0, nb = 0;
+    int32_t *d_vrec = nullptr;
+    uint8_t *d_tail = nullptr;
+    int4 *d_pair = nullptr;
+    int32_t *d_pair_ps = nullptr, *d_krec = nullptr, *d_kps = nullptr;
+    double *d_pq = nullptr, *d_pa = nullptr, *d_pb = nullptr, *d_kc = nullptr, *d_ptab = nullptr;
+    int64_t ptab_cap = 0;
+    std::vector<int32_t> pair_ps;         // dim > 1: parameter set per pair (what the table must hold)
+    double *d_W = nullptr;
+    Part *d_partial = nullptr;
+    double *d_out = nullptr, *h_out = nullptr;      // value | counters; h_out: pinned
+};
+
+template <class T>
+void free_ptr(T *&p) { if (p) (void)hipFree((void *)p); p = nullptr; }
+
+int32_t build(cx_handle *h, Cache &C) {
+    using namespace cxh;
+    const int d = h->cfg.dim;
+    const int64_t nv = h->nv, ne = h->ne, nf = h->nf;
+    std::vector<int32_t> slot_var((size_t)h->nslots, -1), fe1((size_t)nf, -1), fe2((size_t)nf, -1), efac((size_t)ne);
+    for (int64_t e = 0; e < ne; e++) {
+        slot_var[slot_of_edge(h, e)] = h->edge_var[e];
+        const int64_t f = find_factor(h, h->edge_fac_id[e]);
+        efac[e] = (int32_t)f;
+        if (fe1[f] < 0) fe1[f] = (int32_t)e; else if (fe2[f] < 0) fe2[f] = (int32_t)e;
+    }
+    // variables: d_i and which slots hold opaque messages
+    const bool has_tail = !h->big_vars.empty();
+    std::vector<int32_t> vrec((size_t)nv, 0);
+    std::vector<uint8_t> tail(has_tail ? (size_t)(h->nslots - h->big_start) : 1, 0);
+    for (int64_t v = 0; v < nv; v++) {
+        const bool big = (h->vinfo[v] & kDegMask) == kBigDeg;
+        int32_t di = 0, mask = 0;
+        for (int32_t e = h->var_off[v]; e < h->var_off[v + 1]; e++) {
+            const int k = e - h->var_off[v];
+            if (h->fac_kind[efac[e]] == CX_FACTOR_OPAQUE) {
+                if (big) tail[slot_of_edge(h, e) - h->big_start] = 1;
+                else mask |= 1 << k;
+            } else di++;
+        }
+        vrec[v] = di | (mask << 24);
+    }
+    // factors
+    std::vector<int4> pair;
+    std::vector<int32_t> pair_ps;
+    std::vector<double> pq, pa, pb;
+    bool any_ab = false;
+    std::vector<int32_t> krec;
+    C.zero_noise_fac = -1; C.unsupported_fac = -1;
+    int64_t row = 0;
+    for (int64_t f = 0; f < nf; f++) {
+        const int32_t kind = h->fac_kind[f];
+        const double *p = &h->fac_params[f * CX_NPARAM];
+        if (kind == CX_FACTOR_OPAQUE) continue;
+        if (kind == CX_FACTOR_GAUSS_LINEAR_N) {
+            for (int e = 0; e < 8; e++) krec.push_back(h->kary_slot[8 * row + e]);
+            for (int e = 0; e < 8; e++) { const int32_t s = h->kary_slot[8 * row + e]; krec.push_back(s < 0 ? -1 : slot_var[s]); }
+            if (d == 1 && !(h->kary_qb[2 * row] > 0.0) && C.zero_noise_fac < 0) C.zero_noise_fac = h->fac_ids[f];
+            row++;
+            continue;
+        }
+        if ((kind != CX_FACTOR_GAUSS_ADDITIVE && kind != CX_FACTOR_GAUSS_LINEAR) || fe2[f] < 0) { if (C.unsupported_fac < 0) C.unsupported_fac = h->fac_ids[f]; continue; }
+        const int32_t s1 = slot_of_edge(h, fe1[f]), s2 = slot_of_edge(h, fe2[f]);
+        int32_t so = s1, si = s2;
+        if (d > 1) {
+            if ((h->spdir[s1] & 1) == 0) { so = s2; si = s1; }      // spdir[in slot] = 2 * set (the message it sends goes forward)
+            pair_ps.push_back(h->spdir[si] >> 1);
+        } else {
+            if (kind == CX_FACTOR_GAUSS_LINEAR && !h->lin_out_is_second[f]) { so = s1; si = s2; }
+            else if (kind == CX_FACTOR_GAUSS_LINEAR) { so = s2; si = s1; }
+            const double a = kind == CX_FACTOR_GAUSS_LINEAR ? p[1] : 1.0, b = kind == CX_FACTOR_GAUSS_LINEAR ? p[2] : 0.0;
+            pq.push_back(p[0]); pa.push_back(a); pb.push_back(b);
+            any_ab = any_ab || a != 1.0 || b != 0.0;
+            if (!(p[0] > 0.0) && C.zero_noise_fac < 0) C.zero_noise_fac = h->fac_ids[f];
+        }
+        pair.push_back(make_int4(so, si, slot_var[so], slot_var[si]));
+    }
+    if (row != h->n_kary) return fail(h, CX_ERR_STATE, "cx_log_evidence: the k-ary table does not match the factors");
+    C.n_pair = (int64_t)pair.size(); C.n_kary = row;
+    C.pair_ps = pair_ps;
+    int32_t rc;
+    if ((rc = dev_upload(h, &C.d_vrec, vrec)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &C.d_tail, tail)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &C.d_pair, pair)) != CX_OK) return rc;
+    if (d > 1) { if ((rc = dev_upload(h, &C.d_pair_ps, pair_ps)) != CX_OK) return rc; }
+    else {
+        if ((rc = dev_upload(h, &C.d_pq, pq)) != CX_OK) return rc;
+        if (any_ab) {
+            if ((rc = dev_upload(h, &C.d_pa, pa)) != CX_OK) return rc;
+            if ((rc = dev_upload(h, &C.d_pb, pb)) != CX_OK) return rc;
+        }
+    }
+    if ((rc = dev_upload(h, &C.d_krec, krec)) != CX_OK) return rc;
+    const int K = d == 1 ? Lay<1>::K : d == 2 ? Lay<2>::K : d == 3 ? Lay<3>::K : Lay<4>::K;
+    if ((rc = dev_alloc(h, &C.d_W, nv * K)) != CX_OK) return rc;
+    C.nb = (nv + kB - 1) / kB + (C.n_pair + kB - 1) / kB + (C.n_kary + kKB - 1) / kKB;
+    if ((rc = dev_alloc(h, &C.d_partial, C.nb)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_out, 1 + kNCnt)) != CX_OK) return rc;
+    CX_HIP(h, hipHostMalloc((void **)&C.h_out, (1 + kNCnt) * sizeof(double), hipHostMallocDefault));
+    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the host vectors die here)
+    C.built = true;
+    C.epoch = ~0ull;
+    return CX_OK;
+}
+
+// the parameters that may change after cx_graph_create: k-ary coefficients (dim 1), (A, Q) sets and the k-ary edges' sets (dim > 1)
+int32_t refresh_params(cx_handle *h, Cache &C) {
+    using namespace cxh;
+    if (C.epoch == h->param_epoch) return CX_OK;
+    const int d = h->cfg.dim;
+    int32_t rc;
+    if (d == 1) {
+        std::vector<double> kc((size_t)C.n_kary * 10);
+        for (int64_t r = 0; r < C.n_kary; r++) {
+            for (int e = 0; e < 8; e++) kc[r * 10 + e] = h->kary_coef[8 * r + e];
+            kc[r * 10 + 8] = h->kary_qb[2 * r]; kc[r * 10 + 9] = h->kary_qb[2 * r + 1];
+        }
+        free_ptr(C.d_kc);
+        if ((rc = dev_upload(h, &C.d_kc, kc)) != CX_OK) return rc;
+    } else {
+        std::vector<int32_t> kps((size_t)C.n_kary * 8, 0);
+        std::vector<char> used;
+        auto use = [&](int32_t s) { if ((size_t)s >= used.size()) used.resize((size_t)s + 1, 0); used[(size_t)s] = 1; };
+        for (int32_t s : C.pair_ps) use(s);
+        for (int64_t r = 0; r < C.n_kary; r++)
+            for (int e = 0; e < 8; e++) {
+                const int32_t s = h->kary_slot[8 * r + e] < 0 ? 0 : h->kary_pset[8 * r + e];
+                kps[r * 8 + e] = s;
+                if (h->kary_slot[8 * r + e] >= 0) use(s);
+            }
+        const int64_t nsets = (int64_t)used.size(), per = 2 * d * d + 2;
+        std::vector<double> tab((size_t)std::max<int64_t>(nsets, 1) * per, 0.0);
+        for (int64_t s = 0; s < nsets; s++) {
+            if (!used[s]) continue;
+            if (s >= (int64_t)h->psets.size() || h->psets[s].empty())
+                return fail(h, CX_ERR_STATE, "cx_log_evidence: parameter set " + std::to_string(s) + " was never set (cx_set_factor_matrices)");
+            const double *A = h->psets[s].data(), *Q = A + d * d;
+            // Q = L L': log det 2πQ and Q⁻¹ (Q is symmetric positive definite: cx_set_factor_matrices checks it)
+            double L[4][4] = {}, Li[4][4] = {}, ld = d * kLog2Pi;
+            for (int j = 0; j < d; j++) {
+                double t = Q[j * d + j];
+                for (int k = 0; k < j; k++) t -= L[j][k] * L[j][k];
+                L[j][j] = std::sqrt(t); ld += std::log(t);
+                for (int i = j + 1; i < d; i++) {
+                    double u = 0.5 * (Q[i * d + j] + Q[j * d + i]);
+                    for (int k = 0; k < j; k++) u -= L[i][k] * L[j][k];
+                    L[i][j] = u / L[j][j];
+                }
+            }
+            for (int c = 0; c < d; c++)
+                for (int i = 0; i < d; i++) {
+                    double u = i == c ? 1.0 : 0.0;
+                    for (int k = 0; k < i; k++) u -= L[i][k] * Li[k][c];
+                    Li[i][c] = u / L[i][i];
+                }
+            double *o = &tab[(size_t)(s * per)];
+            for (int k = 0; k < d * d; k++) o[k] = A[k];
+            for (int i = 0; i < d; i++)
+                for (int j = 0; j < d; j++) {
+                    double u = 0.0;
+                    for (int k = 0; k < d; k++) u += Li[k][i] * Li[k][j];
+                    o[d * d + i * d + j] = u;
+                }
+            o[2 * d * d] = ld;
+        }
+        if (C.ptab_cap < (int64_t)tab.size()) {
+            free_ptr(C.d_ptab);
+            if ((rc = dev_alloc(h, &C.d_ptab, (int64_t)tab.size())) != CX_OK) return rc;
+            C.ptab_cap = (int64_t)tab.size();
+        }
+        CX_HIP(h, hipMemcpyAsync(C.d_ptab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, h->stream));
+        free_ptr(C.d_kps);
+        if ((rc = dev_upload(h, &C.d_kps, kps)) != CX_OK) return rc;
+        CX_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    C.epoch = h->param_epoch;
+    return CX_OK;
+}
+
+template <int D>
+void launch(cx_handle *h, Cache &C, const double *f2v, const double *v2f) {
+    const int64_t nb_v = (h->nv + kB - 1) / kB, nb_p = (C.n_pair + kB - 1) / kB, nb_k = (C.n_kary + kKB - 1) / kKB;
+    Part *part = C.d_partial;
+    if (nb_v)
+        hipLaunchKernelGGL(k_ev_var<D>, dim3((unsigned)nb_v), dim3(kB), 0, h->stream, h->nv, h->d_vbase, h->d_var_deg, h->d_vinfo, C.d_vrec,
+                           C.d_tail, h->big_start, f2v, C.d_W, part);
+    if (nb_p)
+        hipLaunchKernelGGL(k_ev_pair<D>, dim3((unsigned)nb_p), dim3(kB), 0, h->stream, C.n_pair, C.d_pair, C.d_pair_ps, C.d_pq, C.d_pa, C.d_pb,
+                           C.d_ptab, h->d_vinfo, f2v, v2f, C.d_W, part + nb_v);
+    if (nb_k)
+        hipLaunchKernelGGL(k_ev_kary<D>, dim3((unsigned)nb_k), dim3(kKB), 0, h->stream, C.n_kary, C.d_krec, C.d_kc, C.d_kps, C.d_ptab, h->d_vinfo,
+                           f2v, v2f, C.d_W, part + nb_v + nb_p);
+    hipLaunchKernelGGL(k_ev_final, dim3(1), dim3(kFB), 0, h->stream, C.nb, part, C.d_out);
+}
+
+}  // namespace ev
+
+void evidence_free(cx_handle *h) {
+    if (!h || !h->evidence) return;
+    ev::Cache *C = static_cast<ev::Cache *>(h->evidence);
+    for (void **p : {(void **)&C->d_vrec, (void **)&C->d_tail, (void **)&C->d_pair, (void **)&C->d_pair_ps, (void **)&C->d_krec, (void **)&C->d_kps,
+                     (void **)&C->d_pq, (void **)&C->d_pa, (void **)&C->d_pb, (void **)&C->d_kc, (void **)&C->d_ptab, (void **)&C->d_W,
+                     (void **)&C->d_partial, (void **)&C->d_out})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (C->h_out) (void)hipHostFree(C->h_out);
+    delete C;
+    h->evidence = nullptr;
+}
+
+}  // namespace cx
+
+using namespace cxh;
+
+extern "C" int32_t cx_log_evidence(cx_handle *h, double *value, int64_t *counts4) {
+    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED,
+               "cx_log_evidence: the Gaussian family only (no variational free energy, no Beta-Bernoulli evidence)");
+    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_log_evidence: no graph");
+    CX_REQUIRE(h, value && counts4, CX_ERR_INVALID_ARGUMENT, "cx_log_evidence: null argument");
+    CX_REQUIRE(h, h->cfg.dim >= 1 && h->cfg.dim <= 4 && !h->user_dim, CX_ERR_UNSUPPORTED, "cx_log_evidence: dim 1, 2, 3 and 4 (the matrix-core dims are not implemented)");
+    CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
+               "cx_log_evidence: not for a partitioned handle (halo lists or stand-in variables: its terms would need owners)");
+    try {
+        CX_HIP(h, hipSetDevice(h->cfg.device));
+        if (h->stream) {
+            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+            CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
+            CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, "cx_log_evidence: the handle's stream is being captured (the call is synchronous)");
+        }
+        if (!h->evidence) h->evidence = new cx::ev::Cache();
+        cx::ev::Cache &C = *static_cast<cx::ev::Cache *>(h->evidence);
+        int32_t rc;
+        if (!C.built && (rc = cx::ev::build(h, C)) != CX_OK) { cx::evidence_free(h); return rc; }
+        if (C.unsupported_fac >= 0)
+            return fail(h, CX_ERR_UNSUPPORTED, "cx_log_evidence: factor " + std::to_string(C.unsupported_fac) + " has no sum-product rule (Gaussian factors and opaque messages only)");
+        if (C.zero_noise_fac >= 0)
+            return fail(h, CX_ERR_UNSUPPORTED, "cx_log_evidence: factor " + std::to_string(C.zero_noise_fac) + " has zero noise (q = 0): its density is degenerate");
+        if ((rc = cx::ev::refresh_params(h, C)) != CX_OK) return rc;
+        if (h->cfg.dim > 1 && (rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (chain scan, dim 2..4: the messages go to their slots on demand)
+        const double *f2v = h->cfg.dim == 1 ? (const double *)h->d_f2v : h->d_mv_f2v;
+        const double *v2f = h->cfg.dim == 1 ? (const double *)h->d_v2f : h->d_mv_v2f;
+        switch (h->cfg.dim) {
+        case 1: cx::ev::launch<1>(h, C, f2v, v2f); break;
+        case 2: cx::ev::launch<2>(h, C, f2v, v2f); break;
+        case 3: cx::ev::launch<3>(h, C, f2v, v2f); break;
+        default: cx::ev::launch<4>(h, C, f2v, v2f); break;
+        }
+        CX_HIP(h, hipGetLastError());
+        CX_HIP(h, hipMemcpyAsync(C.h_out, C.d_out, (1 + cx::ev::kNCnt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        CX_HIP(h, hipStreamSynchronize(h->stream));
+        uint64_t cnt[cx::ev::kNCnt];
+        std::memcpy(cnt, C.h_out + 1, sizeof(cnt));
+        CX_REQUIRE(h, cnt[3] == 0, CX_ERR_UNSUPPORTED, "cx_log_evidence: the graph holds stand-in variables of a partition");
+        counts4[0] = C.n_pair + C.n_kary;
+        for (int k = 1; k < 4; k++) counts4[k] = (int64_t)cnt[k - 1];
+        *value = counts4[2] + counts4[3] > 0 ? kNaN : C.h_out[0];
+        return CX_OK;
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence: host allocation failed"); }
+}

@@ -255,6 +255,11 @@ struct cx_handle {
     // variational families (cx_vmp.hip): opaque state
     void *vmp = nullptr;
 
+    // cx_log_evidence (cx_evidence.hip): work lists of the graph and scratch, built on the first call (opaque); param_epoch moves on
+    // with every change of rule parameters after cx_graph_create (matrices, coefficients, edge sets), which the lists' parameter part follows
+    void *evidence = nullptr;
+    uint64_t param_epoch = 0;
+
     // staging for set/get/batch
     void *d_stage = nullptr;
     int64_t stage_bytes = 0;
@@ -393,5 +398,6 @@ void comm_destroy(cx_handle *h);
 bool comm_exchange(cx_handle *h, std::string &err, bool packed_on_comm_stream);
 bool comm_exchange_on(cx_handle *h, hipStream_t stream, std::string &err);
 void ipc_destroy(cx_handle *h);  // cx_api_ipc.hip
+void evidence_free(cx_handle *h);  // cx_evidence.hip
 
 }  // namespace cx

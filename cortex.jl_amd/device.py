@@ -272,6 +272,15 @@ class DeviceGraph:
         self._check(self.lib.cx_message_health(self.h, out))
         return dict(zip(("defined", "undefined", "negative_precision", "non_finite"), [int(x) for x in out]))
 
+    def log_evidence(self):
+        """cx_log_evidence: log p(data) from the stored factor→variable messages — exact on forests at a fixed point, the Bethe
+        estimate elsewhere — and its term counts.  The value is NaN when a term read an undefined message or a belief that is not
+        positive definite (counts "undefined" / "not_positive_definite")."""
+        val = C.c_double()
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.cx_log_evidence(self.h, C.byref(val), out))
+        return float(val.value), dict(zip(("factor_terms", "variable_terms", "undefined", "not_positive_definite"), [int(x) for x in out]))
+
     # -- halo -----------------------------------------------------------------------------------
     def halo_configure(self, send_var, send_fac, recv_var, recv_fac):
         sv, sf, rv, rf = _i64(send_var), _i64(send_fac), _i64(recv_var), _i64(recv_fac)

@@ -491,6 +491,13 @@ class HipProcessor(AbstractInferenceRequestProcessor):
     def refresh_marginals(self, ids):
         self.dev.update_batch([L.ITEM_INDIVIDUAL_MARGINAL] * len(ids), list(ids), [0] * len(ids))
 
+    def log_evidence(self):
+        """log p(data) of the mirrored model from the device's stored messages (DeviceGraph.log_evidence): meaningful after
+        update_marginals in mode "sweep" or "reference" — exact on forests once every message is final, the Bethe estimate on loops."""
+        if self.family != "gaussian":
+            raise NotImplementedError("log_evidence: the Gaussian family only")
+        return self.dev.log_evidence()
+
 
 # ---- variational families (SURVEY.md §8 f3) --------------------------------------------------------------------------
 @dataclass(frozen=True)

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define CX_ABI_VERSION 4   /* 4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
+#define CX_ABI_VERSION 5   /* 5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
 
 /* status codes */
 #define CX_OK 0
@@ -537,6 +537,19 @@ int32_t cx_tree_heavy_path_stats(const cx_handle *h, int64_t *out4);
  * negative precision (dim > 1: a negative diagonal entry of the precision matrix), defined with a non-finite entry (a point mass
  * (y, +inf) of dim 1 is a value, not counted) }.  Synchronous. */
 int32_t cx_message_health(cx_handle *h, int64_t *out4);
+
+/* ---- log-evidence (ABI 5; no counterpart in the reference: its engine computes no numbers) ----
+ * log p(data) of a CX_FAMILY_GAUSSIAN model, dim 1 - 4, from the STORED factor→variable messages and the caller's data (never the
+ * marginals):  log Z = Σ_o c_o + Σ_a log z_a + Σ_i (1 - d_i) log z_i  over the opaque messages o (normalised densities when their
+ * precision is positive definite), the Gaussian factors a (z_a = ∫ f_a Π m_{i→a}, observed variables fixed at their datum) and the
+ * non-observed variables i (d_i = their factors that carry a rule; z_i = ∫ Π m_{a→i}).  Exact on forests at a fixed point — after one
+ * chain-scan or tree sweep, one reference-order call that requested every variable, fused / flooding sweeps run to convergence — and
+ * the Bethe estimate (minus the Bethe free energy) elsewhere.  A factor of zero noise (q = 0) is CX_ERR_UNSUPPORTED;
+ * so are the other families, dim >= 5 and partitioned handles (halo lists, stand-in variables).  Works under every schedule the
+ * handle accepts.
+ * counts4 = {factor terms, variable terms (d_i != 1), terms with an undefined input, terms whose belief is not positive definite};
+ * *value is NaN iff counts4[2] + counts4[3] > 0.  Synchronous; moves no message, marginal, readiness bit or counter. */
+int32_t cx_log_evidence(cx_handle *h, double *value, int64_t *counts4);
 
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)

@@ -123,6 +123,13 @@ class Handle {
     void set_damping(double lambda) { check(cx_set_damping(h_, lambda)); }      // fused / flooding sweeps: new = (1 - lambda) rule + lambda old
     double residual() { double r = 0; check(cx_residual(h_, &r)); return r; }
     std::array<int64_t, 4> message_health() { std::array<int64_t, 4> o{}; check(cx_message_health(h_, o.data())); return o; }      // defined, undefined, negative precision, non-finite
+    // log p(data) from the stored messages (exact on forests at a fixed point, the Bethe estimate elsewhere); counts: factor terms, variable
+    // terms, terms with an undefined input, terms whose belief is not positive definite (the value is NaN when either of the last two is > 0)
+    std::pair<double, std::array<int64_t, 4>> log_evidence() {
+        double v = 0; std::array<int64_t, 4> o{};
+        check(cx_log_evidence(h_, &v, o.data()));
+        return {v, o};
+    }
     std::pair<int32_t, double> sweep_until(double tol, int32_t max_sweeps, int32_t check_every = 10) {
         int32_t n = 0; double r = 0;
         check(cx_sweep_until(h_, tol, max_sweeps, check_every, &n, &r));

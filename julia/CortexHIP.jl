@@ -280,6 +280,15 @@ function message_health(p)             # numerical guards as counters: defined, 
     return out
 end
 
+# log p(data) from the stored messages (ABI 5; dim 1 - 4; exact on forests at a fixed point, the Bethe estimate on loops):
+# (value, [factor terms, variable terms, terms with an undefined input, terms whose belief is not positive definite]); NaN when either of the last two > 0
+function log_evidence(p)
+    value = Ref{Float64}(0.0)
+    out = zeros(Int64, 4)
+    check(p.handle, ccall((:cx_log_evidence, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}), p.handle, value, out))
+    return value[], out
+end
+
 function tree_heavy_path_stats(p)      # light depths, paths, variables on no path, launches per sweep (zeros: the level schedule is in use)
     out = zeros(Int64, 4)
     check(p.handle, ccall((:cx_tree_heavy_path_stats, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), p.handle, out))
