@@ -16,41 +16,17 @@
 //          (k_ev_kary)  one thread per factor of 3 .. 7 variables, its joint precision (up to 28 x 28) packed in LDS
 //   k_ev_final          the per-block partial sums (compensated, f64) in a fixed order: two calls on one state are bit-identical
 // The counters travel with the partial sums (per block, then in index order): no atomics at all.
-#include "cx_host.h"
-#include "cx_mv_core.h"
+#include "cx_evidence_core.h"
 
 namespace cx {
 namespace ev {
 
-constexpr int kB = 256;        // threads per block of the variable, pairwise and final passes
 constexpr int kKB = 16;        // threads per block of the k-ary pass: each thread's joint precision lives in LDS
 constexpr int kFB = 1024;      // threads of the one block of the final sum (C4: 23 k block partials)
-constexpr double kLog2Pi = 1.83787706640934548356;
 
 // counters read back: 0 variable terms, 1 terms with an undefined input, 2 terms whose belief is not positive definite, 3 stand-in
 // variables met (a halo handle: refused); the factor terms are known on the host
 constexpr int kNCnt = 4;
-
-template <int D>
-struct Lay {
-    static constexpr int NT = D * (D + 1) / 2;
-    static constexpr int K = D == 1 ? 2 : ((D + NT + 1) + 1) / 2 * 2;      // doubles per variable of the scratch: a[D] | Λ[NT] | flag
-};
-// a = μ_i when Λ_i is positive definite (flag 1; D = 1: Λ > 0), η_i otherwise (flag 0, centre 0)
-
-// ---- compensated sums -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void neu(double &s, double &c, double x) {
-    const double t = s + x;
-    c += fabs(s) >= fabs(x) ? (s - t) + x : (x - t) + s;
-    s = t;
-}
-
-// per block: the compensated sum and the counters of its terms (variable terms, undefined input, not positive definite, stand-ins);
-// k_ev_final adds the blocks up in index order: no floating-point atomic, no atomic at all
-struct Part {
-    double s, c;
-    unsigned n[4];
-};
 
 // fixed-order tree over the block's threads; thread 0 writes the block's Part
 template <int NB>
@@ -77,68 +53,6 @@ __device__ __forceinline__ void block_part(double s, double c, unsigned n0, unsi
 #pragma unroll
         for (int k = 0; k < 4; k++) p.n[k] = ns[k][0];
         out[blockIdx.x] = p;
-    }
-}
-
-// ---- messages -------------------------------------------------------------------------------------------------------------------
-template <int D>
-__device__ __forceinline__ void ld_msg(const double *__restrict__ buf, int slot, double (&eta)[D], double (&lam)[Lay<D>::NT]) {
-    if constexpr (D == 1) {
-        const double2 m = reinterpret_cast<const double2 *>(buf)[slot];
-        eta[0] = m.x; lam[0] = m.y;
-    } else {
-        const Msg<D> m = slot_load<D, false>(buf, slot);
-#pragma unroll
-        for (int k = 0; k < D; k++) eta[k] = m.eta[k];
-#pragma unroll
-        for (int k = 0; k < Lay<D>::NT; k++) lam[k] = m.lam[k];
-    }
-}
-
-template <int D>
-__device__ __forceinline__ double lam_at(const double (&lam)[Lay<D>::NT], int i, int j) { return i <= j ? lam[tri<D>(i, j)] : lam[tri<D>(j, i)]; }
-
-// in-place lower Cholesky of the full symmetric J (lower triangle read), then h <- L⁻¹ h: log det J and h'J⁻¹h.  false: not positive definite
-template <int N>
-__device__ __forceinline__ bool chol_quad(double (&J)[N][N], double (&h)[N], double &logdet, double &quad) {
-    logdet = 0.0; quad = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double d = J[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= J[j][k] * J[j][k];
-        if (!(d > 0.0)) return false;
-        logdet += log(d);
-        const double l = sqrt(d), il = 1.0 / l;
-        J[j][j] = l;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double s = J[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= J[i][k] * J[j][k];
-            J[i][j] = s * il;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        double s = h[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= J[i][k] * h[k];
-        h[i] = s / J[i][i];
-        quad += h[i] * h[i];
-    }
-    return true;
-}
-
-// Λ μ = η by the factor chol_quad left in L (h = L⁻¹ η on entry): back substitution
-template <int N>
-__device__ __forceinline__ void back_solve(const double (&L)[N][N], const double (&y)[N], double (&x)[N]) {
-#pragma unroll
-    for (int i = N - 1; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; k++) s -= L[k][i] * x[k];
-        x[i] = s / L[i][i];
     }
 }
 
@@ -240,45 +154,6 @@ __global__ __launch_bounds__(kB) void k_ev_var(int64_t nv, const int32_t *__rest
         }
     }
     block_part<kB>(s, c, vterm, undef_t, npd_t, ghost, partial);
-}
-
-// ---- pass 2 helpers -------------------------------------------------------------------------------------------------------------
-// one non-observed edge of a factor: the centred leave-one-out message m~_{i→a} (η~, Λ~) and the centre μ_i
-template <int D>
-__device__ __forceinline__ bool free_edge(const double *__restrict__ f2v, const double *__restrict__ W, int slot, int var, double (&mu)[D],
-                                          double (&et)[D], double (&lm)[Lay<D>::NT]) {
-    constexpr int NT = Lay<D>::NT, K = Lay<D>::K;
-    double e[D], l[NT];
-    ld_msg<D>(f2v, slot, e, l);
-    const double *w = W + (int64_t)var * K;
-    double a[D], L[NT];
-#pragma unroll
-    for (int i = 0; i < D; i++) a[i] = w[i];
-#pragma unroll
-    for (int i = 0; i < NT; i++) L[i] = w[D + i];
-    const bool pd = D == 1 ? L[0] > 0.0 : w[D + NT] != 0.0;
-    bool undef = false;
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-        mu[i] = pd ? a[i] : 0.0;
-        undef = undef || __builtin_isnan(a[i]) || __builtin_isnan(e[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < NT; i++) { lm[i] = L[i] - l[i]; undef = undef || __builtin_isnan(L[i]) || __builtin_isnan(l[i]); }
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-        double t = e[i];
-#pragma unroll
-        for (int j = 0; j < D; j++) t -= lam_at<D>(l, i, j) * mu[j];
-        et[i] = (pd ? 0.0 : a[i]) - t;
-    }
-    return !undef;
-}
-
-template <int D>
-__device__ __forceinline__ void datum(const double *__restrict__ v2f, int slot, double (&y)[D]) {
-    double l[Lay<D>::NT];
-    ld_msg<D>(v2f, slot, y, l);
 }
 
 // ---- pass 2: factors of two variables -------------------------------------------------------------------------------------------
@@ -585,28 +460,11 @@ __global__ __launch_bounds__(kFB) void k_ev_final(int64_t n, const Part *__restr
 }
 
 // ---- host: the work lists -------------------------------------------------------------------------------------------------------
-struct Cache {
-    bool built = false;
-    uint64_t epoch = ~0ull;
-    int64_t zero_noise_fac = -1;          // a factor with q = 0 (dim 1): refused
-    int64_t unsupported_fac = -1;         // a factor of a kind without a sum-product rule
-    int64_t n_pair = 0, n_kary = 0, nb = 0;
-    int32_t *d_vrec = nullptr;
-    uint8_t *d_tail = nullptr;
-    int4 *d_pair = nullptr;
-    int32_t *d_pair_ps = nullptr, *d_krec = nullptr, *d_kps = nullptr;
-    double *d_pq = nullptr, *d_pa = nullptr, *d_pb = nullptr, *d_kc = nullptr, *d_ptab = nullptr;
-    int64_t ptab_cap = 0;
-    std::vector<int32_t> pair_ps;         // dim > 1: parameter set per pair (what the table must hold)
-    double *d_W = nullptr;
-    Part *d_partial = nullptr;
-    double *d_out = nullptr, *h_out = nullptr;      // value | counters; h_out: pinned
-};
 
 template <class T>
 void free_ptr(T *&p) { if (p) (void)hipFree((void *)p); p = nullptr; }
 
-int32_t build(cx_handle *h, Cache &C) {
+int32_t build(cx_handle *h, Cache &C, const std::string &who) {
     using namespace cxh;
     const int d = h->cfg.dim;
     const int64_t nv = h->nv, ne = h->ne, nf = h->nf;
@@ -636,6 +494,7 @@ int32_t build(cx_handle *h, Cache &C) {
     // factors
     std::vector<int4> pair;
     std::vector<int32_t> pair_ps;
+    std::vector<int64_t> pair_fac;
     std::vector<double> pq, pa, pb;
     bool any_ab = false;
     std::vector<int32_t> krec;
@@ -667,10 +526,12 @@ int32_t build(cx_handle *h, Cache &C) {
             if (!(p[0] > 0.0) && C.zero_noise_fac < 0) C.zero_noise_fac = h->fac_ids[f];
         }
         pair.push_back(make_int4(so, si, slot_var[so], slot_var[si]));
+        pair_fac.push_back(f);
     }
-    if (row != h->n_kary) return fail(h, CX_ERR_STATE, "cx_log_evidence: the k-ary table does not match the factors");
+    if (row != h->n_kary) return fail(h, CX_ERR_STATE, who + ": the k-ary table does not match the factors");
     C.n_pair = (int64_t)pair.size(); C.n_kary = row;
     C.pair_ps = pair_ps;
+    C.pair_fac = pair_fac;
     int32_t rc;
     if ((rc = dev_upload(h, &C.d_vrec, vrec)) != CX_OK) return rc;
     if ((rc = dev_upload(h, &C.d_tail, tail)) != CX_OK) return rc;
@@ -697,7 +558,7 @@ int32_t build(cx_handle *h, Cache &C) {
 }
 
 // the parameters that may change after cx_graph_create: k-ary coefficients (dim 1), (A, Q) sets and the k-ary edges' sets (dim > 1)
-int32_t refresh_params(cx_handle *h, Cache &C) {
+int32_t refresh_params(cx_handle *h, Cache &C, const std::string &who) {
     using namespace cxh;
     if (C.epoch == h->param_epoch) return CX_OK;
     const int d = h->cfg.dim;
@@ -726,7 +587,7 @@ int32_t refresh_params(cx_handle *h, Cache &C) {
         for (int64_t s = 0; s < nsets; s++) {
             if (!used[s]) continue;
             if (s >= (int64_t)h->psets.size() || h->psets[s].empty())
-                return fail(h, CX_ERR_STATE, "cx_log_evidence: parameter set " + std::to_string(s) + " was never set (cx_set_factor_matrices)");
+                return fail(h, CX_ERR_STATE, who + ": parameter set " + std::to_string(s) + " was never set (cx_set_factor_matrices)");
             const double *A = h->psets[s].data(), *Q = A + d * d;
             // Q = L L': log det 2πQ and Q⁻¹ (Q is symmetric positive definite: cx_set_factor_matrices checks it)
             double L[4][4] = {}, Li[4][4] = {}, ld = d * kLog2Pi;
@@ -771,12 +632,27 @@ int32_t refresh_params(cx_handle *h, Cache &C) {
 }
 
 template <int D>
+void launch_var(cx_handle *h, Cache &C, const double *f2v) {
+    const int64_t nb_v = (h->nv + kB - 1) / kB;
+    if (nb_v)
+        hipLaunchKernelGGL(k_ev_var<D>, dim3((unsigned)nb_v), dim3(kB), 0, h->stream, h->nv, h->d_vbase, h->d_var_deg, h->d_vinfo, C.d_vrec,
+                           C.d_tail, h->big_start, f2v, C.d_W, C.d_partial);
+}
+
+void var_pass(cx_handle *h, Cache &C) {
+    switch (h->cfg.dim) {
+    case 1: launch_var<1>(h, C, f2v_of(h)); break;
+    case 2: launch_var<2>(h, C, f2v_of(h)); break;
+    case 3: launch_var<3>(h, C, f2v_of(h)); break;
+    default: launch_var<4>(h, C, f2v_of(h)); break;
+    }
+}
+
+template <int D>
 void launch(cx_handle *h, Cache &C, const double *f2v, const double *v2f) {
     const int64_t nb_v = (h->nv + kB - 1) / kB, nb_p = (C.n_pair + kB - 1) / kB, nb_k = (C.n_kary + kKB - 1) / kKB;
     Part *part = C.d_partial;
-    if (nb_v)
-        hipLaunchKernelGGL(k_ev_var<D>, dim3((unsigned)nb_v), dim3(kB), 0, h->stream, h->nv, h->d_vbase, h->d_var_deg, h->d_vinfo, C.d_vrec,
-                           C.d_tail, h->big_start, f2v, C.d_W, part);
+    launch_var<D>(h, C, f2v);
     if (nb_p)
         hipLaunchKernelGGL(k_ev_pair<D>, dim3((unsigned)nb_p), dim3(kB), 0, h->stream, C.n_pair, C.d_pair, C.d_pair_ps, C.d_pq, C.d_pa, C.d_pb,
                            C.d_ptab, h->d_vinfo, f2v, v2f, C.d_W, part + nb_v);
@@ -800,6 +676,34 @@ void evidence_free(cx_handle *h) {
     h->evidence = nullptr;
 }
 
+int32_t ev::prepare(cx_handle *h, const std::string &who, ev::Cache *&Cp) {
+    using namespace cxh;
+    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED,
+               who + ": the Gaussian family only (no variational free energy, no Beta-Bernoulli evidence)");
+    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
+    CX_REQUIRE(h, h->cfg.dim >= 1 && h->cfg.dim <= 4 && !h->user_dim, CX_ERR_UNSUPPORTED, who + ": dim 1, 2, 3 and 4 (the matrix-core dims are not implemented)");
+    CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
+               who + ": not for a partitioned handle (halo lists or stand-in variables: its terms would need owners)");
+    CX_HIP(h, hipSetDevice(h->cfg.device));
+    if (h->stream) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
+        CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
+    }
+    if (!h->evidence) h->evidence = new ev::Cache();
+    ev::Cache &C = *static_cast<ev::Cache *>(h->evidence);
+    int32_t rc;
+    if (!C.built && (rc = ev::build(h, C, who)) != CX_OK) { evidence_free(h); return rc; }
+    if (C.unsupported_fac >= 0)
+        return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(C.unsupported_fac) + " has no sum-product rule (Gaussian factors and opaque messages only)");
+    if (C.zero_noise_fac >= 0)
+        return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(C.zero_noise_fac) + " has zero noise (q = 0): its density is degenerate");
+    if ((rc = ev::refresh_params(h, C, who)) != CX_OK) return rc;
+    if (h->cfg.dim > 1 && (rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (chain scan, dim 2..4: the messages go to their slots on demand)
+    Cp = &C;
+    return CX_OK;
+}
+
 }  // namespace cx
 
 using namespace cxh;
@@ -809,28 +713,12 @@ extern "C" int32_t cx_log_evidence(cx_handle *h, double *value, int64_t *counts4
                "cx_log_evidence: the Gaussian family only (no variational free energy, no Beta-Bernoulli evidence)");
     CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_log_evidence: no graph");
     CX_REQUIRE(h, value && counts4, CX_ERR_INVALID_ARGUMENT, "cx_log_evidence: null argument");
-    CX_REQUIRE(h, h->cfg.dim >= 1 && h->cfg.dim <= 4 && !h->user_dim, CX_ERR_UNSUPPORTED, "cx_log_evidence: dim 1, 2, 3 and 4 (the matrix-core dims are not implemented)");
-    CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
-               "cx_log_evidence: not for a partitioned handle (halo lists or stand-in variables: its terms would need owners)");
     try {
-        CX_HIP(h, hipSetDevice(h->cfg.device));
-        if (h->stream) {
-            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-            CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
-            CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, "cx_log_evidence: the handle's stream is being captured (the call is synchronous)");
-        }
-        if (!h->evidence) h->evidence = new cx::ev::Cache();
-        cx::ev::Cache &C = *static_cast<cx::ev::Cache *>(h->evidence);
+        cx::ev::Cache *Cp = nullptr;
         int32_t rc;
-        if (!C.built && (rc = cx::ev::build(h, C)) != CX_OK) { cx::evidence_free(h); return rc; }
-        if (C.unsupported_fac >= 0)
-            return fail(h, CX_ERR_UNSUPPORTED, "cx_log_evidence: factor " + std::to_string(C.unsupported_fac) + " has no sum-product rule (Gaussian factors and opaque messages only)");
-        if (C.zero_noise_fac >= 0)
-            return fail(h, CX_ERR_UNSUPPORTED, "cx_log_evidence: factor " + std::to_string(C.zero_noise_fac) + " has zero noise (q = 0): its density is degenerate");
-        if ((rc = cx::ev::refresh_params(h, C)) != CX_OK) return rc;
-        if (h->cfg.dim > 1 && (rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (chain scan, dim 2..4: the messages go to their slots on demand)
-        const double *f2v = h->cfg.dim == 1 ? (const double *)h->d_f2v : h->d_mv_f2v;
-        const double *v2f = h->cfg.dim == 1 ? (const double *)h->d_v2f : h->d_mv_v2f;
+        if ((rc = cx::ev::prepare(h, "cx_log_evidence", Cp)) != CX_OK) return rc;
+        cx::ev::Cache &C = *Cp;
+        const double *f2v = cx::ev::f2v_of(h), *v2f = cx::ev::v2f_of(h);
         switch (h->cfg.dim) {
         case 1: cx::ev::launch<1>(h, C, f2v, v2f); break;
         case 2: cx::ev::launch<2>(h, C, f2v, v2f); break;

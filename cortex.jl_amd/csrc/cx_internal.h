@@ -259,6 +259,8 @@ struct cx_handle {
     // with every change of rule parameters after cx_graph_create (matrices, coefficients, edge sets), which the lists' parameter part follows
     void *evidence = nullptr;
     uint64_t param_epoch = 0;
+    // cx_factor_beliefs / cx_factor_statistics (cx_learn.hip): the grouping's work lists and scratch (opaque)
+    void *learn = nullptr;
 
     // staging for set/get/batch
     void *d_stage = nullptr;
@@ -399,5 +401,6 @@ bool comm_exchange(cx_handle *h, std::string &err, bool packed_on_comm_stream);
 bool comm_exchange_on(cx_handle *h, hipStream_t stream, std::string &err);
 void ipc_destroy(cx_handle *h);  // cx_api_ipc.hip
 void evidence_free(cx_handle *h);  // cx_evidence.hip
+void learn_free(cx_handle *h);  // cx_learn.hip
 
 }  // namespace cx

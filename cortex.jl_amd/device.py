@@ -83,6 +83,7 @@ class DeviceGraph:
         if A.shape != (self.dim, self.dim) or Q.shape != (self.dim, self.dim):
             raise ValueError(f"A and Q must be {self.dim}x{self.dim}")
         self._check(self.lib.cx_set_factor_matrices(self.h, int(parameter_set), _p(A, C.c_double), _p(Q, C.c_double)))
+        self._n_sets = max(getattr(self, "_n_sets", 0), int(parameter_set) + 1)      # (the default n_groups of factor_statistics)
 
     def set_factor_edge_sets(self, variable_ids, factor_ids, parameter_sets):
         """cx_set_factor_edge_sets: dim 2..4, the A_i of ROLE_IN edges of CX_FACTOR_GAUSS_LINEAR_N factors by parameter set"""
@@ -280,6 +281,48 @@ class DeviceGraph:
         out = (C.c_int64 * 4)()
         self._check(self.lib.cx_log_evidence(self.h, C.byref(val), out))
         return float(val.value), dict(zip(("factor_terms", "variable_terms", "undefined", "not_positive_definite"), [int(x) for x in out]))
+
+    def factor_beliefs(self, factor_ids):
+        """cx_factor_beliefs: the joint posterior of two-variable Gaussian factors from the stored messages, (means [n, 2d],
+        covariances [n, 2d, 2d]) in the order (out, in) — ADDITIVE: the lower variable id first.  Observed entries are the datum with
+        zero rows and columns; a factor with an undefined input (or a belief that is not positive definite) reads as NaN."""
+        f = _i64(np.atleast_1d(factor_ids))
+        n2 = 2 * self.dim
+        out = np.zeros((len(f), n2 + n2 * n2), dtype=np.float64)
+        self._check(self.lib.cx_factor_beliefs(self.h, len(f), _p(f, C.c_int64), _p(out, C.c_double)))
+        return out[:, :n2].copy(), out[:, n2:].reshape(len(f), n2, n2).copy()
+
+    def factor_statistics(self, factor_ids=None, groups=None, n_groups=None):
+        """cx_factor_statistics: EM statistics in residual coordinates r = x_out - A x_in - b, summed per group.  factor_ids=None
+        (dim 2..4): one group per parameter set (n_groups default: the sets given to set_factor_matrices).  Returns ({"n" [G],
+        "sum_r" [G, d], "sum_x" [G, d], "S_rr", "S_rx", "S_xx" [G, d, d]}, counts) with counts "factors", "groups", "undefined",
+        "not_positive_definite"; a group's arrays (n excepted) are NaN when one of its factors is undefined or not positive definite."""
+        d = self.dim
+        if factor_ids is None:
+            if groups is not None:
+                raise ValueError("groups need factor_ids")
+            if n_groups is None:
+                n_groups = getattr(self, "_n_sets", 0)
+            f = g = None
+            n = 0
+        else:
+            f, g = _i64(np.atleast_1d(factor_ids)), _i64(np.atleast_1d(groups))
+            if len(f) != len(g):
+                raise ValueError("factor_ids and groups differ in length")
+            n = len(f)
+            if n_groups is None:
+                n_groups = int(g.max()) + 1 if n and g.max() >= 0 else 1
+        ns = 1 + 2 * d + 3 * d * d
+        out = np.zeros((max(int(n_groups), 0), ns), dtype=np.float64)
+        cnt = (C.c_int64 * 4)()
+        self._check(self.lib.cx_factor_statistics(self.h, n, None if f is None else _p(f, C.c_int64), None if g is None else _p(g, C.c_int64),
+                                                  int(n_groups), _p(out, C.c_double) if out.size else None, cnt))
+        G = len(out)
+        o = 1 + 2 * d
+        stats = {"n": out[:, 0].copy(), "sum_r": out[:, 1:1 + d].copy(), "sum_x": out[:, 1 + d:o].copy(),
+                 "S_rr": out[:, o:o + d * d].reshape(G, d, d).copy(), "S_rx": out[:, o + d * d:o + 2 * d * d].reshape(G, d, d).copy(),
+                 "S_xx": out[:, o + 2 * d * d:].reshape(G, d, d).copy()}
+        return stats, dict(zip(("factors", "groups", "undefined", "not_positive_definite"), [int(x) for x in cnt]))
 
     # -- halo -----------------------------------------------------------------------------------
     def halo_configure(self, send_var, send_fac, recv_var, recv_fac):

@@ -1,0 +1,111 @@
+"""Parameter learning for linear-Gaussian models on the device: the M-step of EM (Shumway–Stoffer) from the residual statistics of
+DeviceGraph.factor_statistics (cx_factor_statistics), and an EM loop for dim 2..4 parameter sets.  numpy only.  DESIGN.md §4f.
+
+The statistics are in residual coordinates r = x_out - A x_in - b of the CURRENT parameters, so the update is a correction:
+
+    ΔA = S_rx S_xx⁻¹,   A' = A + ΔA,   Q' = (S_rr - ΔA S_rx') / n          (b learned too: regress r on [x_in, 1])
+
+Nothing of the size of the raw second moments is cancelled: a Q-only update Q' = S_rr / n is a plain average of noise-sized terms.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+
+from . import _lib as L
+
+
+def _sym_pd(Q, what="Q"):
+    Q = 0.5 * (Q + Q.T)
+    try:
+        np.linalg.cholesky(Q)
+    except np.linalg.LinAlgError:
+        raise ValueError(f"m_step: the new {what} is not positive definite") from None
+    return Q
+
+
+def m_step(stats, A, b=None, learn=("A", "Q")):
+    """New parameters of one group from its residual statistics.
+
+    stats: one group's entries, {"n", "sum_r" [d], "sum_x" [d], "S_rr", "S_rx", "S_xx" [d, d]} (index the arrays of
+    DeviceGraph.factor_statistics with the group, or pass them as they are when there is one group).  A, b: the parameters the
+    statistics were taken under (b None: 0).  learn: any of "A", "b", "Q".  Returns {"A", "b", "Q"}: A and b as given where not
+    learned; Q None where not learned (the caller keeps its own), else symmetrised and checked positive definite."""
+    d = np.asarray(stats["S_rr"]).reshape(-1).size
+    d = int(round(np.sqrt(d)))
+    n = float(np.asarray(stats["n"]).reshape(-1)[0])
+    if not n > 0:
+        raise ValueError("m_step: the group has no factors")
+    sr = np.asarray(stats["sum_r"], float).reshape(d)
+    sx = np.asarray(stats["sum_x"], float).reshape(d)
+    Srr = np.asarray(stats["S_rr"], float).reshape(d, d)
+    Srx = np.asarray(stats["S_rx"], float).reshape(d, d)
+    Sxx = np.asarray(stats["S_xx"], float).reshape(d, d)
+    if not (np.isfinite(Srr).all() and np.isfinite(Srx).all() and np.isfinite(Sxx).all()):
+        raise ValueError("m_step: the statistics are NaN (an undefined input or a belief that is not positive definite)")
+    A = np.asarray(A, float).reshape(d, d)
+    b = np.zeros(d) if b is None else np.asarray(b, float).reshape(d)
+    learn = set(learn)
+    if not learn <= {"A", "b", "Q"}:
+        raise ValueError(f"m_step: unknown entries in learn: {sorted(learn - {'A', 'b', 'Q'})}")
+    if "A" in learn and "b" in learn:
+        # r ≈ [ΔA Δb] z, z = [x_in; 1]
+        Srz = np.hstack([Srx, sr[:, None]])
+        Szz = np.block([[Sxx, sx[:, None]], [sx[None, :], np.array([[n]])]])
+        D = np.linalg.solve(Szz, Srz.T).T
+        dA, db = D[:, :d], D[:, d]
+        corr = D @ Srz.T
+    elif "A" in learn:
+        dA, db = np.linalg.solve(Sxx, Srx.T).T, np.zeros(d)
+        corr = dA @ Srx.T
+    elif "b" in learn:
+        dA, db = np.zeros((d, d)), sr / n
+        corr = np.outer(db, sr)
+    else:
+        dA, db, corr = np.zeros((d, d)), np.zeros(d), np.zeros((d, d))
+    Q = _sym_pd((Srr - corr) / n) if "Q" in learn else None
+    return {"A": A + dA, "b": b + db, "Q": Q}
+
+
+def group(stats, g):
+    """the entries of group g of DeviceGraph.factor_statistics' first result"""
+    return {k: np.asarray(v)[g] for k, v in stats.items()}
+
+
+def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q")):
+    """EM on the parameter sets of a dim 2..4 DeviceGraph: per iteration sweep(sweeps_per_iter) → log_evidence → factor_statistics
+    (one group per parameter set) → m_step → set_factor_matrices.
+
+    sets: {set: (A, Q)}, the starting parameters (set on the handle here).  learn: a tuple for every set, or {set: tuple}.
+    Returns (trace, params): trace[i] = log p(data) under the parameters of iteration i (n_iter + 1 values, the last under the final
+    parameters) and params = {set: (A, Q)}.
+
+    The log-evidence trace is non-decreasing only where the E-step is exact: a chain-scan or tree sweep, or one reference-order
+    call, on a forest.  Fused / flooding sweeps give Bethe beliefs (exact on forests only once converged) and loops give Bethe
+    statistics: the iteration is then a generalised EM without that guarantee."""
+    if dev.dim < 2:
+        raise ValueError("em: dim 2..4 (dim 1 has per-factor parameters: call factor_statistics with explicit groups and m_step)")
+    if dev.schedule not in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE):
+        warnings.warn("em: the log-evidence is guaranteed non-decreasing only under an exact E-step (chain scan, tree, reference order on "
+                      "a forest)", RuntimeWarning, stacklevel=2)
+    params = {int(s): (np.array(A, float), np.array(Q, float)) for s, (A, Q) in sets.items()}
+    n_groups = max(params) + 1
+    for s, (A, Q) in params.items():
+        dev.set_factor_matrices(s, A, Q)
+    trace = []
+    for it in range(n_iter + 1):
+        dev.sweep(sweeps_per_iter)
+        value, cnt = dev.log_evidence()
+        trace.append(value)
+        if it == n_iter:
+            break
+        stats, _ = dev.factor_statistics(n_groups=n_groups)
+        for s, (A, Q) in params.items():
+            ls = learn.get(s, ("A", "Q")) if isinstance(learn, dict) else learn
+            if not ls:
+                continue
+            new = m_step(group(stats, s), A, learn=ls)
+            params[s] = (new["A"], Q if new["Q"] is None else new["Q"])
+            dev.set_factor_matrices(s, *params[s])
+    return trace, params

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define CX_ABI_VERSION 5   /* 5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
+#define CX_ABI_VERSION 6   /* 6: cx_factor_beliefs, cx_factor_statistics (additive).  5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
 
 /* status codes */
 #define CX_OK 0
@@ -550,6 +550,44 @@ int32_t cx_message_health(cx_handle *h, int64_t *out4);
  * counts4 = {factor terms, variable terms (d_i != 1), terms with an undefined input, terms whose belief is not positive definite};
  * *value is NaN iff counts4[2] + counts4[3] > 0.  Synchronous; moves no message, marginal, readiness bit or counter. */
 int32_t cx_log_evidence(cx_handle *h, double *value, int64_t *counts4);
+
+/* ---- factor beliefs and EM statistics (ABI 6; no counterpart in the reference) ----
+ * Both read what cx_log_evidence reads (the STORED factor→variable messages and the data; never the marginals), work after any
+ * schedule, are exact on forests at a fixed point and give the Bethe factor beliefs elsewhere.  Covered: the
+ * two-variable factors CX_FACTOR_GAUSS_ADDITIVE and CX_FACTOR_GAUSS_LINEAR of dim 1, CX_FACTOR_GAUSS_LINEAR of dim 2 - 4.  Refused
+ * exactly as cx_log_evidence refuses (other families, dim >= 5, partitioned handles, zero-noise factors, a captured stream).
+ * Out of scope: dims 5 - 64, factors of more than two variables (CX_FACTOR_GAUSS_LINEAR_N), variational families.
+ * Synchronous; they move no message, marginal, readiness bit or counter.
+ *
+ * cx_factor_beliefs: the joint Gaussian posterior of each named factor's two variables.  out: n rows of 2d + (2d)^2 doubles, the
+ * 2d means then the 2d x 2d covariance, row-major, in the order (out, in): CX_ROLE_OUT then CX_ROLE_IN; CX_FACTOR_GAUSS_ADDITIVE
+ * (no roles) takes the edge of the lower variable id as `out`.  An observed variable's entries are its datum with zero rows and
+ * columns in the covariance.  A factor with an undefined input, or whose belief is not positive definite, reads as NaN.
+ * An unknown id is CX_ERR_NOT_FOUND; any other factor kind is CX_ERR_UNSUPPORTED (naming it).  At dim 1 this is the stored-message
+ * counterpart of a scheduled CX_ITEM_JOINT_MARGINAL (cx_get_joint_marginals).
+ */
+int32_t cx_factor_beliefs(cx_handle *h, int64_t n, const int64_t *factor_ids, double *out);
+
+/* cx_factor_statistics: the expected sufficient statistics of EM (Shumway–Stoffer), summed per group of factors that share A, in
+ * RESIDUAL coordinates r = x_out - A x_in - b under the factor's current parameters (dim 1: (a, b) of CX_FACTOR_GAUSS_LINEAR, (1, 0)
+ * of CX_FACTOR_GAUSS_ADDITIVE; dim 2 - 4: the parameter set's A, b = 0).  out: n_groups rows of 1 + 2d + 3d^2 doubles,
+ *     n_g | Σ E[r] (d) | Σ E[x_in] (d) | Σ E[r r'] (d x d) | Σ E[r x_in'] (d x d) | Σ E[x_in x_in'] (d x d)     (row-major)
+ * from which the M-step is  ΔA = S_rx S_xx^-1,  A' = A + ΔA,  Q' = (S_rr - ΔA S_rx') / n_g  (a Q-only update: Q' = S_rr / n_g).
+ * Sums are compensated (f64) and taken in a fixed order: two calls on one state are bit-identical.
+ * Grouping:
+ *   factor_ids == NULL (and groups == NULL; n is ignored), dim 2 - 4: the group of a factor is its parameter set; every
+ *     CX_FACTOR_GAUSS_LINEAR factor counts; n_groups must exceed the largest set in use (rows of unused sets: zeros, n_g = 0).
+ *     A set also read by a CX_FACTOR_GAUSS_LINEAR_N factor (its own or an edge set of cx_set_factor_edge_sets) is
+ *     CX_ERR_UNSUPPORTED: its statistics would be incomplete.  At dim 1 a NULL factor_ids is CX_ERR_INVALID_ARGUMENT.
+ *   factor_ids, groups (length n): factor factor_ids[i] goes to row groups[i] (-1: skipped).  A group's factors must share their A
+ *     (dim 2 - 4: one parameter set; dim 1: the same kind, a and b; q may differ), else CX_ERR_INVALID_ARGUMENT naming two of them;
+ *     a factor listed twice is CX_ERR_INVALID_ARGUMENT; an unknown id CX_ERR_NOT_FOUND; a factor of another kind CX_ERR_UNSUPPORTED.
+ * The work list of the last grouping is cached: a call with the same arrays costs an O(n) comparison on the host; a new grouping is
+ * checked and its lists built and uploaded (O(n + n_groups) on the host).
+ * counts4 = {factors counted, non-empty groups, factors with an undefined input, factors whose belief is not positive definite};
+ * a group's row is NaN (n_g excepted) when one of its factors is counted in either of the last two. */
+int32_t cx_factor_statistics(cx_handle *h, int64_t n, const int64_t *factor_ids, const int64_t *groups, int64_t n_groups, double *out,
+                             int64_t *counts4);
 
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)

@@ -130,6 +130,25 @@ class Handle {
         check(cx_log_evidence(h_, &v, o.data()));
         return {v, o};
     }
+    // the joint posterior of two-variable Gaussian factors from the stored messages: per factor 2d means then the 2d x 2d covariance
+    // (row-major), (out, in) (NaN rows: an undefined input or a belief that is not positive definite)
+    std::vector<double> factor_beliefs(const std::vector<int64_t> &factor_ids) {
+        std::vector<double> out(factor_ids.size() * (size_t)(2 * dim_ + 4 * dim_ * dim_));
+        check(cx_factor_beliefs(h_, (int64_t)factor_ids.size(), factor_ids.data(), out.data()));
+        return out;
+    }
+    // EM statistics in residual coordinates, summed per group: n_groups rows of 1 + 2d + 3d^2 doubles (n | Σ E[r] | Σ E[x_in] | S_rr | S_rx |
+    // S_xx); empty factor_ids and groups: one group per parameter set (dim 2 - 4).  counts: factors, non-empty groups, undefined, not pd
+    std::pair<std::vector<double>, std::array<int64_t, 4>> factor_statistics(const std::vector<int64_t> &factor_ids, const std::vector<int64_t> &groups,
+                                                                             int64_t n_groups) {
+        need(groups.size(), factor_ids.size(), "factor_statistics groups");
+        std::vector<double> out((size_t)n_groups * (size_t)(1 + 2 * dim_ + 3 * dim_ * dim_));
+        std::array<int64_t, 4> o{};
+        const bool by_set = factor_ids.empty();
+        check(cx_factor_statistics(h_, (int64_t)factor_ids.size(), by_set ? nullptr : factor_ids.data(), by_set ? nullptr : groups.data(), n_groups,
+                                   out.data(), o.data()));
+        return {out, o};
+    }
     std::pair<int32_t, double> sweep_until(double tol, int32_t max_sweeps, int32_t check_every = 10) {
         int32_t n = 0; double r = 0;
         check(cx_sweep_until(h_, tol, max_sweeps, check_every, &n, &r));

@@ -289,6 +289,32 @@ function log_evidence(p)
     return value[], out
 end
 
+# the joint posterior of two-variable Gaussian factors from the stored messages (ABI 6; dim 1 - 4): a (2d + 4d^2) x n matrix, column f =
+# the 2d means then the 2d x 2d covariance (row-major, (out, in)); NaN columns: an undefined input or a belief that is not positive definite
+function factor_beliefs(p, factor_ids::Vector{Int64})
+    d = p.dim
+    out = zeros(Float64, 2d + 4d * d, length(factor_ids))
+    check(p.handle, ccall((:cx_factor_beliefs, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}), p.handle, length(factor_ids), factor_ids, out))
+    return out
+end
+
+# EM statistics in residual coordinates r = x_out - A x_in - b, summed per group (ABI 6): a (1 + 2d + 3d^2) x n_groups matrix, column g =
+# n | Σ E[r] | Σ E[x_in] | S_rr | S_rx | S_xx (row-major blocks), and [factors, non-empty groups, undefined, not positive definite].
+# factor_ids === nothing: one group per parameter set (dim 2 - 4)
+function factor_statistics(p, factor_ids::Union{Nothing, Vector{Int64}}, groups::Union{Nothing, Vector{Int64}}, n_groups::Integer)
+    d = p.dim
+    out = zeros(Float64, 1 + 2d + 3d * d, n_groups)
+    counts = zeros(Int64, 4)
+    n = factor_ids === nothing ? 0 : length(factor_ids)
+    fp = factor_ids === nothing ? Ptr{Int64}(C_NULL) : pointer(factor_ids)
+    gp = groups === nothing ? Ptr{Int64}(C_NULL) : pointer(groups)
+    GC.@preserve factor_ids groups begin
+        check(p.handle, ccall((:cx_factor_statistics, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, n, fp, gp, n_groups, out, counts))
+    end
+    return out, counts
+end
+
 function tree_heavy_path_stats(p)      # light depths, paths, variables on no path, launches per sweep (zeros: the level schedule is in use)
     out = zeros(Int64, 4)
     check(p.handle, ccall((:cx_tree_heavy_path_stats, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), p.handle, out))
