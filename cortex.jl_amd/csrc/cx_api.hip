@@ -39,6 +39,7 @@ void dev_free_all(cx_handle *h) {
     cx::kary_free(h);
     cx::evidence_free(h);
     cx::learn_free(h);
+    cx::sample_free(h);
     if (h->d_prod) (void)hipFree(h->d_prod);
     if (h->d_joint) (void)hipFree(h->d_joint);
     h->d_prod = nullptr; h->d_joint = nullptr; h->prod_cap = h->joint_cap = 0; h->prod_index.clear(); h->joint_index.clear();

@@ -273,18 +273,6 @@ __global__ __launch_bounds__(kB) void k_ev_pair(int64_t n, const int4 *__restric
 // dim 1: kc[f] = C_e[8] (+1 OUT, -a_i IN) | q | b.  dim > 1: kps[f] = parameter set per entry (IN: its A; OUT: Q); ptab as k_ev_pair's.
 // The joint precision over the free entries (packed lower triangle, up to 28 x 28) and its right-hand side live in LDS, thread-interleaved.
 template <int D>
-struct KLay {
-    static constexpr int NM = 7 * D, NP = NM * (NM + 1) / 2;
-};
-__device__ __forceinline__ int pk(int i, int j) { return i * (i + 1) / 2 + j; }      // i >= j
-
-template <int D>
-__device__ __forceinline__ double cel(const double *__restrict__ Ae, double ce, int p, int q) {      // C_e[p][q]
-    if constexpr (D == 1) return ce;
-    else return Ae ? -Ae[p * D + q] : (p == q ? 1.0 : 0.0);
-}
-
-template <int D>
 __global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, const int32_t *__restrict__ krec, const double *__restrict__ kc, const int32_t *__restrict__ kps,
                                                  const double *__restrict__ ptab, const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v,
                                                  const double *__restrict__ v2f, const double *__restrict__ W, Part *__restrict__ partial) {
@@ -296,104 +284,12 @@ __global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, const int32_t *__res
     double s = 0.0, c = 0.0;
     bool undef_t = false, npd_t = false;
     if (f < n) {
-        const int32_t *sl = krec + f * 16, *vr = sl + 8;
-        double Qi[D][D], ldq, bp[D];
-        // C_e of entry e: dim 1 the coefficient, dim > 1 I (OUT) or -A of the entry's set (read where used: no per-thread arrays)
-        auto Aof = [&](int e) -> const double * {
-            if constexpr (D == 1) return nullptr;
-            else return e == 0 ? nullptr : ptab + (int64_t)kps[f * 8 + e] * PS;
-        };
-        auto Cof = [&](int e) -> double {
-            if constexpr (D == 1) return kc[f * 10 + e];
-            else return 0.0;
-        };
-        if constexpr (D == 1) {
-            const double *k = kc + f * 10;
-            Qi[0][0] = 1.0 / k[8]; ldq = log(k[8]) + kLog2Pi; bp[0] = k[9];
-        } else {
-            const double *tq = ptab + (int64_t)kps[f * 8] * PS;
-#pragma unroll
-            for (int p = 0; p < D; p++) {
-                bp[p] = 0.0;
-#pragma unroll
-                for (int q = 0; q < D; q++) Qi[p][q] = tq[D * D + p * D + q];
-            }
-            ldq = tq[2 * D * D];
-        }
-        unsigned freemask = 0;
-        int nfree = 0;
-        bool ok = true;
-        for (int e = 0; e < 8; e++) {
-            if (sl[e] < 0) continue;
-            double x[D];
-            if (vinfo[vr[e]] & kClamped) datum<D>(v2f, sl[e], x);
-            else {
-                double et[D], lm[NT];
-                ok = free_edge<D>(f2v, W, sl[e], vr[e], x, et, lm) && ok;
-                const int o = nfree * D;
-                for (int r = 0; r < D; r++) {
-                    hv[(o + r) * kKB] = et[r];
-                    for (int q = 0; q <= r; q++) J[pk(o + r, o + q) * kKB] = lam_at<D>(lm, r, q);
-                    for (int j = 0; j < o; j++) J[pk(o + r, j) * kKB] = 0.0;
-                }
-                freemask |= 1u << e;
-                nfree++;
-            }
-            // b'' -= C_e x
-#pragma unroll
-            for (int p = 0; p < D; p++) {
-                double u = 0.0;
-#pragma unroll
-                for (int q = 0; q < D; q++) u += cel<D>(Aof(e), Cof(e), p, q) * x[q];
-                bp[p] -= u;
-            }
-        }
-        double g[D], cq = 0.0;
-#pragma unroll
-        for (int p = 0; p < D; p++) {
-            double u = 0.0;
-#pragma unroll
-            for (int q = 0; q < D; q++) u += Qi[p][q] * bp[q];
-            g[p] = u; cq += bp[p] * u;
-        }
+        double Qi[D][D], ldq, bp[D], g[D], cq;
+        unsigned freemask;
+        int nfree;
+        bool ok;
+        kary_joint<D, kKB>(f, krec, kc, kps, ptab, vinfo, f2v, v2f, W, J, hv, Qi, ldq, bp, g, cq, freemask, nfree, ok);
         double lz = -0.5 * cq - 0.5 * ldq;
-        // J += C_u' Q⁻¹ C_u, h += C_u' Q⁻¹ b''
-        int jk = 0;
-        for (int k = 0; k < 8; k++) {
-            if (!((freemask >> k) & 1)) continue;
-            double G[D][D];          // Q⁻¹ C_k
-#pragma unroll
-            for (int p = 0; p < D; p++)
-#pragma unroll
-                for (int q = 0; q < D; q++) {
-                    double u = 0.0;
-#pragma unroll
-                    for (int m = 0; m < D; m++) u += Qi[p][m] * cel<D>(Aof(k), Cof(k), m, q);
-                    G[p][q] = u;
-                }
-#pragma unroll
-            for (int r = 0; r < D; r++) {
-                double u = 0.0;
-#pragma unroll
-                for (int p = 0; p < D; p++) u += cel<D>(Aof(k), Cof(k), p, r) * g[p];
-                hv[(jk * D + r) * kKB] += u;
-            }
-            int jj = 0;
-            for (int j = 0; j <= k; j++) {
-                if (!((freemask >> j) & 1)) continue;
-                // block (k, j) of the lower triangle: C_k' Q⁻¹ C_j = G_k'... written as rows of k, columns of j
-                for (int r = 0; r < D; r++)
-                    for (int q = 0; q < D; q++) {
-                        if (jj == jk && q > r) continue;
-                        double u = 0.0;
-#pragma unroll
-                        for (int p = 0; p < D; p++) u += cel<D>(Aof(j), Cof(j), p, q) * G[p][r];      // (C_j' Q⁻¹ C_k)[q][r] = (C_k' Q⁻¹ C_j)[r][q]
-                        J[pk(jk * D + r, jj * D + q) * kKB] += u;
-                    }
-                jj++;
-            }
-            jk++;
-        }
         // Cholesky in place, then the forward solve
         const int N = nfree * D;
         bool pd = true;

@@ -133,6 +133,190 @@ __device__ __forceinline__ void datum(const double *__restrict__ v2f, int slot, 
     ld_msg<D>(v2f, slot, y, l);
 }
 
+// ---- a factor of two variables x_out = A x_in + b + N(0, Q): its parameters and its belief's joint, shared by cx_factor_beliefs /
+// cx_factor_statistics (cx_learn.hip) and the sampler (cx_sample.hip).  Pair row p of the table of cx_evidence.hip: dim 1 (q, a, b) per
+// row (pa, pb may be null: a = 1, b = 0); dim > 1 the row's parameter set in ptab = [set][A | Q⁻¹ | log det 2πQ, 0] (b = 0).
+template <int D>
+__device__ __forceinline__ void pair_params(int64_t p, const int32_t *__restrict__ pset, const double *__restrict__ pq, const double *__restrict__ pa,
+                                            const double *__restrict__ pb, const double *__restrict__ ptab, double (&A)[D][D], double (&Qi)[D][D],
+                                            double (&bb)[D]) {
+    if constexpr (D == 1) {
+        A[0][0] = pa ? pa[p] : 1.0; Qi[0][0] = 1.0 / pq[p]; bb[0] = pb ? pb[p] : 0.0;
+    } else {
+        const double *t = ptab + (int64_t)pset[p] * (2 * D * D + 2);
+#pragma unroll
+        for (int i = 0; i < D; i++) {
+            bb[i] = 0.0;
+#pragma unroll
+            for (int j = 0; j < D; j++) { A[i][j] = t[i * D + j]; Qi[i][j] = t[D * D + i * D + j]; }
+        }
+    }
+}
+
+// the factor belief's precision J and right-hand side h over (out, in), 2d x 2d, in coordinates centred on the ends' centres (rc = c_out -
+// A c_in - b; η~, Λ~ the centred leave-one-out messages of free ends): an observed end (fo / fi false) is an identity block with h = 0
+template <int D>
+__device__ __forceinline__ void pair_joint(const double (&A)[D][D], const double (&Qi)[D][D], const double (&rc)[D], bool fo, bool fi, const double (&eo)[D],
+                                           const double (&lo)[Lay<D>::NT], const double (&ei)[D], const double (&li)[Lay<D>::NT],
+                                           double (&J)[2 * D][2 * D], double (&h)[2 * D]) {
+    double g[D], T[D][D];       // g = -Q⁻¹ rc, T = Q⁻¹ A
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; j++) t -= Qi[i][j] * rc[j];
+        g[i] = t;
+#pragma unroll
+        for (int j = 0; j < D; j++) {
+            double u = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; k++) u += Qi[i][k] * A[k][j];
+            T[i][j] = u;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; k++) t += A[k][i] * g[k];
+        h[i] = fo ? g[i] + eo[i] : 0.0;
+        h[D + i] = fi ? -t + ei[i] : 0.0;
+#pragma unroll
+        for (int j = 0; j < D; j++) {
+            double u = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; k++) u += A[k][i] * T[k][j];
+            J[i][j] = fo ? Qi[i][j] + lam_at<D>(lo, i, j) : (i == j ? 1.0 : 0.0);
+            J[D + i][D + j] = fi ? u + lam_at<D>(li, i, j) : (i == j ? 1.0 : 0.0);
+            J[D + i][j] = fo && fi ? -T[j][i] : 0.0;
+            J[j][D + i] = J[D + i][j];
+        }
+    }
+}
+
+// ---- the joint of a factor of 3 .. 7 variables (k-ary table row f), shared by k_ev_kary and the sampler's k_sp_cond_kary -----------
+// x_out = Σ A_k x_k + b + N(0, Q), entries in the k-ary table's order (OUT first).  krec[f] = slots[8] | vars[8] (-1: none).
+// dim 1: kc[f] = C_e[8] (+1 OUT, -a_i IN) | q | b.  dim > 1: kps[f] = parameter set per entry (IN: its A; OUT: Q); ptab as k_ev_pair's.
+// Writes the joint precision over the free entries (packed lower triangle, element k at J[k * NB]) and its right-hand side (hv), in
+// coordinates centred on the free entries' belief means; returns Q⁻¹, log det 2πQ, b'' = b - Σ C_e x_e at the data / the centres,
+// g = Q⁻¹ b'', cq = b'' g, the mask and count of the free entries and whether every input is defined.
+template <int D>
+struct KLay {
+    static constexpr int NM = 7 * D, NP = NM * (NM + 1) / 2;
+};
+__device__ __forceinline__ int pk(int i, int j) { return i * (i + 1) / 2 + j; }      // i >= j
+
+template <int D>
+__device__ __forceinline__ double cel(const double *__restrict__ Ae, double ce, int p, int q) {      // C_e[p][q]
+    if constexpr (D == 1) return ce;
+    else return Ae ? -Ae[p * D + q] : (p == q ? 1.0 : 0.0);
+}
+
+template <int D, int NB>
+__device__ __forceinline__ void kary_joint(int64_t f, const int32_t *__restrict__ krec, const double *__restrict__ kc, const int32_t *__restrict__ kps,
+                                           const double *__restrict__ ptab, const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v,
+                                           const double *__restrict__ v2f, const double *__restrict__ W, double *__restrict__ J, double *__restrict__ hv,
+                                           double (&Qi)[D][D], double &ldq, double (&bp)[D], double (&g)[D], double &cq, unsigned &freemask, int &nfree,
+                                           bool &ok) {
+    constexpr int NT = Lay<D>::NT, PS = 2 * D * D + 2;
+    const int32_t *sl = krec + f * 16, *vr = sl + 8;
+    // C_e of entry e: dim 1 the coefficient, dim > 1 I (OUT) or -A of the entry's set (read where used: no per-thread arrays)
+    auto Aof = [&](int e) -> const double * {
+        if constexpr (D == 1) return nullptr;
+        else return e == 0 ? nullptr : ptab + (int64_t)kps[f * 8 + e] * PS;
+    };
+    auto Cof = [&](int e) -> double {
+        if constexpr (D == 1) return kc[f * 10 + e];
+        else return 0.0;
+    };
+    if constexpr (D == 1) {
+        const double *k = kc + f * 10;
+        Qi[0][0] = 1.0 / k[8]; ldq = log(k[8]) + kLog2Pi; bp[0] = k[9];
+    } else {
+        const double *tq = ptab + (int64_t)kps[f * 8] * PS;
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            bp[p] = 0.0;
+#pragma unroll
+            for (int q = 0; q < D; q++) Qi[p][q] = tq[D * D + p * D + q];
+        }
+        ldq = tq[2 * D * D];
+    }
+    freemask = 0;
+    nfree = 0;
+    ok = true;
+    for (int e = 0; e < 8; e++) {
+        if (sl[e] < 0) continue;
+        double x[D];
+        if (vinfo[vr[e]] & kClamped) datum<D>(v2f, sl[e], x);
+        else {
+            double et[D], lm[NT];
+            ok = free_edge<D>(f2v, W, sl[e], vr[e], x, et, lm) && ok;
+            const int o = nfree * D;
+            for (int r = 0; r < D; r++) {
+                hv[(o + r) * NB] = et[r];
+                for (int q = 0; q <= r; q++) J[pk(o + r, o + q) * NB] = lam_at<D>(lm, r, q);
+                for (int j = 0; j < o; j++) J[pk(o + r, j) * NB] = 0.0;
+            }
+            freemask |= 1u << e;
+            nfree++;
+        }
+        // b'' -= C_e x
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            double u = 0.0;
+#pragma unroll
+            for (int q = 0; q < D; q++) u += cel<D>(Aof(e), Cof(e), p, q) * x[q];
+            bp[p] -= u;
+        }
+    }
+    cq = 0.0;
+#pragma unroll
+    for (int p = 0; p < D; p++) {
+        double u = 0.0;
+#pragma unroll
+        for (int q = 0; q < D; q++) u += Qi[p][q] * bp[q];
+        g[p] = u; cq += bp[p] * u;
+    }
+    // J += C_u' Q⁻¹ C_u, h += C_u' Q⁻¹ b''
+    int jk = 0;
+    for (int k = 0; k < 8; k++) {
+        if (!((freemask >> k) & 1)) continue;
+        double G[D][D];          // Q⁻¹ C_k
+#pragma unroll
+        for (int p = 0; p < D; p++)
+#pragma unroll
+            for (int q = 0; q < D; q++) {
+                double u = 0.0;
+#pragma unroll
+                for (int m = 0; m < D; m++) u += Qi[p][m] * cel<D>(Aof(k), Cof(k), m, q);
+                G[p][q] = u;
+            }
+#pragma unroll
+        for (int r = 0; r < D; r++) {
+            double u = 0.0;
+#pragma unroll
+            for (int p = 0; p < D; p++) u += cel<D>(Aof(k), Cof(k), p, r) * g[p];
+            hv[(jk * D + r) * NB] += u;
+        }
+        int jj = 0;
+        for (int j = 0; j <= k; j++) {
+            if (!((freemask >> j) & 1)) continue;
+            // block (k, j) of the lower triangle: C_k' Q⁻¹ C_j = G_k'... written as rows of k, columns of j
+            for (int r = 0; r < D; r++)
+                for (int q = 0; q < D; q++) {
+                    if (jj == jk && q > r) continue;
+                    double u = 0.0;
+#pragma unroll
+                    for (int p = 0; p < D; p++) u += cel<D>(Aof(j), Cof(j), p, q) * G[p][r];      // (C_j' Q⁻¹ C_k)[q][r] = (C_k' Q⁻¹ C_j)[r][q]
+                    J[pk(jk * D + r, jj * D + q) * NB] += u;
+                }
+            jj++;
+        }
+        jk++;
+    }
+}
+
 // ---- host: the work lists -------------------------------------------------------------------------------------------------------
 struct Cache {
     bool built = false;

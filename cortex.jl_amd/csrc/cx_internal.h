@@ -261,6 +261,8 @@ struct cx_handle {
     uint64_t param_epoch = 0;
     // cx_factor_beliefs / cx_factor_statistics (cx_learn.hip): the grouping's work lists and scratch (opaque)
     void *learn = nullptr;
+    // cx_sample_posterior (cx_sample.hip): the forest plan, the links and the per-call scratch (opaque)
+    void *sample = nullptr;
 
     // staging for set/get/batch
     void *d_stage = nullptr;
@@ -402,5 +404,6 @@ bool comm_exchange_on(cx_handle *h, hipStream_t stream, std::string &err);
 void ipc_destroy(cx_handle *h);  // cx_api_ipc.hip
 void evidence_free(cx_handle *h);  // cx_evidence.hip
 void learn_free(cx_handle *h);  // cx_learn.hip
+void sample_free(cx_handle *h);  // cx_sample.hip
 
 }  // namespace cx

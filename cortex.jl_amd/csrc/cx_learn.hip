@@ -43,17 +43,7 @@ __device__ __forceinline__ int pair_belief(int64_t p, const int4 *__restrict__ r
     constexpr int NT = Lay<D>::NT, N = 2 * D;
     const int4 r = rec[p];
     double Qi[D][D], bb[D];
-    if constexpr (D == 1) {
-        A[0][0] = pa ? pa[p] : 1.0; Qi[0][0] = 1.0 / pq[p]; bb[0] = pb ? pb[p] : 0.0;
-    } else {
-        const double *t = ptab + (int64_t)pset[p] * (2 * D * D + 2);
-#pragma unroll
-        for (int i = 0; i < D; i++) {
-            bb[i] = 0.0;
-#pragma unroll
-            for (int j = 0; j < D; j++) { A[i][j] = t[i * D + j]; Qi[i][j] = t[D * D + i * D + j]; }
-        }
-    }
+    ev::pair_params<D>(p, pset, pq, pa, pb, ptab, A, Qi, bb);
     const bool fo = !(vinfo[r.z] & kClamped), fi = !(vinfo[r.w] & kClamped);
     double mo[D], eo[D], lo[NT], mi[D], ei[D], li[NT];
     bool ok = true;
@@ -70,40 +60,8 @@ __device__ __forceinline__ int pair_belief(int64_t p, const int4 *__restrict__ r
         rc[i] = t;
     }
     if (!ok) return 1;
-    double g[D], T[D][D];       // g = -Q⁻¹ rc, T = Q⁻¹ A
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-        double t = 0.0;
-#pragma unroll
-        for (int j = 0; j < D; j++) t -= Qi[i][j] * rc[j];
-        g[i] = t;
-#pragma unroll
-        for (int j = 0; j < D; j++) {
-            double u = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; k++) u += Qi[i][k] * A[k][j];
-            T[i][j] = u;
-        }
-    }
     double J[N][N], h[N];
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; k++) t += A[k][i] * g[k];
-        h[i] = fo ? g[i] + eo[i] : 0.0;
-        h[D + i] = fi ? -t + ei[i] : 0.0;
-#pragma unroll
-        for (int j = 0; j < D; j++) {
-            double u = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; k++) u += A[k][i] * T[k][j];
-            J[i][j] = fo ? Qi[i][j] + ev::lam_at<D>(lo, i, j) : (i == j ? 1.0 : 0.0);
-            J[D + i][D + j] = fi ? u + ev::lam_at<D>(li, i, j) : (i == j ? 1.0 : 0.0);
-            J[D + i][j] = fo && fi ? -T[j][i] : 0.0;
-            J[j][D + i] = J[D + i][j];
-        }
-    }
+    ev::pair_joint<D>(A, Qi, rc, fo, fi, eo, lo, ei, li, J, h);
     double logdet, quad;
     if (!ev::chol_quad<N>(J, h, logdet, quad)) return 2;
     ev::back_solve<N>(J, h, dl);

@@ -324,6 +324,31 @@ class DeviceGraph:
                  "S_xx": out[:, o + 2 * d * d:].reshape(G, d, d).copy()}
         return stats, dict(zip(("factors", "groups", "undefined", "not_positive_definite"), [int(x) for x in cnt]))
 
+    def sample_posterior(self, n_samples, seed=0, variable_ids=None, noise=None):
+        """cx_sample_posterior: joint draws from p(x | data) on a forest (the simulation smoother), from the stored messages.
+        Returns (samples [n_samples, n, d] for variable_ids — None: every variable in ascending id —, counts) with counts "free",
+        "components", "undefined", "not_positive_definite".  noise: the standard normals [n_samples, n_variables, d] in ascending
+        variable-id order (observed rows ignored) in place of the device's Philox4x32-10 draws; the result is then affine in noise."""
+        d = self.dim
+        S = int(n_samples)
+        if variable_ids is None:
+            ids, n = None, self.stats()["n_variables"]
+        else:
+            ids = _i64(np.atleast_1d(variable_ids))
+            n = len(ids)
+        eps = None
+        if noise is not None:
+            nv = self.stats()["n_variables"]
+            eps = _f64(noise)
+            if eps.shape != (S, nv, d):
+                raise ValueError(f"noise must be [{S}, {nv}, {d}]")
+        out = np.zeros((max(S, 0), n, d), dtype=np.float64)
+        cnt = (C.c_int64 * 4)()
+        self._check(self.lib.cx_sample_posterior(self.h, S, C.c_uint64(int(seed) & (2 ** 64 - 1)), None if eps is None else _p(eps, C.c_double),
+                                                 n if ids is not None else 0, None if ids is None else _p(ids, C.c_int64),
+                                                 _p(out, C.c_double) if S >= 1 else None, cnt))
+        return out, dict(zip(("free", "components", "undefined", "not_positive_definite"), [int(x) for x in cnt]))
+
     # -- halo -----------------------------------------------------------------------------------
     def halo_configure(self, send_var, send_fac, recv_var, recv_fac):
         sv, sf, rv, rf = _i64(send_var), _i64(send_fac), _i64(recv_var), _i64(recv_fac)

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define CX_ABI_VERSION 6   /* 6: cx_factor_beliefs, cx_factor_statistics (additive).  5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
+#define CX_ABI_VERSION 7   /* 7: cx_sample_posterior (additive).  6: cx_factor_beliefs, cx_factor_statistics (additive).  5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
 
 /* status codes */
 #define CX_OK 0
@@ -588,6 +588,34 @@ int32_t cx_factor_beliefs(cx_handle *h, int64_t n, const int64_t *factor_ids, do
  * a group's row is NaN (n_g excepted) when one of its factors is counted in either of the last two. */
 int32_t cx_factor_statistics(cx_handle *h, int64_t n, const int64_t *factor_ids, const int64_t *groups, int64_t n_groups, double *out,
                              int64_t *counts4);
+
+/* ---- joint posterior samples (ABI 7; no counterpart in the reference) ----
+ * cx_sample_posterior: n_samples joint draws of the non-observed variables of a Gaussian forest — the simulation smoother (forward
+ * filtering, backward sampling) on any forest, dim 1 - 4.  Each component of the forest of non-observed variables is
+ * rooted where the tree schedule's heavy-path plan roots it (an end of a longest path) and drawn from
+ *     q(x) = b_r(x_r) Π_a b_a(x_{C_a} | x_{p_a}),
+ * b_r the root's belief (the sum of its stored factor→variable messages), b_a the factor belief of cx_factor_beliefs (§4e / §4f), p_a
+ * the factor's variable nearest the root and C_a its other non-observed variables (drawn jointly; up to 6 for a k-ary factor).
+ * It reads what cx_log_evidence reads (the STORED messages and the data, never the marginals).  At a fixed point on a forest q is
+ * exactly p(x | data), whatever the root; when the messages are not at a fixed point q is still a proper distribution, but it depends
+ * on the root.  Covered: CX_FACTOR_GAUSS_ADDITIVE, CX_FACTOR_GAUSS_LINEAR and CX_FACTOR_GAUSS_LINEAR_N (3 - 7 edges) at dim 1,
+ * CX_FACTOR_GAUSS_LINEAR and CX_FACTOR_GAUSS_LINEAR_N at dim 2 - 4, opaque messages as part of each variable's sum.
+ * out: a host array [n_samples][n][dim] (row-major) for variable_ids (NULL: every variable in ascending id; n is ignored).  An
+ * observed variable's rows hold its datum.  Every row of a component with an undefined input, or whose root belief or a conditional
+ * precision J_CC is not positive definite, is NaN; other components are unaffected.  A non-observed variable on no factor is NaN.
+ * noise == NULL: the standard normals come from Philox4x32-10 on the device, counter (j, v, s mod 2^32, s / 2^32), key (seed mod 2^32,
+ * seed / 2^32), for components 2j and 2j + 1 of the variable of index v (ascending id order) in sample s; the four words give two
+ * uniforms u = (w53 + 0.5) 2^-53 from (word 1 << 32 | word 0) >> 11 and (word 3 << 32 | word 2) >> 11, and Box–Muller:
+ * ε_2j = sqrt(-2 ln u1) cos(2π u2), ε_2j+1 = sqrt(-2 ln u1) sin(2π u2).  A draw does not depend on n_samples, variable_ids or the launch.
+ * noise != NULL: the caller's ε, a host array [n_samples][n_variables][dim] in ascending variable-id order (n_variables of
+ * cx_graph_stats; the rows of observed variables are ignored); the call is then a fixed affine map of ε.
+ * counts4 = {free variables sampled, components, components with an undefined input, components not positive definite}.
+ * Refused as cx_log_evidence refuses, with the same codes (other families, dim >= 5, partitioned handles, zero-noise factors, a
+ * captured stream); a cycle among the non-observed variables is CX_ERR_UNSUPPORTED; n_samples < 1, a NULL out or counts4, or n < 0
+ * with ids is CX_ERR_INVALID_ARGUMENT; an unknown id CX_ERR_NOT_FOUND.  The plan is cached and rebuilt when the graph or the observed
+ * flags change.  Synchronous; moves no message, marginal, readiness bit or counter. */
+int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t seed, const double *noise, int64_t n, const int64_t *variable_ids,
+                            double *out, int64_t *counts4);
 
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)

@@ -149,6 +149,19 @@ class Handle {
                                    out.data(), o.data()));
         return {out, o};
     }
+    // joint posterior draws on a forest (the simulation smoother): n_samples x n x dim doubles for variable_ids (empty: every variable in
+    // ascending id); noise (optional): the standard normals, n_samples x n_variables x dim in ascending id order, in place of the device's
+    // Philox4x32-10 draws.  counts: free variables, components, components with an undefined input, components not positive definite
+    std::pair<std::vector<double>, std::array<int64_t, 4>> sample_posterior(int64_t n_samples, uint64_t seed, const std::vector<int64_t> &variable_ids,
+                                                                            const std::vector<double> *noise = nullptr) {
+        const int64_t nv = stats().n_variables, n = variable_ids.empty() ? nv : (int64_t)variable_ids.size();
+        if (noise) need(noise->size(), (size_t)(n_samples * nv * dim_), "sample_posterior noise");
+        std::vector<double> out((size_t)((n_samples > 0 ? n_samples : 0) * n * dim_));
+        std::array<int64_t, 4> o{};
+        check(cx_sample_posterior(h_, n_samples, seed, noise ? noise->data() : nullptr, n, variable_ids.empty() ? nullptr : variable_ids.data(),
+                                  out.data(), o.data()));
+        return {out, o};
+    }
     std::pair<int32_t, double> sweep_until(double tol, int32_t max_sweeps, int32_t check_every = 10) {
         int32_t n = 0; double r = 0;
         check(cx_sweep_until(h_, tol, max_sweeps, check_every, &n, &r));

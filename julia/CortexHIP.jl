@@ -315,6 +315,28 @@ function factor_statistics(p, factor_ids::Union{Nothing, Vector{Int64}}, groups:
     return out, counts
 end
 
+# joint posterior draws on a forest, the simulation smoother (ABI 7; dim 1 - 4): a d x n x n_samples array (column-major: sample s of
+# variable i is out[:, i, s]) for variable_ids (nothing: every variable in ascending id), and [free, components, undefined, not pd].
+# noise (optional): the standard normals, a d x n_variables x n_samples array in ascending id order, in place of the device's Philox4x32-10
+function sample_posterior(p, n_samples::Integer; seed::Integer = 0, variable_ids::Union{Nothing, Vector{Int64}} = nothing,
+                          noise::Union{Nothing, Array{Float64, 3}} = nothing)
+    d = p.dim
+    st = zeros(Int64, 9)                                                  # cx_stats: n_variables first
+    check(p.handle, ccall((:cx_graph_stats, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), p.handle, st))
+    n = variable_ids === nothing ? Int(st[1]) : length(variable_ids)
+    noise === nothing || size(noise) == (d, Int(st[1]), n_samples) ||
+        throw(ArgumentError("noise must be $d x $(st[1]) x $n_samples, got $(size(noise))"))
+    out = zeros(Float64, d, n, n_samples)
+    counts = zeros(Int64, 4)
+    ip = variable_ids === nothing ? Ptr{Int64}(C_NULL) : pointer(variable_ids)
+    np_ = noise === nothing ? Ptr{Float64}(C_NULL) : pointer(noise)
+    GC.@preserve variable_ids noise begin
+        check(p.handle, ccall((:cx_sample_posterior, lib), Int32, (Ptr{Cvoid}, Int64, UInt64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, n_samples, UInt64(seed), np_, variable_ids === nothing ? 0 : n, ip, out, counts))
+    end
+    return out, counts
+end
+
 function tree_heavy_path_stats(p)      # light depths, paths, variables on no path, launches per sweep (zeros: the level schedule is in use)
     out = zeros(Int64, 4)
     check(p.handle, ccall((:cx_tree_heavy_path_stats, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), p.handle, out))
