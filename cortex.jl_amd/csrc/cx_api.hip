@@ -15,47 +15,19 @@ using namespace cxh;
 namespace cxh {
 
 void dev_free_all(cx_handle *h) {
-    void *ptrs[] = {h->d_slice_off, h->d_partner, h->d_vbase, h->d_var_deg, h->d_big, h->d_big_slots, h->d_big_slot_var, h->d_big_tmp,
-                    h->d_vinfo, h->d_q, h->d_a, h->d_b, h->d_sq, h->d_sa, h->d_sb, h->d_f2v, h->d_v2f, h->d_marg,
-                    h->d_f2v_alt, h->d_prev, h->d_scratch, h->d_send_slots, h->d_recv_slots, h->d_send_vars,
-                    h->ext_halo_buffers ? nullptr : (void *)h->d_send_buf, h->ext_halo_buffers ? nullptr : (void *)h->d_recv_buf,
-                    h->d_stage, h->d_spdir, h->d_ptab, h->d_ptab_bt, h->d_zero_msg, h->d_mv_f2v, h->d_mv_f2v_alt, h->d_mv_v2f, h->d_mv_marg, h->d_mv_prev, h->d_mv_prod, h->d_point64_slots, h->d_rule64_rec, h->d_chain_pos_var, h->d_chain_skip0, h->d_chain_skip1, h->d_chain_link_pos, h->d_chain_from,
-                    h->d_chain_to, h->d_chain_head_fwd, h->d_chain_head_bwd, h->d_chain_side, h->d_chain_totals, h->d_chain_tab_fwd, h->d_chain_tab_bwd,
-                    h->d_mvc_side, h->d_mvc_totals, h->d_mvc_side_l, h->d_mvc_alpha, h->d_mvc_gamma, h->d_mvc_prefix, h->d_mvc_wave_carry, h->d_mvc_block,
-                    h->d_tree_rec, h->d_tree_kary, h->d_partner16, h->d_mvc_var_link, h->d_tree_stage_off, h->d_tree_skip1_down, h->d_tree_a, h->d_tree_b, h->d_pre64_slots, h->d_pre64_vars, h->d_tree_pre_slots, h->d_tree_pre_vars};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    h->d_tree_rec = h->d_tree_kary = nullptr; h->d_tree_skip1_down = nullptr; h->d_tree_a = h->d_tree_b = nullptr; h->d_pre64_slots = h->d_pre64_vars = h->d_tree_pre_slots = h->d_tree_pre_vars = nullptr; h->n_pre64 = 0; h->tree_hp = false; h->tree_dirty = true; h->d_partner16 = nullptr; h->d_mvc_var_link = nullptr; h->d_tree_stage_off = nullptr;
-    tree_graph_drop(h); h->tree_graph_failed = false;
+    // captured graphs hold device addresses: they go before the memory they name
+    tree_graph_drop(h);
     batch_graph_drop(h);
-    if (h->d_cluster_ctl) { (void)hipFree(h->d_cluster_ctl); h->d_cluster_ctl = nullptr; }
-    h->cluster_state = 0;
-    h->set_memos.clear();
     ref_free(h);
+    // the raw exceptions (cx_internal.h), freed where they always were
     cx::chain64_free(h);
     cx::chain_onepass_free(h);
     for (void *p : {(void *)h->d_marg64_sums, (void *)h->d_marg64_tab, (void *)h->d_marg64_rec}) if (p) (void)hipFree(p);
     h->d_marg64_sums = h->d_marg64_tab = nullptr; h->d_marg64_rec = nullptr; h->marg64_cap = 0;
     cx::chain64_tree_free(h);
-    cx::kary_free(h);
-    cx::evidence_free(h);
-    cx::learn_free(h);
-    cx::sample_free(h);
-    if (h->d_prod) (void)hipFree(h->d_prod);
-    if (h->d_joint) (void)hipFree(h->d_joint);
-    h->d_prod = nullptr; h->d_joint = nullptr; h->prod_cap = h->joint_cap = 0; h->prod_index.clear(); h->joint_index.clear();
-    h->d_point64_slots = h->d_rule64_rec = nullptr; h->work64_dirty = h->point64_dirty = true;
-    h->d_spdir = nullptr; h->d_ptab = nullptr; h->d_ptab_bt = nullptr; h->d_zero_msg = nullptr; h->d_mv_f2v = h->d_mv_f2v_alt = h->d_mv_v2f = h->d_mv_marg = h->d_mv_prev = nullptr; h->d_mv_prod = nullptr; h->mv_prod_cap = 0; h->ptab_sets = 0; h->ptab_bt_sets = 0;
-    h->d_chain_pos_var = h->d_chain_skip0 = h->d_chain_skip1 = h->d_chain_link_pos = h->d_chain_from = h->d_chain_to = nullptr;
-    h->d_chain_head_fwd = h->d_chain_head_bwd = nullptr; h->d_chain_side = nullptr; h->d_chain_totals = nullptr; h->chains_dirty = true; h->tree_dirty = true;
-    h->d_chain_tab_fwd = h->d_chain_tab_bwd = nullptr; h->d_mvc_side = h->d_mvc_totals = nullptr; h->d_mvc_side_l = h->d_mvc_alpha = h->d_mvc_gamma = h->d_mvc_prefix = h->d_mvc_wave_carry = h->d_mvc_block = nullptr;
-    h->d_slice_off = h->d_partner = h->d_vbase = h->d_var_deg = h->d_big = h->d_big_slots = h->d_big_slot_var = nullptr;
-    h->d_big_tmp = nullptr; h->d_vinfo = nullptr;
-    h->d_q = h->d_a = h->d_b = h->d_sq = h->d_sa = h->d_sb = nullptr;
-    h->d_f2v = h->d_v2f = h->d_marg = h->d_f2v_alt = h->d_prev = nullptr;
-    h->mv_max_deg = 0; h->sweep_max_w = 0;
-    h->d_scratch = nullptr; h->d_send_slots = h->d_recv_slots = h->d_send_vars = nullptr;
-    h->d_send_buf = h->d_recv_buf = nullptr;
-    h->d_stage = nullptr; h->stage_bytes = 0; h->device_bytes = 0;
+    // every buffer, cache, flag and counter of the graph on the device
+    static_cast<cx::DevState &>(*h) = cx::DevState();
+    h->device_bytes = 0;
 }
 
 }  // namespace cxh
@@ -190,7 +162,7 @@ static int32_t upload_ptab(cx_handle *h) {
     // The tree schedule's stages are captured into a HIP graph with the table pointers baked in by value (cx_api_sweep.hip:
     // tree_sweep): the tables are rewritten IN PLACE while their size holds, and a graph captured over a table that has to move is
     // dropped before the old allocation goes (the next sweep captures again).
-    if (h->d_ptab && h->ptab_sets < nsets) { tree_graph_drop(h); ref_graphs_drop(h); (void)hipFree(h->d_ptab); h->d_ptab = nullptr; }      // (the reference-order plans' graphs too: cx_api_ref.hip)
+    if (h->d_ptab && h->ptab_sets < nsets) { tree_graph_drop(h); ref_graphs_drop(h); h->d_ptab.reset(); }      // (the reference-order plans' graphs too: cx_api_ref.hip)
     if (!h->d_ptab) { int32_t rc = dev_alloc(h, &h->d_ptab, (int64_t)(per * nsets)); if (rc != CX_OK) return rc; h->ptab_sets = nsets; }
     CX_HIP(h, hipMemcpy(h->d_ptab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
     h->pot64_fresh = false;
@@ -206,7 +178,7 @@ static int32_t upload_ptab(cx_handle *h) {
             if (rc0 != CX_OK) return rc0;
             CX_HIP(h, hipMemset(h->d_zero_msg, 0, (size_t)(d + d * d) * 8));
         }
-        if (h->d_ptab_bt && h->ptab_bt_sets < nsets) { tree_graph_drop(h); (void)hipFree(h->d_ptab_bt); h->d_ptab_bt = nullptr; }
+        if (h->d_ptab_bt && h->ptab_bt_sets < nsets) { tree_graph_drop(h); h->d_ptab_bt.reset(); }
         if (!h->d_ptab_bt) {
             int32_t rc = dev_alloc(h, &h->d_ptab_bt, (int64_t)bt.size());
             if (rc != CX_OK) return rc;

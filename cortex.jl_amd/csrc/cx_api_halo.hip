@@ -41,10 +41,7 @@ int32_t cx_halo_configure(cx_handle *h, int64_t n_send, const int64_t *sv, const
         h->chains_dirty = true; h->tree_dirty = true;
         CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
         cx::ipc_destroy(h);          // the receive areas are sized by the halo lists
-        for (void *p : {(void *)h->d_send_slots, (void *)h->d_recv_slots, (void *)h->d_send_vars}) if (p) (void)hipFree(p);
-        if (!h->ext_halo_buffers) { if (h->d_send_buf) (void)hipFree(h->d_send_buf); if (h->d_recv_buf) (void)hipFree(h->d_recv_buf); }
-        h->d_send_slots = h->d_recv_slots = h->d_send_vars = nullptr; h->d_send_buf = h->d_recv_buf = nullptr;
-        h->ext_halo_buffers = false;
+        cx::reset_all(h->d_send_slots, h->d_recv_slots, h->d_send_vars, h->d_send_buf, h->d_recv_buf);      // (the caller's buffers are let go, not freed)
         if (mv_chain_block) {      // no message buffers: the stand-ins are marked, nothing else
             h->send_slots.clear(); h->recv_slots.clear();
             h->spdir_dirty = true; h->chain_partition = true; h->work64_dirty = true;
@@ -88,10 +85,7 @@ int32_t cx_halo_configure_state(cx_handle *h, int64_t n_send, const int64_t *sv,
             CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
         }
         cx::ipc_destroy(h);          // the receive areas are sized by the halo lists
-        for (void *p : {(void *)h->d_send_slots, (void *)h->d_recv_slots, (void *)h->d_send_vars}) if (p) (void)hipFree(p);
-        if (!h->ext_halo_buffers) { if (h->d_send_buf) (void)hipFree(h->d_send_buf); if (h->d_recv_buf) (void)hipFree(h->d_recv_buf); }
-        h->d_send_slots = h->d_recv_slots = h->d_send_vars = nullptr; h->d_send_buf = h->d_recv_buf = nullptr;
-        h->ext_halo_buffers = false;
+        cx::reset_all(h->d_send_slots, h->d_recv_slots, h->d_send_vars, h->d_send_buf, h->d_recv_buf);      // (the caller's buffers are let go, not freed)
         rc = dev_upload(h, &h->d_send_slots, h->send_slots); if (rc != CX_OK) return rc;
         rc = dev_upload(h, &h->d_recv_slots, h->recv_slots); if (rc != CX_OK) return rc;
         const int64_t per = halo_doubles(h);     // doubles per message: 2 (scalar), packed natural form for dim 2..4, 4160 for dim 64
@@ -176,9 +170,7 @@ int32_t cx_halo_set_buffers(cx_handle *h, void *send_ptr, void *recv_ptr) {
     CX_REQUIRE(h, (send_ptr || h->send_slots.empty()) && (recv_ptr || h->recv_slots.empty()), CX_ERR_INVALID_ARGUMENT,
                "cx_halo_set_buffers: null buffer for a non-empty halo list");
     CX_HIP(h, hipStreamSynchronize(h->stream));
-    if (!h->ext_halo_buffers) { if (h->d_send_buf) (void)hipFree(h->d_send_buf); if (h->d_recv_buf) (void)hipFree(h->d_recv_buf); }
-    h->d_send_buf = (double2 *)send_ptr; h->d_recv_buf = (double2 *)recv_ptr;
-    h->ext_halo_buffers = true;
+    h->d_send_buf.borrow((double2 *)send_ptr); h->d_recv_buf.borrow((double2 *)recv_ptr);      // (the handle's own, if any, are freed)
     return CX_OK;
 }
 

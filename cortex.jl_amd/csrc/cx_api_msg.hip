@@ -248,40 +248,32 @@ int32_t cx_get_marginals(cx_handle *h, int64_t n, const int64_t *variable_ids, d
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_get_marginals: host allocation failed"); }
 }
 
-// grow a device store to hold `need` records of `per_record` elements, keeping its contents; new records read as UndefValue()
+// grow a device store to hold `need` records of `per_record` elements, keeping its contents; new records read as UndefValue().
+// Captured launches hold the store's address by value: their graphs are dropped before the old store goes
 extern "C++" {
 template <class T>
-static int32_t grow_store(cx_handle *h, T **buf, int64_t *cap, int64_t need, int64_t per_record) {
-    if (need <= *cap) return CX_OK;
-    int64_t ncap = std::max<int64_t>(need, std::max<int64_t>(256, *cap * 2));
-    T *nb = nullptr;
-    CX_HIP(h, hipMalloc((void **)&nb, (size_t)(ncap * per_record) * sizeof(T)));
-    hipError_t e = hipMemsetAsync(nb, 0xff, (size_t)(ncap * per_record) * sizeof(T), h->stream);
-    if (e == hipSuccess && *buf) {
-        e = hipMemcpyAsync(nb, *buf, (size_t)(*cap * per_record) * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+static int32_t grow_store(cx_handle *h, cx::DevBuf<T> &buf, int64_t need, int64_t per_record) {
+    const int64_t cap = buf.size() / per_record;
+    if (need <= cap) return CX_OK;
+    const int64_t ncap = std::max<int64_t>(need, std::max<int64_t>(256, cap * 2));
+    cx::DevBuf<T> nb;
+    const int32_t rc = nb.alloc(h, ncap * per_record, false);
+    if (rc != CX_OK) return rc;
+    CX_HIP(h, hipMemsetAsync(nb, 0xff, (size_t)(ncap * per_record) * sizeof(T), h->stream));
+    if (buf) {
+        CX_HIP(h, hipMemcpyAsync(nb, buf, (size_t)(cap * per_record) * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+        CX_HIP(h, hipStreamSynchronize(h->stream));
+        tree_graph_drop(h); ref_graphs_drop(h);
     }
-    if (e != hipSuccess) { (void)hipFree(nb); CX_HIP(h, e); }
-    if (*buf) (void)hipFree(*buf);
-    *buf = nb; *cap = ncap;
+    buf = std::move(nb);
     return CX_OK;
 }
 }  // extern "C++"
 
 extern "C++" {
 namespace cxh {
-int32_t ensure_prod_store(cx_handle *h) {
-    const double2 *before = h->d_prod;
-    const int32_t rc = grow_store(h, &h->d_prod, &h->prod_cap, (int64_t)h->prod_index.size(), 1);
-    if (before && h->d_prod != before) { tree_graph_drop(h); ref_graphs_drop(h); }      // captured launches hold the store's address by value
-    return rc;
-}
-int32_t ensure_joint_store(cx_handle *h) {
-    const double *before = h->d_joint;
-    const int32_t rc = grow_store(h, &h->d_joint, &h->joint_cap, (int64_t)h->joint_index.size(), 6);
-    if (before && h->d_joint != before) { tree_graph_drop(h); ref_graphs_drop(h); }
-    return rc;
-}
+int32_t ensure_prod_store(cx_handle *h) { return grow_store(h, h->d_prod, (int64_t)h->prod_index.size(), 1); }
+int32_t ensure_joint_store(cx_handle *h) { return grow_store(h, h->d_joint, (int64_t)h->joint_index.size(), 6); }
 }  // namespace cxh
 }  // extern "C++"
 
@@ -372,12 +364,11 @@ static int32_t update_batch(cx_handle *h, const cx_item *items, int64_t n) {
         if (!kary_entries.empty()) {
             if ((rc = cx::kary_upload(h)) != CX_OK) return rc;
             const int64_t nk = (int64_t)kary_entries.size();
-            int32_t *d_en = nullptr;
-            CX_HIP(h, hipMalloc((void **)&d_en, (size_t)nk * 4));
-            hipError_t ce = hipMemcpyAsync(d_en, kary_entries.data(), (size_t)nk * 4, hipMemcpyHostToDevice, h->stream);
-            if (ce == hipSuccess) { cx::launch_kary_items(h, d_en, nk); ce = hipStreamSynchronize(h->stream); }
-            (void)hipFree(d_en);
-            CX_HIP(h, ce);
+            cx::DevBuf<int32_t> d_en;      // (of this call only)
+            if ((rc = d_en.alloc(h, nk, false)) != CX_OK) return rc;
+            CX_HIP(h, hipMemcpyAsync(d_en, kary_entries.data(), (size_t)nk * 4, hipMemcpyHostToDevice, h->stream));
+            cx::launch_kary_items(h, d_en, nk);
+            CX_HIP(h, hipStreamSynchronize(h->stream));
         }
         if (n <= cx::kSmallBatch) {
             // a per-signal process! or a wavefront of a few signals: the records ride in the kernel arguments and the call returns
@@ -449,7 +440,7 @@ int32_t cx_get_products(cx_handle *h, int64_t n, const int64_t *variable_ids, co
     }
     try {
         // a batch that failed half-way may have indexed nodes the store was never grown for: they read as UndefValue()
-        std::vector<double2> store((size_t)std::min<int64_t>((int64_t)h->prod_index.size(), h->prod_cap));
+        std::vector<double2> store((size_t)std::min<int64_t>((int64_t)h->prod_index.size(), h->d_prod.size()));
         if (!store.empty()) {
             CX_HIP(h, hipMemcpyAsync(store.data(), h->d_prod, store.size() * 16, hipMemcpyDeviceToHost, h->stream));
             CX_HIP(h, hipStreamSynchronize(h->stream));
@@ -472,7 +463,7 @@ int32_t cx_get_joint_marginals(cx_handle *h, int64_t n, const int64_t *factor_id
     if (n == 0) return CX_OK;
     CX_REQUIRE(h, n > 0 && factor_ids && out, CX_ERR_INVALID_ARGUMENT, "cx_get_joint_marginals: null argument");
     try {
-        std::vector<double> store((size_t)6 * std::min<int64_t>((int64_t)h->joint_index.size(), h->joint_cap));
+        std::vector<double> store((size_t)6 * std::min<int64_t>((int64_t)h->joint_index.size(), h->d_joint.size() / 6));
         if (!store.empty()) {
             CX_HIP(h, hipMemcpyAsync(store.data(), h->d_joint, store.size() * 8, hipMemcpyDeviceToHost, h->stream));
             CX_HIP(h, hipStreamSynchronize(h->stream));

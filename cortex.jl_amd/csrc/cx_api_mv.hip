@@ -290,8 +290,7 @@ int32_t build_work64(cx_handle *h) {
         } else
         rec.insert(rec.end(), {s, others[0], others[1], others[2], h->spdir[s], p, deg < 2 ? 1 : 0, 0});      // (flag 1, degree-1 leaf: its stored message is the input)
     }
-    for (void *p : {(void *)h->d_point64_slots, (void *)h->d_rule64_rec, (void *)h->d_pre64_slots, (void *)h->d_pre64_vars}) if (p) (void)hipFree(p);
-    h->d_point64_slots = h->d_rule64_rec = h->d_pre64_slots = h->d_pre64_vars = nullptr;
+    cx::reset_all(h->d_point64_slots, h->d_rule64_rec, h->d_pre64_slots, h->d_pre64_vars);
     h->n_rule64 = (int64_t)rec.size() / 8; h->n_point64 = (int64_t)ps.size(); h->n_pre64 = (int64_t)pre_s.size();
     int32_t rc;
     if ((rc = dev_upload(h, &h->d_pre64_slots, pre_s)) != CX_OK) return rc;
@@ -503,17 +502,16 @@ int32_t mv_ensure_prod_store(cx_handle *h) {
     const bool d64 = cx::is_mfma_dim(h->cfg.dim);
     const int64_t cap = std::max<int64_t>(2 * h->mv_prod_cap, (((int64_t)h->prod_index.size() + 255) / 256) * 256);
     const int64_t per = d64 ? h->nc : h->ncs;
-    double *bigger = nullptr;
+    cx::DevBuf<double> bigger;
     int32_t rc;
-    if ((rc = dev_alloc(h, &bigger, cap * per)) != CX_OK) return rc;
+    if ((rc = bigger.alloc(h, cap * per)) != CX_OK) return rc;
     CX_HIP(h, hipMemsetAsync(bigger, 0xff, (size_t)(cap * per) * 8, h->stream));
     if (h->d_mv_prod) {
         CX_HIP(h, hipMemcpyAsync(bigger, h->d_mv_prod, (size_t)(h->mv_prod_cap * per) * 8, hipMemcpyDeviceToDevice, h->stream));
         CX_HIP(h, hipStreamSynchronize(h->stream));
         tree_graph_drop(h); ref_graphs_drop(h);      // captured launches hold the table's address by value
-        (void)hipFree(h->d_mv_prod);
     }
-    h->d_mv_prod = bigger; h->mv_prod_cap = cap;
+    h->d_mv_prod = std::move(bigger); h->mv_prod_cap = cap;      // (the old table is freed here)
     return CX_OK;
 }
 

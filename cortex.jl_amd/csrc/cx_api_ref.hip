@@ -20,21 +20,21 @@ namespace {
 
 struct PlanEntry {
     uint64_t key = 0, req_key = 0;
-    int32_t *d_rec = nullptr, *d_list = nullptr, *d_wide_rec = nullptr, *d_flat = nullptr;
-    double *d_wide_partial = nullptr;           // 64 pairs of scratch per wide item of the widest stage (k_wide_sum)
-    int64_t *d_stage_off = nullptr;
+    cx::DevBuf<int32_t> d_rec, d_list, d_wide_rec, d_flat;
+    cx::DevBuf<double> d_wide_partial;          // 64 pairs of scratch per wide item of the widest stage (k_wide_sum)
+    cx::DevBuf<int64_t> d_stage_off;
     std::vector<int64_t> stage_off, wide_off;
     // chains of pairs that run as scans (cx_refsched.h: ScanStep; cx_planscan.hip): the links' arrays, the steps, the first step of every stage (-1: none)
     std::vector<rs::ScanStep> scans;
     std::vector<int32_t> scan_at;
-    int32_t *d_sl_lead_dst = nullptr, *d_sl_lead_var = nullptr, *d_sl_fol_dst = nullptr, *d_sl_prec = nullptr, *d_sl_src_off = nullptr, *d_sl_src = nullptr;
-    uint8_t *d_sl_head = nullptr;
-    void *d_scan_scratch = nullptr;
+    cx::DevBuf<int32_t> d_sl_lead_dst, d_sl_lead_var, d_sl_fol_dst, d_sl_prec, d_sl_src_off, d_sl_src;
+    cx::DevBuf<uint8_t> d_sl_head;
+    cx::DevBuf<char> d_scan_scratch;
     int64_t n_chain_exec = 0;
     // dim 64: a stage is up to four launches of the kernels a dim 64 sweep is made of — sums of a range of a variable's messages into the
     // product table (k_range_sum64), variable→factor sums (k_v2f64), the messages out of observed variables (k_point64), the MFMA rule on
     // a stored variable→factor message (k_rule64w) — over these lists, by stage
-    int32_t *d64_prod = nullptr, *d64_v2f_slot = nullptr, *d64_v2f_var = nullptr, *d64_point = nullptr, *d64_rule = nullptr;
+    cx::DevBuf<int32_t> d64_prod, d64_v2f_slot, d64_v2f_var, d64_point, d64_rule;
     std::vector<int64_t> off64_prod, off64_v2f, off64_point, off64_rule;
     hipGraphExec_t exec = nullptr;
     bool graph_failed = false;
@@ -43,7 +43,7 @@ struct PlanEntry {
     std::vector<int32_t> order;                 // the executions, in the reference's order (cx_ref_trace)
     int64_t n_messages = 0, n_marginals = 0, n_products = 0, rounds = 0, launches = 0, list_entries = 0;
     uint64_t last_used = 0;
-    int64_t device_bytes = 0;
+    int64_t device_bytes = 0;                   // what its buffers added to the handle's figure (the plan cache's max_bytes budget)
 };
 
 struct RefSched {
@@ -73,16 +73,8 @@ struct RefSched {
 
 RefSched *ref_of(cx_handle *h) { return (RefSched *)h->ref; }
 
-void entry_free(cx_handle *h, PlanEntry &e) {
-    if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; }
-    for (void *p : {(void *)e.d_rec, (void *)e.d_list, (void *)e.d_stage_off, (void *)e.d_wide_rec, (void *)e.d_flat, (void *)e.d_wide_partial, (void *)e.d_sl_lead_dst, (void *)e.d_sl_lead_var,
-                    (void *)e.d_sl_fol_dst, (void *)e.d_sl_prec, (void *)e.d_sl_src_off, (void *)e.d_sl_src, (void *)e.d_sl_head, e.d_scan_scratch,
-                    (void *)e.d64_prod, (void *)e.d64_v2f_slot, (void *)e.d64_v2f_var, (void *)e.d64_point, (void *)e.d64_rule}) if (p) (void)hipFree(p);
-    e.d64_prod = e.d64_v2f_slot = e.d64_v2f_var = e.d64_point = e.d64_rule = nullptr;
-    e.d_rec = e.d_list = e.d_wide_rec = e.d_flat = nullptr; e.d_stage_off = nullptr; e.d_wide_partial = nullptr;
-    e.d_sl_lead_dst = e.d_sl_lead_var = e.d_sl_fol_dst = e.d_sl_prec = e.d_sl_src_off = e.d_sl_src = nullptr; e.d_sl_head = nullptr; e.d_scan_scratch = nullptr;
-    h->device_bytes -= e.device_bytes; e.device_bytes = 0;
-}
+// a captured plan names its entry's buffers: it goes before the entry is erased (the buffers free themselves)
+void entry_graph_drop(PlanEntry &e) { if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; } }
 
 rs::State &writable(RefSched *R) {
     R->touched = true;
@@ -282,7 +274,7 @@ bool cluster_prepare(cx_handle *h) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0 && std::strncmp(prop.gcnArchName, "gfx942", 6) != 0) return false;
-    if (hipMalloc(&h->d_cluster_ctl, 512) != hipSuccess) { (void)hipGetLastError(); h->d_cluster_ctl = nullptr; return false; }
+    if (h->d_cluster_ctl.alloc(h, 512, false) != CX_OK) { (void)hipGetLastError(); return false; }
     h->cluster_cu = cus;
     h->cluster_state = 1;
     return true;
@@ -369,7 +361,7 @@ int32_t cluster_run(cx_handle *h, const int32_t *d_flat, const int32_t *d_rec, c
 void ref_free(cx_handle *h) {
     RefSched *R = ref_of(h);
     if (!R) return;
-    for (auto &e : R->cache) entry_free(h, e);
+    ref_graphs_drop(h);
     delete R;
     h->ref = nullptr; h->d_ref_list = nullptr;
 }
@@ -378,7 +370,7 @@ void ref_free(cx_handle *h) {
 void ref_graphs_drop(cx_handle *h) {
     RefSched *R = ref_of(h);
     if (!R) return;
-    for (auto &e : R->cache) if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; }
+    for (auto &e : R->cache) entry_graph_drop(e);
 }
 
 // the segment-tree nodes of the variables of degree > 5 live in the handle's product store, under the keys cx_update_batch's
@@ -605,7 +597,7 @@ int32_t ref_sweep(cx_handle *h, const int32_t *req, int64_t n, const uint64_t *k
                 size_t lru = 0;
                 for (size_t i = 1; i < R->cache.size(); i++) if (R->cache[i].last_used < R->cache[lru].last_used) lru = i;
                 CX_HIP(h, hipStreamSynchronize(h->stream));
-                entry_free(h, R->cache[lru]);
+                entry_graph_drop(R->cache[lru]);
                 R->cache.erase(R->cache.begin() + lru);
             }
             PlanEntry e;
@@ -630,21 +622,15 @@ int32_t ref_sweep(cx_handle *h, const int32_t *req, int64_t n, const uint64_t *k
             int32_t rc2;
             if ((rc2 = dev_upload(h, &e.d_rec, P.rec)) != CX_OK || (rc2 = dev_upload(h, &e.d_list, P.list)) != CX_OK || (rc2 = dev_upload(h, &e.d_stage_off, P.stage_off)) != CX_OK ||
                 (rc2 = dev_upload(h, &e.d_wide_rec, P.wide_rec)) != CX_OK || (want_flat && (rc2 = dev_upload(h, &e.d_flat, flat)) != CX_OK) ||
-                (!P.wide_rec.empty() && (rc2 = dev_alloc(h, &e.d_wide_partial, (int64_t)(P.wide_rec.size() / 5) * 64 * 2)) != CX_OK)) {
-                e.device_bytes = h->device_bytes - before; entry_free(h, e); return rc2;
-            }
-            if (cx::is_mfma_dim(h->cfg.dim) && (rc2 = plan64(h, R, P, e)) != CX_OK) { e.device_bytes = h->device_bytes - before; entry_free(h, e); return rc2; }
+                (!P.wide_rec.empty() && (rc2 = dev_alloc(h, &e.d_wide_partial, (int64_t)(P.wide_rec.size() / 5) * 64 * 2)) != CX_OK)) return rc2;
+            if (cx::is_mfma_dim(h->cfg.dim) && (rc2 = plan64(h, R, P, e)) != CX_OK) return rc2;
             if (!P.scans.empty()) {
                 int64_t widest = 0;
                 for (auto &sc : P.scans) widest = std::max(widest, sc.hi - sc.lo);
-                char *scratch = nullptr;
                 if ((rc2 = dev_upload(h, &e.d_sl_lead_dst, P.sl_lead_dst)) != CX_OK || (rc2 = dev_upload(h, &e.d_sl_lead_var, P.sl_lead_var)) != CX_OK ||
                     (rc2 = dev_upload(h, &e.d_sl_fol_dst, P.sl_fol_dst)) != CX_OK || (rc2 = dev_upload(h, &e.d_sl_prec, P.sl_prec)) != CX_OK ||
                     (rc2 = dev_upload(h, &e.d_sl_src_off, P.sl_src_off)) != CX_OK || (rc2 = dev_upload(h, &e.d_sl_src, P.sl_src)) != CX_OK ||
-                    (rc2 = dev_upload(h, &e.d_sl_head, P.sl_head)) != CX_OK || (rc2 = dev_alloc(h, &scratch, cx::plan_scan_scratch_bytes(widest))) != CX_OK) {
-                    e.d_scan_scratch = scratch; e.device_bytes = h->device_bytes - before; entry_free(h, e); return rc2;
-                }
-                e.d_scan_scratch = scratch;
+                    (rc2 = dev_upload(h, &e.d_sl_head, P.sl_head)) != CX_OK || (rc2 = dev_alloc(h, &e.d_scan_scratch, cx::plan_scan_scratch_bytes(widest))) != CX_OK) return rc2;
             }
             e.device_bytes = h->device_bytes - before;
             CX_HIP(h, hipStreamSynchronize(h->stream));      // the plan's host vectors die here
@@ -814,7 +800,7 @@ int32_t cx_graph_wire(cx_handle *h, int64_t n, const cx_item *signals, const cx_
         const int32_t rc = rs::build_user_wiring(h, n, s.data(), d.data(), flags, W, err);
         if (rc != CX_OK) return fail(h, rc, err);
         CX_HIP(h, hipStreamSynchronize(h->stream));
-        for (auto &e : R->cache) entry_free(h, e);
+        ref_graphs_drop(h);
         R->cache.clear(); R->last = -1; R->set_trans.clear();
         R->W = std::move(W);
         R->S = std::make_shared<rs::State>();

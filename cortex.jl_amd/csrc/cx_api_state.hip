@@ -184,8 +184,8 @@ int32_t cx_state_import(cx_handle *h, const void *buf, int64_t bytes) {
     h->offchain_marg_dirty = (hd.v2f_stale & 2) != 0;     // the marginals themselves travelled in section 5
     h->chain_msgs_stale = false; h->mvc_marg_pending = false;     // (the imported marginals are final)
     h->spdir_dirty = h->work64_dirty = h->point64_dirty = h->chains_dirty = true; h->tree_dirty = true;   // derived from the observed flags
-    if (h->d_prev) { (void)hipFree(h->d_prev); h->d_prev = nullptr; }               // residual snapshots restart
-    if (h->d_mv_prev) { (void)hipFree(h->d_mv_prev); h->d_mv_prev = nullptr; }
+    h->d_prev.reset();              // residual snapshots restart
+    h->d_mv_prev.reset();
     return CX_OK;
 }
 

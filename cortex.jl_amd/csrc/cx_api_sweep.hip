@@ -37,12 +37,9 @@ int32_t build_chains(cx_handle *h) {
         auto &pos_var = co.pos_var; auto &skip0 = co.skip0; auto &skip1 = co.skip1; auto &link_pos = co.link_pos; auto &from = co.from; auto &to = co.to;
         auto &head_fwd = co.head_fwd; auto &head_bwd = co.head_bwd; auto &tab_fwd = co.tab_fwd; auto &tab_bwd = co.tab_bwd;
         const int64_t nv = h->nv;
-        for (void *p : {(void *)h->d_chain_pos_var, (void *)h->d_chain_skip0, (void *)h->d_chain_skip1, (void *)h->d_chain_link_pos,
-                        (void *)h->d_chain_from, (void *)h->d_chain_to, (void *)h->d_chain_head_fwd, (void *)h->d_chain_head_bwd,
-                        (void *)h->d_chain_side, h->d_chain_totals, (void *)h->d_chain_tab_fwd, (void *)h->d_chain_tab_bwd, (void *)h->d_mvc_side,
-                        (void *)h->d_mvc_totals, (void *)h->d_mvc_side_l, (void *)h->d_mvc_alpha, (void *)h->d_mvc_gamma, (void *)h->d_mvc_prefix, (void *)h->d_mvc_wave_carry, (void *)h->d_mvc_block, (void *)h->d_mvc_var_link}) if (p) (void)hipFree(p);
-        h->d_chain_tab_fwd = h->d_chain_tab_bwd = nullptr; h->d_mvc_side = h->d_mvc_totals = nullptr;
-        h->d_mvc_side_l = h->d_mvc_alpha = h->d_mvc_gamma = h->d_mvc_prefix = h->d_mvc_wave_carry = h->d_mvc_block = nullptr; h->d_mvc_var_link = nullptr;
+        cx::reset_all(h->d_chain_pos_var, h->d_chain_skip0, h->d_chain_skip1, h->d_chain_link_pos, h->d_chain_from, h->d_chain_to, h->d_chain_head_fwd,
+                      h->d_chain_head_bwd, h->d_chain_side, h->d_chain_totals, h->d_chain_tab_fwd, h->d_chain_tab_bwd, h->d_mvc_side, h->d_mvc_totals,
+                      h->d_mvc_side_l, h->d_mvc_alpha, h->d_mvc_gamma, h->d_mvc_prefix, h->d_mvc_wave_carry, h->d_mvc_block, h->d_mvc_var_link);
         h->chain_npos = (int64_t)pos_var.size(); h->chain_nlinks = (int64_t)link_pos.size();
         h->chain_side_dirty = true; h->chain_linkpar_dirty = true;
         h->chain_pos0 = link_pos.empty() ? -1 : link_pos[0];      // one path: positions follow the links
@@ -61,10 +58,8 @@ int32_t build_chains(cx_handle *h) {
         if ((rc = dev_upload(h, &h->d_chain_head_bwd, head_bwd)) != CX_OK) return rc;
         if (cx::is_mfma_dim(h->cfg.dim)) {
             // wide messages: a plan of compositions and walks (cx_chain64_plan.h) instead of the per-thread scan of dim 2..4
-            h->d_chain_side = nullptr; h->d_chain_totals = nullptr;
             if ((rc = cx::chain64_build(h, pos_var, skip0, skip1, link_pos, from, to, head_fwd, head_bwd, tab_fwd, tab_bwd)) != CX_OK) return rc;
         } else if (h->cfg.dim > 1) {
-            h->d_chain_side = nullptr; h->d_chain_totals = nullptr;
             if ((rc = dev_upload(h, &h->d_chain_tab_fwd, tab_fwd)) != CX_OK) return rc;
             if ((rc = dev_upload(h, &h->d_chain_tab_bwd, tab_bwd)) != CX_OK) return rc;
             h->mvc_K = cx::mvc_links_per_thread(h->chain_nlinks);
@@ -84,9 +79,7 @@ int32_t build_chains(cx_handle *h) {
             }
         } else {
             if ((rc = dev_alloc(h, &h->d_chain_side, h->chain_npos)) != CX_OK) return rc;
-            char *tot = nullptr;
-            if ((rc = dev_alloc(h, &tot, (int64_t)cx::chain_total_bytes(h->chain_nlinks))) != CX_OK) return rc;
-            h->d_chain_totals = tot;
+            if ((rc = dev_alloc(h, &h->d_chain_totals, (int64_t)cx::chain_total_bytes(h->chain_nlinks))) != CX_OK) return rc;
         }
         CX_HIP(h, hipStreamSynchronize(h->stream));
         h->chains_dirty = false;
@@ -112,9 +105,8 @@ int32_t build_tree(cx_handle *h) {
         std::string terr;
         const int32_t rc = cx::treeplan::build(h, plan, terr);
         if (rc != CX_OK) return fail(h, rc, terr);
-        for (void *p : {(void *)h->d_tree_rec, (void *)h->d_tree_kary}) if (p) (void)hipFree(p);
-        h->d_tree_rec = h->d_tree_kary = nullptr;
-        tree_graph_drop(h);
+        tree_graph_drop(h);      // (it holds the addresses of what goes next)
+        cx::reset_all(h->d_tree_rec, h->d_tree_kary);
         int32_t rc2;
         // Heavy paths (cx_tree_plan.h: build_hp; scalar messages): the same exact sweep as O(log n) rounds of scans and item stages.  Taken
         // when it needs fewer launches than the level schedule's 2 x depth + 1 — chains with side branches, not bushy trees.
@@ -165,11 +157,8 @@ int32_t build_tree(cx_handle *h) {
                 std::memcpy(h->tree_hp_stats, hs, sizeof hs);
                 plan.rec = std::move(hp.rec); plan.stage_off = std::move(hp.stage_off); plan.kary = std::move(hp.kary); plan.kary_off = std::move(hp.kary_off);
             } else if (take) {
-                for (void *p : {(void *)h->d_chain_pos_var, (void *)h->d_chain_skip0, (void *)h->d_chain_skip1, (void *)h->d_tree_skip1_down, (void *)h->d_chain_link_pos,
-                                (void *)h->d_chain_from, (void *)h->d_chain_to, (void *)h->d_chain_head_fwd, (void *)h->d_chain_head_bwd, (void *)h->d_chain_side,
-                                h->d_chain_totals}) if (p) (void)hipFree(p);
-                h->d_chain_pos_var = h->d_chain_skip0 = h->d_chain_skip1 = h->d_tree_skip1_down = h->d_chain_link_pos = h->d_chain_from = h->d_chain_to = nullptr;
-                h->d_chain_head_fwd = h->d_chain_head_bwd = nullptr; h->d_chain_side = nullptr; h->d_chain_totals = nullptr;
+                cx::reset_all(h->d_chain_pos_var, h->d_chain_skip0, h->d_chain_skip1, h->d_tree_skip1_down, h->d_chain_link_pos, h->d_chain_from, h->d_chain_to,
+                              h->d_chain_head_fwd, h->d_chain_head_bwd, h->d_chain_side, h->d_chain_totals);
                 if ((rc2 = dev_upload(h, &h->d_chain_pos_var, hp.pos_var)) != CX_OK) return rc2;
                 if ((rc2 = dev_upload(h, &h->d_chain_skip0, hp.skip0)) != CX_OK) return rc2;
                 if ((rc2 = dev_upload(h, &h->d_chain_skip1, hp.skip1_up)) != CX_OK) return rc2;
@@ -182,14 +171,10 @@ int32_t build_tree(cx_handle *h) {
                 h->tree_hp_K.clear(); h->tree_hp_npos = (int64_t)hp.pos_var.size();
                 if (!hp_mv) {
                     if ((rc2 = dev_alloc(h, &h->d_chain_side, (int64_t)hp.pos_var.size())) != CX_OK) return rc2;
-                    char *tot = nullptr;
-                    if ((rc2 = dev_alloc(h, &tot, (int64_t)cx::chain_total_bytes((int64_t)hp.link_pos.size()))) != CX_OK) return rc2;
-                    h->d_chain_totals = tot;
+                    if ((rc2 = dev_alloc(h, &h->d_chain_totals, (int64_t)cx::chain_total_bytes((int64_t)hp.link_pos.size()))) != CX_OK) return rc2;
                 } else {
-                    for (void *p : {(void *)h->d_chain_tab_fwd, (void *)h->d_chain_tab_bwd, (void *)h->d_mvc_side, (void *)h->d_mvc_totals, (void *)h->d_mvc_side_l,
-                                    (void *)h->d_mvc_alpha, (void *)h->d_mvc_gamma, (void *)h->d_mvc_prefix, (void *)h->d_mvc_wave_carry}) if (p) (void)hipFree(p);
-                    h->d_chain_tab_fwd = h->d_chain_tab_bwd = nullptr; h->d_mvc_side = h->d_mvc_totals = nullptr;
-                    h->d_mvc_side_l = h->d_mvc_alpha = h->d_mvc_gamma = h->d_mvc_prefix = h->d_mvc_wave_carry = nullptr;
+                    cx::reset_all(h->d_chain_tab_fwd, h->d_chain_tab_bwd, h->d_mvc_side, h->d_mvc_totals, h->d_mvc_side_l, h->d_mvc_alpha, h->d_mvc_gamma,
+                                  h->d_mvc_prefix, h->d_mvc_wave_carry);
                     std::vector<int32_t> tab_fwd(hp.from.size()), tab_bwd(hp.from.size());
                     for (size_t l = 0; l < hp.from.size(); l++) { tab_fwd[l] = h->spdir[hp.from[l]]; tab_bwd[l] = h->spdir[hp.to[l]]; }      // the SENDING slot's table (cx_chains.h)
                     if ((rc2 = dev_upload(h, &h->d_chain_tab_fwd, tab_fwd)) != CX_OK) return rc2;
@@ -212,8 +197,7 @@ int32_t build_tree(cx_handle *h) {
                     if ((rc2 = dev_alloc(h, &h->d_mvc_wave_carry, wc)) != CX_OK) return rc2;
                     if ((rc2 = dev_alloc(h, &h->d_mvc_totals, tot)) != CX_OK) return rc2;
                 }
-                for (void *p : {(void *)h->d_tree_a, (void *)h->d_tree_b}) if (p) (void)hipFree(p);
-                h->d_tree_a = h->d_tree_b = nullptr;
+                cx::reset_all(h->d_tree_a, h->d_tree_b);
                 h->tree_hp_kary_links = hp.n_kary_links;
                 if (hp.n_kary_links > 0 && !h->any_linear) {      // no (a, b) per slot on this graph: the links' own, 1 and 0 everywhere else
                     const std::vector<double> one((size_t)h->nslots, 1.0), zero((size_t)h->nslots, 0.0);
@@ -266,8 +250,6 @@ int32_t build_tree(cx_handle *h) {
                 off.push_back((int64_t)rec.size() / 8);
                 h->tree_pre_off.push_back((int64_t)pre_s.size());
             }
-            for (void *p : {(void *)h->d_tree_pre_slots, (void *)h->d_tree_pre_vars}) if (p) (void)hipFree(p);
-            h->d_tree_pre_slots = h->d_tree_pre_vars = nullptr;
             if ((rc2 = dev_upload(h, &h->d_tree_pre_slots, pre_s)) != CX_OK) return rc2;
             if ((rc2 = dev_upload(h, &h->d_tree_pre_vars, pre_v)) != CX_OK) return rc2;
         } else
@@ -281,7 +263,6 @@ int32_t build_tree(cx_handle *h) {
         // taken out again: a tree's levels are thin next to the roots, where one workgroup's runs cost 1 us a stage, and one huge level of
         // leaves, which wants the whole chip; the 1.09 M-edge forest took 1.24 ms on the cluster against 0.63 as launches, and no forest of
         // tools/bench_configs.py or the tests has the many stages of 1 - 16 k items the cluster wins on.)
-        if (h->d_tree_stage_off) { (void)hipFree(h->d_tree_stage_off); h->d_tree_stage_off = nullptr; }
         if ((rc2 = dev_upload(h, &h->d_tree_stage_off, off)) != CX_OK) return rc2;
         CX_HIP(h, hipStreamSynchronize(h->stream));
         h->tree_stage_off = off; h->tree_kary_off = koff;
@@ -589,7 +570,7 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
     if (batch_graphs && s == 0 && n_sweeps >= 4 && h->halo_state && h->halo_depth > 0 && h->cfg.schedule == CX_SCHED_FUSED && h->big_vars.empty() && h->n_kary == 0 &&
         !h->profiling && h->cfg.materialize_messages_to_factor == 0) {
         uint64_t key = 0x9e3779b97f4a7c15ull;
-        for (uint64_t x : {(uint64_t)h->sweeps_since_exchange, (uint64_t)n_sweeps, (uint64_t)(uintptr_t)h->d_f2v, (uint64_t)(uintptr_t)h->d_f2v_alt, h->batch_epoch, (uint64_t)(uintptr_t)h->stream})
+        for (uint64_t x : {(uint64_t)h->sweeps_since_exchange, (uint64_t)n_sweeps, (uint64_t)(uintptr_t)h->d_f2v.get(), (uint64_t)(uintptr_t)h->d_f2v_alt.get(), h->batch_epoch, (uint64_t)(uintptr_t)h->stream})
             key = (key ^ x) * 0xbf58476d1ce4e5b9ull + (key >> 29);
         for (auto &g : h->batch_graph) if (g.key == key) bg = &g;
         if (!bg) {      // a new batch: takes the slot that is not the most recent one's

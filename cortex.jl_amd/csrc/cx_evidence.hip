@@ -357,9 +357,6 @@ __global__ __launch_bounds__(kFB) void k_ev_final(int64_t n, const Part *__restr
 
 // ---- host: the work lists -------------------------------------------------------------------------------------------------------
 
-template <class T>
-void free_ptr(T *&p) { if (p) (void)hipFree((void *)p); p = nullptr; }
-
 int32_t build(cx_handle *h, Cache &C, const std::string &who) {
     using namespace cxh;
     const int d = h->cfg.dim;
@@ -465,7 +462,6 @@ int32_t refresh_params(cx_handle *h, Cache &C, const std::string &who) {
             for (int e = 0; e < 8; e++) kc[r * 10 + e] = h->kary_coef[8 * r + e];
             kc[r * 10 + 8] = h->kary_qb[2 * r]; kc[r * 10 + 9] = h->kary_qb[2 * r + 1];
         }
-        free_ptr(C.d_kc);
         if ((rc = dev_upload(h, &C.d_kc, kc)) != CX_OK) return rc;
     } else {
         std::vector<int32_t> kps((size_t)C.n_kary * 8, 0);
@@ -513,13 +509,8 @@ int32_t refresh_params(cx_handle *h, Cache &C, const std::string &who) {
                 }
             o[2 * d * d] = ld;
         }
-        if (C.ptab_cap < (int64_t)tab.size()) {
-            free_ptr(C.d_ptab);
-            if ((rc = dev_alloc(h, &C.d_ptab, (int64_t)tab.size())) != CX_OK) return rc;
-            C.ptab_cap = (int64_t)tab.size();
-        }
+        if ((rc = C.d_ptab.ensure(h, (int64_t)tab.size())) != CX_OK) return rc;
         CX_HIP(h, hipMemcpyAsync(C.d_ptab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, h->stream));
-        free_ptr(C.d_kps);
         if ((rc = dev_upload(h, &C.d_kps, kps)) != CX_OK) return rc;
         CX_HIP(h, hipStreamSynchronize(h->stream));
     }
@@ -560,17 +551,7 @@ void launch(cx_handle *h, Cache &C, const double *f2v, const double *v2f) {
 
 }  // namespace ev
 
-void evidence_free(cx_handle *h) {
-    if (!h || !h->evidence) return;
-    ev::Cache *C = static_cast<ev::Cache *>(h->evidence);
-    for (void **p : {(void **)&C->d_vrec, (void **)&C->d_tail, (void **)&C->d_pair, (void **)&C->d_pair_ps, (void **)&C->d_krec, (void **)&C->d_kps,
-                     (void **)&C->d_pq, (void **)&C->d_pa, (void **)&C->d_pb, (void **)&C->d_kc, (void **)&C->d_ptab, (void **)&C->d_W,
-                     (void **)&C->d_partial, (void **)&C->d_out})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (C->h_out) (void)hipHostFree(C->h_out);
-    delete C;
-    h->evidence = nullptr;
-}
+template <> void Deleter<ev::Cache>::operator()(ev::Cache *C) const { delete C; }
 
 int32_t ev::prepare(cx_handle *h, const std::string &who, ev::Cache *&Cp) {
     using namespace cxh;
@@ -586,10 +567,10 @@ int32_t ev::prepare(cx_handle *h, const std::string &who, ev::Cache *&Cp) {
         CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
         CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
     }
-    if (!h->evidence) h->evidence = new ev::Cache();
-    ev::Cache &C = *static_cast<ev::Cache *>(h->evidence);
+    if (!h->evidence) h->evidence.reset(new ev::Cache());
+    ev::Cache &C = *h->evidence;
     int32_t rc;
-    if (!C.built && (rc = ev::build(h, C, who)) != CX_OK) { evidence_free(h); return rc; }
+    if (!C.built && (rc = ev::build(h, C, who)) != CX_OK) { h->evidence.reset(); return rc; }
     if (C.unsupported_fac >= 0)
         return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(C.unsupported_fac) + " has no sum-product rule (Gaussian factors and opaque messages only)");
     if (C.zero_noise_fac >= 0)

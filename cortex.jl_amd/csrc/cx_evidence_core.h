@@ -324,17 +324,20 @@ struct Cache {
     int64_t zero_noise_fac = -1;          // a factor with q = 0 (dim 1): refused
     int64_t unsupported_fac = -1;         // a factor of a kind without a sum-product rule
     int64_t n_pair = 0, n_kary = 0, nb = 0;
-    int32_t *d_vrec = nullptr;
-    uint8_t *d_tail = nullptr;
-    int4 *d_pair = nullptr;
-    int32_t *d_pair_ps = nullptr, *d_krec = nullptr, *d_kps = nullptr;
-    double *d_pq = nullptr, *d_pa = nullptr, *d_pb = nullptr, *d_kc = nullptr, *d_ptab = nullptr;
-    int64_t ptab_cap = 0;
+    DevBuf<int32_t> d_vrec;
+    DevBuf<uint8_t> d_tail;
+    DevBuf<int4> d_pair;
+    DevBuf<int32_t> d_pair_ps, d_krec, d_kps;
+    DevBuf<double> d_pq, d_pa, d_pb, d_kc, d_ptab;
     std::vector<int32_t> pair_ps;         // dim > 1: parameter set per pair (what the table must hold)
     std::vector<int64_t> pair_fac;        // factor index of every pair row (rows in factor order)
-    double *d_W = nullptr;
-    Part *d_partial = nullptr;
-    double *d_out = nullptr, *h_out = nullptr;      // value | counters; h_out: pinned
+    DevBuf<double> d_W;
+    DevBuf<Part> d_partial;
+    DevBuf<double> d_out;
+    double *h_out = nullptr;              // value | counters, pinned
+    Cache() = default;
+    Cache(const Cache &) = delete;
+    ~Cache() { if (h_out) (void)hipHostFree(h_out); }
 };
 
 // the checks every evidence-type call makes (family, dim, partitions, captured stream, rule kinds, zero noise), then the work lists,

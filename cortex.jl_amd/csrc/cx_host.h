@@ -67,13 +67,14 @@ int32_t dev_upload(cx_handle *h, T **p, const std::vector<T> &v) {
     return CX_OK;
 }
 
+// the same for an owning buffer, so that a row of uploads reads alike for both kinds
+template <class T> int32_t dev_alloc(cx_handle *h, cx::DevBuf<T> *b, int64_t count) { return b->alloc(h, count); }
+template <class T> int32_t dev_upload(cx_handle *h, cx::DevBuf<T> *b, const std::vector<T> &v) { return b->upload(h, v); }
+
 inline int32_t ensure_stage(cx_handle *h, int64_t bytes) {
-    if (bytes <= h->stage_bytes) return CX_OK;
-    if (h->d_stage) { CX_HIP(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_stage); h->d_stage = nullptr; }
-    int64_t want = std::max<int64_t>(bytes, 1 << 20);
-    CX_HIP(h, hipMalloc(&h->d_stage, (size_t)want));
-    h->stage_bytes = want;
-    return CX_OK;
+    if (bytes <= h->d_stage.size()) return CX_OK;
+    if (h->d_stage) CX_HIP(h, hipStreamSynchronize(h->stream));
+    return h->d_stage.alloc(h, std::max<int64_t>(bytes, 1 << 20), false);
 }
 
 // (variable_id, factor_id) -> edge index; edges are sorted by (variable, factor)
@@ -198,3 +199,32 @@ void ref_state_write(cx_handle *h, char *out);
 bool ref_state_read(cx_handle *h, const char *in, int64_t bytes);
 
 }  // namespace cxh
+
+// ---- cx::DevBuf (cx_internal.h) ---------------------------------------------------------------------------------------
+// counted == false: owned and freed like any other, but outside cx_stats().device_bytes (staging, the batched API's stores and the
+// cluster's control block never were part of that figure)
+template <class T>
+int32_t cx::DevBuf<T>::alloc(cx_handle *h, int64_t n, bool counted) {
+    reset();
+    T *p = nullptr;
+    const int32_t rc = cxh::dev_alloc(h, &p, n);      // (adds to h->device_bytes)
+    if (rc != CX_OK) return rc;
+    p_ = p; n_ = std::max<int64_t>(n, 1);
+    if (counted) bytes_ = &h->device_bytes; else h->device_bytes -= n_ * (int64_t)sizeof(T);
+    return CX_OK;
+}
+
+template <class T>
+int32_t cx::DevBuf<T>::upload(cx_handle *h, const std::vector<T> &v) {
+    const int32_t rc = alloc(h, (int64_t)v.size());
+    if (rc != CX_OK) return rc;
+    if (!v.empty()) CX_HIP(h, hipMemcpyAsync(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return CX_OK;
+}
+
+template <class T>
+int32_t cx::DevBuf<T>::ensure(cx_handle *h, int64_t n, bool *moved) {
+    const bool grow = n_ < n;
+    if (moved) *moved = grow;
+    return grow ? alloc(h, n) : CX_OK;
+}

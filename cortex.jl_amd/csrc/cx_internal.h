@@ -6,12 +6,15 @@
 
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <string>
 #include <vector>
 
 #include "cortex_hip.h"
 #include "cx_const.h"
+
+struct cx_handle;
 
 namespace cx {
 
@@ -20,9 +23,162 @@ struct ProfileRec {
     hipEvent_t start, stop;
 };
 
+// One device allocation and its owner: move-only, freed by reset() and by the destructor, counted in the handle's device_bytes while
+// it lives (what alloc adds, reset takes away).  Converts to T* so that launch sites read as with a raw pointer; nothing converts
+// back, so a buffer cannot be assigned a pointer by accident.  alloc / upload / ensure are defined in cx_host.h (they report through
+// CX_HIP like every other call).  Captured graphs hold addresses: ensure() says when the buffer moved and never drops a graph itself,
+// whoever owns a graph that names the buffer drops it BEFORE calling (see upload_ptab, ensure_prod_store).
+template <class T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), n_(o.n_), bytes_(o.bytes_) { o.p_ = nullptr; o.n_ = 0; o.bytes_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; bytes_ = o.bytes_; o.p_ = nullptr; o.n_ = 0; o.bytes_ = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    operator T *() const { return p_; }
+    template <class U> explicit operator U *() const { return (U *)p_; }      // (the launchers' C casts to another element type)
+    T *get() const { return p_; }
+    int64_t size() const { return n_; }                                       // elements asked for (0: empty or borrowed)
+    void reset() {
+        if (p_ && n_) (void)hipFree((void *)p_);      // (n_ == 0: borrowed)
+        if (bytes_) *bytes_ -= n_ * (int64_t)sizeof(T);
+        p_ = nullptr; n_ = 0; bytes_ = nullptr;
+    }
+    void borrow(T *p) { reset(); p_ = p; }                                    // memory of the caller's: used, never freed or counted
+    int32_t alloc(cx_handle *h, int64_t n, bool counted = true);              // a fresh buffer of max(n, 1) elements (the old one is released first)
+    int32_t upload(cx_handle *h, const std::vector<T> &v);                    // alloc + asynchronous copy on the handle's stream
+    int32_t ensure(cx_handle *h, int64_t n, bool *moved = nullptr);           // room for n elements; grows only, the contents are NOT kept
+private:
+    T *p_ = nullptr;
+    int64_t n_ = 0;
+    int64_t *bytes_ = nullptr;      // the owning handle's device_bytes; null: borrowed, or owned but not counted
+};
+
+template <class... B> void reset_all(B &...b) { (b.reset(), ...); }
+
+// what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample): the deleter is defined there
+template <class T> struct Deleter { void operator()(T *p) const; };
+namespace ev { struct Cache; }
+namespace fs { struct Cache; }
+namespace sp { struct Plan; }
+
 }  // namespace cx
 
-struct cx_handle {
+namespace cx {
+
+// Everything a handle owns on the device for its graph, with the flags and counters that describe it.  cxh::dev_free_all drops the
+// captured graphs (they hold these addresses) and then assigns a default-constructed DevState: a member added here is freed and reset
+// with no second mention anywhere, and the state after a reset is what the initialisers below say.
+struct DevState {
+    DevBuf<int32_t> d_slice_off, d_partner, d_vbase, d_var_deg;
+    DevBuf<int32_t> d_big, d_big_slots, d_big_slot_var;      // (dim 2..4: the variable of every slot of the CSR tail)
+    DevBuf<double2> d_big_tmp;      // prefix scratch of the big-variable kernel, one entry per big slot
+    DevBuf<uint8_t> d_vinfo;
+    DevBuf<double> d_q, d_a, d_b;        // per RECEIVING slot: effective rule parameters
+    DevBuf<double> d_sq, d_sa, d_sb;     // the same, indexed by the SENDING slot (push)
+    DevBuf<double2> d_f2v, d_v2f, d_marg;     // natural-form messages, moment-form marginals
+    DevBuf<double2> d_f2v_alt;      // second factor→variable buffer (Jacobi double buffering of the fused sweep)
+    DevBuf<double2> d_prev;         // snapshot for cx_residual
+    DevBuf<double> d_scratch;       // small reduction scratch
+    int sweep_max_w = 0;            // the widest SELL slice (0: not yet computed): picks the register footprint of the fused sweep
+    DevBuf<int16_t> d_partner16;    // partner[s] - s where every difference fits (kNoPartner16: none); null otherwise (cx_kernels.hip: PACK)
+    DevBuf<char> d_stage;           // staging for set/get/batch, in bytes (cxh::ensure_stage)
+
+    // factors with more than two edges (cx_kary.hip, CX_FACTOR_GAUSS_LINEAR_N): entry = 8 * row + edge position (OUT first, then IN by
+    // ascending variable id); coefficient c_e = +1 (OUT) / -a_i (IN); their slots have partner -1 (no pairwise rule touches them)
+    int64_t n_kary = 0;
+    std::vector<int32_t> kary_slot, slot_kary;      // [8 n_kary] slot per entry (-1 padding); [nslots] entry of a slot, -1 otherwise
+    std::vector<int32_t> kary_pset;                 // dim 2..4 (cx_kary_mv.hip): [8 n_kary] parameter set of the entry — an IN entry's A, the OUT entry's Q
+    DevBuf<int32_t> d_kary_pset, d_kary_v2f_slots, d_kary_v2f_vars;
+    DevBuf<double> d_kary_aq;                       // [sets][2][d * d]: A | Q raw
+    int64_t n_kary_v2f = 0, kary_aq_sets = 0;
+    std::vector<double> kary_coef, kary_qb;         // [8 n_kary] c_e; [2 n_kary] q, b
+    DevBuf<int32_t> d_kary_slot, d_slot_kary;
+    DevBuf<double> d_kary_coef, d_kary_qb;
+    bool kary_dirty = true;
+
+    // multivariate path (cx_mv.hip)
+    DevBuf<int32_t> d_spdir;        // per SENDING slot: 2*pset + direction of the receiving edge; -1: receiver observed
+    DevBuf<double> d_ptab;          // [2*npsets][3][d*d]: (P, B, C) triples
+    DevBuf<double> d_zero_msg;      // d = 64: one message of zeros (what an absent source reads)
+    DevBuf<double> d_ptab_bt;       // d = 64: [2*npsets][d*d], the transposes of the B tables (cx_mv64w.hip)
+    int64_t ptab_sets = 0, ptab_bt_sets = 0;      // parameter sets the device tables have room for (rewritten in place while that holds)
+    DevBuf<double> d_mv_f2v, d_mv_f2v_alt, d_mv_v2f, d_mv_marg, d_mv_prev;
+    int mv_max_deg = 0;             // dim 2..4: widest slice of the graph (0: not computed yet)
+    // d = 64 work lists (built lazily: they depend on which variables are observed)
+    bool work64_dirty = true, point64_dirty = true;
+    DevBuf<int32_t> d_point64_slots;
+    DevBuf<int32_t> d_rule64_rec;   // 8 words per work item (see k_rule64)
+    // senders of degree 5 .. 8 (a rule sums at most three sources): their variable→factor messages are summed first (k_v2f64) and the
+    // rule reads the stored message; the same per stage of the tree schedule
+    int64_t n_pre64 = 0;
+    DevBuf<int32_t> d_pre64_slots, d_pre64_vars, d_tree_pre_slots, d_tree_pre_vars;
+
+    // CX_SCHED_TREE (cx_tree_plan.h): the stages' items and k-ary entries, the stage table (runs of thin stages go out as one launch)
+    bool chains_dirty = true, tree_dirty = true;
+    bool tree_graph_failed = false;      // capture or instantiation refused once: plain launches from then on
+    DevBuf<int32_t> d_tree_rec, d_tree_kary;
+    DevBuf<int64_t> d_tree_stage_off;
+    // the same sweep over heavy paths (cx_tree_plan.h: build_hp), chosen when it takes fewer launches: the paths' arrays live in the chain
+    // fields (d_chain_pos_var .. d_chain_totals; d_chain_skip1 is the way up's), item stages in d_tree_rec as before
+    bool tree_hp = false;
+    DevBuf<int32_t> d_tree_skip1_down;
+    // heavy paths through factors with more than two edges: their pairwise parameters per receiving slot are written every sweep
+    // (cx_kary.hip: k_kary_link_params) into d_q and into d_a / d_b — or, on a graph without pairwise linear factors, into these
+    DevBuf<double> d_tree_a, d_tree_b;
+
+    // chain-scan schedule (cx_chain.hip)
+    DevBuf<int32_t> d_chain_pos_var, d_chain_skip0, d_chain_skip1;
+    DevBuf<int32_t> d_chain_link_pos, d_chain_from, d_chain_to;
+    DevBuf<uint8_t> d_chain_head_fwd, d_chain_head_bwd;
+    DevBuf<double2> d_chain_side;
+    DevBuf<char> d_chain_totals;    // bytes: the tile totals of whichever scan the dim runs
+    // dim 2..4 (cx_mvchain.hip): rule-table index of each link's two messages, side sums [nc][npos], tile totals of the map scan
+    DevBuf<int32_t> d_chain_tab_fwd, d_chain_tab_bwd;
+    DevBuf<double> d_mvc_side, d_mvc_totals;
+    DevBuf<int32_t> d_mvc_var_link;      // per variable: the chain link whose RIGHT end it is, -1 otherwise (dim 2..4; marginals on demand)
+    DevBuf<double> d_mvc_side_l, d_mvc_alpha, d_mvc_gamma, d_mvc_prefix, d_mvc_wave_carry, d_mvc_block;   // thread-interleaved by link, [nc][ntiles * 256 * K]
+
+    // halo: the lists, and the pack / unpack buffers — the handle's own, or the caller's (cx_halo_set_buffers: DevBuf::borrow)
+    DevBuf<int32_t> d_send_slots, d_recv_slots, d_send_vars;
+    DevBuf<double2> d_send_buf, d_recv_buf;
+
+    // cx_set_messages of a long list the caller repeats: see cx_handle::set_memo_tick
+    struct SetMemo { uint64_t key = 0, used = 0; int32_t direction = 0; std::vector<int64_t> var_ids, fac_ids, edges; std::vector<int32_t> idx, vars; };
+    std::vector<SetMemo> set_memos;
+
+    // stores of the batched API's intermediates: ProductOfMessages nodes (variable, lo, hi) and JointMarginal nodes (factor); the
+    // stores hold size() entries (multiples of 256)
+    std::map<std::tuple<int32_t, int32_t, int32_t>, int32_t> prod_index;
+    std::map<int32_t, int32_t> joint_index;
+    DevBuf<double2> d_prod;
+    DevBuf<double> d_joint;
+    DevBuf<double> d_mv_prod;       // dim > 1: the ProductOfMessages table (natural form; dim 2..4 in the messages' pair form, dim 64 one row of 4,160 doubles each)
+    int64_t mv_prod_cap = 0;        // entries it holds (a multiple of 256)
+
+    // the XCD-resident cluster (cx_api_ref.hip: cluster_prepare)
+    DevBuf<char> d_cluster_ctl;     // 512 B the launch scribbles on (cx_batch.hip: ClusterCtl)
+    int cluster_state = 0;          // 0 not prepared, 1 ready, -1 off (CX_REF_CLUSTER=0, no memory, another architecture, or a barrier once timed out)
+
+    // cx_log_evidence (cx_evidence.hip): work lists of the graph and scratch, built on the first call; cx_factor_beliefs /
+    // cx_factor_statistics (cx_learn.hip): the grouping's work lists and scratch; cx_sample_posterior (cx_sample.hip): the forest
+    // plan, the links and the per-call scratch
+    std::unique_ptr<ev::Cache, Deleter<ev::Cache>> evidence;
+    std::unique_ptr<fs::Cache, Deleter<fs::Cache>> learn;
+    std::unique_ptr<sp::Plan, Deleter<sp::Plan>> sample;
+};
+
+}  // namespace cx
+
+// The raw exceptions.  The launchers that live in the profiled kernel sources (build.py: KERNEL_SOURCES) assign or take the address of
+// d_chain_linkpar, d_chain_onepass, d_chain_abort (cx_chain.hip), d_marg64_sums, d_marg64_tab, d_marg64_rec (cx_mv64.hip) and own the
+// chain64 (cx_mv64chain.hip) and vmp (cx_vmp.hip) sub-states; an edit of those files' code would void the counter profiles kept
+// under profiles/, so these stay raw pointers of cx_handle, freed where they always were (chain_onepass_free, chain64_free,
+// chain64_tree_free, vmp_free, dev_free_all for the three d_marg64_*).  Everything else a handle owns on the device is in DevState.
+struct cx_handle : cx::DevState {
     cx_config cfg{};
     std::string err;
     hipStream_t stream = nullptr;
@@ -50,13 +206,7 @@ struct cx_handle {
     bool any_linear = false;
 
     // ---- device buffers ----
-    int32_t *d_slice_off = nullptr, *d_partner = nullptr, *d_vbase = nullptr, *d_var_deg = nullptr;
-    int32_t *d_big = nullptr, *d_big_slots = nullptr, *d_big_slot_var = nullptr;      // (dim 2..4: the variable of every slot of the CSR tail)
-    double2 *d_big_tmp = nullptr;   // prefix scratch of the big-variable kernel, one entry per big slot
     int32_t big_start = 0;          // first slot of the big-variable CSR tail
-    uint8_t *d_vinfo = nullptr;
-    double *d_q = nullptr, *d_a = nullptr, *d_b = nullptr;     // per RECEIVING slot: effective rule parameters
-    double *d_sq = nullptr, *d_sa = nullptr, *d_sb = nullptr;  // the same, indexed by the SENDING slot (push)
     // chain scan, set by an owner that drives this handle (cx_vmp.hip's inner handle; never owned here):
     const int32_t *d_q_gamma = nullptr;   // per slot: index into d_q_gmean of the precision variable whose mean sets this factor's variance
     const double *d_q_gmean = nullptr;    //   q = 1 / d_q_gmean[d_q_gamma[slot]] read in place of d_q[slot] (no per-slot table to rewrite per call)
@@ -67,80 +217,37 @@ struct cx_handle {
     int32_t pot64_end_slots[6] = {-1, -1, -1, -1, -1, -1};      // side slots of the path's two END positions: no composition reads them
     bool chain_msgs_unread = false;       // the owner reads the chain links' variable→factor messages and marginals only: the scan need not store
                                           // the factor→variable messages of the links (nothing of this handle is asked for them)
-    double2 *d_f2v = nullptr, *d_v2f = nullptr, *d_marg = nullptr;  // natural-form messages, moment-form marginals
-    double2 *d_f2v_alt = nullptr;   // second factor→variable buffer (Jacobi double buffering of the fused sweep)
-    double2 *d_prev = nullptr;      // snapshot for cx_residual
-    double *d_scratch = nullptr;    // small reduction scratch
-    int64_t device_bytes = 0;
-
-    // factors with more than two edges (cx_kary.hip, CX_FACTOR_GAUSS_LINEAR_N): entry = 8 * row + edge position (OUT first, then IN by
-    // ascending variable id); coefficient c_e = +1 (OUT) / -a_i (IN); their slots have partner -1 (no pairwise rule touches them)
-    int64_t n_kary = 0;
-    std::vector<int32_t> kary_slot, slot_kary;      // [8 n_kary] slot per entry (-1 padding); [nslots] entry of a slot, -1 otherwise
-    std::vector<int32_t> kary_pset;                 // dim 2..4 (cx_kary_mv.hip): [8 n_kary] parameter set of the entry — an IN entry's A, the OUT entry's Q
-    int32_t *d_kary_pset = nullptr, *d_kary_v2f_slots = nullptr, *d_kary_v2f_vars = nullptr;
-    double *d_kary_aq = nullptr;                    // [sets][2][d * d]: A | Q raw
-    int64_t n_kary_v2f = 0, kary_aq_sets = 0;
-    std::vector<double> kary_coef, kary_qb;         // [8 n_kary] c_e; [2 n_kary] q, b
-    int32_t *d_kary_slot = nullptr, *d_slot_kary = nullptr;
-    double *d_kary_coef = nullptr, *d_kary_qb = nullptr;
-    bool kary_dirty = true;
+    int64_t device_bytes = 0;       // the sum of the live DevBufs of this handle (+ what the raw exceptions below added)
 
     // multivariate path (cx_mv.hip), dim in {2,3,4}: SoA component-major buffers [nc][nslots], packed symmetric Lambda
     int nc = 2;                                    // doubles per message (eta + packed Lambda; 64 + 64*64 for dim 64)
     int ncs = 2;                                   // STORED doubles per message slot: dim 2..4 pad nc to whole 16-byte pairs (cx_mv_core.h)
     std::vector<std::vector<double>> psets;        // per parameter set: A (d*d) then Q (d*d)
-    int32_t *d_spdir = nullptr;                    // per SENDING slot: 2*pset + direction of the receiving edge; -1: receiver observed
     std::vector<int32_t> spdir;                    // host copy without the observed-receiver mask
     bool spdir_dirty = true;
     int observed_passes_due = 2;                   // sweeps that still have to write the messages out of observed variables
-    double *d_ptab = nullptr;                      // [2*npsets][3][d*d]: (P, B, C) triples
-    double *d_zero_msg = nullptr;                  // d = 64: one message of zeros (what an absent source reads)
     // dim 16 / 32: the marginal read-out's scratch (sums of the listed variables' messages + their rule records) and identity table
     double *d_marg64_sums = nullptr, *d_marg64_tab = nullptr;
     int32_t *d_marg64_rec = nullptr;
     int64_t marg64_cap = 0;
-    double *d_ptab_bt = nullptr;                   // d = 64: [2*npsets][d*d], the transposes of the B tables (cx_mv64w.hip)
-    int64_t ptab_sets = 0, ptab_bt_sets = 0, max_pset = -1;     // parameter sets the device tables have room for (rewritten in place while that holds)
-    double *d_mv_f2v = nullptr, *d_mv_f2v_alt = nullptr, *d_mv_v2f = nullptr, *d_mv_marg = nullptr, *d_mv_prev = nullptr;
-    // d = 64 work lists (built lazily: they depend on which variables are observed)
-    bool work64_dirty = true, point64_dirty = true;
-    int64_t n_rule64 = 0, n_point64 = 0;
-    int32_t *d_point64_slots = nullptr;
-    int32_t *d_rule64_rec = nullptr;               // 8 words per work item (see k_rule64)
-    // senders of degree 5 .. 8 (a rule sums at most three sources): their variable→factor messages are summed first (k_v2f64) and the
-    // rule reads the stored message; the same per stage of the tree schedule
-    int64_t n_pre64 = 0;
-    int32_t *d_pre64_slots = nullptr, *d_pre64_vars = nullptr, *d_tree_pre_slots = nullptr, *d_tree_pre_vars = nullptr;
+    int64_t max_pset = -1;
+    int64_t n_rule64 = 0, n_point64 = 0;           // d = 64 work lists (DevState: d_rule64_rec, d_point64_slots)
     std::vector<int64_t> tree_pre_off;
 
     // chain-scan schedule (cx_chain.hip): paths of free variables, built lazily by build_chains()
     // cfg.dim of 5 .. 63 as the caller gave it (0 otherwise): such a handle runs as dim 64 with every message, datum and rule matrix
     // embedded block-diagonally (cx_api.hip: pad_* helpers); cfg.dim holds 64
     int user_dim = 0;
-    int sweep_max_w = 0;                 // the widest SELL slice (0: not yet computed): picks the register footprint of the fused sweep
-    int16_t *d_partner16 = nullptr;      // partner[s] - s where every difference fits (kNoPartner16: none); null otherwise (cx_kernels.hip: PACK)
-    bool chains_dirty = true;
-    // CX_SCHED_TREE (cx_tree_plan.h): the stages' items and k-ary entries on the device, their offsets on the host
-    bool tree_dirty = true;
-    int32_t *d_tree_rec = nullptr, *d_tree_kary = nullptr;
-    int64_t *d_tree_stage_off = nullptr;      // the stage table on the device (runs of thin stages go out as one launch)
+    // CX_SCHED_TREE (cx_tree_plan.h): the stages' items and k-ary entries on the device (DevState), their offsets on the host
     std::vector<int64_t> tree_stage_off, tree_kary_off;
     hipGraphExec_t tree_exec = nullptr;    // the stages of one sweep as ONE graph launch (hundreds of small launches otherwise: the sweep was bound by
     hipStream_t tree_capture_stream = nullptr;      //  the host's launch rate); captured on a stream of the handle's own, launched on the caller's
-    bool tree_graph_failed = false;        // capture or instantiation refused once: plain launches from then on
     int64_t tree_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // depth, stages, items, k-ary entries, components, up, down, marginals
-    // the same sweep over heavy paths (cx_tree_plan.h: build_hp), chosen when it takes fewer launches: the paths' arrays live in the chain
-    // fields (d_chain_pos_var .. d_chain_totals; d_chain_skip1 is the way up's), item stages in d_tree_rec as before
-    bool tree_hp = false;
-    int32_t *d_tree_skip1_down = nullptr;
+    // the same sweep over heavy paths (DevState: tree_hp)
     std::vector<int32_t> tree_hp_steps;            // pairs (kind, index): 0 item stage, 1 scan of a light depth on the way up, 2 its final scan
     std::vector<int64_t> tree_hp_pos_off, tree_hp_link_off;
     int32_t tree_hp_marginal_stage = -1;
     int64_t tree_hp_stats[4] = {0, 0, 0, 0};       // light depths, paths of two or more, variables on no such path, launches per sweep
-    // heavy paths through factors with more than two edges: their pairwise parameters per receiving slot are written every sweep
-    // (cx_kary.hip: k_kary_link_params) into d_q and into d_a / d_b — or, on a graph without pairwise linear factors, into these
-    double *d_tree_a = nullptr, *d_tree_b = nullptr;
     int64_t tree_hp_kary_links = 0;
     // dim 2 .. 4 over heavy paths: the scans of cx_mvchain.hip on a light depth's range; links per thread chosen per depth, the
     // interleaved buffers (d_mvc_*) sized for the largest depth and shared by all of them
@@ -154,11 +261,6 @@ struct cx_handle {
     bool chain_side_dirty = true;    // the leaf messages / side sums of the chain positions must be recomputed (data or rule parameters changed)
     bool chain_partition = false;    // the handle holds a time block of a partitioned chain (cx_chain_block_maps was called)
     bool chain_covers_all = false;   // every variable that reads messages is a chain position: the scan's side pass produces all leaf messages
-    int32_t *d_chain_pos_var = nullptr, *d_chain_skip0 = nullptr, *d_chain_skip1 = nullptr;
-    int32_t *d_chain_link_pos = nullptr, *d_chain_from = nullptr, *d_chain_to = nullptr;
-    uint8_t *d_chain_head_fwd = nullptr, *d_chain_head_bwd = nullptr;
-    double2 *d_chain_side = nullptr;
-    void *d_chain_totals = nullptr;
     // the sweeps between two exchanges of a deep-halo partition as ONE graph launch (cx_api_sweep.hip: cx_sweep): the same (first sweep after
     // the exchange, sweeps, buffers) seen a second time is captured, from then on replayed; two slots (an odd batch alternates its buffers)
     struct BatchGraph { uint64_t key = 0; hipGraphExec_t exec = nullptr; int seen = 0; bool failed = false; };
@@ -173,21 +275,13 @@ struct cx_handle {
     void *d_chain_linkpar = nullptr; int64_t chain_linkpar_cap = 0; bool chain_linkpar_dirty = true; const void *chain_linkpar_qg = nullptr; int chain_pos0 = -1;
     int chain_onepass_state = 0, chain_onepass_cus = 0;      // 0 not prepared, 1 ready, -1 off (CX_CHAIN_ONEPASS=0, no memory, or a wait once timed out)
     int64_t chain_onepass_launches = 0;
-    // dim 2..4 (cx_mvchain.hip): rule-table index of each link's two messages, side sums [nc][npos], tile totals of the map scan
-    int32_t *d_chain_tab_fwd = nullptr, *d_chain_tab_bwd = nullptr;
-    double *d_mvc_side = nullptr, *d_mvc_totals = nullptr;
-    int32_t *d_mvc_var_link = nullptr;     // per variable: the chain link whose RIGHT end it is, -1 otherwise (dim 2..4; marginals on demand)
     bool mvc_marg_pending = false;      // dim 2..4 chain scan, compute_marginals_in_sweep == 2: the last sweep left alpha and gamma, the marginals are formed when read
-    double *d_mvc_side_l = nullptr, *d_mvc_alpha = nullptr, *d_mvc_gamma = nullptr, *d_mvc_prefix = nullptr, *d_mvc_wave_carry = nullptr, *d_mvc_block = nullptr;   // thread-interleaved by link, [nc][ntiles * 256 * K]
     int mvc_K = 4;                   // links per thread of the scan (fixed when the chains are built)
     void *chain64 = nullptr;         // dim 64 chain scan (cx_mv64chain.hip): the plan's records, potential and entry arenas on the device
     bool chain_msgs_stale = false;   // dim 2..4 chain scan: the chain messages in d_mv_f2v are older than the last sweep (refreshed on demand)
 
     // halo
     std::vector<int32_t> send_slots, recv_slots;
-    int32_t *d_send_slots = nullptr, *d_recv_slots = nullptr, *d_send_vars = nullptr;
-    double2 *d_send_buf = nullptr, *d_recv_buf = nullptr;
-    bool ext_halo_buffers = false;
     bool halo_state = false;         // halo lists name factor→variable messages of redundant variables (deep halo)
     // deep halo: redundant layer of each variable (cx_halo_set_layers) -> slice range that sweep j after an exchange has to run
     int halo_depth = 0, sweeps_since_exchange = 0;
@@ -205,6 +299,8 @@ struct cx_handle {
     // deep-halo exchange through IPC-mapped receive areas and epoch flags (cx_api_ipc.hip)
     struct IpcConn { void *opened = nullptr; void *mapped = nullptr; char handle[64] = {0}; unsigned long long *flag = nullptr; double2 *area[2] = {nullptr, nullptr}; bool connected = false; };
     std::vector<IpcConn> ipc_conn;   // one per peer entry: where this rank pushes
+    // raw on purpose: the block comes from hipExtMallocWithFlags and is exported to the peers, whose mapped views are not ours to free;
+    // both are made and freed by cx_api_ipc.hip alone (ipc_destroy), apart from the graph's memory and uncounted
     void *d_ipc_block = nullptr;     // this rank's flags + two receive areas (fine-grained, exported)
     void *d_ipc_local = nullptr;     // push completion counter, error word
     int64_t ipc_area_bytes = 0, ipc_epoch = 0, ipc_pushed = 0;   // epochs unpacked / pushed
@@ -215,35 +311,22 @@ struct cx_handle {
     double damping = 0.0;            // cx_set_damping: new = (1 - damping) rule + damping old (fused and flooding sweeps)
     // cx_set_messages of a long list the caller repeats (an iteration re-sets its priors before every call): ids -> slots / variables / edges,
     // kept for the last lists (the ids themselves are kept and compared: a hash alone would be trusted with the device's memory)
-    struct SetMemo { uint64_t key = 0, used = 0; int32_t direction = 0; std::vector<int64_t> var_ids, fac_ids, edges; std::vector<int32_t> idx, vars; };
-    std::vector<SetMemo> set_memos;
     uint64_t set_memo_tick = 0;
     uint64_t vinfo_epoch = 0;        // bumped whenever the observed flags of vinfo change (a cached "every free variable" request is then stale)
     bool in_sweep = false;
     bool v2f_stale = false;          // fused schedule without materialisation: v2f must be recomputed before use
-    int mv_max_deg = 0;              // dim 2..4: widest slice of the graph (0: not computed yet)
     bool chain_v2f_from_scan = false; // the scan also stores the variable→factor messages of the chain links (set by cx_vmp.hip on its inner handle)
     bool offchain_marg_dirty = true; // chain scan: marginals of variables OFF the chains (observed, stand-ins) are due — they depend on
                                      // stored factor→variable messages only, so a full variable phase runs after those were set
 
     // stores of the batched API's intermediates: ProductOfMessages nodes (variable, lo, hi) and JointMarginal nodes (factor)
-    std::map<std::tuple<int32_t, int32_t, int32_t>, int32_t> prod_index;
-    std::map<int32_t, int32_t> joint_index;
     std::vector<uint8_t> lin_out_is_second;   // per factor (GAUSS_LINEAR): the OUT edge is the edge of the higher variable id
     std::vector<int8_t> np_role;              // per CSR edge: the role on a CX_FACTOR_NORMAL_PRECISION factor, -1 elsewhere (empty: no such factor)
     std::vector<uint8_t> var_gamma;           // per variable: 1 = the precision of such factors, Gamma-distributed (marginal stored as (shape, scale))
     std::vector<int32_t> fac_edges;           // [2 nf] CSR edges of each (≤ 2-edge) factor, built on first use
-    double2 *d_prod = nullptr;
-    double *d_joint = nullptr;
-    int64_t prod_cap = 0, joint_cap = 0;
-    double *d_mv_prod = nullptr;         // dim > 1: the ProductOfMessages table (natural form; dim 2..4 in the messages' pair form, dim 64 one row of 4,160 doubles each)
-    int64_t mv_prod_cap = 0;             // entries it holds (a multiple of 256)
-
 
     // the XCD-resident cluster (cx_batch.hip: k_ref_cluster; cx_api_ref.hip: cluster_prepare / cluster_run): stage plans of wide stages in ONE launch
-    void *d_cluster_ctl = nullptr;   // 512 B the launch scribbles on (cx_batch.hip: ClusterCtl)
     int cluster_cu = 0;              // compute units = workgroups of a cluster launch
-    int cluster_state = 0;           // 0 not prepared, 1 ready, -1 off (CX_REF_CLUSTER=0, no memory, another architecture, or a barrier once timed out)
     int64_t cluster_recoveries = 0;  // calls whose cluster gave up at a barrier and that were finished on plain launches (cx_cluster_stats)
     std::string cluster_note;        // what happened, for cx_last_error's reader
     int64_t cluster_max_items = 16384, cluster_min_items = 128;      // a stage wider than max (one pass of the members) is a launch of its own on the whole chip; plans of fewer than min items per stage are chains
@@ -257,16 +340,7 @@ struct cx_handle {
 
     // cx_log_evidence (cx_evidence.hip): work lists of the graph and scratch, built on the first call (opaque); param_epoch moves on
     // with every change of rule parameters after cx_graph_create (matrices, coefficients, edge sets), which the lists' parameter part follows
-    void *evidence = nullptr;
     uint64_t param_epoch = 0;
-    // cx_factor_beliefs / cx_factor_statistics (cx_learn.hip): the grouping's work lists and scratch (opaque)
-    void *learn = nullptr;
-    // cx_sample_posterior (cx_sample.hip): the forest plan, the links and the per-call scratch (opaque)
-    void *sample = nullptr;
-
-    // staging for set/get/batch
-    void *d_stage = nullptr;
-    int64_t stage_bytes = 0;
 
     // profiling
     bool profiling = false, prof_armed = false;
@@ -309,13 +383,11 @@ void launch_gather(cx_handle *h, const double2 *src, const int32_t *d_idx, doubl
 void launch_seed(cx_handle *h, double2 *buf, int64_t n, double2 value, const int32_t *partner);
 // factors with more than two edges (cx_kary.hip)
 int32_t kary_upload(cx_handle *h);
-void kary_free(cx_handle *h);
 void launch_kary(cx_handle *h, const double2 *v2f, double2 *f2v_out);
 void launch_kary_items(cx_handle *h, const int32_t *d_entries, int64_t n);
 void launch_kary_link_params(cx_handle *h, int64_t link_lo, int64_t nlinks, double *a, double *b);
 // the same factors for dim 2..4 (cx_kary_mv.hip)
 int32_t kary_mv_upload(cx_handle *h);
-void kary_mv_free(cx_handle *h);
 void mv_launch_kary(cx_handle *h, double *f2v_out = nullptr);
 void launch_residual(cx_handle *h, const double2 *cur, const double2 *prev, int64_t n, double *d_out);
 void launch_chain_scan(cx_handle *h, double2 *f2v, bool fused_leaves, int marg_form, bool chain_v2f);
@@ -402,8 +474,5 @@ void comm_destroy(cx_handle *h);
 bool comm_exchange(cx_handle *h, std::string &err, bool packed_on_comm_stream);
 bool comm_exchange_on(cx_handle *h, hipStream_t stream, std::string &err);
 void ipc_destroy(cx_handle *h);  // cx_api_ipc.hip
-void evidence_free(cx_handle *h);  // cx_evidence.hip
-void learn_free(cx_handle *h);  // cx_learn.hip
-void sample_free(cx_handle *h);  // cx_sample.hip
 
 }  // namespace cx

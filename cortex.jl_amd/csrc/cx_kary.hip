@@ -117,13 +117,6 @@ int32_t kary_upload(cx_handle *h) {
     return CX_OK;
 }
 
-void kary_free(cx_handle *h) {
-    kary_mv_free(h);
-    for (void *p : {(void *)h->d_kary_slot, (void *)h->d_kary_coef, (void *)h->d_kary_qb, (void *)h->d_slot_kary}) if (p) (void)hipFree(p);
-    h->d_kary_slot = h->d_slot_kary = nullptr; h->d_kary_coef = h->d_kary_qb = nullptr;
-    h->n_kary = 0; h->kary_slot.clear(); h->kary_coef.clear(); h->kary_qb.clear(); h->slot_kary.clear(); h->kary_pset.clear(); h->kary_dirty = true;
-}
-
 // all factor→variable messages of the k-ary factors from the stored variable→factor messages
 void launch_kary(cx_handle *h, const double2 *v2f, double2 *f2v_out) {
     if (h->n_kary == 0) return;

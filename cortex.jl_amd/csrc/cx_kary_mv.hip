@@ -44,17 +44,12 @@ int32_t kary_mv_upload(cx_handle *h) {
     const size_t per = (size_t)2 * d * d, nsets = h->psets.size();
     std::vector<double> aq(per * std::max<size_t>(nsets, 1), 0.0);
     for (size_t i = 0; i < nsets; i++) if (!h->psets[i].empty()) std::memcpy(&aq[per * i], h->psets[i].data(), per * 8);
-    if (h->d_kary_aq && h->kary_aq_sets < (int64_t)nsets) { tree_graph_drop(h); ref_graphs_drop(h); (void)hipFree(h->d_kary_aq); h->d_kary_aq = nullptr; }      // (captured launches hold the address)
+    if (h->d_kary_aq && h->kary_aq_sets < (int64_t)nsets) { tree_graph_drop(h); ref_graphs_drop(h); h->d_kary_aq.reset(); }      // (captured launches hold the address)
     if (!h->d_kary_aq) { if ((rc = dev_alloc(h, &h->d_kary_aq, (int64_t)aq.size())) != CX_OK) return rc; h->kary_aq_sets = (int64_t)nsets; }
     CX_HIP(h, hipMemcpy(h->d_kary_aq, aq.data(), aq.size() * 8, hipMemcpyHostToDevice));
     CX_HIP(h, hipMemcpy(h->d_kary_pset, h->kary_pset.data(), h->kary_pset.size() * 4, hipMemcpyHostToDevice));
     h->kary_dirty = false;
     return CX_OK;
-}
-
-void kary_mv_free(cx_handle *h) {
-    for (void *p : {(void *)h->d_kary_pset, (void *)h->d_kary_aq, (void *)h->d_kary_v2f_slots, (void *)h->d_kary_v2f_vars}) if (p) (void)hipFree(p);
-    h->d_kary_pset = nullptr; h->d_kary_aq = nullptr; h->d_kary_v2f_slots = h->d_kary_v2f_vars = nullptr; h->n_kary_v2f = 0; h->kary_aq_sets = 0;
 }
 
 // the k-ary part of one fused sweep (input buffer d_mv_f2v, output f2v_out)

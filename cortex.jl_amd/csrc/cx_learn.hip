@@ -212,33 +212,31 @@ struct Cache {
     int64_t n_groups = 0;
     std::vector<int64_t> ids, groups;
     // the lists: items (pair rows by group, then factor index), chunks, the reduction levels
-    int64_t n_items = 0, n_chunks = 0, rows_cap = 0;
+    int64_t n_items = 0, n_chunks = 0;
     std::vector<int64_t> level_off, level_n;       // per level: offset into d_seg, output rows
     std::vector<int64_t> out_group;                // the group of every final row (ascending)
-    int32_t *d_items = nullptr, *d_cbeg = nullptr, *d_seg = nullptr;
-    double *d_rows[2] = {nullptr, nullptr};
+    DevBuf<int32_t> d_items, d_cbeg, d_seg;
+    DevBuf<double> d_rows[2];
     double *h_rows = nullptr;                      // pinned: the final rows
-    int64_t h_rows_cap = 0;
-    // beliefs
-    int32_t *d_brows = nullptr;
-    double *d_bout = nullptr;
-    int64_t brows_cap = 0, bout_cap = 0;
+    // beliefs (grown on demand)
+    DevBuf<int32_t> d_brows;
+    DevBuf<double> d_bout;
     std::vector<int32_t> row_of_fac;               // pair row of every factor index (-1: none)
+    Cache() = default;
+    Cache(const Cache &) = delete;
+    ~Cache() { if (h_rows) (void)hipHostFree(h_rows); }
 };
 
-template <class T>
-void free_ptr(T *&p) { if (p) (void)hipFree((void *)p); p = nullptr; }
-
 void free_lists(Cache &L) {
-    free_ptr(L.d_items); free_ptr(L.d_cbeg); free_ptr(L.d_seg); free_ptr(L.d_rows[0]); free_ptr(L.d_rows[1]);
+    reset_all(L.d_items, L.d_cbeg, L.d_seg, L.d_rows[0], L.d_rows[1]);
     if (L.h_rows) (void)hipHostFree(L.h_rows);
-    L.h_rows = nullptr; L.h_rows_cap = 0; L.rows_cap = 0;
+    L.h_rows = nullptr;
     L.valid = false;
 }
 
 Cache &cache_of(cx_handle *h, const ev::Cache &E) {
-    if (!h->learn) h->learn = new Cache();
-    Cache &L = *static_cast<Cache *>(h->learn);
+    if (!h->learn) h->learn.reset(new Cache());
+    Cache &L = *h->learn;
     if (L.row_of_fac.size() != (size_t)h->nf) {
         L.row_of_fac.assign((size_t)h->nf, -1);
         for (size_t r = 0; r < E.pair_fac.size(); r++) L.row_of_fac[(size_t)E.pair_fac[r]] = (int32_t)r;
@@ -349,9 +347,7 @@ int32_t build_lists(cx_handle *h, Cache &L, const std::vector<int32_t> &grp, int
     const int64_t rows = std::max<int64_t>(max_rows, 1) * 2 * nw;
     if ((rc = dev_alloc(h, &L.d_rows[0], rows)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &L.d_rows[1], rows)) != CX_OK) return rc;
-    L.rows_cap = rows;
-    L.h_rows_cap = std::max<int64_t>((int64_t)row_group.size(), 1) * 2 * nw;
-    CX_HIP(h, hipHostMalloc((void **)&L.h_rows, (size_t)L.h_rows_cap * sizeof(double), hipHostMallocDefault));
+    CX_HIP(h, hipHostMalloc((void **)&L.h_rows, (size_t)(std::max<int64_t>((int64_t)row_group.size(), 1) * 2 * nw) * sizeof(double), hipHostMallocDefault));
     CX_HIP(h, hipStreamSynchronize(h->stream));      // (the host vectors die here)
     L.n_items = n_items;
     L.n_chunks = (int64_t)cbeg.size() - 1;
@@ -386,15 +382,7 @@ int nb_of(int d) { return d == 1 ? SLay<1>::NB : d == 2 ? SLay<2>::NB : d == 3 ?
 
 }  // namespace fs
 
-void learn_free(cx_handle *h) {
-    if (!h || !h->learn) return;
-    fs::Cache *L = static_cast<fs::Cache *>(h->learn);
-    fs::free_lists(*L);
-    fs::free_ptr(L->d_brows);
-    fs::free_ptr(L->d_bout);
-    delete L;
-    h->learn = nullptr;
-}
+template <> void Deleter<fs::Cache>::operator()(fs::Cache *L) const { delete L; }
 
 }  // namespace cx
 
@@ -419,16 +407,7 @@ extern "C" int32_t cx_factor_beliefs(cx_handle *h, int64_t n, const int64_t *fac
             if (rows[(size_t)i] < 0) return fail(h, CX_ERR_UNSUPPORTED, "cx_factor_beliefs: factor " + std::to_string(factor_ids[i]) + " is not a Gaussian factor of two variables");
         }
         const int d = h->cfg.dim, nb = cx::fs::nb_of(d);
-        if (L.brows_cap < n) {
-            cx::fs::free_ptr(L.d_brows);
-            if ((rc = dev_alloc(h, &L.d_brows, n)) != CX_OK) return rc;
-            L.brows_cap = n;
-        }
-        if (L.bout_cap < n * nb) {
-            cx::fs::free_ptr(L.d_bout);
-            if ((rc = dev_alloc(h, &L.d_bout, n * nb)) != CX_OK) return rc;
-            L.bout_cap = n * nb;
-        }
+        if ((rc = L.d_brows.ensure(h, n)) != CX_OK || (rc = L.d_bout.ensure(h, n * nb)) != CX_OK) return rc;
         CX_HIP(h, hipMemcpyAsync(L.d_brows, rows.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
         cx::ev::var_pass(h, E);
         switch (d) {

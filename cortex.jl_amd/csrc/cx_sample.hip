@@ -556,44 +556,30 @@ struct Depth {
     int64_t top_off = 0;                      // offset into d_top
 };
 
-struct Plan {
+// the plan's device side; a rebuild starts from a default-constructed one
+struct PlanDev {
+    DevBuf<int32_t> d_pos_var, d_var_pos, d_comp, d_cpos, d_cbeg, d_dslot;
+    DevBuf<int32_t> d_roots, d_klink, d_xoff, d_xvar;
+    DevBuf<int4> d_plink, d_top;
+    DevBuf<int2> d_rng;
+    DevBuf<double> d_link, d_xblk;
+    DevBuf<int32_t> d_ccb;                    // per component: its chunks of the status pass
+    DevBuf<uint8_t> d_st, d_cflag, d_cpart;
+    // per call, grown on demand: z, the level buffers, the caller's noise, the requested variables, the output
+    DevBuf<double> d_Z, d_noise, d_out;
+    std::vector<DevBuf<double>> d_Gc, d_oc, d_carry;      // per level
+    DevBuf<int32_t> d_vid;
+};
+
+struct Plan : PlanDev {
     bool valid = false;
     int64_t nv = -1, ne = -1;
     std::vector<uint8_t> vinfo;               // what the plan was built for (the observed flags)
-    int64_t npos = 0, n_comp = 0, n_root = 0, n_plink = 0, n_klink = 0, n_xent = 0;
+    int64_t npos = 0, n_comp = 0, n_root = 0, n_plink = 0, n_klink = 0, n_xent = 0, n_chunk = 0;
     std::vector<Depth> depths;
     std::vector<int64_t> level_cap;           // per level (index 1 ..): the most items any depth has there
-    int32_t *d_pos_var = nullptr, *d_var_pos = nullptr, *d_comp = nullptr, *d_cpos = nullptr, *d_cbeg = nullptr, *d_dslot = nullptr;
-    int32_t *d_roots = nullptr, *d_klink = nullptr, *d_xoff = nullptr, *d_xvar = nullptr;
-    int4 *d_plink = nullptr, *d_top = nullptr;
-    int2 *d_rng = nullptr;
-    double *d_link = nullptr, *d_xblk = nullptr;
-    int32_t *d_ccb = nullptr;                 // per component: its chunks of the status pass
-    int64_t n_chunk = 0;
-    uint8_t *d_st = nullptr, *d_cflag = nullptr, *d_cpart = nullptr;
     std::vector<uint8_t> h_cflag;
-    // per call, grown on demand: z, the level buffers, the caller's noise, the requested variables, the output
-    int64_t z_cap = 0, lvl_scap = -1, noise_cap = 0, vid_cap = 0, out_cap = 0;
-    double *d_Z = nullptr, *d_noise = nullptr, *d_out = nullptr;
-    std::vector<double *> d_Gc, d_oc, d_carry;
-    int32_t *d_vid = nullptr;
 };
-
-template <class T>
-void free_ptr(T *&p) { if (p) (void)hipFree((void *)p); p = nullptr; }
-
-void free_plan(Plan &P) {
-    for (int32_t **p : {&P.d_pos_var, &P.d_var_pos, &P.d_comp, &P.d_cpos, &P.d_cbeg, &P.d_dslot, &P.d_roots, &P.d_klink, &P.d_xoff, &P.d_xvar, &P.d_vid})
-        free_ptr(*p);
-    free_ptr(P.d_plink); free_ptr(P.d_top); free_ptr(P.d_rng);
-    free_ptr(P.d_link); free_ptr(P.d_xblk); free_ptr(P.d_st); free_ptr(P.d_cflag); free_ptr(P.d_cpart); free_ptr(P.d_ccb);
-    free_ptr(P.d_Z); free_ptr(P.d_noise); free_ptr(P.d_out);
-    for (auto *v : {&P.d_Gc, &P.d_oc, &P.d_carry})
-        for (double *&p : *v) free_ptr(p);
-    P.d_Gc.clear(); P.d_oc.clear(); P.d_carry.clear();
-    P.z_cap = P.noise_cap = P.vid_cap = P.out_cap = 0; P.lvl_scap = -1;
-    P.valid = false;
-}
 
 int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string &who) {
     using namespace cxh;
@@ -775,7 +761,8 @@ int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string 
     std::vector<int32_t> dslot((size_t)nv, 0);
     for (int64_t v = 0; v < nv; v++) if (h->var_off[v + 1] > h->var_off[v]) dslot[v] = slot_of_edge(h, h->var_off[v]);
     (void)ne;
-    free_plan(P);
+    static_cast<PlanDev &>(P) = PlanDev();
+    P.valid = false;
     const int d = h->cfg.dim, ln = 2 * d * d + d;
     if ((rc = dev_upload(h, &P.d_pos_var, pos_var)) != CX_OK) return rc;
     if ((rc = dev_upload(h, &P.d_var_pos, var_pos)) != CX_OK) return rc;
@@ -799,7 +786,7 @@ int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string 
     if ((rc = dev_alloc(h, &P.d_st, P.npos)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &P.d_cflag, P.n_comp)) != CX_OK) return rc;
     const int levels = (int)P.level_cap.size() - 1;
-    P.d_Gc.assign((size_t)levels + 1, nullptr); P.d_oc.assign((size_t)levels + 1, nullptr); P.d_carry.assign((size_t)levels + 1, nullptr);
+    P.d_Gc.resize((size_t)levels + 1); P.d_oc.resize((size_t)levels + 1); P.d_carry.resize((size_t)levels + 1);
     for (int l = 1; l <= levels; l++)
         if ((rc = dev_alloc(h, &P.d_Gc[(size_t)l], P.level_cap[(size_t)l] * d * d)) != CX_OK) return rc;
     CX_HIP(h, hipStreamSynchronize(h->stream));      // (the host vectors die here)
@@ -815,30 +802,12 @@ int32_t ensure_chunk(cx_handle *h, Plan &P, int64_t S, int64_t n_out, bool noise
     using namespace cxh;
     const int d = h->cfg.dim;
     int32_t rc;
-    if (P.z_cap < P.npos * S * d) {
-        free_ptr(P.d_Z);
-        if ((rc = dev_alloc(h, &P.d_Z, std::max<int64_t>(P.npos * S * d, 1))) != CX_OK) return rc;
-        P.z_cap = P.npos * S * d;
-    }
-    if (P.lvl_scap < S) {
-        for (size_t l = 1; l < P.level_cap.size(); l++) {
-            free_ptr(P.d_oc[l]); free_ptr(P.d_carry[l]);
-            if ((rc = dev_alloc(h, &P.d_oc[l], P.level_cap[l] * S * d)) != CX_OK) return rc;
-            if ((rc = dev_alloc(h, &P.d_carry[l], P.level_cap[l] * S * d)) != CX_OK) return rc;
-        }
-        P.lvl_scap = S;
-    }
-    if (noise && P.noise_cap < S * h->nv * d) {
-        free_ptr(P.d_noise);
-        if ((rc = dev_alloc(h, &P.d_noise, S * h->nv * d)) != CX_OK) return rc;
-        P.noise_cap = S * h->nv * d;
-    }
-    if (P.out_cap < S * n_out * d) {
-        free_ptr(P.d_out);
-        if ((rc = dev_alloc(h, &P.d_out, std::max<int64_t>(S * n_out * d, 1))) != CX_OK) return rc;
-        P.out_cap = S * n_out * d;
-    }
-    return CX_OK;
+    if ((rc = P.d_Z.ensure(h, P.npos * S * d)) != CX_OK) return rc;
+    for (size_t l = 1; l < P.level_cap.size(); l++)
+        if ((rc = P.d_oc[l].ensure(h, std::max<int64_t>(P.level_cap[l] * S * d, 1))) != CX_OK ||
+            (rc = P.d_carry[l].ensure(h, std::max<int64_t>(P.level_cap[l] * S * d, 1))) != CX_OK) return rc;
+    if (noise && (rc = P.d_noise.ensure(h, S * h->nv * d)) != CX_OK) return rc;
+    return P.d_out.ensure(h, S * n_out * d);
 }
 
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
@@ -912,13 +881,7 @@ void launch_all(cx_handle *h, const ev::Cache &E, Plan &P, int S, const Gen &g, 
 
 }  // namespace sp
 
-void sample_free(cx_handle *h) {
-    if (!h || !h->sample) return;
-    sp::Plan *P = static_cast<sp::Plan *>(h->sample);
-    sp::free_plan(*P);
-    delete P;
-    h->sample = nullptr;
-}
+template <> void Deleter<sp::Plan>::operator()(sp::Plan *P) const { delete P; }
 
 }  // namespace cx
 
@@ -936,8 +899,8 @@ extern "C" int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t
         int32_t rc;
         if ((rc = cx::ev::prepare(h, who, Ep)) != CX_OK) return rc;
         cx::ev::Cache &E = *Ep;
-        if (!h->sample) h->sample = new cx::sp::Plan();
-        cx::sp::Plan &P = *static_cast<cx::sp::Plan *>(h->sample);
+        if (!h->sample) h->sample.reset(new cx::sp::Plan());
+        cx::sp::Plan &P = *h->sample;
         // the plan follows the graph (a new graph frees it) and the observed flags
         if (!P.valid || P.nv != h->nv || P.ne != h->ne || P.vinfo != h->vinfo) {
             P.valid = false;
@@ -953,11 +916,7 @@ extern "C" int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t
                 if (v < 0) return fail(h, CX_ERR_NOT_FOUND, who + ": no variable " + std::to_string(variable_ids[i]));
                 vids[(size_t)i] = (int32_t)v;
             }
-            if (P.vid_cap < n) {
-                cx::sp::free_ptr(P.d_vid);
-                if ((rc = dev_alloc(h, &P.d_vid, n)) != CX_OK) return rc;
-                P.vid_cap = n;
-            }
+            if ((rc = P.d_vid.ensure(h, n)) != CX_OK) return rc;
             if (n) CX_HIP(h, hipMemcpyAsync(P.d_vid, vids.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
         }
         // samples in chunks of at most ~2^27 doubles of scratch (z, the level buffers, the output, the caller's noise)
