@@ -15,19 +15,15 @@ using namespace cxh;
 namespace cxh {
 
 void dev_free_all(cx_handle *h) {
-    // captured graphs hold device addresses: they go before the memory they name
-    tree_graph_drop(h);
-    batch_graph_drop(h);
-    ref_free(h);
     // the raw exceptions (cx_internal.h), freed where they always were
     cx::chain64_free(h);
     cx::chain_onepass_free(h);
     for (void *p : {(void *)h->d_marg64_sums, (void *)h->d_marg64_tab, (void *)h->d_marg64_rec}) if (p) (void)hipFree(p);
     h->d_marg64_sums = h->d_marg64_tab = nullptr; h->d_marg64_rec = nullptr; h->marg64_cap = 0;
     cx::chain64_tree_free(h);
-    // every buffer, cache, flag and counter of the graph on the device
+    // every graph, buffer, cache, flag and counter of the graph on the device, in DevState's order
     static_cast<cx::DevState &>(*h) = cx::DevState();
-    h->device_bytes = 0;
+    h->device_bytes = 0; h->d_ref_list = nullptr; h->batch_epoch++;
 }
 
 }  // namespace cxh
@@ -125,8 +121,6 @@ int32_t cx_destroy(cx_handle *h) {
     for (auto &r : h->recs) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
     cx::comm_destroy(h);
     cx::ipc_destroy(h);
-    tree_graph_drop(h);
-    if (h->tree_capture_stream) { (void)hipStreamDestroy(h->tree_capture_stream); h->tree_capture_stream = nullptr; }
     cx::vmp_free(h);
     dev_free_all(h);
     delete h;
@@ -159,10 +153,9 @@ static int32_t upload_ptab(cx_handle *h) {
             return fail(h, CX_ERR_INVALID_ARGUMENT, "cx_set_factor_matrices: Q of parameter set " + std::to_string(i) + " is not positive definite");
     }
     CX_HIP(h, hipStreamSynchronize(h->stream));
-    // The tree schedule's stages are captured into a HIP graph with the table pointers baked in by value (cx_api_sweep.hip:
-    // tree_sweep): the tables are rewritten IN PLACE while their size holds, and a graph captured over a table that has to move is
-    // dropped before the old allocation goes (the next sweep captures again).
-    if (h->d_ptab && h->ptab_sets < nsets) { tree_graph_drop(h); ref_graphs_drop(h); h->d_ptab.reset(); }      // (the reference-order plans' graphs too: cx_api_ref.hip)
+    // Captured sweeps hold the table pointers by value (cx_api_sweep.hip: tree_sweep; cx_api_ref.hip: run_entry): the tables are rewritten
+    // IN PLACE while their size holds, and the graphs are dropped before a table that has to move goes (the next sweep captures again).
+    if (h->d_ptab && h->ptab_sets < nsets) { captured_graphs_drop(h); h->d_ptab.reset(); }
     if (!h->d_ptab) { int32_t rc = dev_alloc(h, &h->d_ptab, (int64_t)(per * nsets)); if (rc != CX_OK) return rc; h->ptab_sets = nsets; }
     CX_HIP(h, hipMemcpy(h->d_ptab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
     h->pot64_fresh = false;
@@ -178,7 +171,7 @@ static int32_t upload_ptab(cx_handle *h) {
             if (rc0 != CX_OK) return rc0;
             CX_HIP(h, hipMemset(h->d_zero_msg, 0, (size_t)(d + d * d) * 8));
         }
-        if (h->d_ptab_bt && h->ptab_bt_sets < nsets) { tree_graph_drop(h); h->d_ptab_bt.reset(); }
+        if (h->d_ptab_bt && h->ptab_bt_sets < nsets) { captured_graphs_drop(h); h->d_ptab_bt.reset(); }
         if (!h->d_ptab_bt) {
             int32_t rc = dev_alloc(h, &h->d_ptab_bt, (int64_t)bt.size());
             if (rc != CX_OK) return rc;

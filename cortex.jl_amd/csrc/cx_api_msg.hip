@@ -263,7 +263,7 @@ static int32_t grow_store(cx_handle *h, cx::DevBuf<T> &buf, int64_t need, int64_
     if (buf) {
         CX_HIP(h, hipMemcpyAsync(nb, buf, (size_t)(cap * per_record) * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
         CX_HIP(h, hipStreamSynchronize(h->stream));
-        tree_graph_drop(h); ref_graphs_drop(h);
+        captured_graphs_drop(h);
     }
     buf = std::move(nb);
     return CX_OK;

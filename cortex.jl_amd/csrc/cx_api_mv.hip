@@ -509,7 +509,7 @@ int32_t mv_ensure_prod_store(cx_handle *h) {
     if (h->d_mv_prod) {
         CX_HIP(h, hipMemcpyAsync(bigger, h->d_mv_prod, (size_t)(h->mv_prod_cap * per) * 8, hipMemcpyDeviceToDevice, h->stream));
         CX_HIP(h, hipStreamSynchronize(h->stream));
-        tree_graph_drop(h); ref_graphs_drop(h);      // captured launches hold the table's address by value
+        captured_graphs_drop(h);      // captured launches hold the table's address by value
     }
     h->d_mv_prod = std::move(bigger); h->mv_prod_cap = cap;      // (the old table is freed here)
     return CX_OK;

@@ -16,7 +16,7 @@
 using namespace cxh;
 namespace rs = cx::refsched;
 
-namespace {
+namespace cx {
 
 struct PlanEntry {
     uint64_t key = 0, req_key = 0;
@@ -36,8 +36,7 @@ struct PlanEntry {
     // a stored variable→factor message (k_rule64w) — over these lists, by stage
     cx::DevBuf<int32_t> d64_prod, d64_v2f_slot, d64_v2f_var, d64_point, d64_rule;
     std::vector<int64_t> off64_prod, off64_v2f, off64_point, off64_rule;
-    hipGraphExec_t exec = nullptr;
-    bool graph_failed = false;
+    cx::GraphExec graph;                        // the launches of the plan as one; names the buffers above, declared after them: destroyed before them
     bool cluster = false;                       // every stage in ONE launch of an XCD-resident cluster (cx_batch.hip: k_ref_cluster)
     std::shared_ptr<const rs::State> post;      // the readiness state the call leaves
     std::vector<int32_t> order;                 // the executions, in the reference's order (cx_ref_trace)
@@ -71,10 +70,14 @@ struct RefSched {
     int max_entries = 16, run_max = 1024;      // C4 as launches, ms per call: every stage a launch 57.6, runs of stages <= 1024 items 52.8, <= 4096 items 102 (one workgroup is slow on a wide stage)
 };
 
-RefSched *ref_of(cx_handle *h) { return (RefSched *)h->ref; }
+template <> void Deleter<RefSched>::operator()(RefSched *R) const { delete R; }
 
-// a captured plan names its entry's buffers: it goes before the entry is erased (the buffers free themselves)
-void entry_graph_drop(PlanEntry &e) { if (e.exec) { (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; } }
+}  // namespace cx
+
+namespace {
+
+using cx::PlanEntry, cx::RefSched;
+RefSched *ref_of(cx_handle *h) { return h->ref.get(); }
 
 rs::State &writable(RefSched *R) {
     R->touched = true;
@@ -152,26 +155,9 @@ int32_t run_entry(cx_handle *h, RefSched *R, PlanEntry &e) {
         return cluster_run(h, e.d_flat, e.d_rec, e.d_stage_off, e.stage_off, (int64_t)e.stage_off.size() - 1, &e.launches);
     }
     static const bool graphs = [] { const char *v = std::getenv("CX_REF_GRAPH"); return !(v && v[0] == '0'); }();
-    if (graphs && !e.graph_failed && !h->profiling && !e.exec && e.launches > 1) {
-        hipError_t er = hipSuccess;
-        if (!h->tree_capture_stream) er = hipStreamCreateWithFlags(&h->tree_capture_stream, hipStreamNonBlocking);
-        hipGraph_t g = nullptr;
-        if (er == hipSuccess) er = hipStreamBeginCapture(h->tree_capture_stream, hipStreamCaptureModeThreadLocal);
-        if (er == hipSuccess) {
-            hipStream_t user = h->stream;
-            h->stream = h->tree_capture_stream;
-            (void)issue(h, R, e, false);
-            h->stream = user;
-            er = hipStreamEndCapture(h->tree_capture_stream, &g);
-        }
-        if (er == hipSuccess && g) er = hipGraphInstantiate(&e.exec, g, nullptr, nullptr, 0);
-        if (g) (void)hipGraphDestroy(g);
-        if (er != hipSuccess || !e.exec) { (void)hipGetLastError(); e.exec = nullptr; e.graph_failed = true; }
-    }
-    if (e.exec && !h->profiling) {
-        if (hipGraphLaunch(e.exec, h->stream) == hipSuccess) return CX_OK;
-        (void)hipGetLastError();
-        (void)hipGraphExecDestroy(e.exec); e.exec = nullptr; e.graph_failed = true;
+    if (!h->profiling) {
+        if (graphs && !e.graph && !e.graph.failed() && e.launches > 1) (void)capture(h, e.graph, [&] { (void)issue(h, R, e, false); });
+        if (e.graph && launch(h, e.graph)) return CX_OK;
     }
     (void)issue(h, R, e, false);
     return CX_OK;
@@ -358,19 +344,10 @@ int32_t cluster_run(cx_handle *h, const int32_t *d_flat, const int32_t *d_rec, c
     return CX_OK;
 }
 
-void ref_free(cx_handle *h) {
-    RefSched *R = ref_of(h);
-    if (!R) return;
-    ref_graphs_drop(h);
-    delete R;
-    h->ref = nullptr; h->d_ref_list = nullptr;
-}
-
-// the captured graphs hold the product store's address by value: dropped when the store moves
-void ref_graphs_drop(cx_handle *h) {
-    RefSched *R = ref_of(h);
-    if (!R) return;
-    for (auto &e : R->cache) entry_graph_drop(e);
+void captured_graphs_drop(cx_handle *h) {
+    h->tree_graph.reset();
+    batch_graph_drop(h);
+    if (h->ref) for (auto &e : h->ref->cache) e.graph.reset();
 }
 
 // the segment-tree nodes of the variables of degree > 5 live in the handle's product store, under the keys cx_update_batch's
@@ -410,7 +387,7 @@ int32_t ref_build(cx_handle *h) {
     (void)cluster_prepare(h);
     if (const char *v = std::getenv("CX_REF_CACHE_MB")) R->max_bytes = std::max<int64_t>(1, std::atoll(v)) << 20;
     if (const char *v = std::getenv("CX_REF_RUN_MAX")) R->run_max = std::min(1024, std::max(0, std::atoi(v)));      // (k_flat_run: a stage is one pass of 1,024 threads)
-    h->ref = R.release();
+    h->ref.reset(R.release());
     return CX_OK;
 }
 
@@ -597,7 +574,7 @@ int32_t ref_sweep(cx_handle *h, const int32_t *req, int64_t n, const uint64_t *k
                 size_t lru = 0;
                 for (size_t i = 1; i < R->cache.size(); i++) if (R->cache[i].last_used < R->cache[lru].last_used) lru = i;
                 CX_HIP(h, hipStreamSynchronize(h->stream));
-                entry_graph_drop(R->cache[lru]);
+                R->cache[lru].graph.reset();      // (it names the entry's buffers, which erase() releases first)
                 R->cache.erase(R->cache.begin() + lru);
             }
             PlanEntry e;
@@ -800,8 +777,7 @@ int32_t cx_graph_wire(cx_handle *h, int64_t n, const cx_item *signals, const cx_
         const int32_t rc = rs::build_user_wiring(h, n, s.data(), d.data(), flags, W, err);
         if (rc != CX_OK) return fail(h, rc, err);
         CX_HIP(h, hipStreamSynchronize(h->stream));
-        ref_graphs_drop(h);
-        R->cache.clear(); R->last = -1; R->set_trans.clear();
+        R->cache.clear(); R->last = -1; R->set_trans.clear();      // (every plan with its graph, the graph first)
         R->W = std::move(W);
         R->S = std::make_shared<rs::State>();
         rs::init_state(R->W, *R->S);

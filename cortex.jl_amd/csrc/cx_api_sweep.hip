@@ -90,12 +90,8 @@ int32_t build_chains(cx_handle *h) {
 
 // ---- CX_SCHED_TREE: the stages of cx_tree_plan.h, built once per set of observed variables ----------------------------
 void batch_graph_drop(cx_handle *h) {
-    for (auto &g : h->batch_graph) { if (g.exec) (void)hipGraphExecDestroy(g.exec); g = cx_handle::BatchGraph(); }
+    for (auto &g : h->batch_graph) g = cx_handle::BatchGraph();
     h->batch_epoch++;
-}
-
-void tree_graph_drop(cx_handle *h) {
-    if (h->tree_exec) { (void)hipGraphExecDestroy(h->tree_exec); h->tree_exec = nullptr; }
 }
 
 int32_t build_tree(cx_handle *h) {
@@ -105,7 +101,7 @@ int32_t build_tree(cx_handle *h) {
         std::string terr;
         const int32_t rc = cx::treeplan::build(h, plan, terr);
         if (rc != CX_OK) return fail(h, rc, terr);
-        tree_graph_drop(h);      // (it holds the addresses of what goes next)
+        h->tree_graph.reset();      // (it holds the addresses of what goes next)
         cx::reset_all(h->d_tree_rec, h->d_tree_kary);
         int32_t rc2;
         // Heavy paths (cx_tree_plan.h: build_hp; scalar messages): the same exact sweep as O(log n) rounds of scans and item stages.  Taken
@@ -334,33 +330,15 @@ static void tree_issue(cx_handle *h) {
 }
 
 // The stages are hundreds of small launches whose arguments never change between sweeps (device-resident lists, the handle's
-// buffers): they are captured ONCE into a HIP graph — on a stream of the handle's own, so that the caller's stream may be the null
-// stream — and a sweep is one hipGraphLaunch on the caller's stream.  Measured on the 1.09 M-edge forest of tools/bench_configs.py
-// (206 launches): the sweep was bound by the host's launch rate.  CX_TREE_GRAPH=0: plain launches (A/B); a refused capture or
-// instantiation also falls back to them, for good.
+// buffers): they are captured ONCE into a HIP graph (cx_host.h: capture) and a sweep is one launch of it on the caller's stream.
+// Measured on the 1.09 M-edge forest of tools/bench_configs.py (206 launches): the sweep was bound by the host's launch rate.
+// CX_TREE_GRAPH=0: plain launches (A/B); a refused capture, instantiation or launch also falls back to them, for good.
 int32_t tree_sweep(cx_handle *h) {
     static const bool graphs = [] { const char *e = std::getenv("CX_TREE_GRAPH"); return !(e && e[0] == '0'); }();
-    if (graphs && !h->tree_graph_failed && !h->profiling && !h->tree_exec) {
-        hipError_t e = hipSuccess;
-        if (!h->tree_capture_stream) e = hipStreamCreateWithFlags(&h->tree_capture_stream, hipStreamNonBlocking);
-        hipGraph_t g = nullptr;
-        if (e == hipSuccess) e = hipStreamBeginCapture(h->tree_capture_stream, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            hipStream_t user = h->stream;
-            h->stream = h->tree_capture_stream;
-            tree_issue(h);
-            h->stream = user;
-            e = hipStreamEndCapture(h->tree_capture_stream, &g);
-        }
-        if (e == hipSuccess && g) e = hipGraphInstantiate(&h->tree_exec, g, nullptr, nullptr, 0);
-        if (g) (void)hipGraphDestroy(g);
-        if (e != hipSuccess || !h->tree_exec) { (void)hipGetLastError(); h->tree_exec = nullptr; h->tree_graph_failed = true; }
-    }
-    if (h->tree_exec && !h->profiling) {
-        if (hipGraphLaunch(h->tree_exec, h->stream) == hipSuccess) return CX_OK;
-        (void)hipGetLastError();
-        tree_graph_drop(h);
-        h->tree_graph_failed = true;
+    cx::GraphExec &g = h->tree_graph;
+    if (graphs && !h->profiling) {
+        if (!g && !g.failed()) (void)capture(h, g, [h] { tree_issue(h); });
+        if (g && launch(h, g)) return CX_OK;
     }
     tree_issue(h);
     return CX_OK;
@@ -555,7 +533,6 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
         CX_HIP(h, hipGetLastError());
         return CX_OK;
     }
-    int32_t s = 0;
     // The sweeps between two exchanges of a deep-halo partition (cx_halo_configure_state + layers): 12 .. 32 launches of 10 us whose slice
     // ranges repeat batch after batch.  CX_HALO_GRAPH=1: the second time the same batch is asked for it is captured, from then on ONE graph
     // launch.  OFF by default: on the 1/8 strip of C4 (depth 16) the replayed graph measured 10.10 - 10.25 us per sweep against 9.90 - 9.92
@@ -565,9 +542,7 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
     const char *bg_env = std::getenv("CX_HALO_GRAPH");      // (read per call: a test runs both forms in one process)
     const bool batch_graphs = bg_env && bg_env[0] == '1';
     cx_handle::BatchGraph *bg = nullptr;
-    bool capturing = false;
-    hipStream_t user_stream = h->stream;
-    if (batch_graphs && s == 0 && n_sweeps >= 4 && h->halo_state && h->halo_depth > 0 && h->cfg.schedule == CX_SCHED_FUSED && h->big_vars.empty() && h->n_kary == 0 &&
+    if (batch_graphs && n_sweeps >= 4 && h->halo_state && h->halo_depth > 0 && h->cfg.schedule == CX_SCHED_FUSED && h->big_vars.empty() && h->n_kary == 0 &&
         !h->profiling && h->cfg.materialize_messages_to_factor == 0) {
         uint64_t key = 0x9e3779b97f4a7c15ull;
         for (uint64_t x : {(uint64_t)h->sweeps_since_exchange, (uint64_t)n_sweeps, (uint64_t)(uintptr_t)h->d_f2v.get(), (uint64_t)(uintptr_t)h->d_f2v_alt.get(), h->batch_epoch, (uint64_t)(uintptr_t)h->stream})
@@ -575,45 +550,36 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
         for (auto &g : h->batch_graph) if (g.key == key) bg = &g;
         if (!bg) {      // a new batch: takes the slot that is not the most recent one's
             bg = h->batch_graph[0].seen <= h->batch_graph[1].seen ? &h->batch_graph[0] : &h->batch_graph[1];
-            if (bg->exec) (void)hipGraphExecDestroy(bg->exec);
             *bg = cx_handle::BatchGraph();
             bg->key = key;
         }
         bg->seen++;
-        if (!bg->exec && !bg->failed && bg->seen >= 2) {
-            hipError_t er = hipSuccess;
-            if (!h->tree_capture_stream) er = hipStreamCreateWithFlags(&h->tree_capture_stream, hipStreamNonBlocking);
-            if (er == hipSuccess) er = hipStreamBeginCapture(h->tree_capture_stream, hipStreamCaptureModeThreadLocal);
-            if (er == hipSuccess) { capturing = true; h->stream = h->tree_capture_stream; }
-            else { (void)hipGetLastError(); bg->failed = true; }
-        }
     }
-    const bool replay = bg && bg->exec && !capturing;
-    for (; s < n_sweeps; s++) {
-        h->run_slice0 = 0; h->run_nslices = 0;
-        if (h->halo_state && h->halo_depth > 0 && h->cfg.schedule == CX_SCHED_FUSED && h->big_vars.empty()) {
-            const int j = std::min(h->sweeps_since_exchange + 1, h->halo_depth);     // this is sweep j after the exchange
-            const int L = h->halo_depth - j + 1;                                       // layers that have to run
-            if (h->trim_hi[L] >= h->trim_lo[L]) { h->run_slice0 = h->trim_lo[L]; h->run_nslices = h->trim_hi[L] - h->trim_lo[L] + 1; }
+    // the sweeps of the call: their launches (issue; not when a graph replays them) and the host state they leave (always)
+    bool ran = false;
+    auto sweeps = [&](bool issue) {
+        ran = true;
+        for (int32_t s = 0; s < n_sweeps; s++) {
+            h->run_slice0 = 0; h->run_nslices = 0;
+            if (h->halo_state && h->halo_depth > 0 && h->cfg.schedule == CX_SCHED_FUSED && h->big_vars.empty()) {
+                const int j = std::min(h->sweeps_since_exchange + 1, h->halo_depth);     // this is sweep j after the exchange
+                const int L = h->halo_depth - j + 1;                                       // layers that have to run
+                if (h->trim_hi[L] >= h->trim_lo[L]) { h->run_slice0 = h->trim_lo[L]; h->run_nslices = h->trim_hi[L] - h->trim_lo[L] + 1; }
+            }
+            if (issue) sweep_main(h, false);
+            sweep_finish(h);
+            h->run_slice0 = 0; h->run_nslices = 0;
+            h->sweeps_since_exchange++;
         }
-        if (!replay) sweep_main(h, false);      // (a replayed batch: the launches are in the graph, the host state below is not)
-        sweep_finish(h);
-        h->run_slice0 = 0; h->run_nslices = 0;
-        h->sweeps_since_exchange++;
+    };
+    // nothing is launched while capturing and the host state moves on: a capture that fails after its sweeps ran cannot be repeated from here
+    if (bg && !bg->graph && !bg->graph.failed() && bg->seen >= 2 && !capture(h, bg->graph, [&] { sweeps(true); }) && ran)
+        return fail(h, CX_ERR_DEVICE, "cx_sweep: capturing the sweeps of a halo batch as a graph failed; set CX_HALO_GRAPH=0");
+    if (!ran) sweeps(!(bg && bg->graph));
+    if (bg && bg->graph) {
+        if (!launch(h, bg->graph)) return fail(h, CX_ERR_DEVICE, "cx_sweep: launching the captured sweeps of a halo batch failed; set CX_HALO_GRAPH=0");
+        h->batch_graph_launches++;
     }
-    if (capturing) {
-        h->stream = user_stream;
-        hipGraph_t g = nullptr;
-        hipError_t er = hipStreamEndCapture(h->tree_capture_stream, &g);
-        if (er == hipSuccess && g) er = hipGraphInstantiate(&bg->exec, g, nullptr, nullptr, 0);
-        if (g) (void)hipGraphDestroy(g);
-        if (er != hipSuccess || !bg->exec) {
-            // nothing was launched while capturing and the host state has moved on: the batch cannot be repeated from here
-            (void)hipGetLastError(); bg->exec = nullptr; bg->failed = true;
-            return fail(h, CX_ERR_DEVICE, "cx_sweep: capturing the sweeps of a halo batch as a graph failed; set CX_HALO_GRAPH=0");
-        }
-    }
-    if (bg && bg->exec) { CX_HIP(h, hipGraphLaunch(bg->exec, h->stream)); h->batch_graph_launches++; }
     CX_HIP(h, hipGetLastError());
     return CX_OK;
 }

@@ -77,6 +77,38 @@ inline int32_t ensure_stage(cx_handle *h, int64_t bytes) {
     return h->d_stage.alloc(h, std::max<int64_t>(bytes, 1 << 20), false);
 }
 
+// What `issue` launches through h->stream, captured as ONE graph into g: on a stream of the handle's own (non-blocking, made on first
+// use), so that the caller's stream may be the null stream; thread-local capture mode; one linear stream.  h->stream is the capture
+// stream while `issue` runs and the caller's again on every path out (an exception from `issue` leaves the capture open: the next one
+// is refused and g's owner launches plainly).  Returns whether g holds an exec; if not, the sticky error is cleared and g is empty and
+// marked failed.
+template <class F>
+bool capture(cx_handle *h, cx::GraphExec &g, F &&issue) {
+    struct Swap { cx_handle *h; hipStream_t user; ~Swap() { h->stream = user; } };
+    hipStream_t cs = h->capture_stream.get();
+    hipError_t e = hipSuccess;
+    if (!cs && (e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking)) == hipSuccess) h->capture_stream.reset(cs);
+    if (e == hipSuccess) e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    if (e == hipSuccess) {
+        { Swap back{h, h->stream}; h->stream = cs; issue(); }
+        e = hipStreamEndCapture(cs, &graph);
+    }
+    if (e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (e == hipSuccess && exec) g.adopt(exec); else { (void)hipGetLastError(); g.fail(); }
+    return (bool)g;
+}
+
+// g on the caller's stream; false: the launch was refused — the error is cleared, g is empty and marked failed, the caller issues plainly
+inline bool launch(cx_handle *h, cx::GraphExec &g) {
+    if (hipGraphLaunch(g.get(), h->stream) == hipSuccess) return true;
+    (void)hipGetLastError();
+    g.fail();
+    return false;
+}
+
 // (variable_id, factor_id) -> edge index; edges are sorted by (variable, factor)
 inline int64_t find_var(const cx_handle *h, int64_t var_id);
 inline int64_t find_edge(const cx_handle *h, int64_t var_id, int64_t fac_id) {
@@ -169,19 +201,19 @@ int32_t ensure_v2f(cx_handle *h);
 int32_t build_chains(cx_handle *h);
 int32_t build_tree(cx_handle *h);
 int32_t tree_sweep(cx_handle *h);        // every stage of the plan on the handle's stream (one graph launch, or an XCD-resident cluster for scalar plans of wide stages)
-void batch_graph_drop(cx_handle *h);       // the captured sweeps of a deep-halo batch (cx_api_sweep.hip: cx_sweep)
-void tree_graph_drop(cx_handle *h);        // CX_SCHED_TREE: the stages of cx_tree_plan.h on the device (rebuilt when the set of observed variables changed)
+void batch_graph_drop(cx_handle *h);       // the captured sweeps of a deep-halo batch (cx_api_sweep.hip: cx_sweep), for what they bake in besides addresses
 void sweep_main(cx_handle *h, bool skip_ghosts);
 void sweep_finish(cx_handle *h);
 // ---- cx_api_msg.hip -------------------------------------------------------------------------------------------------
 int32_t ref_set_marginals(cx_handle *h, int64_t n, const int64_t *variable_ids, int32_t form, const double *payload);   // cx_api_ref.hip
 void ref_on_set_marginals(cx_handle *h, int64_t n, const int32_t *vars);
 int32_t ensure_joint_store(cx_handle *h);  // the same for the joint-marginal store (registered factors: cx_handle::joint_index)
-int32_t ensure_prod_store(cx_handle *h);   // the product store holds every registered ProductOfMessages node (graphs that captured its address are dropped when it moves)
+int32_t ensure_prod_store(cx_handle *h);   // the product store holds every registered ProductOfMessages node
 // ---- cx_api_ref.hip: CX_SCHED_REFERENCE -----------------------------------------------------------------------------
 int32_t ref_build(cx_handle *h);
-void ref_free(cx_handle *h);
-void ref_graphs_drop(cx_handle *h);
+// Every graph of the handle that bakes in a device address: the tree sweep's, every reference-order plan's, both halo-batch slots.
+// Whoever moves a buffer that a captured launch names calls this BEFORE; a graph that did not name it costs one more capture
+void captured_graphs_drop(cx_handle *h);
 void ref_on_set(cx_handle *h, int64_t n, const int64_t *edges, int32_t direction, uint64_t set_key = 0);      // set_key != 0: the list is one cx_set_messages keeps (the state it leads to is kept too)
 void ref_on_seed(cx_handle *h, int32_t direction);
 void ref_on_batch(cx_handle *h, const cx_item *items, int64_t n);

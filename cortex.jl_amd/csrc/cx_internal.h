@@ -8,6 +8,7 @@
 #include <map>
 #include <memory>
 #include <tuple>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -26,8 +27,8 @@ struct ProfileRec {
 // One device allocation and its owner: move-only, freed by reset() and by the destructor, counted in the handle's device_bytes while
 // it lives (what alloc adds, reset takes away).  Converts to T* so that launch sites read as with a raw pointer; nothing converts
 // back, so a buffer cannot be assigned a pointer by accident.  alloc / upload / ensure are defined in cx_host.h (they report through
-// CX_HIP like every other call).  Captured graphs hold addresses: ensure() says when the buffer moved and never drops a graph itself,
-// whoever owns a graph that names the buffer drops it BEFORE calling (see upload_ptab, ensure_prod_store).
+// CX_HIP like every other call).  Captured graphs hold addresses: ensure() says when the buffer moved and never drops a graph itself;
+// whoever moves a buffer that a captured launch names calls cxh::captured_graphs_drop BEFORE (see upload_ptab, grow_store).
 template <class T>
 class DevBuf {
 public:
@@ -59,8 +60,30 @@ private:
 
 template <class... B> void reset_all(B &...b) { (b.reset(), ...); }
 
-// what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample): the deleter is defined there
+// One instantiated graph and its owner: move-only, destroyed by reset() and by the destructor.  failed(): capture, instantiation or
+// launch was refused once — plain launches from then on; reset() keeps that, only a fresh GraphExec forgets it.  Filled and launched by
+// cxh::capture / cxh::launch (cx_host.h), which are the only users of get / adopt / fail.
+class GraphExec {
+public:
+    explicit operator bool() const { return (bool)exec_; }
+    bool failed() const { return failed_; }
+    void reset() { exec_.reset(); }
+    hipGraphExec_t get() const { return exec_.get(); }
+    void adopt(hipGraphExec_t e) { exec_.reset(e); }
+    void fail() { reset(); failed_ = true; }
+private:
+    struct Destroy { void operator()(hipGraphExec_t e) const { (void)hipGraphExecDestroy(e); } };
+    std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, Destroy> exec_;
+    bool failed_ = false;
+};
+
+// the stream captures are taken on: the handle's own, made on first use (cxh::capture)
+struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+using OwnedStream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
+
+// what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample, reference order): the deleter is defined there
 template <class T> struct Deleter { void operator()(T *p) const; };
+struct RefSched;      // cx_api_ref.hip
 namespace ev { struct Cache; }
 namespace fs { struct Cache; }
 namespace sp { struct Plan; }
@@ -69,10 +92,19 @@ namespace sp { struct Plan; }
 
 namespace cx {
 
-// Everything a handle owns on the device for its graph, with the flags and counters that describe it.  cxh::dev_free_all drops the
-// captured graphs (they hold these addresses) and then assigns a default-constructed DevState: a member added here is freed and reset
-// with no second mention anywhere, and the state after a reset is what the initialisers below say.
+// Everything a handle owns on the device for its graph, with the flags and counters that describe it.  cxh::dev_free_all assigns a
+// default-constructed DevState: a member added here is freed and reset with no second mention anywhere, and the state after a reset is
+// what the initialisers below say.  Assignment goes member by member in the order written here, so the captured graphs come FIRST:
+// they hold the addresses of the buffers below and go before them.
 struct DevState {
+    OwnedStream capture_stream;
+    GraphExec tree_graph;      // CX_SCHED_TREE: the stages of one sweep as ONE graph launch (hundreds of small launches otherwise)
+    // the sweeps between two exchanges of a deep-halo partition as ONE graph launch (cx_api_sweep.hip: cx_sweep): the same (first sweep after
+    // the exchange, sweeps, buffers) seen a second time is captured, from then on replayed; two slots (an odd batch alternates its buffers)
+    struct BatchGraph { uint64_t key = 0; GraphExec graph; int seen = 0; };
+    BatchGraph batch_graph[2];
+    std::unique_ptr<RefSched, Deleter<RefSched>> ref;      // CX_SCHED_REFERENCE (cx_refsched.h, cx_api_ref.hip): wiring + shadow readiness state + plans, each with its buffers and graph
+
     DevBuf<int32_t> d_slice_off, d_partner, d_vbase, d_var_deg;
     DevBuf<int32_t> d_big, d_big_slots, d_big_slot_var;      // (dim 2..4: the variable of every slot of the CSR tail)
     DevBuf<double2> d_big_tmp;      // prefix scratch of the big-variable kernel, one entry per big slot
@@ -119,7 +151,6 @@ struct DevState {
 
     // CX_SCHED_TREE (cx_tree_plan.h): the stages' items and k-ary entries, the stage table (runs of thin stages go out as one launch)
     bool chains_dirty = true, tree_dirty = true;
-    bool tree_graph_failed = false;      // capture or instantiation refused once: plain launches from then on
     DevBuf<int32_t> d_tree_rec, d_tree_kary;
     DevBuf<int64_t> d_tree_stage_off;
     // the same sweep over heavy paths (cx_tree_plan.h: build_hp), chosen when it takes fewer launches: the paths' arrays live in the chain
@@ -177,7 +208,8 @@ struct DevState {
 // d_chain_linkpar, d_chain_onepass, d_chain_abort (cx_chain.hip), d_marg64_sums, d_marg64_tab, d_marg64_rec (cx_mv64.hip) and own the
 // chain64 (cx_mv64chain.hip) and vmp (cx_vmp.hip) sub-states; an edit of those files' code would void the counter profiles kept
 // under profiles/, so these stay raw pointers of cx_handle, freed where they always were (chain_onepass_free, chain64_free,
-// chain64_tree_free, vmp_free, dev_free_all for the three d_marg64_*).  Everything else a handle owns on the device is in DevState.
+// chain64_tree_free, vmp_free, dev_free_all for the three d_marg64_*).  Everything else a handle owns on the device is in DevState,
+// the captured graphs (cx::GraphExec) and the stream they are captured on included.
 struct cx_handle : cx::DevState {
     cx_config cfg{};
     std::string err;
@@ -240,8 +272,6 @@ struct cx_handle : cx::DevState {
     int user_dim = 0;
     // CX_SCHED_TREE (cx_tree_plan.h): the stages' items and k-ary entries on the device (DevState), their offsets on the host
     std::vector<int64_t> tree_stage_off, tree_kary_off;
-    hipGraphExec_t tree_exec = nullptr;    // the stages of one sweep as ONE graph launch (hundreds of small launches otherwise: the sweep was bound by
-    hipStream_t tree_capture_stream = nullptr;      //  the host's launch rate); captured on a stream of the handle's own, launched on the caller's
     int64_t tree_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // depth, stages, items, k-ary entries, components, up, down, marginals
     // the same sweep over heavy paths (DevState: tree_hp)
     std::vector<int32_t> tree_hp_steps;            // pairs (kind, index): 0 item stage, 1 scan of a light depth on the way up, 2 its final scan
@@ -261,11 +291,7 @@ struct cx_handle : cx::DevState {
     bool chain_side_dirty = true;    // the leaf messages / side sums of the chain positions must be recomputed (data or rule parameters changed)
     bool chain_partition = false;    // the handle holds a time block of a partitioned chain (cx_chain_block_maps was called)
     bool chain_covers_all = false;   // every variable that reads messages is a chain position: the scan's side pass produces all leaf messages
-    // the sweeps between two exchanges of a deep-halo partition as ONE graph launch (cx_api_sweep.hip: cx_sweep): the same (first sweep after
-    // the exchange, sweeps, buffers) seen a second time is captured, from then on replayed; two slots (an odd batch alternates its buffers)
-    struct BatchGraph { uint64_t key = 0; hipGraphExec_t exec = nullptr; int seen = 0; bool failed = false; };
-    BatchGraph batch_graph[2];
-    uint64_t batch_epoch = 1;        // moved on by whatever a captured batch bakes in (layers, damping, the graph itself): cxh::batch_graph_drop
+    uint64_t batch_epoch = 1;        // deep-halo batch graphs (DevState: batch_graph): moved on by whatever a captured batch bakes in (layers, damping, the graph itself): cxh::batch_graph_drop
     int64_t batch_graph_launches = 0;
     // the chain scan as ONE launch (cx_chain.hip: k_chain_onepass): tile totals + flags on the device, the word in mapped host memory that a
     // workgroup raises when a wait of it times out (checked by every CX_HIP of the host: the call that finds it fails, the handle goes back to two launches)
@@ -331,8 +357,7 @@ struct cx_handle : cx::DevState {
     std::string cluster_note;        // what happened, for cx_last_error's reader
     int64_t cluster_max_items = 16384, cluster_min_items = 128;      // a stage wider than max (one pass of the members) is a launch of its own on the whole chip; plans of fewer than min items per stage are chains
 
-    // CX_SCHED_REFERENCE (cx_refsched.h, cx_api_ref.hip): wiring + shadow readiness state + plans (opaque); the list of the plan being launched
-    void *ref = nullptr;
+    // CX_SCHED_REFERENCE (DevState: ref): the list of the plan being launched, an alias into that plan (cx_batch.hip reads it)
     int32_t *d_ref_list = nullptr;
 
     // variational families (cx_vmp.hip): opaque state
