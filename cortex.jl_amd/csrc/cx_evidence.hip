@@ -157,126 +157,48 @@ __global__ __launch_bounds__(kB) void k_ev_var(int64_t nv, const int32_t *__rest
 }
 
 // ---- pass 2: factors of two variables -------------------------------------------------------------------------------------------
-// x_out = A x_in + b + N(0, Q): the residual C x - b with C_out = I, C_in = -A is N(0, Q).  rec = (slot out, slot in, var out, var in).
-// dim 1: (q, a, b) per factor (pa, pb may be null: a = 1, b = 0); dim > 1: the factor's parameter set in ptab = [set][A | Q⁻¹ | log det 2πQ, 0]
+// x_out = A x_in + b + N(0, Q): log z_a = -½ rc'Q⁻¹rc - ½ log det 2πQ + ½ h'J⁻¹h - ½ log det J + (free entries) ½ log 2π, with J, h of
+// ev::pair_joint.  Both ends free: the 2d x 2d joint; one end observed (half the factors of a state-space chain): its d x d block
 template <int D>
-__global__ __launch_bounds__(kB) void k_ev_pair(int64_t n, const int4 *__restrict__ rec, const int32_t *__restrict__ pset, const double *__restrict__ pq,
-                                                const double *__restrict__ pa, const double *__restrict__ pb, const double *__restrict__ ptab,
-                                                const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v, const double *__restrict__ v2f,
-                                                const double *__restrict__ W, Part *__restrict__ partial) {
-    constexpr int NT = Lay<D>::NT;
+__global__ __launch_bounds__(kB) void k_ev_pair(int64_t n, PairTab tab, Msgs msg, Part *__restrict__ partial) {
     const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
     double s = 0.0, c = 0.0;
     bool undef_t = false, npd_t = false;
     if (i < n) {
-        const int4 r = rec[i];
-        double A[D][D], Qi[D][D], ldq, bb[D];
-        if constexpr (D == 1) {
-            const double q = pq[i];
-            A[0][0] = pa ? pa[i] : 1.0; Qi[0][0] = 1.0 / q; ldq = log(q) + kLog2Pi; bb[0] = pb ? pb[i] : 0.0;
-        } else {
-            const double *t = ptab + (int64_t)pset[i] * (2 * D * D + 2);
+        PairJoint<D> B;
+        pair_joint<D>(i, tab, msg, B);
+        double cq = 0.0;
 #pragma unroll
-            for (int p = 0; p < D; p++) {
-                bb[p] = 0.0;
-#pragma unroll
-                for (int q = 0; q < D; q++) { A[p][q] = t[p * D + q]; Qi[p][q] = t[D * D + p * D + q]; }
-            }
-            ldq = t[2 * D * D];
-        }
-        const bool fo = !(vinfo[r.z] & kClamped), fi = !(vinfo[r.w] & kClamped);
-        double mo[D], eo[D], lo[NT], mi[D], ei[D], li[NT];
-        bool ok = true;
-        if (fo) ok = free_edge<D>(f2v, W, r.x, r.z, mo, eo, lo) && ok;
-        else datum<D>(v2f, r.x, mo);
-        if (fi) ok = free_edge<D>(f2v, W, r.y, r.w, mi, ei, li) && ok;
-        else datum<D>(v2f, r.y, mi);
-        // b'' = b - C_out x_out - C_in x_in at the data / the centres
-        double bp[D];
-#pragma unroll
-        for (int p = 0; p < D; p++) {
-            double t = bb[p] - mo[p];
-#pragma unroll
-            for (int q = 0; q < D; q++) t += A[p][q] * mi[q];
-            bp[p] = t;
-        }
-        double g[D], cq = 0.0;      // g = Q⁻¹ b''
-#pragma unroll
-        for (int p = 0; p < D; p++) {
-            double t = 0.0;
-#pragma unroll
-            for (int q = 0; q < D; q++) t += Qi[p][q] * bp[q];
-            g[p] = t; cq += bp[p] * t;
-        }
-        double lz = -0.5 * cq - 0.5 * ldq, logdet = 0.0, quad = 0.0;
+        for (int p = 0; p < D; p++) cq -= B.rc[p] * B.g[p];
+        double lz = -0.5 * cq - 0.5 * B.ldq, logdet = 0.0, quad = 0.0;
         bool pd = true;
-        double T[D][D];             // T = Q⁻¹ A
-#pragma unroll
-        for (int p = 0; p < D; p++)
-#pragma unroll
-            for (int q = 0; q < D; q++) {
-                double t = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; k++) t += Qi[p][k] * A[k][q];
-                T[p][q] = t;
-            }
-        if (fo && fi) {
-            double J[2 * D][2 * D], h[2 * D];
-#pragma unroll
-            for (int p = 0; p < D; p++) {
-                h[p] = g[p] + eo[p];
-                double t = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; k++) t += A[k][p] * g[k];
-                h[D + p] = -t + ei[p];
-#pragma unroll
-                for (int q = 0; q < D; q++) {
-                    J[p][q] = Qi[p][q] + lam_at<D>(lo, p, q);
-                    J[D + p][q] = -T[q][p];          // (-Q⁻¹A)' below the diagonal
-                    J[q][D + p] = -T[q][p];
-                    double u = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; k++) u += A[k][p] * T[k][q];
-                    J[D + p][D + q] = u + lam_at<D>(li, p, q);
-                }
-            }
-            pd = chol_quad<2 * D>(J, h, logdet, quad);
+        if (B.fo && B.fi) {
+            pd = chol_quad<2 * D>(B.J, B.h, logdet, quad);
             lz += 0.5 * quad - 0.5 * logdet + D * kLog2Pi;
-        } else if (fo || fi) {
+        } else if (B.fo || B.fi) {
             double J[D][D], h[D];
 #pragma unroll
             for (int p = 0; p < D; p++) {
-                double t = 0.0;
+                h[p] = B.fo ? B.h[p] : B.h[D + p];
 #pragma unroll
-                for (int k = 0; k < D; k++) t += A[k][p] * g[k];
-                h[p] = fo ? g[p] + eo[p] : -t + ei[p];
-#pragma unroll
-                for (int q = 0; q < D; q++) {
-                    double u = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; k++) u += A[k][p] * T[k][q];
-                    J[p][q] = fo ? Qi[p][q] + lam_at<D>(lo, p, q) : u + lam_at<D>(li, p, q);
-                }
+                for (int q = 0; q < D; q++) J[p][q] = B.fo ? B.J[p][q] : B.J[D + p][D + q];
             }
             pd = chol_quad<D>(J, h, logdet, quad);
             lz += 0.5 * quad - 0.5 * logdet + 0.5 * D * kLog2Pi;
         }
-        undef_t = !ok;
-        npd_t = ok && !pd;
-        if (ok && pd) neu(s, c, lz);
+        undef_t = !B.ok;
+        npd_t = B.ok && !pd;
+        if (B.ok && pd) neu(s, c, lz);
     }
     block_part<kB>(s, c, 0, undef_t, npd_t, 0, partial);
 }
 
 // ---- pass 2: factors of 3 .. 7 variables ----------------------------------------------------------------------------------------
-// x_out = Σ A_k x_k + b + N(0, Q), entries in the k-ary table's order (OUT first).  krec[f] = slots[8] | vars[8] (-1: none).
-// dim 1: kc[f] = C_e[8] (+1 OUT, -a_i IN) | q | b.  dim > 1: kps[f] = parameter set per entry (IN: its A; OUT: Q); ptab as k_ev_pair's.
-// The joint precision over the free entries (packed lower triangle, up to 28 x 28) and its right-hand side live in LDS, thread-interleaved.
+// The joint precision over the free entries (ev::kary_joint: packed lower triangle, up to 28 x 28) and its right-hand side live in LDS,
+// thread-interleaved.
 template <int D>
-__global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, const int32_t *__restrict__ krec, const double *__restrict__ kc, const int32_t *__restrict__ kps,
-                                                 const double *__restrict__ ptab, const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v,
-                                                 const double *__restrict__ v2f, const double *__restrict__ W, Part *__restrict__ partial) {
-    constexpr int NT = Lay<D>::NT, NP = KLay<D>::NP, NM = KLay<D>::NM, PS = 2 * D * D + 2;
+__global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, KaryTab tab, Msgs msg, Part *__restrict__ partial) {
+    constexpr int NP = KLay<D>::NP, NM = KLay<D>::NM;
     __shared__ double sJ[NP * kKB], sh[NM * kKB];
     const int t = threadIdx.x;
     double *J = sJ + t, *hv = sh + t;      // element k at [k * kKB]
@@ -288,33 +210,17 @@ __global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, const int32_t *__res
         unsigned freemask;
         int nfree;
         bool ok;
-        kary_joint<D, kKB>(f, krec, kc, kps, ptab, vinfo, f2v, v2f, W, J, hv, Qi, ldq, bp, g, cq, freemask, nfree, ok);
+        kary_joint<D, kKB>(f, tab, msg, J, hv, Qi, ldq, bp, g, cq, freemask, nfree, ok);
         double lz = -0.5 * cq - 0.5 * ldq;
-        // Cholesky in place, then the forward solve
         const int N = nfree * D;
-        bool pd = true;
+        auto at = [&](int i, int j) -> double & { return J[pk(i, j) * kKB]; };
+        auto y = [&](int i) -> double & { return hv[i * kKB]; };
         double logdet = 0.0, quad = 0.0;
-        for (int j = 0; j < N && pd; j++) {
-            double d = J[pk(j, j) * kKB];
-            for (int k = 0; k < j; k++) { const double l = J[pk(j, k) * kKB]; d -= l * l; }
-            if (!(d > 0.0)) { pd = false; break; }
-            logdet += log(d);
-            const double l = sqrt(d), il = 1.0 / l;
-            J[pk(j, j) * kKB] = l;
-            for (int i = j + 1; i < N; i++) {
-                double u = J[pk(i, j) * kKB];
-                for (int k = 0; k < j; k++) u -= J[pk(i, k) * kKB] * J[pk(j, k) * kKB];
-                J[pk(i, j) * kKB] = u * il;
-            }
+        const bool pd = chol_at(N, at, &logdet);
+        if (pd) {
+            fwd_solve_at(N, at, y);
+            for (int i = 0; i < N; i++) quad += y(i) * y(i);
         }
-        if (pd)
-            for (int i = 0; i < N; i++) {
-                double u = hv[i * kKB];
-                for (int k = 0; k < i; k++) u -= J[pk(i, k) * kKB] * hv[k * kKB];
-                u /= J[pk(i, i) * kKB];
-                hv[i * kKB] = u;
-                quad += u * u;
-            }
         lz += 0.5 * quad - 0.5 * logdet + 0.5 * N * kLog2Pi;
         undef_t = !ok;
         npd_t = ok && !pd;
@@ -385,12 +291,13 @@ int32_t build(cx_handle *h, Cache &C, const std::string &who) {
         vrec[v] = di | (mask << 24);
     }
     // factors
-    std::vector<int4> pair;
-    std::vector<int32_t> pair_ps;
-    std::vector<int64_t> pair_fac;
+    // (C is a fresh Cache: prepare drops a Cache whose build failed, so the rows below are appended to empty vectors)
+    std::vector<int4> &pair = C.pair;
+    std::vector<int32_t> &pair_ps = C.pair_ps, &krec = C.krec;
+    std::vector<int64_t> &pair_fac = C.pair_fac;
     std::vector<double> pq, pa, pb;
     bool any_ab = false;
-    std::vector<int32_t> krec;
+    C.row_of_fac.assign((size_t)nf, -1); C.kary_row_of_fac.assign((size_t)nf, -1);
     C.zero_noise_fac = -1; C.unsupported_fac = -1;
     int64_t row = 0;
     for (int64_t f = 0; f < nf; f++) {
@@ -401,7 +308,7 @@ int32_t build(cx_handle *h, Cache &C, const std::string &who) {
             for (int e = 0; e < 8; e++) krec.push_back(h->kary_slot[8 * row + e]);
             for (int e = 0; e < 8; e++) { const int32_t s = h->kary_slot[8 * row + e]; krec.push_back(s < 0 ? -1 : slot_var[s]); }
             if (d == 1 && !(h->kary_qb[2 * row] > 0.0) && C.zero_noise_fac < 0) C.zero_noise_fac = h->fac_ids[f];
-            row++;
+            C.kary_row_of_fac[(size_t)f] = (int32_t)row++;
             continue;
         }
         if ((kind != CX_FACTOR_GAUSS_ADDITIVE && kind != CX_FACTOR_GAUSS_LINEAR) || fe2[f] < 0) { if (C.unsupported_fac < 0) C.unsupported_fac = h->fac_ids[f]; continue; }
@@ -418,13 +325,12 @@ int32_t build(cx_handle *h, Cache &C, const std::string &who) {
             any_ab = any_ab || a != 1.0 || b != 0.0;
             if (!(p[0] > 0.0) && C.zero_noise_fac < 0) C.zero_noise_fac = h->fac_ids[f];
         }
+        C.row_of_fac[(size_t)f] = (int32_t)pair.size();
         pair.push_back(make_int4(so, si, slot_var[so], slot_var[si]));
         pair_fac.push_back(f);
     }
     if (row != h->n_kary) return fail(h, CX_ERR_STATE, who + ": the k-ary table does not match the factors");
     C.n_pair = (int64_t)pair.size(); C.n_kary = row;
-    C.pair_ps = pair_ps;
-    C.pair_fac = pair_fac;
     int32_t rc;
     if ((rc = dev_upload(h, &C.d_vrec, vrec)) != CX_OK) return rc;
     if ((rc = dev_upload(h, &C.d_tail, tail)) != CX_OK) return rc;
@@ -438,13 +344,12 @@ int32_t build(cx_handle *h, Cache &C, const std::string &who) {
         }
     }
     if ((rc = dev_upload(h, &C.d_krec, krec)) != CX_OK) return rc;
-    const int K = d == 1 ? Lay<1>::K : d == 2 ? Lay<2>::K : d == 3 ? Lay<3>::K : Lay<4>::K;
-    if ((rc = dev_alloc(h, &C.d_W, nv * K)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_W, nv * with_dim(d, [](auto D) { return Lay<D()>::K; }))) != CX_OK) return rc;
     C.nb = (nv + kB - 1) / kB + (C.n_pair + kB - 1) / kB + (C.n_kary + kKB - 1) / kKB;
     if ((rc = dev_alloc(h, &C.d_partial, C.nb)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &C.d_out, 1 + kNCnt)) != CX_OK) return rc;
     CX_HIP(h, hipHostMalloc((void **)&C.h_out, (1 + kNCnt) * sizeof(double), hipHostMallocDefault));
-    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the host vectors die here)
+    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
     C.built = true;
     C.epoch = ~0ull;
     return CX_OK;
@@ -519,33 +424,23 @@ int32_t refresh_params(cx_handle *h, Cache &C, const std::string &who) {
 }
 
 template <int D>
-void launch_var(cx_handle *h, Cache &C, const double *f2v) {
+void launch_var(cx_handle *h, Cache &C) {
     const int64_t nb_v = (h->nv + kB - 1) / kB;
     if (nb_v)
         hipLaunchKernelGGL(k_ev_var<D>, dim3((unsigned)nb_v), dim3(kB), 0, h->stream, h->nv, h->d_vbase, h->d_var_deg, h->d_vinfo, C.d_vrec,
-                           C.d_tail, h->big_start, f2v, C.d_W, C.d_partial);
+                           C.d_tail, h->big_start, f2v_of(h), C.d_W, C.d_partial);
 }
 
-void var_pass(cx_handle *h, Cache &C) {
-    switch (h->cfg.dim) {
-    case 1: launch_var<1>(h, C, f2v_of(h)); break;
-    case 2: launch_var<2>(h, C, f2v_of(h)); break;
-    case 3: launch_var<3>(h, C, f2v_of(h)); break;
-    default: launch_var<4>(h, C, f2v_of(h)); break;
-    }
-}
+void var_pass(cx_handle *h, Cache &C) { with_dim(h->cfg.dim, [&](auto D) { launch_var<D()>(h, C); }); }
 
 template <int D>
-void launch(cx_handle *h, Cache &C, const double *f2v, const double *v2f) {
+void launch(cx_handle *h, Cache &C) {
     const int64_t nb_v = (h->nv + kB - 1) / kB, nb_p = (C.n_pair + kB - 1) / kB, nb_k = (C.n_kary + kKB - 1) / kKB;
     Part *part = C.d_partial;
-    launch_var<D>(h, C, f2v);
-    if (nb_p)
-        hipLaunchKernelGGL(k_ev_pair<D>, dim3((unsigned)nb_p), dim3(kB), 0, h->stream, C.n_pair, C.d_pair, C.d_pair_ps, C.d_pq, C.d_pa, C.d_pb,
-                           C.d_ptab, h->d_vinfo, f2v, v2f, C.d_W, part + nb_v);
-    if (nb_k)
-        hipLaunchKernelGGL(k_ev_kary<D>, dim3((unsigned)nb_k), dim3(kKB), 0, h->stream, C.n_kary, C.d_krec, C.d_kc, C.d_kps, C.d_ptab, h->d_vinfo,
-                           f2v, v2f, C.d_W, part + nb_v + nb_p);
+    const Msgs msg = msgs_of(h, C);
+    launch_var<D>(h, C);
+    if (nb_p) hipLaunchKernelGGL(k_ev_pair<D>, dim3((unsigned)nb_p), dim3(kB), 0, h->stream, C.n_pair, C.pair_tab(), msg, part + nb_v);
+    if (nb_k) hipLaunchKernelGGL(k_ev_kary<D>, dim3((unsigned)nb_k), dim3(kKB), 0, h->stream, C.n_kary, C.kary_tab(), msg, part + nb_v + nb_p);
     hipLaunchKernelGGL(k_ev_final, dim3(1), dim3(kFB), 0, h->stream, C.nb, part, C.d_out);
 }
 
@@ -553,11 +448,11 @@ void launch(cx_handle *h, Cache &C, const double *f2v, const double *v2f) {
 
 template <> void Deleter<ev::Cache>::operator()(ev::Cache *C) const { delete C; }
 
-int32_t ev::prepare(cx_handle *h, const std::string &who, ev::Cache *&Cp) {
+int32_t ev::prepare(cx_handle *h, const std::string &who, const char *bad_args, ev::Cache *&Cp, const char *family_note) {
     using namespace cxh;
-    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED,
-               who + ": the Gaussian family only (no variational free energy, no Beta-Bernoulli evidence)");
+    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only" + family_note);
     CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
+    CX_REQUIRE(h, !bad_args, CX_ERR_INVALID_ARGUMENT, who + ": " + bad_args);
     CX_REQUIRE(h, h->cfg.dim >= 1 && h->cfg.dim <= 4 && !h->user_dim, CX_ERR_UNSUPPORTED, who + ": dim 1, 2, 3 and 4 (the matrix-core dims are not implemented)");
     CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
                who + ": not for a partitioned handle (halo lists or stand-in variables: its terms would need owners)");
@@ -586,22 +481,13 @@ int32_t ev::prepare(cx_handle *h, const std::string &who, ev::Cache *&Cp) {
 using namespace cxh;
 
 extern "C" int32_t cx_log_evidence(cx_handle *h, double *value, int64_t *counts4) {
-    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED,
-               "cx_log_evidence: the Gaussian family only (no variational free energy, no Beta-Bernoulli evidence)");
-    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_log_evidence: no graph");
-    CX_REQUIRE(h, value && counts4, CX_ERR_INVALID_ARGUMENT, "cx_log_evidence: null argument");
     try {
         cx::ev::Cache *Cp = nullptr;
         int32_t rc;
-        if ((rc = cx::ev::prepare(h, "cx_log_evidence", Cp)) != CX_OK) return rc;
+        if ((rc = cx::ev::prepare(h, "cx_log_evidence", value && counts4 ? nullptr : "null argument", Cp,
+                                  " (no variational free energy, no Beta-Bernoulli evidence)")) != CX_OK) return rc;
         cx::ev::Cache &C = *Cp;
-        const double *f2v = cx::ev::f2v_of(h), *v2f = cx::ev::v2f_of(h);
-        switch (h->cfg.dim) {
-        case 1: cx::ev::launch<1>(h, C, f2v, v2f); break;
-        case 2: cx::ev::launch<2>(h, C, f2v, v2f); break;
-        case 3: cx::ev::launch<3>(h, C, f2v, v2f); break;
-        default: cx::ev::launch<4>(h, C, f2v, v2f); break;
-        }
+        cx::ev::with_dim(h->cfg.dim, [&](auto D) { cx::ev::launch<D()>(h, C); });
         CX_HIP(h, hipGetLastError());
         CX_HIP(h, hipMemcpyAsync(C.h_out, C.d_out, (1 + cx::ev::kNCnt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         CX_HIP(h, hipStreamSynchronize(h->stream));

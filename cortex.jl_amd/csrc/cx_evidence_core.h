@@ -1,7 +1,9 @@
-// cx_evidence_core.h — what the log-evidence (cx_evidence.hip) and the factor-statistics (cx_learn.hip) passes share: the
-// per-variable scratch of the variable pass, compensated sums, message loads, small Cholesky solves, the centred leave-one-out
-// message of one factor edge, and the cached work lists of a handle.  Derivations: DESIGN.md §4e and §4f.
+// cx_evidence_core.h — what the read-outs of the stored messages share (cx_evidence.hip, cx_learn.hip, cx_sample.hip): the dimension
+// dispatch, the per-variable scratch of the variable pass, compensated sums, message loads, the small-matrix kit (Cholesky, triangular
+// solves and inverses, in registers and on the packed joint in LDS), the centred leave-one-out message of one factor edge, the belief
+// joints of a two-variable and of a k-ary factor, and the cached tables of a handle.  Derivations: DESIGN.md §4e, §4f and §4g.
 #pragma once
+#include <type_traits>
 #include "cx_host.h"
 #include "cx_mv_core.h"
 
@@ -10,6 +12,17 @@ namespace ev {
 
 constexpr int kB = 256;        // threads per block of the variable, pairwise and final passes
 constexpr double kLog2Pi = 1.83787706640934548356;
+
+// f(std::integral_constant<int, d>) for d = 1 .. 4 (ev::prepare has refused every other dim): the only switch on the dimension
+template <class F>
+decltype(auto) with_dim(int d, F &&f) {
+    switch (d) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    default: return f(std::integral_constant<int, 4>());
+    }
+}
 
 template <int D>
 struct Lay {
@@ -50,41 +63,49 @@ __device__ __forceinline__ void ld_msg(const double *__restrict__ buf, int slot,
 template <int D>
 __device__ __forceinline__ double lam_at(const double (&lam)[Lay<D>::NT], int i, int j) { return i <= j ? lam[tri<D>(i, j)] : lam[tri<D>(j, i)]; }
 
-// in-place lower Cholesky of the full symmetric J (lower triangle read), then h <- L⁻¹ h: log det J and h'J⁻¹h.  false: not positive definite
+// ---- the small-matrix kit ---------------------------------------------------------------------------------------------------------
+// Register form (N a template parameter, every loop unrolled) and accessor form (n at run time, the matrix behind at(i, j) -> double &
+// with i >= j, vectors behind y(i) -> double &: the packed joint in LDS).  Same operations in the same order in both.
+#define CX_LA __host__ __device__ __forceinline__
+
+// A = L L' in place (the lower triangle is read and written); logdet, if given, gains log det A.  false: not positive definite
 template <int N>
-__device__ __forceinline__ bool chol_quad(double (&J)[N][N], double (&h)[N], double &logdet, double &quad) {
-    logdet = 0.0; quad = 0.0;
+CX_LA bool chol(double (&A)[N][N], double *logdet = nullptr) {
 #pragma unroll
     for (int j = 0; j < N; j++) {
-        double d = J[j][j];
+        double d = A[j][j];
 #pragma unroll
-        for (int k = 0; k < j; k++) d -= J[j][k] * J[j][k];
+        for (int k = 0; k < j; k++) d -= A[j][k] * A[j][k];
         if (!(d > 0.0)) return false;
-        logdet += log(d);
+        if (logdet) *logdet += log(d);
         const double l = sqrt(d), il = 1.0 / l;
-        J[j][j] = l;
+        A[j][j] = l;
 #pragma unroll
         for (int i = j + 1; i < N; i++) {
-            double s = J[i][j];
+            double s = A[i][j];
 #pragma unroll
-            for (int k = 0; k < j; k++) s -= J[i][k] * J[j][k];
-            J[i][j] = s * il;
+            for (int k = 0; k < j; k++) s -= A[i][k] * A[j][k];
+            A[i][j] = s * il;
         }
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        double s = h[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= J[i][k] * h[k];
-        h[i] = s / J[i][i];
-        quad += h[i] * h[i];
     }
     return true;
 }
 
-// Λ μ = η by the factor chol_quad left in L (h = L⁻¹ η on entry): back substitution
+// y <- L⁻¹ y
 template <int N>
-__device__ __forceinline__ void back_solve(const double (&L)[N][N], const double (&y)[N], double (&x)[N]) {
+CX_LA void fwd_solve(const double (&L)[N][N], double (&y)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        double s = y[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) s -= L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+}
+
+// x = L⁻ᵀ y
+template <int N>
+CX_LA void back_solve(const double (&L)[N][N], const double (&y)[N], double (&x)[N]) {
 #pragma unroll
     for (int i = N - 1; i >= 0; i--) {
         double s = y[i];
@@ -93,6 +114,123 @@ __device__ __forceinline__ void back_solve(const double (&L)[N][N], const double
         x[i] = s / L[i][i];
     }
 }
+
+// J = L L' in place, h <- L⁻¹ h: log det J and h'J⁻¹h.  false: not positive definite
+template <int N>
+CX_LA bool chol_quad(double (&J)[N][N], double (&h)[N], double &logdet, double &quad) {
+    logdet = 0.0; quad = 0.0;
+    if (!chol<N>(J, &logdet)) return false;
+    fwd_solve<N>(J, h);
+#pragma unroll
+    for (int i = 0; i < N; i++) quad += h[i] * h[i];
+    return true;
+}
+
+// x = (L L')⁻¹ b
+template <int N>
+CX_LA void chol_solve(const double (&L)[N][N], const double (&b)[N], double (&x)[N]) {
+    double y[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) y[i] = b[i];
+    fwd_solve<N>(L, y);
+    back_solve<N>(L, y, x);
+}
+
+// The two inverses reach L⁻¹ by different orders of operations and differ in the last bits: each caller keeps the one it was checked with.
+// L <- L⁻¹ in place, row by row (row i reads L's row i to the right of the entry it writes, and the rows of L⁻¹ above it)
+template <int N>
+CX_LA void inv_lower(double (&L)[N][N]) {
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+#pragma unroll
+        for (int j = 0; j < i; j++) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = j; k < i; k++) s += L[i][k] * L[k][j];
+            L[i][j] = -s / L[i][i];
+        }
+        L[i][i] = 1.0 / L[i][i];
+    }
+}
+
+// the lower triangle of S = Li' Li for a lower Li: (L L')⁻¹ from inv_lower's L⁻¹
+template <int N>
+CX_LA void gram_lower(const double (&Li)[N][N], double (&S)[N][N]) {
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = i; k < N; k++) s += Li[k][i] * Li[k][j];
+            S[i][j] = s;
+        }
+}
+
+// M = L⁻ᵀ (upper), by a forward solve per unit vector: row r of M = column r of L⁻¹
+template <int N>
+CX_LA void inv_t(const double (&L)[N][N], double (&M)[N][N]) {
+#pragma unroll
+    for (int r = 0; r < N; r++) {
+        double y[N];
+#pragma unroll
+        for (int c = 0; c < N; c++) {
+            double s = c == r ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = 0; k < c; k++) s -= L[c][k] * y[k];
+            y[c] = c < r ? 0.0 : s / L[c][c];
+        }
+#pragma unroll
+        for (int c = 0; c < N; c++) M[r][c] = y[c];
+    }
+}
+
+// the same on a matrix behind at(i, j)
+template <class At>
+CX_LA bool chol_at(int n, At at, double *logdet = nullptr) {
+    for (int j = 0; j < n; j++) {
+        double d = at(j, j);
+        for (int k = 0; k < j; k++) { const double l = at(j, k); d -= l * l; }
+        if (!(d > 0.0)) return false;
+        if (logdet) *logdet += log(d);
+        const double l = sqrt(d), il = 1.0 / l;
+        at(j, j) = l;
+        for (int i = j + 1; i < n; i++) {
+            double u = at(i, j);
+            for (int k = 0; k < j; k++) u -= at(i, k) * at(j, k);
+            at(i, j) = u * il;
+        }
+    }
+    return true;
+}
+
+// y <- L⁻¹ y
+template <class At, class Y>
+CX_LA void fwd_solve_at(int n, At at, Y y) {
+    for (int i = 0; i < n; i++) {
+        double u = y(i);
+        for (int k = 0; k < i; k++) u -= at(i, k) * y(k);
+        y(i) = u / at(i, i);
+    }
+}
+
+// y <- L⁻ᵀ y
+template <class At, class Y>
+CX_LA void back_solve_at(int n, At at, Y y) {
+    for (int i = n - 1; i >= 0; i--) {
+        double u = y(i);
+        for (int k = i + 1; k < n; k++) u -= at(k, i) * y(k);
+        y(i) = u / at(i, i);
+    }
+}
+
+// y <- (L L')⁻¹ y
+template <class At, class Y>
+CX_LA void chol_solve_at(int n, At at, Y y) {
+    fwd_solve_at(n, at, y);
+    back_solve_at(n, at, y);
+}
+#undef CX_LA
 
 // ---- pass 2 helpers -------------------------------------------------------------------------------------------------------------
 // one non-observed edge of a factor: the centred leave-one-out message m~_{i→a} (η~, Λ~) and the centre μ_i
@@ -133,70 +271,109 @@ __device__ __forceinline__ void datum(const double *__restrict__ v2f, int slot, 
     ld_msg<D>(v2f, slot, y, l);
 }
 
-// ---- a factor of two variables x_out = A x_in + b + N(0, Q): its parameters and its belief's joint, shared by cx_factor_beliefs /
-// cx_factor_statistics (cx_learn.hip) and the sampler (cx_sample.hip).  Pair row p of the table of cx_evidence.hip: dim 1 (q, a, b) per
-// row (pa, pb may be null: a = 1, b = 0); dim > 1 the row's parameter set in ptab = [set][A | Q⁻¹ | log det 2πQ, 0] (b = 0).
+// ---- the tables and the messages, as the kernels take them (filled by Cache::pair_tab / kary_tab and msgs_of) --------------------------
+// pair row p: rec[p] = (slot out, slot in, var out, var in) of x_out = A x_in + b + N(0, Q).  dim 1: (q, a, b) per row (pa, pb may be
+// null: a = 1, b = 0); dim > 1: the row's parameter set pset[p] in ptab = [set][A | Q⁻¹ | log det 2πQ, 0] (b = 0)
+struct PairTab {
+    const int4 *rec;
+    const int32_t *pset;
+    const double *pq, *pa, *pb, *ptab;
+};
+// k-ary row f: x_out = Σ A_k x_k + b + N(0, Q), entries in the k-ary table's order (OUT first).  krec[f] = slots[8] | vars[8] (-1: none).
+// dim 1: kc[f] = C_e[8] (+1 OUT, -a_i IN) | q | b.  dim > 1: kps[f] = parameter set per entry (IN: its A; OUT: Q); ptab as PairTab's
+struct KaryTab {
+    const int32_t *krec;
+    const double *kc;
+    const int32_t *kps;
+    const double *ptab;
+};
+// the observed flags, the stored messages of both directions and the scratch of the variable pass
+struct Msgs {
+    const uint8_t *vinfo;
+    const double *f2v, *v2f, *W;
+};
+
+// ---- the belief of pair row p, centred on its ends' centres c (a free end: its belief mean, free_edge; an observed end: its datum):
+// precision J and right-hand side h over (out, in), 2d x 2d, with rc = c_out - A c_in - b, g = -Q⁻¹ rc and η~, Λ~ the centred
+// leave-one-out messages of the free ends.  An observed end (fo / fi false) is an identity block with h = 0, so the D x D block of
+// the free end of a factor with one observed end is that factor's whole joint.  ok: every input is defined.
 template <int D>
-__device__ __forceinline__ void pair_params(int64_t p, const int32_t *__restrict__ pset, const double *__restrict__ pq, const double *__restrict__ pa,
-                                            const double *__restrict__ pb, const double *__restrict__ ptab, double (&A)[D][D], double (&Qi)[D][D],
-                                            double (&bb)[D]) {
+struct PairJoint {
+    bool fo, fi, ok;
+    double A[D][D], c[2 * D], rc[D], g[D], ldq;      // ldq = log det 2πQ
+    double J[2 * D][2 * D], h[2 * D];
+};
+
+template <int D>
+__device__ __forceinline__ void pair_joint(int64_t p, const PairTab &T, const Msgs &M, PairJoint<D> &B) {
+    constexpr int NT = Lay<D>::NT;
+    double (&A)[D][D] = B.A;
+    double Qi[D][D], bb[D];
     if constexpr (D == 1) {
-        A[0][0] = pa ? pa[p] : 1.0; Qi[0][0] = 1.0 / pq[p]; bb[0] = pb ? pb[p] : 0.0;
+        const double q = T.pq[p];
+        A[0][0] = T.pa ? T.pa[p] : 1.0; Qi[0][0] = 1.0 / q; B.ldq = log(q) + kLog2Pi; bb[0] = T.pb ? T.pb[p] : 0.0;
     } else {
-        const double *t = ptab + (int64_t)pset[p] * (2 * D * D + 2);
+        const double *t = T.ptab + (int64_t)T.pset[p] * (2 * D * D + 2);
 #pragma unroll
         for (int i = 0; i < D; i++) {
             bb[i] = 0.0;
 #pragma unroll
             for (int j = 0; j < D; j++) { A[i][j] = t[i * D + j]; Qi[i][j] = t[D * D + i * D + j]; }
         }
+        B.ldq = t[2 * D * D];
     }
-}
-
-// the factor belief's precision J and right-hand side h over (out, in), 2d x 2d, in coordinates centred on the ends' centres (rc = c_out -
-// A c_in - b; η~, Λ~ the centred leave-one-out messages of free ends): an observed end (fo / fi false) is an identity block with h = 0
-template <int D>
-__device__ __forceinline__ void pair_joint(const double (&A)[D][D], const double (&Qi)[D][D], const double (&rc)[D], bool fo, bool fi, const double (&eo)[D],
-                                           const double (&lo)[Lay<D>::NT], const double (&ei)[D], const double (&li)[Lay<D>::NT],
-                                           double (&J)[2 * D][2 * D], double (&h)[2 * D]) {
-    double g[D], T[D][D];       // g = -Q⁻¹ rc, T = Q⁻¹ A
+    const int4 r = T.rec[p];
+    const bool fo = B.fo = !(M.vinfo[r.z] & kClamped), fi = B.fi = !(M.vinfo[r.w] & kClamped);
+    double mo[D], eo[D], lo[NT], mi[D], ei[D], li[NT];
+    B.ok = true;
+    if (fo) B.ok = free_edge<D>(M.f2v, M.W, r.x, r.z, mo, eo, lo) && B.ok;
+    else datum<D>(M.v2f, r.x, mo);
+    if (fi) B.ok = free_edge<D>(M.f2v, M.W, r.y, r.w, mi, ei, li) && B.ok;
+    else datum<D>(M.v2f, r.y, mi);
+    double T_[D][D];       // Q⁻¹ A
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+        B.c[i] = mo[i]; B.c[D + i] = mi[i];
+        double t = mo[i] - bb[i];
+#pragma unroll
+        for (int j = 0; j < D; j++) t -= A[i][j] * mi[j];
+        B.rc[i] = t;
+    }
 #pragma unroll
     for (int i = 0; i < D; i++) {
         double t = 0.0;
 #pragma unroll
-        for (int j = 0; j < D; j++) t -= Qi[i][j] * rc[j];
-        g[i] = t;
+        for (int j = 0; j < D; j++) t -= Qi[i][j] * B.rc[j];
+        B.g[i] = t;
 #pragma unroll
         for (int j = 0; j < D; j++) {
             double u = 0.0;
 #pragma unroll
             for (int k = 0; k < D; k++) u += Qi[i][k] * A[k][j];
-            T[i][j] = u;
+            T_[i][j] = u;
         }
     }
 #pragma unroll
     for (int i = 0; i < D; i++) {
         double t = 0.0;
 #pragma unroll
-        for (int k = 0; k < D; k++) t += A[k][i] * g[k];
-        h[i] = fo ? g[i] + eo[i] : 0.0;
-        h[D + i] = fi ? -t + ei[i] : 0.0;
+        for (int k = 0; k < D; k++) t += A[k][i] * B.g[k];
+        B.h[i] = fo ? B.g[i] + eo[i] : 0.0;
+        B.h[D + i] = fi ? -t + ei[i] : 0.0;
 #pragma unroll
         for (int j = 0; j < D; j++) {
             double u = 0.0;
 #pragma unroll
-            for (int k = 0; k < D; k++) u += A[k][i] * T[k][j];
-            J[i][j] = fo ? Qi[i][j] + lam_at<D>(lo, i, j) : (i == j ? 1.0 : 0.0);
-            J[D + i][D + j] = fi ? u + lam_at<D>(li, i, j) : (i == j ? 1.0 : 0.0);
-            J[D + i][j] = fo && fi ? -T[j][i] : 0.0;
-            J[j][D + i] = J[D + i][j];
+            for (int k = 0; k < D; k++) u += A[k][i] * T_[k][j];
+            B.J[i][j] = fo ? Qi[i][j] + lam_at<D>(lo, i, j) : (i == j ? 1.0 : 0.0);
+            B.J[D + i][D + j] = fi ? u + lam_at<D>(li, i, j) : (i == j ? 1.0 : 0.0);
+            B.J[D + i][j] = fo && fi ? -T_[j][i] : 0.0;
+            B.J[j][D + i] = B.J[D + i][j];
         }
     }
 }
 
 // ---- the joint of a factor of 3 .. 7 variables (k-ary table row f), shared by k_ev_kary and the sampler's k_sp_cond_kary -----------
-// x_out = Σ A_k x_k + b + N(0, Q), entries in the k-ary table's order (OUT first).  krec[f] = slots[8] | vars[8] (-1: none).
-// dim 1: kc[f] = C_e[8] (+1 OUT, -a_i IN) | q | b.  dim > 1: kps[f] = parameter set per entry (IN: its A; OUT: Q); ptab as k_ev_pair's.
 // Writes the joint precision over the free entries (packed lower triangle, element k at J[k * NB]) and its right-hand side (hv), in
 // coordinates centred on the free entries' belief means; returns Q⁻¹, log det 2πQ, b'' = b - Σ C_e x_e at the data / the centres,
 // g = Q⁻¹ b'', cq = b'' g, the mask and count of the free entries and whether every input is defined.
@@ -213,27 +390,25 @@ __device__ __forceinline__ double cel(const double *__restrict__ Ae, double ce, 
 }
 
 template <int D, int NB>
-__device__ __forceinline__ void kary_joint(int64_t f, const int32_t *__restrict__ krec, const double *__restrict__ kc, const int32_t *__restrict__ kps,
-                                           const double *__restrict__ ptab, const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v,
-                                           const double *__restrict__ v2f, const double *__restrict__ W, double *__restrict__ J, double *__restrict__ hv,
+__device__ __forceinline__ void kary_joint(int64_t f, const KaryTab &T, const Msgs &M, double *__restrict__ J, double *__restrict__ hv,
                                            double (&Qi)[D][D], double &ldq, double (&bp)[D], double (&g)[D], double &cq, unsigned &freemask, int &nfree,
                                            bool &ok) {
     constexpr int NT = Lay<D>::NT, PS = 2 * D * D + 2;
-    const int32_t *sl = krec + f * 16, *vr = sl + 8;
+    const int32_t *sl = T.krec + f * 16, *vr = sl + 8;
     // C_e of entry e: dim 1 the coefficient, dim > 1 I (OUT) or -A of the entry's set (read where used: no per-thread arrays)
     auto Aof = [&](int e) -> const double * {
         if constexpr (D == 1) return nullptr;
-        else return e == 0 ? nullptr : ptab + (int64_t)kps[f * 8 + e] * PS;
+        else return e == 0 ? nullptr : T.ptab + (int64_t)T.kps[f * 8 + e] * PS;
     };
     auto Cof = [&](int e) -> double {
-        if constexpr (D == 1) return kc[f * 10 + e];
+        if constexpr (D == 1) return T.kc[f * 10 + e];
         else return 0.0;
     };
     if constexpr (D == 1) {
-        const double *k = kc + f * 10;
+        const double *k = T.kc + f * 10;
         Qi[0][0] = 1.0 / k[8]; ldq = log(k[8]) + kLog2Pi; bp[0] = k[9];
     } else {
-        const double *tq = ptab + (int64_t)kps[f * 8] * PS;
+        const double *tq = T.ptab + (int64_t)T.kps[f * 8] * PS;
 #pragma unroll
         for (int p = 0; p < D; p++) {
             bp[p] = 0.0;
@@ -248,10 +423,10 @@ __device__ __forceinline__ void kary_joint(int64_t f, const int32_t *__restrict_
     for (int e = 0; e < 8; e++) {
         if (sl[e] < 0) continue;
         double x[D];
-        if (vinfo[vr[e]] & kClamped) datum<D>(v2f, sl[e], x);
+        if (M.vinfo[vr[e]] & kClamped) datum<D>(M.v2f, sl[e], x);
         else {
             double et[D], lm[NT];
-            ok = free_edge<D>(f2v, W, sl[e], vr[e], x, et, lm) && ok;
+            ok = free_edge<D>(M.f2v, M.W, sl[e], vr[e], x, et, lm) && ok;
             const int o = nfree * D;
             for (int r = 0; r < D; r++) {
                 hv[(o + r) * NB] = et[r];
@@ -329,8 +504,11 @@ struct Cache {
     DevBuf<int4> d_pair;
     DevBuf<int32_t> d_pair_ps, d_krec, d_kps;
     DevBuf<double> d_pq, d_pa, d_pb, d_kc, d_ptab;
+    std::vector<int4> pair;               // the pair rows (d_pair) and the k-ary rows (d_krec) as uploaded
+    std::vector<int32_t> krec;
     std::vector<int32_t> pair_ps;         // dim > 1: parameter set per pair (what the table must hold)
     std::vector<int64_t> pair_fac;        // factor index of every pair row (rows in factor order)
+    std::vector<int32_t> row_of_fac, kary_row_of_fac;      // pair row / k-ary row of every factor index (-1: none)
     DevBuf<double> d_W;
     DevBuf<Part> d_partial;
     DevBuf<double> d_out;
@@ -338,15 +516,19 @@ struct Cache {
     Cache() = default;
     Cache(const Cache &) = delete;
     ~Cache() { if (h_out) (void)hipHostFree(h_out); }
+    PairTab pair_tab() const { return {d_pair, d_pair_ps, d_pq, d_pa, d_pb, d_ptab}; }
+    KaryTab kary_tab() const { return {d_krec, d_kc, d_kps, d_ptab}; }
 };
 
-// the checks every evidence-type call makes (family, dim, partitions, captured stream, rule kinds, zero noise), then the work lists,
-// the parameter table and (chain scan, dim 2..4) the messages in their slots; `who` prefixes every error text
-int32_t prepare(cx_handle *h, const std::string &who, Cache *&C);
+// the checks every evidence-type call makes, in this order: family (its text ends in family_note), graph, the entry's own arguments
+// (bad_args: what is wrong with them, null: nothing), dim, partitions, captured stream, rule kinds, zero noise; then the work lists,
+// the parameter table and (chain scan, dim 2..4) the messages in their slots.  `who` prefixes every error text
+int32_t prepare(cx_handle *h, const std::string &who, const char *bad_args, Cache *&C, const char *family_note = "");
 // pass 1 only (k_ev_var) on the handle's stream: the per-variable scratch C.d_W; the handle's stored f2v messages
 void var_pass(cx_handle *h, Cache &C);
 inline const double *f2v_of(const cx_handle *h) { return h->cfg.dim == 1 ? (const double *)h->d_f2v : h->d_mv_f2v; }
 inline const double *v2f_of(const cx_handle *h) { return h->cfg.dim == 1 ? (const double *)h->d_v2f : h->d_mv_v2f; }
+inline Msgs msgs_of(const cx_handle *h, const Cache &C) { return {h->d_vinfo, f2v_of(h), v2f_of(h), C.d_W}; }
 
 }  // namespace ev
 }  // namespace cx

@@ -33,85 +33,43 @@ struct SLay {
 
 // the joint belief of pair row p, centred: centre c (the belief means of the free ends, the data of the observed ones), offset dl
 // (zero on observed ends) and covariance S (zero rows and columns on observed ends); also the factor's A and residual at the
-// centre, rc = c_out - A c_in - b.  Returns 0, 1 (an undefined input) or 2 (the belief is not positive definite).
+// centre, rc = c_out - A c_in - b (in B).  Returns 0, 1 (an undefined input) or 2 (the belief is not positive definite).
 template <int D>
-__device__ __forceinline__ int pair_belief(int64_t p, const int4 *__restrict__ rec, const int32_t *__restrict__ pset, const double *__restrict__ pq,
-                                           const double *__restrict__ pa, const double *__restrict__ pb, const double *__restrict__ ptab,
-                                           const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v, const double *__restrict__ v2f,
-                                           const double *__restrict__ W, double (&c)[2 * D], double (&dl)[2 * D], double (&S)[2 * D][2 * D],
-                                           double (&A)[D][D], double (&rc)[D]) {
-    constexpr int NT = Lay<D>::NT, N = 2 * D;
-    const int4 r = rec[p];
-    double Qi[D][D], bb[D];
-    ev::pair_params<D>(p, pset, pq, pa, pb, ptab, A, Qi, bb);
-    const bool fo = !(vinfo[r.z] & kClamped), fi = !(vinfo[r.w] & kClamped);
-    double mo[D], eo[D], lo[NT], mi[D], ei[D], li[NT];
-    bool ok = true;
-    if (fo) ok = ev::free_edge<D>(f2v, W, r.x, r.z, mo, eo, lo) && ok;
-    else ev::datum<D>(v2f, r.x, mo);
-    if (fi) ok = ev::free_edge<D>(f2v, W, r.y, r.w, mi, ei, li) && ok;
-    else ev::datum<D>(v2f, r.y, mi);
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-        c[i] = mo[i]; c[D + i] = mi[i];
-        double t = mo[i] - bb[i];
-#pragma unroll
-        for (int j = 0; j < D; j++) t -= A[i][j] * mi[j];
-        rc[i] = t;
-    }
-    if (!ok) return 1;
-    double J[N][N], h[N];
-    ev::pair_joint<D>(A, Qi, rc, fo, fi, eo, lo, ei, li, J, h);
+__device__ __forceinline__ int pair_belief(int64_t p, const ev::PairTab &tab, const ev::Msgs &msg, ev::PairJoint<D> &B, double (&dl)[2 * D],
+                                           double (&S)[2 * D][2 * D]) {
+    constexpr int N = 2 * D;
+    ev::pair_joint<D>(p, tab, msg, B);
+    if (!B.ok) return 1;
     double logdet, quad;
-    if (!ev::chol_quad<N>(J, h, logdet, quad)) return 2;
-    ev::back_solve<N>(J, h, dl);
-    // L⁻¹ in place, row by row (row i reads L's row i to the right of the entry it writes, and the rows of L⁻¹ above it)
+    if (!ev::chol_quad<N>(B.J, B.h, logdet, quad)) return 2;
+    ev::back_solve<N>(B.J, B.h, dl);
+    ev::inv_lower<N>(B.J);
+    ev::gram_lower<N>(B.J, S);      // Σ = L⁻ᵀ L⁻¹: its lower triangle, masked and mirrored below
 #pragma unroll
     for (int i = 0; i < N; i++) {
-#pragma unroll
-        for (int j = 0; j < i; j++) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = j; k < i; k++) s += J[i][k] * J[k][j];
-            J[i][j] = -s / J[i][i];
-        }
-        J[i][i] = 1.0 / J[i][i];
-    }
-    // Σ = L⁻ᵀ L⁻¹
-#pragma unroll
-    for (int i = 0; i < N; i++)
+        if (!(i < D ? B.fo : B.fi)) dl[i] = 0.0;
 #pragma unroll
         for (int j = 0; j <= i; j++) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = i; k < N; k++) s += J[k][i] * J[k][j];
-            const bool keep = (i < D ? fo : fi) && (j < D ? fo : fi);
-            S[i][j] = keep ? s : 0.0;
+            S[i][j] = (i < D ? B.fo : B.fi) && (j < D ? B.fo : B.fi) ? S[i][j] : 0.0;
             S[j][i] = S[i][j];
         }
-#pragma unroll
-    for (int i = 0; i < D; i++) {
-        if (!fo) dl[i] = 0.0;
-        if (!fi) dl[D + i] = 0.0;
     }
     return 0;
 }
 
 // ---- beliefs: one thread per requested pair row -----------------------------------------------------------------------------------
 template <int D>
-__global__ __launch_bounds__(kW) void k_fs_belief(int64_t n, const int32_t *__restrict__ rows, const int4 *__restrict__ rec, const int32_t *__restrict__ pset,
-                                                  const double *__restrict__ pq, const double *__restrict__ pa, const double *__restrict__ pb,
-                                                  const double *__restrict__ ptab, const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v,
-                                                  const double *__restrict__ v2f, const double *__restrict__ W, double *__restrict__ out) {
+__global__ __launch_bounds__(kW) void k_fs_belief(int64_t n, const int32_t *__restrict__ rows, ev::PairTab tab, ev::Msgs msg, double *__restrict__ out) {
     constexpr int N = 2 * D;
     const int64_t i = (int64_t)blockIdx.x * kW + threadIdx.x;
     if (i >= n) return;
     const double nan = __builtin_nan("");
-    double c[N], dl[N], S[N][N], A[D][D], rc[D];
-    const int st = pair_belief<D>(rows[i], rec, pset, pq, pa, pb, ptab, vinfo, f2v, v2f, W, c, dl, S, A, rc);
+    ev::PairJoint<D> B;
+    double dl[N], S[N][N];
+    const int st = pair_belief<D>(rows[i], tab, msg, B, dl, S);
     double *o = out + i * SLay<D>::NB;
 #pragma unroll
-    for (int k = 0; k < N; k++) o[k] = st ? nan : c[k] + dl[k];
+    for (int k = 0; k < N; k++) o[k] = st ? nan : B.c[k] + dl[k];
 #pragma unroll
     for (int k = 0; k < N; k++)
 #pragma unroll
@@ -120,10 +78,7 @@ __global__ __launch_bounds__(kW) void k_fs_belief(int64_t n, const int32_t *__re
 
 // ---- statistics: one block per chunk of one group; row k of part = sums[NW] | compensations[NW] -----------------------------------
 template <int D>
-__global__ __launch_bounds__(kW) void k_fs_stats(const int32_t *__restrict__ cbeg, const int32_t *__restrict__ items, const int4 *__restrict__ rec,
-                                                 const int32_t *__restrict__ pset, const double *__restrict__ pq, const double *__restrict__ pa,
-                                                 const double *__restrict__ pb, const double *__restrict__ ptab, const uint8_t *__restrict__ vinfo,
-                                                 const double *__restrict__ f2v, const double *__restrict__ v2f, const double *__restrict__ W,
+__global__ __launch_bounds__(kW) void k_fs_stats(const int32_t *__restrict__ cbeg, const int32_t *__restrict__ items, ev::PairTab tab, ev::Msgs msg,
                                                  double *__restrict__ part) {
     constexpr int N = 2 * D, NW = SLay<D>::NW, P = kW + 1;     // (P: entry j of the 64 threads spreads over the banks)
     __shared__ double sv[NW * P];
@@ -131,8 +86,10 @@ __global__ __launch_bounds__(kW) void k_fs_stats(const int32_t *__restrict__ cbe
     const int64_t i = (int64_t)cbeg[blockIdx.x] + t;
     double *v = sv + t;                                        // entry k of this thread at v[k * P]
     if (i < cbeg[blockIdx.x + 1]) {
-        double c[N], dl[N], S[N][N], A[D][D], rc[D];
-        const int st = pair_belief<D>(items[i], rec, pset, pq, pa, pb, ptab, vinfo, f2v, v2f, W, c, dl, S, A, rc);
+        ev::PairJoint<D> B;
+        double dl[N], S[N][N];
+        const int st = pair_belief<D>(items[i], tab, msg, B, dl, S);
+        const double (&A)[D][D] = B.A;
         v[0] = 1.0;
         if (st) {
 #pragma unroll
@@ -143,11 +100,11 @@ __global__ __launch_bounds__(kW) void k_fs_stats(const int32_t *__restrict__ cbe
             double er[D], ex[D], CS[D][N];          // E[r], E[x_in], C Σ
 #pragma unroll
             for (int p = 0; p < D; p++) {
-                double t0 = rc[p] + dl[p];
+                double t0 = B.rc[p] + dl[p];
 #pragma unroll
                 for (int q = 0; q < D; q++) t0 -= A[p][q] * dl[D + q];
                 er[p] = t0;
-                ex[p] = c[D + p] + dl[D + p];
+                ex[p] = B.c[D + p] + dl[D + p];
 #pragma unroll
                 for (int k = 0; k < N; k++) {
                     double u = S[p][k];
@@ -221,7 +178,6 @@ struct Cache {
     // beliefs (grown on demand)
     DevBuf<int32_t> d_brows;
     DevBuf<double> d_bout;
-    std::vector<int32_t> row_of_fac;               // pair row of every factor index (-1: none)
     Cache() = default;
     Cache(const Cache &) = delete;
     ~Cache() { if (h_rows) (void)hipHostFree(h_rows); }
@@ -234,18 +190,13 @@ void free_lists(Cache &L) {
     L.valid = false;
 }
 
-Cache &cache_of(cx_handle *h, const ev::Cache &E) {
+Cache &cache_of(cx_handle *h) {
     if (!h->learn) h->learn.reset(new Cache());
-    Cache &L = *h->learn;
-    if (L.row_of_fac.size() != (size_t)h->nf) {
-        L.row_of_fac.assign((size_t)h->nf, -1);
-        for (size_t r = 0; r < E.pair_fac.size(); r++) L.row_of_fac[(size_t)E.pair_fac[r]] = (int32_t)r;
-    }
-    return L;
+    return *h->learn;
 }
 
 // the group of every pair row (-1: not counted), checked; the caller's arrays (explicit) or the parameter sets (ids == null, dim > 1)
-int32_t assign_groups(cx_handle *h, const ev::Cache &E, Cache &L, int64_t n, const int64_t *ids, const int64_t *groups, int64_t n_groups,
+int32_t assign_groups(cx_handle *h, const ev::Cache &E, int64_t n, const int64_t *ids, const int64_t *groups, int64_t n_groups,
                       std::vector<int32_t> &grp) {
     using namespace cxh;
     const std::string who = "cx_factor_statistics";
@@ -281,7 +232,7 @@ int32_t assign_groups(cx_handle *h, const ev::Cache &E, Cache &L, int64_t n, con
         const int64_t g = groups[i];
         if (g < -1 || g >= n_groups) return fail(h, CX_ERR_INVALID_ARGUMENT, who + ": group " + std::to_string(g) + " of factor " + std::to_string(ids[i]) + " is not in -1 .. n_groups - 1");
         if (g < 0) continue;
-        const int32_t p = L.row_of_fac[(size_t)f];
+        const int32_t p = E.row_of_fac[(size_t)f];
         if (p < 0) return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(ids[i]) + " is not a Gaussian factor of two variables");
         if (grp[(size_t)p] >= 0) return fail(h, CX_ERR_INVALID_ARGUMENT, who + ": factor " + std::to_string(ids[i]) + " is listed twice");
         grp[(size_t)p] = (int32_t)g;
@@ -358,11 +309,9 @@ int32_t build_lists(cx_handle *h, Cache &L, const std::vector<int32_t> &grp, int
 template <int D>
 void launch_stats(cx_handle *h, const ev::Cache &E, const Cache &L, int &final_buf) {
     constexpr int NW = SLay<D>::NW;
-    const double *f2v = ev::f2v_of(h), *v2f = ev::v2f_of(h);
     final_buf = 0;
     if (L.n_chunks == 0) return;
-    hipLaunchKernelGGL(k_fs_stats<D>, dim3((unsigned)L.n_chunks), dim3(kW), 0, h->stream, L.d_cbeg, L.d_items, E.d_pair, E.d_pair_ps, E.d_pq, E.d_pa,
-                       E.d_pb, E.d_ptab, h->d_vinfo, f2v, v2f, E.d_W, L.d_rows[0]);
+    hipLaunchKernelGGL(k_fs_stats<D>, dim3((unsigned)L.n_chunks), dim3(kW), 0, h->stream, L.d_cbeg, L.d_items, E.pair_tab(), ev::msgs_of(h, E), L.d_rows[0]);
     for (size_t l = 0; l < L.level_n.size(); l++) {
         hipLaunchKernelGGL(k_fs_reduce, dim3((unsigned)L.level_n[l]), dim3(kW), 0, h->stream, L.d_seg + L.level_off[l], NW, L.d_rows[final_buf],
                            L.d_rows[1 - final_buf]);
@@ -372,13 +321,11 @@ void launch_stats(cx_handle *h, const ev::Cache &E, const Cache &L, int &final_b
 
 template <int D>
 void launch_beliefs(cx_handle *h, const ev::Cache &E, const Cache &L, int64_t n) {
-    const double *f2v = ev::f2v_of(h), *v2f = ev::v2f_of(h);
-    hipLaunchKernelGGL(k_fs_belief<D>, dim3((unsigned)((n + kW - 1) / kW)), dim3(kW), 0, h->stream, n, L.d_brows, E.d_pair, E.d_pair_ps, E.d_pq,
-                       E.d_pa, E.d_pb, E.d_ptab, h->d_vinfo, f2v, v2f, E.d_W, L.d_bout);
+    hipLaunchKernelGGL(k_fs_belief<D>, dim3((unsigned)((n + kW - 1) / kW)), dim3(kW), 0, h->stream, n, L.d_brows, E.pair_tab(), ev::msgs_of(h, E), L.d_bout);
 }
 
-int nw_of(int d) { return d == 1 ? SLay<1>::NW : d == 2 ? SLay<2>::NW : d == 3 ? SLay<3>::NW : SLay<4>::NW; }
-int nb_of(int d) { return d == 1 ? SLay<1>::NB : d == 2 ? SLay<2>::NB : d == 3 ? SLay<3>::NB : SLay<4>::NB; }
+int nw_of(int d) { return ev::with_dim(d, [](auto D) { return SLay<D()>::NW; }); }
+int nb_of(int d) { return ev::with_dim(d, [](auto D) { return SLay<D()>::NB; }); }
 
 }  // namespace fs
 
@@ -389,33 +336,26 @@ template <> void Deleter<fs::Cache>::operator()(fs::Cache *L) const { delete L; 
 using namespace cxh;
 
 extern "C" int32_t cx_factor_beliefs(cx_handle *h, int64_t n, const int64_t *factor_ids, double *out) {
-    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, "cx_factor_beliefs: the Gaussian family only");
-    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_factor_beliefs: no graph");
-    CX_REQUIRE(h, n >= 0 && (n == 0 || (factor_ids && out)), CX_ERR_INVALID_ARGUMENT, "cx_factor_beliefs: null argument or negative count");
     try {
         cx::ev::Cache *Ep = nullptr;
         int32_t rc;
-        if ((rc = cx::ev::prepare(h, "cx_factor_beliefs", Ep)) != CX_OK) return rc;
+        const char *bad = n >= 0 && (n == 0 || (factor_ids && out)) ? nullptr : "null argument or negative count";
+        if ((rc = cx::ev::prepare(h, "cx_factor_beliefs", bad, Ep)) != CX_OK) return rc;
         if (n == 0) return CX_OK;
         cx::ev::Cache &E = *Ep;
-        cx::fs::Cache &L = cx::fs::cache_of(h, E);
+        cx::fs::Cache &L = cx::fs::cache_of(h);
         std::vector<int32_t> rows((size_t)n);
         for (int64_t i = 0; i < n; i++) {
             const int64_t f = find_factor(h, factor_ids[i]);
             if (f < 0) return fail(h, CX_ERR_NOT_FOUND, "cx_factor_beliefs: no factor " + std::to_string(factor_ids[i]));
-            rows[(size_t)i] = L.row_of_fac[(size_t)f];
+            rows[(size_t)i] = E.row_of_fac[(size_t)f];
             if (rows[(size_t)i] < 0) return fail(h, CX_ERR_UNSUPPORTED, "cx_factor_beliefs: factor " + std::to_string(factor_ids[i]) + " is not a Gaussian factor of two variables");
         }
         const int d = h->cfg.dim, nb = cx::fs::nb_of(d);
         if ((rc = L.d_brows.ensure(h, n)) != CX_OK || (rc = L.d_bout.ensure(h, n * nb)) != CX_OK) return rc;
         CX_HIP(h, hipMemcpyAsync(L.d_brows, rows.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
         cx::ev::var_pass(h, E);
-        switch (d) {
-        case 1: cx::fs::launch_beliefs<1>(h, E, L, n); break;
-        case 2: cx::fs::launch_beliefs<2>(h, E, L, n); break;
-        case 3: cx::fs::launch_beliefs<3>(h, E, L, n); break;
-        default: cx::fs::launch_beliefs<4>(h, E, L, n); break;
-        }
+        cx::ev::with_dim(d, [&](auto D) { cx::fs::launch_beliefs<D()>(h, E, L, n); });
         CX_HIP(h, hipGetLastError());
         CX_HIP(h, hipMemcpyAsync(out, L.d_bout, (size_t)(n * nb) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         CX_HIP(h, hipStreamSynchronize(h->stream));
@@ -425,20 +365,19 @@ extern "C" int32_t cx_factor_beliefs(cx_handle *h, int64_t n, const int64_t *fac
 
 extern "C" int32_t cx_factor_statistics(cx_handle *h, int64_t n, const int64_t *factor_ids, const int64_t *groups, int64_t n_groups, double *out,
                                         int64_t *counts4) {
-    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, "cx_factor_statistics: the Gaussian family only");
-    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_factor_statistics: no graph");
-    CX_REQUIRE(h, out && counts4 && n_groups > 0, CX_ERR_INVALID_ARGUMENT, "cx_factor_statistics: null output or n_groups < 1");
-    CX_REQUIRE(h, factor_ids ? (n >= 0 && (n == 0 || groups)) : !groups, CX_ERR_INVALID_ARGUMENT,
-               "cx_factor_statistics: factor_ids and groups go together (n >= 0), or both null for the parameter-set grouping");
     try {
         cx::ev::Cache *Ep = nullptr;
         int32_t rc;
-        if ((rc = cx::ev::prepare(h, "cx_factor_statistics", Ep)) != CX_OK) return rc;
+        const char *bad = !(out && counts4 && n_groups > 0) ? "null output or n_groups < 1"
+                          : !(factor_ids ? (n >= 0 && (n == 0 || groups)) : !groups)
+                              ? "factor_ids and groups go together (n >= 0), or both null for the parameter-set grouping"
+                              : nullptr;
+        if ((rc = cx::ev::prepare(h, "cx_factor_statistics", bad, Ep)) != CX_OK) return rc;
         const int d = h->cfg.dim;
         CX_REQUIRE(h, factor_ids || d > 1, CX_ERR_INVALID_ARGUMENT,
                    "cx_factor_statistics: dim 1 has per-factor parameters: name the factors and their groups (factor_ids, groups)");
         cx::ev::Cache &E = *Ep;
-        cx::fs::Cache &L = cx::fs::cache_of(h, E);
+        cx::fs::Cache &L = cx::fs::cache_of(h);
         const int nw = cx::fs::nw_of(d), ns = nw - 2;
         // an explicit grouping is compared with the cached one (O(n) on the host); a new one is checked and its lists are rebuilt
         const bool same = L.valid && L.epoch == h->param_epoch && L.n_groups == n_groups && L.explicit_ids == (factor_ids != nullptr) &&
@@ -447,7 +386,7 @@ extern "C" int32_t cx_factor_statistics(cx_handle *h, int64_t n, const int64_t *
         if (!same) {
             L.valid = false;
             std::vector<int32_t> grp;
-            if ((rc = cx::fs::assign_groups(h, E, L, n, factor_ids, groups, n_groups, grp)) != CX_OK) return rc;
+            if ((rc = cx::fs::assign_groups(h, E, n, factor_ids, groups, n_groups, grp)) != CX_OK) return rc;
             if ((rc = cx::fs::build_lists(h, L, grp, n_groups, nw)) != CX_OK) return rc;
             L.explicit_ids = factor_ids != nullptr;
             L.ids.assign(factor_ids, factor_ids ? factor_ids + n : factor_ids);
@@ -458,12 +397,7 @@ extern "C" int32_t cx_factor_statistics(cx_handle *h, int64_t n, const int64_t *
         }
         int fb = 0;
         cx::ev::var_pass(h, E);
-        switch (d) {
-        case 1: cx::fs::launch_stats<1>(h, E, L, fb); break;
-        case 2: cx::fs::launch_stats<2>(h, E, L, fb); break;
-        case 3: cx::fs::launch_stats<3>(h, E, L, fb); break;
-        default: cx::fs::launch_stats<4>(h, E, L, fb); break;
-        }
+        cx::ev::with_dim(d, [&](auto D) { cx::fs::launch_stats<D()>(h, E, L, fb); });
         CX_HIP(h, hipGetLastError());
         const int64_t nrows = L.n_chunks ? (int64_t)L.out_group.size() : 0;
         if (nrows) CX_HIP(h, hipMemcpyAsync(L.h_rows, L.d_rows[fb], (size_t)(nrows * 2 * nw) * sizeof(double), hipMemcpyDeviceToHost, h->stream));

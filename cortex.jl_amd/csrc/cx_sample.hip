@@ -120,67 +120,6 @@ __device__ __forceinline__ void link_step(const double *__restrict__ link, int64
     for (int i = 0; i < D; i++) z[i] = n[i];
 }
 
-// ---- small dense helpers (registers) --------------------------------------------------------------------------------------------
-// in-place lower Cholesky; false: not positive definite
-template <int N>
-__device__ __forceinline__ bool chol(double (&A)[N][N]) {
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double d = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= A[j][k] * A[j][k];
-        if (!(d > 0.0)) return false;
-        const double l = sqrt(d), il = 1.0 / l;
-        A[j][j] = l;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= A[i][k] * A[j][k];
-            A[i][j] = s * il;
-        }
-    }
-    return true;
-}
-
-// x = (L L')⁻¹ b
-template <int N>
-__device__ __forceinline__ void chol_solve(const double (&L)[N][N], const double (&b)[N], double (&x)[N]) {
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= L[i][k] * y[k];
-        y[i] = s / L[i][i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; k++) s -= L[k][i] * x[k];
-        x[i] = s / L[i][i];
-    }
-}
-
-// M = L⁻ᵀ (upper): row i of M = column i of L⁻¹
-template <int N>
-__device__ __forceinline__ void inv_t(const double (&L)[N][N], double (&M)[N][N]) {
-#pragma unroll
-    for (int r = 0; r < N; r++) {
-        double y[N];
-#pragma unroll
-        for (int c = 0; c < N; c++) {
-            double s = c == r ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = 0; k < c; k++) s -= L[c][k] * y[k];
-            y[c] = c < r ? 0.0 : s / L[c][c];
-        }
-#pragma unroll
-        for (int c = 0; c < N; c++) M[r][c] = y[c];
-    }
-}
-
 template <int D>
 __device__ __forceinline__ void put_link(double *__restrict__ link, int64_t q, const double (&G)[D][D], const double (&off)[D], const double (&M)[D][D]) {
     double *l = link + q * LR<D>::N;
@@ -197,11 +136,9 @@ __device__ __forceinline__ void put_link(double *__restrict__ link, int64_t q, c
 // st[q] = 0 ok, 1 an undefined input, 2 not positive definite
 template <int D>
 __global__ __launch_bounds__(kT) void k_sp_cond(int64_t n_root, int64_t n_link, const int32_t *__restrict__ roots, const int4 *__restrict__ plink,
-                                                const int32_t *__restrict__ pos_var, const int4 *__restrict__ rec, const int32_t *__restrict__ pset,
-                                                const double *__restrict__ pq, const double *__restrict__ pa, const double *__restrict__ pb,
-                                                const double *__restrict__ ptab, const double *__restrict__ f2v, const double *__restrict__ W,
-                                                double *__restrict__ link, uint8_t *__restrict__ st) {
-    constexpr int NT = Lay<D>::NT, K = Lay<D>::K;
+                                                const int32_t *__restrict__ pos_var, ev::PairTab tab, ev::Msgs msg, double *__restrict__ link,
+                                                uint8_t *__restrict__ st) {
+    constexpr int K = Lay<D>::K;
     const int64_t t = (int64_t)blockIdx.x * kT + threadIdx.x;
     if (t >= n_root + n_link) return;
     double G[D][D], off[D], L[D][D], M[D][D];
@@ -216,7 +153,7 @@ __global__ __launch_bounds__(kT) void k_sp_cond(int64_t n_root, int64_t n_link, 
     if (t < n_root) {
         // the root's belief: precision Λ_r (the sum of its stored messages), centre μ_r; z_r = L_r⁻ᵀ ε
         q = roots[t];
-        const double *w = W + (int64_t)pos_var[q] * K;
+        const double *w = msg.W + (int64_t)pos_var[q] * K;
         bool undef = false;
 #pragma unroll
         for (int i = 0; i < D; i++) undef = undef || __builtin_isnan(w[i]);
@@ -228,55 +165,42 @@ __global__ __launch_bounds__(kT) void k_sp_cond(int64_t n_root, int64_t n_link, 
                 undef = undef || __builtin_isnan(L[i][j]);
             }
         if (undef) status = 1;
-        else if (!chol<D>(L)) status = 2;
+        else if (!ev::chol<D>(L)) status = 2;
     } else {
         const int4 lk = plink[t - n_root];
         q = lk.z;
-        const int64_t p = lk.x;
-        const int4 r = rec[p];
-        double A[D][D], Qi[D][D], bb[D];
-        ev::pair_params<D>(p, pset, pq, pa, pb, ptab, A, Qi, bb);
-        double mo[D], eo[D], lo[NT], mi[D], ei[D], li[NT];
-        bool ok = ev::free_edge<D>(f2v, W, r.x, r.z, mo, eo, lo);
-        ok = ev::free_edge<D>(f2v, W, r.y, r.w, mi, ei, li) && ok;
-        // the factor belief, centred, over (out, in): rc = c_out - A c_in - b
-        double rc[D], J[2 * D][2 * D], h[2 * D];
-#pragma unroll
-        for (int i = 0; i < D; i++) {
-            double u = mo[i] - bb[i];
-#pragma unroll
-            for (int j = 0; j < D; j++) u -= A[i][j] * mi[j];
-            rc[i] = u;
-        }
-        ev::pair_joint<D>(A, Qi, rc, true, true, eo, lo, ei, li, J, h);
+        // the factor belief, centred, over (out, in).  Both ends are free: the plan makes a link only between two free variables and
+        // is rebuilt when the observed flags change
+        ev::PairJoint<D> B;
+        ev::pair_joint<D>(lk.x, tab, msg, B);
         // the child's block C and the parent's block p (selects, not a runtime offset: the arrays stay in registers)
         const bool child_out = lk.y != 0;
         double hc[D], Jcp[D][D];
 #pragma unroll
         for (int i = 0; i < D; i++) {
-            hc[i] = child_out ? h[i] : h[D + i];
+            hc[i] = child_out ? B.h[i] : B.h[D + i];
 #pragma unroll
             for (int j = 0; j < D; j++) {
-                L[i][j] = child_out ? J[i][j] : J[D + i][D + j];
-                Jcp[i][j] = child_out ? J[i][D + j] : J[D + i][j];
+                L[i][j] = child_out ? B.J[i][j] : B.J[D + i][D + j];
+                Jcp[i][j] = child_out ? B.J[i][D + j] : B.J[D + i][j];
             }
         }
-        if (!ok) status = 1;
-        else if (!chol<D>(L)) status = 2;
+        if (!B.ok) status = 1;
+        else if (!ev::chol<D>(L)) status = 2;
         else {
-            chol_solve<D>(L, hc, off);
+            ev::chol_solve<D>(L, hc, off);
 #pragma unroll
             for (int k = 0; k < D; k++) {
                 double b[D], x[D];
 #pragma unroll
                 for (int i = 0; i < D; i++) b[i] = -Jcp[i][k];
-                chol_solve<D>(L, b, x);
+                ev::chol_solve<D>(L, b, x);
 #pragma unroll
                 for (int i = 0; i < D; i++) G[i][k] = x[i];
             }
         }
     }
-    if (status == 0) inv_t<D>(L, M);
+    if (status == 0) ev::inv_t<D>(L, M);
     else {
 #pragma unroll
         for (int i = 0; i < D; i++)
@@ -291,11 +215,9 @@ __global__ __launch_bounds__(kT) void k_sp_cond(int64_t n_root, int64_t n_link, 
 // klink[k] = kary row | parent entry | child position per entry (-1: not a child), 10 int32.  The joint over the free entries is
 // k_ev_kary's (cx_evidence.hip), packed in LDS; J_CC is factored in place through an index map that skips the parent's block.
 template <int D>
-__global__ __launch_bounds__(kKT) void k_sp_cond_kary(int64_t n, const int32_t *__restrict__ klink, const int32_t *__restrict__ krec,
-                                                      const double *__restrict__ kc, const int32_t *__restrict__ kps, const double *__restrict__ ptab,
-                                                      const uint8_t *__restrict__ vinfo, const double *__restrict__ f2v, const double *__restrict__ v2f,
-                                                      const double *__restrict__ W, const int32_t *__restrict__ xoff, double *__restrict__ link,
-                                                      double *__restrict__ xblk, uint8_t *__restrict__ st) {
+__global__ __launch_bounds__(kKT) void k_sp_cond_kary(int64_t n, const int32_t *__restrict__ klink, ev::KaryTab tab, ev::Msgs msg,
+                                                      const int32_t *__restrict__ xoff, double *__restrict__ link, double *__restrict__ xblk,
+                                                      uint8_t *__restrict__ st) {
     constexpr int NP = ev::KLay<D>::NP, NM = ev::KLay<D>::NM;
     __shared__ double sJ[NP * kKT], sh[NM * kKT], sy[NM * kKT];
     __shared__ int32_t sp[7 * kKT];
@@ -310,39 +232,14 @@ __global__ __launch_bounds__(kKT) void k_sp_cond_kary(int64_t n, const int32_t *
     unsigned freemask;
     int nfree;
     bool ok;
-    ev::kary_joint<D, kKT>(row, krec, kc, kps, ptab, vinfo, f2v, v2f, W, J, hv, Qi, ldq, bp, g, cq, freemask, nfree, ok);
+    ev::kary_joint<D, kKT>(row, tab, msg, J, hv, Qi, ldq, bp, g, cq, freemask, nfree, ok);
     const int fpo = __builtin_popcount(freemask & ((1u << ep) - 1u));      // the parent's ordinal among the free entries
     // the child space: joint index of child index r (the parent's block is skipped)
     const int m = (nfree - 1) * D;
     auto mapi = [&](int r) { return r / D < fpo ? r : r + D; };
     auto JC = [&](int r, int c) -> double & { return J[ev::pk(mapi(r), mapi(c)) * kKT]; };      // r >= c
-    int status = ok ? 0 : 1;
-    if (status == 0)
-        for (int j = 0; j < m; j++) {
-            double d = JC(j, j);
-            for (int k = 0; k < j; k++) { const double l = JC(j, k); d -= l * l; }
-            if (!(d > 0.0)) { status = 2; break; }
-            const double l = sqrt(d), il = 1.0 / l;
-            JC(j, j) = l;
-            for (int i = j + 1; i < m; i++) {
-                double u = JC(i, j);
-                for (int k = 0; k < j; k++) u -= JC(i, k) * JC(j, k);
-                JC(i, j) = u * il;
-            }
-        }
-    // (L L')⁻¹ b for b in yv (child indices), in place
-    auto solve = [&]() {
-        for (int i = 0; i < m; i++) {
-            double u = yv[i * kKT];
-            for (int k = 0; k < i; k++) u -= JC(i, k) * yv[k * kKT];
-            yv[i * kKT] = u / JC(i, i);
-        }
-        for (int i = m - 1; i >= 0; i--) {
-            double u = yv[i * kKT];
-            for (int k = i + 1; k < m; k++) u -= JC(k, i) * yv[k * kKT];
-            yv[i * kKT] = u / JC(i, i);
-        }
-    };
+    auto y = [&](int i) -> double & { return yv[i * kKT]; };
+    const int status = !ok ? 1 : ev::chol_at(m, JC) ? 0 : 2;
     // the child positions, in child order
     int nc = 0;
     for (int e = 0; e < 8; e++)
@@ -356,7 +253,7 @@ __global__ __launch_bounds__(kKT) void k_sp_cond_kary(int64_t n, const int32_t *
     if (status) return;
     // off = J_CC⁻¹ h_C
     for (int i = 0; i < m; i++) yv[i * kKT] = hv[mapi(i) * kKT];
-    solve();
+    ev::chol_solve_at(m, JC, y);
     for (int i = 0; i < m; i++) link[(int64_t)pos[(i / D) * kKT] * LR<D>::N + LR<D>::OFF + i % D] = yv[i * kKT];
     // G = -J_CC⁻¹ J_Cp, column by column
     for (int k = 0; k < D; k++) {
@@ -365,7 +262,7 @@ __global__ __launch_bounds__(kKT) void k_sp_cond_kary(int64_t n, const int32_t *
             const int a = mapi(i);
             yv[i * kKT] = -(a >= pj ? J[ev::pk(a, pj) * kKT] : J[ev::pk(pj, a) * kKT]);
         }
-        solve();
+        ev::chol_solve_at(m, JC, y);
         for (int i = 0; i < m; i++) link[(int64_t)pos[(i / D) * kKT] * LR<D>::N + LR<D>::G + (i % D) * D + k] = yv[i * kKT];
     }
     // L⁻ᵀ row by row: row r = column r of L⁻¹; entry (r, c) goes to the own block (c / D == r / D) or to sibling c / D's extra block
@@ -583,7 +480,7 @@ struct Plan : PlanDev {
 
 int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string &who) {
     using namespace cxh;
-    const int64_t nv = h->nv, nf = h->nf, ne = h->ne;
+    const int64_t nv = h->nv, nf = h->nf;
     treeplan::Rooted R;
     std::string err;
     int32_t rc = treeplan::root_forest(h, R, err, true);
@@ -600,17 +497,7 @@ int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string 
                                                "): no sampler is defined on a loopy graph");
     }
     auto is_free = [&](int32_t v) { return !(h->vinfo[v] & (kClamped | kGhost)); };
-    // the two tables of cx_evidence.hip on the host: pair rows (out slot, in slot, out var, in var) and k-ary rows (slots | vars)
-    std::vector<int4> prec((size_t)E.n_pair);
-    std::vector<int32_t> krec((size_t)E.n_kary * 16);
-    if (E.n_pair) CX_HIP(h, hipMemcpy(prec.data(), E.d_pair, prec.size() * sizeof(int4), hipMemcpyDeviceToHost));
-    if (E.n_kary) CX_HIP(h, hipMemcpy(krec.data(), E.d_krec, krec.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<int32_t> pair_of_fac((size_t)nf, -1), kary_of_fac((size_t)nf, -1);
-    for (size_t r = 0; r < E.pair_fac.size(); r++) pair_of_fac[(size_t)E.pair_fac[r]] = (int32_t)r;
-    {
-        int32_t row = 0;
-        for (int64_t f = 0; f < nf; f++) if (h->fac_kind[(size_t)f] == CX_FACTOR_GAUSS_LINEAR_N) kary_of_fac[(size_t)f] = row++;
-    }
+    // (E.pair, E.krec: the pair rows (out slot, in slot, out var, in var) and k-ary rows (slots | vars) of cx_evidence.hip, on the host)
     // the variable tree: parent variable and parent factor of every free variable (members: parents before children)
     std::vector<int32_t> vpar((size_t)nv, -1), vfac((size_t)nv, -1), vcomp((size_t)nv, -1), order;
     int32_t comp = -1;
@@ -704,18 +591,18 @@ int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string 
         const int32_t f = vfac[v];
         if (f < 0 || seen[f]) continue;
         seen[f] = 1;
-        if (pair_of_fac[f] >= 0) {
-            const int32_t r = pair_of_fac[f];
-            plink.push_back(make_int4(r, prec[r].z == v ? 1 : 0, var_pos[v], 0));
-        } else if (kary_of_fac[f] >= 0) {
+        if (E.row_of_fac[f] >= 0) {
+            const int32_t r = E.row_of_fac[f];
+            plink.push_back(make_int4(r, E.pair[r].z == v ? 1 : 0, var_pos[v], 0));
+        } else if (E.kary_row_of_fac[f] >= 0) {
             kfac.push_back({f, vpar[v]});
         } else return fail(h, CX_ERR_STATE, who + ": factor " + std::to_string(h->fac_ids[f]) + " joins two free variables but has no Gaussian table row");
     }
     std::vector<int32_t> xoff((size_t)P.npos + 1, 0), xvar;
     std::vector<std::vector<int32_t>> kchild;
     for (auto &kp : kfac) {
-        const int32_t row = kary_of_fac[kp.first];
-        const int32_t *vr = &krec[(size_t)row * 16 + 8], *sl = &krec[(size_t)row * 16];
+        const int32_t row = E.kary_row_of_fac[kp.first];
+        const int32_t *vr = &E.krec[(size_t)row * 16 + 8], *sl = &E.krec[(size_t)row * 16];
         int32_t rec[10];
         rec[0] = row; rec[1] = -1;
         std::vector<int32_t> ch;
@@ -760,7 +647,6 @@ int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string 
     // a slot of every observed variable (its datum)
     std::vector<int32_t> dslot((size_t)nv, 0);
     for (int64_t v = 0; v < nv; v++) if (h->var_off[v + 1] > h->var_off[v]) dslot[v] = slot_of_edge(h, h->var_off[v]);
-    (void)ne;
     static_cast<PlanDev &>(P) = PlanDev();
     P.valid = false;
     const int d = h->cfg.dim, ln = 2 * d * d + d;
@@ -814,13 +700,13 @@ inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 template <int D>
 void launch_cond(cx_handle *h, const ev::Cache &E, Plan &P) {
-    const double *f2v = ev::f2v_of(h), *v2f = ev::v2f_of(h);
+    const ev::Msgs msg = ev::msgs_of(h, E);
     if (P.n_root + P.n_plink)
         hipLaunchKernelGGL(k_sp_cond<D>, dim3(blocks(P.n_root + P.n_plink, kT)), dim3(kT), 0, h->stream, P.n_root, P.n_plink, P.d_roots, P.d_plink,
-                           P.d_pos_var, E.d_pair, E.d_pair_ps, E.d_pq, E.d_pa, E.d_pb, E.d_ptab, f2v, E.d_W, P.d_link, P.d_st);
+                           P.d_pos_var, E.pair_tab(), msg, P.d_link, P.d_st);
     if (P.n_klink)
-        hipLaunchKernelGGL(k_sp_cond_kary<D>, dim3(blocks(P.n_klink, kKT)), dim3(kKT), 0, h->stream, P.n_klink, P.d_klink, E.d_krec, E.d_kc, E.d_kps,
-                           E.d_ptab, h->d_vinfo, f2v, v2f, E.d_W, P.d_xoff, P.d_link, P.d_xblk, P.d_st);
+        hipLaunchKernelGGL(k_sp_cond_kary<D>, dim3(blocks(P.n_klink, kKT)), dim3(kKT), 0, h->stream, P.n_klink, P.d_klink, E.kary_tab(), msg, P.d_xoff,
+                           P.d_link, P.d_xblk, P.d_st);
     if (P.n_comp) {
         hipLaunchKernelGGL(k_sp_flag, dim3((unsigned)P.n_chunk), dim3(kT), 0, h->stream, P.d_cbeg, P.d_cpos, P.d_st, P.d_cpart);
         hipLaunchKernelGGL(k_sp_flag_comp, dim3(blocks(P.n_comp, kT)), dim3(kT), 0, h->stream, P.n_comp, P.d_ccb, P.d_cpart, P.d_cflag);
@@ -890,14 +776,12 @@ using namespace cxh;
 extern "C" int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t seed, const double *noise, int64_t n, const int64_t *variable_ids,
                                        double *out, int64_t *counts4) {
     const std::string who = "cx_sample_posterior";
-    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only");
-    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
-    CX_REQUIRE(h, n_samples >= 1 && out && counts4 && (!variable_ids || n >= 0), CX_ERR_INVALID_ARGUMENT,
-               who + ": n_samples < 1, a null output or counts4, or a negative count with variable ids");
     try {
         cx::ev::Cache *Ep = nullptr;
         int32_t rc;
-        if ((rc = cx::ev::prepare(h, who, Ep)) != CX_OK) return rc;
+        const char *bad = n_samples >= 1 && out && counts4 && (!variable_ids || n >= 0)
+                              ? nullptr : "n_samples < 1, a null output or counts4, or a negative count with variable ids";
+        if ((rc = cx::ev::prepare(h, who, bad, Ep)) != CX_OK) return rc;
         cx::ev::Cache &E = *Ep;
         if (!h->sample) h->sample.reset(new cx::sp::Plan());
         cx::sp::Plan &P = *h->sample;
@@ -932,24 +816,14 @@ extern "C" int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t
             if (noise) CX_HIP(h, hipMemcpyAsync(P.d_noise, noise + s0 * nv * d, (size_t)(S * nv * d) * sizeof(double), hipMemcpyHostToDevice, h->stream));
             const cx::sp::Gen g{noise ? P.d_noise : nullptr, nv * d, seed, s0};
             const int32_t *dv = variable_ids ? P.d_vid : nullptr;
-            if (nout) {
-                switch (d) {
-                case 1: cx::sp::launch_all<1>(h, E, P, S, g, nout, dv, s0 == 0); break;
-                case 2: cx::sp::launch_all<2>(h, E, P, S, g, nout, dv, s0 == 0); break;
-                case 3: cx::sp::launch_all<3>(h, E, P, S, g, nout, dv, s0 == 0); break;
-                default: cx::sp::launch_all<4>(h, E, P, S, g, nout, dv, s0 == 0); break;
-                }
-                CX_HIP(h, hipGetLastError());
-                CX_HIP(h, hipMemcpyAsync(out + s0 * nout * d, P.d_out, (size_t)(S * nout * d) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            } else if (s0 == 0) {
-                switch (d) {
-                case 1: cx::sp::launch_cond<1>(h, E, P); break;
-                case 2: cx::sp::launch_cond<2>(h, E, P); break;
-                case 3: cx::sp::launch_cond<3>(h, E, P); break;
-                default: cx::sp::launch_cond<4>(h, E, P); break;
-                }
+            if (nout || s0 == 0) {
+                cx::ev::with_dim(d, [&](auto D) {
+                    if (nout) cx::sp::launch_all<D()>(h, E, P, S, g, nout, dv, s0 == 0);
+                    else cx::sp::launch_cond<D()>(h, E, P);
+                });
                 CX_HIP(h, hipGetLastError());
             }
+            if (nout) CX_HIP(h, hipMemcpyAsync(out + s0 * nout * d, P.d_out, (size_t)(S * nout * d) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             CX_HIP(h, hipStreamSynchronize(h->stream));      // (the caller's noise chunk is read before the next one is copied)
         }
         if (P.n_comp) CX_HIP(h, hipMemcpy(P.h_cflag.data(), P.d_cflag, (size_t)P.n_comp, hipMemcpyDeviceToHost));
