@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CORTEX_HIP_LIB", os.path.join(HERE, "libcortex_hip.so"))  # override: A/B builds of the same ABI
 
 # mirrors of the #defines in include/cortex_hip.h
-ABI_VERSION = 7
+ABI_VERSION = 8
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_NOT_FOUND, ERR_UNSUPPORTED, ERR_STATE, ERR_DEVICE, ERR_NO_DEVICE, ERR_OUT_OF_MEMORY = (
     -1, -2, -3, -4, -5, -6, -7)
@@ -28,6 +28,7 @@ WIRE_WEAK, WIRE_INTERMEDIATE, WIRE_NO_LISTEN, WIRE_DEFAULT_VARIABLE, WIRE_LINK =
 KERNEL_VAR_TO_FACTOR, KERNEL_FACTOR_TO_VAR, KERNEL_FUSED, KERNEL_BATCH, KERNEL_BIG_VAR = 0, 1, 2, 3, 4
 KERNEL_HALO_BEGIN, KERNEL_HALO_END = 5, 6
 KERNEL_COUNT = 8
+PREDICT_LOO, PREDICT_CAUSAL = 0, 1
 
 
 class Config(C.Structure):
@@ -85,6 +86,8 @@ SIGNATURES = {
     "cx_factor_beliefs": (_i32, [_vp, _i64, _pi64, _pd]),
     "cx_factor_statistics": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pd, _pi64]),
     "cx_sample_posterior": (_i32, [_vp, _i64, C.c_uint64, _pd, _i64, _pi64, _pd, _pi64]),
+    "cx_predictive": (_i32, [_vp, _i32, _i64, _pi64, _pd, _pd, _pi64]),
+    "cx_predictive_rows": (_i32, [_vp, _i64, _pi64, _pi64]),
     "cx_halo_configure": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64]),
     "cx_halo_buffers": (_i32, [_vp, C.POINTER(_vp), _pi64, C.POINTER(_vp), _pi64]),
     "cx_halo_set_buffers": (_i32, [_vp, _vp, _vp]),

@@ -24,38 +24,6 @@ namespace ev {
 constexpr int kKB = 16;        // threads per block of the k-ary pass: each thread's joint precision lives in LDS
 constexpr int kFB = 1024;      // threads of the one block of the final sum (C4: 23 k block partials)
 
-// counters read back: 0 variable terms, 1 terms with an undefined input, 2 terms whose belief is not positive definite, 3 stand-in
-// variables met (a halo handle: refused); the factor terms are known on the host
-constexpr int kNCnt = 4;
-
-// fixed-order tree over the block's threads; thread 0 writes the block's Part
-template <int NB>
-__device__ __forceinline__ void block_part(double s, double c, unsigned n0, unsigned n1, unsigned n2, unsigned n3, Part *__restrict__ out) {
-    __shared__ double ss[NB], cs[NB];
-    __shared__ unsigned ns[4][NB];
-    const int t = threadIdx.x;
-    ss[t] = s; cs[t] = c; ns[0][t] = n0; ns[1][t] = n1; ns[2][t] = n2; ns[3][t] = n3;
-    __syncthreads();
-#pragma unroll
-    for (int w = NB / 2; w > 0; w >>= 1) {
-        if (t < w) {
-            double a = ss[t], ac = cs[t];
-            neu(a, ac, ss[t + w]);
-            ss[t] = a; cs[t] = ac + cs[t + w];
-#pragma unroll
-            for (int k = 0; k < 4; k++) ns[k][t] += ns[k][t + w];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        Part p;
-        p.s = ss[0]; p.c = cs[0];
-#pragma unroll
-        for (int k = 0; k < 4; k++) p.n[k] = ns[k][0];
-        out[blockIdx.x] = p;
-    }
-}
-
 // ---- pass 1: variables ----------------------------------------------------------------------------------------------------------
 // vrec[v] = d_v (low 24 bits) | opaque mask of the SELL slots (bits 24..31); variables of the CSR tail read tail_opq[slot - tail0]
 template <int D>
@@ -431,6 +399,8 @@ void launch_var(cx_handle *h, Cache &C) {
                            C.d_tail, h->big_start, f2v_of(h), C.d_W, C.d_partial);
 }
 
+void final_sum(cx_handle *h, int64_t n, const Part *partial, double *out) { hipLaunchKernelGGL(k_ev_final, dim3(1), dim3(kFB), 0, h->stream, n, partial, out); }
+
 void var_pass(cx_handle *h, Cache &C) { with_dim(h->cfg.dim, [&](auto D) { launch_var<D()>(h, C); }); }
 
 template <int D>
@@ -441,7 +411,7 @@ void launch(cx_handle *h, Cache &C) {
     launch_var<D>(h, C);
     if (nb_p) hipLaunchKernelGGL(k_ev_pair<D>, dim3((unsigned)nb_p), dim3(kB), 0, h->stream, C.n_pair, C.pair_tab(), msg, part + nb_v);
     if (nb_k) hipLaunchKernelGGL(k_ev_kary<D>, dim3((unsigned)nb_k), dim3(kKB), 0, h->stream, C.n_kary, C.kary_tab(), msg, part + nb_v + nb_p);
-    hipLaunchKernelGGL(k_ev_final, dim3(1), dim3(kFB), 0, h->stream, C.nb, part, C.d_out);
+    final_sum(h, C.nb, part, C.d_out);
 }
 
 }  // namespace ev

@@ -1,4 +1,4 @@
-// cx_evidence_core.h — what the read-outs of the stored messages share (cx_evidence.hip, cx_learn.hip, cx_sample.hip): the dimension
+// cx_evidence_core.h — what the read-outs of the stored messages share (cx_evidence.hip, cx_learn.hip, cx_sample.hip, cx_predict.hip): the dimension
 // dispatch, the per-variable scratch of the variable pass, compensated sums, message loads, the small-matrix kit (Cholesky, triangular
 // solves and inverses, in registers and on the packed joint in LDS), the centred leave-one-out message of one factor edge, the belief
 // joints of a two-variable and of a k-ary factor, and the cached tables of a handle.  Derivations: DESIGN.md §4e, §4f and §4g.
@@ -44,6 +44,38 @@ struct Part {
     double s, c;
     unsigned n[4];
 };
+
+// counters read back: 0 variable terms, 1 terms with an undefined input, 2 terms whose belief is not positive definite, 3 stand-in
+// variables met (a halo handle: refused); the factor terms are known on the host
+constexpr int kNCnt = 4;
+
+// fixed-order tree over the block's threads; thread 0 writes the block's Part
+template <int NB>
+__device__ __forceinline__ void block_part(double s, double c, unsigned n0, unsigned n1, unsigned n2, unsigned n3, Part *__restrict__ out) {
+    __shared__ double ss[NB], cs[NB];
+    __shared__ unsigned ns[4][NB];
+    const int t = threadIdx.x;
+    ss[t] = s; cs[t] = c; ns[0][t] = n0; ns[1][t] = n1; ns[2][t] = n2; ns[3][t] = n3;
+    __syncthreads();
+#pragma unroll
+    for (int w = NB / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            double a = ss[t], ac = cs[t];
+            neu(a, ac, ss[t + w]);
+            ss[t] = a; cs[t] = ac + cs[t + w];
+#pragma unroll
+            for (int k = 0; k < 4; k++) ns[k][t] += ns[k][t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        Part p;
+        p.s = ss[0]; p.c = cs[0];
+#pragma unroll
+        for (int k = 0; k < 4; k++) p.n[k] = ns[k][0];
+        out[blockIdx.x] = p;
+    }
+}
 
 // ---- messages -------------------------------------------------------------------------------------------------------------------
 template <int D>
@@ -526,6 +558,8 @@ struct Cache {
 int32_t prepare(cx_handle *h, const std::string &who, const char *bad_args, Cache *&C, const char *family_note = "");
 // pass 1 only (k_ev_var) on the handle's stream: the per-variable scratch C.d_W; the handle's stored f2v messages
 void var_pass(cx_handle *h, Cache &C);
+// k_ev_final on the handle's stream: the n block partials in index order -> out = value | counters[kNCnt] (u64)
+void final_sum(cx_handle *h, int64_t n, const Part *partial, double *out);
 inline const double *f2v_of(const cx_handle *h) { return h->cfg.dim == 1 ? (const double *)h->d_f2v : h->d_mv_f2v; }
 inline const double *v2f_of(const cx_handle *h) { return h->cfg.dim == 1 ? (const double *)h->d_v2f : h->d_mv_v2f; }
 inline Msgs msgs_of(const cx_handle *h, const Cache &C) { return {h->d_vinfo, f2v_of(h), v2f_of(h), C.d_W}; }

@@ -81,12 +81,13 @@ private:
 struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
 using OwnedStream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
 
-// what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample, reference order): the deleter is defined there
+// what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample, predict, reference order): the deleter is defined there
 template <class T> struct Deleter { void operator()(T *p) const; };
 struct RefSched;      // cx_api_ref.hip
 namespace ev { struct Cache; }
 namespace fs { struct Cache; }
 namespace sp { struct Plan; }
+namespace pr { struct Plan; }
 
 }  // namespace cx
 
@@ -196,10 +197,11 @@ struct DevState {
 
     // cx_log_evidence (cx_evidence.hip): work lists of the graph and scratch, built on the first call; cx_factor_beliefs /
     // cx_factor_statistics (cx_learn.hip): the grouping's work lists and scratch; cx_sample_posterior (cx_sample.hip): the forest
-    // plan, the links and the per-call scratch
+    // plan, the links and the per-call scratch; cx_predictive (cx_predict.hip): the rows of the last (mode, factor_ids) and their scratch
     std::unique_ptr<ev::Cache, Deleter<ev::Cache>> evidence;
     std::unique_ptr<fs::Cache, Deleter<fs::Cache>> learn;
     std::unique_ptr<sp::Plan, Deleter<sp::Plan>> sample;
+    std::unique_ptr<pr::Plan, Deleter<pr::Plan>> predict;
 };
 
 }  // namespace cx

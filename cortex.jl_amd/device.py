@@ -324,6 +324,42 @@ class DeviceGraph:
                  "S_xx": out[:, o + 2 * d * d:].reshape(G, d, d).copy()}
         return stats, dict(zip(("factors", "groups", "undefined", "not_positive_definite"), [int(x) for x in cnt]))
 
+    def predictive_rows(self):
+        """cx_predictive_rows: the factor ids of the rows predictive(factor_ids=None) scores, ascending"""
+        n = C.c_int64()
+        self._check(self.lib.cx_predictive_rows(self.h, 0, None, C.byref(n)))
+        ids = np.zeros(n.value, dtype=np.int64)
+        if n.value:
+            self._check(self.lib.cx_predictive_rows(self.h, n.value, _p(ids, C.c_int64), C.byref(n)))
+        return ids
+
+    def predictive(self, mode="loo", factor_ids=None, rows=True):
+        """cx_predictive: the predictive distribution of every datum that a Gaussian rule factor generates (its OUT end the one observed
+        variable), from the stored messages.  mode "loo": given all other data (the sum of log_density is the leave-one-out score);
+        "causal": given the data of its inputs' ancestors only (on a chain: the Kalman innovations, the sum is log_evidence).
+        factor_ids=None: every row in ascending factor id.  Returns {"factor_ids", "mean" [n, d], "cov" [n, d, d], "log_density" [n],
+        "mahalanobis" [n], "total", "counts"}; a row with an undefined input or an improper predictive is NaN (counts "undefined" /
+        "improper"), "total" sums the scored rows only.  rows=False: the total and the counts alone (the arrays are None)."""
+        m = {"loo": L.PREDICT_LOO, "causal": L.PREDICT_CAUSAL}.get(mode, mode)
+        d = self.dim
+        f = None if factor_ids is None else _i64(np.atleast_1d(factor_ids))
+        pf = None if f is None else _p(f, C.c_int64)
+        n = 0 if f is None else len(f)
+        tot, cnt = C.c_double(), (C.c_int64 * 4)()
+        keys = ("rows", "scored", "undefined", "improper")
+        if not rows:
+            self._check(self.lib.cx_predictive(self.h, int(m), n, pf, None, C.byref(tot), cnt))
+            return {"factor_ids": f, "mean": None, "cov": None, "log_density": None, "mahalanobis": None, "total": float(tot.value),
+                    "counts": dict(zip(keys, [int(x) for x in cnt]))}
+        if f is None:
+            f = self.predictive_rows()
+        out = np.zeros((len(f), d + d * d + 2), dtype=np.float64)
+        self._check(self.lib.cx_predictive(self.h, int(m), n, pf, _p(out, C.c_double) if out.size else None, C.byref(tot), cnt))
+        assert cnt[0] == len(out)
+        return {"factor_ids": f, "mean": out[:, :d].copy(), "cov": out[:, d:d + d * d].reshape(len(f), d, d).copy(),
+                "log_density": out[:, d + d * d].copy(), "mahalanobis": out[:, d + d * d + 1].copy(), "total": float(tot.value),
+                "counts": dict(zip(keys, [int(x) for x in cnt]))}
+
     def sample_posterior(self, n_samples, seed=0, variable_ids=None, noise=None):
         """cx_sample_posterior: joint draws from p(x | data) on a forest (the simulation smoother), from the stored messages.
         Returns (samples [n_samples, n, d] for variable_ids — None: every variable in ascending id —, counts) with counts "free",

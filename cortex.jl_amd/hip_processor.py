@@ -498,6 +498,13 @@ class HipProcessor(AbstractInferenceRequestProcessor):
             raise NotImplementedError("log_evidence: the Gaussian family only")
         return self.dev.log_evidence()
 
+    def predictive(self, mode="loo", factor_ids=None, rows=True):
+        """the predictive scores of the mirrored model's data from the device's stored messages (DeviceGraph.predictive): meaningful
+        where log_evidence is"""
+        if self.family != "gaussian":
+            raise NotImplementedError("predictive: the Gaussian family only")
+        return self.dev.predictive(mode=mode, factor_ids=factor_ids, rows=rows)
+
 
 # ---- variational families (SURVEY.md §8 f3) --------------------------------------------------------------------------
 @dataclass(frozen=True)

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define CX_ABI_VERSION 7   /* 7: cx_sample_posterior (additive).  6: cx_factor_beliefs, cx_factor_statistics (additive).  5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
+#define CX_ABI_VERSION 8   /* 8: cx_predictive, cx_predictive_rows (additive).  7: cx_sample_posterior (additive).  6: cx_factor_beliefs, cx_factor_statistics (additive).  5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
 
 /* status codes */
 #define CX_OK 0
@@ -616,6 +616,49 @@ int32_t cx_factor_statistics(cx_handle *h, int64_t n, const int64_t *factor_ids,
  * flags change.  Synchronous; moves no message, marginal, readiness bit or counter. */
 int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t seed, const double *noise, int64_t n, const int64_t *variable_ids,
                             double *out, int64_t *counts4);
+
+/* ---- predictive scores of the data (ABI 8; no counterpart in the reference) ----
+ * cx_predictive: for every observation that a Gaussian rule factor generates, the predictive distribution of that datum given other
+ * data, its log score and its squared standardised residual — the leave-one-out cross-validation terms, or the innovations of the
+ * prediction-error decomposition.  Dim 1 - 4, CX_FAMILY_GAUSSIAN.  It reads what cx_log_evidence reads (the STORED
+ * factor→variable messages and the caller's data, never the marginals) and works after every schedule the handle accepts.
+ * A ROW is a rule factor a,  y = Σ_i A_i x_i + b + N(0, Q),  whose CX_ROLE_OUT end is observed (the datum y) and whose other ends are
+ * all non-observed: CX_FACTOR_GAUSS_LINEAR, CX_FACTOR_GAUSS_LINEAR_N (3 - 7 edges), and CX_FACTOR_GAUSS_ADDITIVE at dim 1 with either
+ * end observed (it is symmetric).  For every input i the cavity  m_{i\a} = M_i - m_{a→i} - (what the mode leaves out),  M_i the sum of
+ * ALL stored messages into i (the opaque ones included), has mean μ_i^c and covariance Σ_i^c, and
+ *     ŷ = Σ_i A_i μ_i^c + b,   S = Σ_i A_i Σ_i^c A_i' + Q,   log_density = log N(y; ŷ, S),   maha = (y - ŷ)' S^-1 (y - ŷ).
+ * Exact on a forest at a fixed point (the cavities of distinct inputs are independent once a is removed), the cavity (Bethe)
+ * approximation elsewhere.
+ *   CX_PREDICT_LOO     nothing is left out but the factor's own message: p(y_a | all other data).  Σ log_density is the leave-one-out
+ *                      cross-validation score.
+ *   CX_PREDICT_CAUSAL  also left out of input i's cavity: every message into i from a rule factor on which i is a CX_ROLE_IN end — what
+ *                      flows back from what i generates (its other observations, its successors).  CX_FACTOR_GAUSS_ADDITIVE has no
+ *                      roles: as in cx_factor_beliefs the lower variable id is `out`, the higher `in`.  On a chain with at most one
+ *                      observation per state this is the one-step-ahead prediction p(y_t | y_<t): the rows are the Kalman innovations
+ *                      (ŷ_t, S_t) and Σ log_density equals cx_log_evidence.  On a chain of CX_FACTOR_GAUSS_ADDITIVE transitions (ids
+ *                      ascending in time) it is the reverse-time filter p(y_t | y_>t), with the same sum.  On a branching graph a row
+ *                      conditions on the data of its inputs' ancestors only, and the sum is NOT the evidence.
+ * Rows: factor_ids == NULL: every row in ascending factor id (n is ignored; cx_predictive_rows names them); otherwise the n named
+ * factors in the caller's order — an unknown id is CX_ERR_NOT_FOUND, a factor that is not a row CX_ERR_UNSUPPORTED (naming it).
+ * out: NULL, or a host array of counts4[0] rows of d + d^2 + 2 doubles:  ŷ[d] | S[d][d] (row-major) | log_density | maha.  A row with
+ * an undefined (NaN) input is NaN; a row whose cavity or S is not positive definite — an improper predictive, such as the first
+ * observation of a chain without a prior, which the Kalman decomposition also leaves out — is NaN and counted apart (a cavity from
+ * which every message into the variable is taken out is improper by structure, whatever the subtraction rounds to).
+ * counts4 = {rows, rows scored, rows with an undefined input, rows improper} (never NULL; a call with out == NULL sizes the array).
+ * *total (may be NULL): the compensated f64 sum of log_density over the SCORED rows only, in a fixed order: two calls on one state are
+ * bit-identical.  With out == NULL only the total and the counters come back (a learning loop's objective).
+ * The rows of the last (mode, factor_ids) are cached: the same call again costs an O(n) comparison on the host; they are rebuilt when
+ * the graph or the observed flags change; rule parameters are re-read when they change.
+ * Refused as cx_log_evidence refuses, with the same codes (other families, dim >= 5, partitioned handles, zero-noise factors, a
+ * captured stream); an unknown mode, a NULL counts4 or n < 0 with ids is CX_ERR_INVALID_ARGUMENT.  Out of scope: a datum on the
+ * CX_ROLE_IN end of a non-additive factor.  Synchronous; moves no message, marginal, readiness bit or counter.
+ *
+ * cx_predictive_rows: the factor ids of the rows a NULL factor_ids scores, ascending: *n_rows of them, the first min(cap, *n_rows)
+ * written to factor_ids (cap == 0: factor_ids may be NULL).  Host work only; refused as cx_predictive. */
+#define CX_PREDICT_LOO 0
+#define CX_PREDICT_CAUSAL 1
+int32_t cx_predictive(cx_handle *h, int32_t mode, int64_t n, const int64_t *factor_ids, double *out, double *total, int64_t *counts4);
+int32_t cx_predictive_rows(cx_handle *h, int64_t cap, int64_t *factor_ids, int64_t *n_rows);
 
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)

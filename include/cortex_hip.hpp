@@ -149,6 +149,26 @@ class Handle {
                                    out.data(), o.data()));
         return {out, o};
     }
+    // the predictive score of every datum that a Gaussian rule factor generates, from the stored messages (cx_predictive): per row ŷ (d), S
+    // (d x d, row-major), log density, squared standardised residual; factor_ids empty: every row in ascending factor id (`ids` names them).
+    // mode CX_PREDICT_LOO: given all other data; CX_PREDICT_CAUSAL: given the data of the inputs' ancestors (a chain: the Kalman innovations,
+    // total = log_evidence).  counts: rows, scored, with an undefined input, improper; total: Σ log density of the scored rows.
+    // rows == false: total and counts only
+    struct Predictive { std::vector<int64_t> ids; std::vector<double> rows; double total = 0; std::array<int64_t, 4> counts{}; };
+    Predictive predictive(int32_t mode, const std::vector<int64_t> &factor_ids = {}, bool rows = true) {
+        Predictive r;
+        r.ids = factor_ids;
+        const int64_t *ids = factor_ids.empty() ? nullptr : factor_ids.data();
+        if (rows && factor_ids.empty()) {
+            int64_t n = 0;
+            check(cx_predictive_rows(h_, 0, nullptr, &n));
+            r.ids.resize((size_t)n);
+            if (n) check(cx_predictive_rows(h_, n, r.ids.data(), &n));
+        }
+        if (rows) r.rows.resize(r.ids.size() * (size_t)(dim_ + dim_ * dim_ + 2));
+        check(cx_predictive(h_, mode, (int64_t)factor_ids.size(), ids, rows && !r.rows.empty() ? r.rows.data() : nullptr, &r.total, r.counts.data()));
+        return r;
+    }
     // joint posterior draws on a forest (the simulation smoother): n_samples x n x dim doubles for variable_ids (empty: every variable in
     // ascending id); noise (optional): the standard normals, n_samples x n_variables x dim in ascending id order, in place of the device's
     // Philox4x32-10 draws.  counts: free variables, components, components with an undefined input, components not positive definite

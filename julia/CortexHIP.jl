@@ -315,6 +315,32 @@ function factor_statistics(p, factor_ids::Union{Nothing, Vector{Int64}}, groups:
     return out, counts
 end
 
+# the predictive score of every datum that a Gaussian rule factor generates, from the stored messages (ABI 8; dim 1 - 4): mode :loo (given
+# all other data) or :causal (given the data of the inputs' ancestors; a chain: the Kalman innovations, total = log_evidence).
+# (factor ids, a (d + d^2 + 2) x n matrix — column f = ŷ | S (row-major) | log density | squared standardised residual —, total, [rows,
+# scored, undefined, improper]); factor_ids === nothing: every row in ascending factor id; rows = false: the total and the counts alone
+function predictive(p; mode::Symbol = :loo, factor_ids::Union{Nothing, Vector{Int64}} = nothing, rows::Bool = true)
+    d = p.dim
+    m = mode === :loo ? Int32(0) : mode === :causal ? Int32(1) : throw(ArgumentError("mode is :loo or :causal"))
+    ids = factor_ids
+    if ids === nothing && rows
+        n = Ref{Int64}(0)
+        check(p.handle, ccall((:cx_predictive_rows, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), p.handle, 0, C_NULL, n))
+        ids = zeros(Int64, n[])
+        check(p.handle, ccall((:cx_predictive_rows, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), p.handle, n[], ids, n))
+    end
+    out = zeros(Float64, d + d * d + 2, rows ? length(ids) : 0)
+    total = Ref{Float64}(0.0)
+    counts = zeros(Int64, 4)
+    fp = factor_ids === nothing ? Ptr{Int64}(C_NULL) : pointer(factor_ids)
+    op = rows && length(out) > 0 ? pointer(out) : Ptr{Float64}(C_NULL)
+    GC.@preserve factor_ids out begin
+        check(p.handle, ccall((:cx_predictive, lib), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, m, factor_ids === nothing ? 0 : length(factor_ids), fp, op, total, counts))
+    end
+    return ids, out, total[], counts
+end
+
 # joint posterior draws on a forest, the simulation smoother (ABI 7; dim 1 - 4): a d x n x n_samples array (column-major: sample s of
 # variable i is out[:, i, s]) for variable_ids (nothing: every variable in ascending id), and [free, components, undefined, not pd].
 # noise (optional): the standard normals, a d x n_variables x n_samples array in ascending id order, in place of the device's Philox4x32-10
