@@ -260,7 +260,17 @@ int32_t cx_graph_create(cx_handle *h, int64_t n_edges, const int64_t *edge_var, 
                 else if (dl < -32767 || dl > 32767) fits = false;
                 else p16[sl] = (int16_t)dl;
             }
-            if (fits) CX_TRY(dev_upload(h, &h->d_partner16, p16));
+            if (fits) {
+                CX_TRY(dev_upload(h, &h->d_partner16, p16));
+                // ... and as wave-uniform runs (cx_partner_runs.h): built only with the differences — the packed sweep is their only reader
+                std::vector<cx::pruns::Entry> runs;
+                h->partner_run_fallback = cx::pruns::build(h->partner, h->slice_off, h->vinfo, h->nv, runs);
+                h->partner_run_entries = (int64_t)runs.size();
+                static_assert(sizeof(cx::pruns::Entry) == 16, "four words per entry");
+                std::vector<int32_t> words(runs.size() * 4);
+                if (!runs.empty()) std::memcpy(words.data(), runs.data(), words.size() * 4);
+                CX_TRY(dev_upload(h, &h->d_partner_runs, words));
+            }
         }
         CX_TRY(dev_upload(h, &h->d_vbase, h->vbase));
         CX_TRY(dev_upload(h, &h->d_var_deg, var_deg));

@@ -662,6 +662,7 @@ int32_t mv_sweep(cx_handle *h, int32_t n_sweeps) {
         }
     }
     if (!cx::is_mfma_dim(h->cfg.dim)) { int32_t rc = mv_refresh_spdir(h); if (rc != CX_OK) return rc; }
+    const bool last_marg_only = !cx::is_mfma_dim(h->cfg.dim) && last_sweep_marginals_only(h);      // dim 2 .. 4, as for scalars (cx_host.h)
     for (int32_t s = 0; s < n_sweeps; s++) {
         if (cx::is_mfma_dim(h->cfg.dim)) {
             cx::mv64_launch_v2f(h, (int)h->n_pre64, h->d_pre64_slots, h->d_pre64_vars, h->d_mv_f2v);      // senders of degree 5 .. 8
@@ -669,8 +670,11 @@ int32_t mv_sweep(cx_handle *h, int32_t n_sweeps) {
             cx::mv64_launch_damp(h, (int)h->n_rule64, h->d_rule64_rec, h->d_mv_f2v, h->d_mv_f2v_alt, h->damping);
         } else {
             if (h->observed_passes_due > 0) { cx::mv_launch_sweep(h, false, 1); h->observed_passes_due--; }
-            cx::mv_launch_sweep(h, h->cfg.compute_marginals_in_sweep != 0, 0);
-            cx::mv_launch_big(h, h->cfg.compute_marginals_in_sweep != 0);      // variables of degree > 8 (none on most graphs: no launch)
+            const bool skip = last_marg_only && s + 1 < n_sweeps;
+            const bool marg = h->cfg.compute_marginals_in_sweep != 0 && !skip;
+            if (skip) h->sweeps_without_marginals++;
+            cx::mv_launch_sweep(h, marg, 0);
+            cx::mv_launch_big(h, marg);      // variables of degree > 8 (none on most graphs: no launch)
             cx::mv_launch_kary(h);                                             // factors of more than two variables (the same)
         }
         std::swap(h->d_mv_f2v, h->d_mv_f2v_alt);

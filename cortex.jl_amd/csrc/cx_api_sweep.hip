@@ -346,7 +346,7 @@ int32_t tree_sweep(cx_handle *h) {
 
 // ---- the sweep ----------------------------------------------------------------------------------------------------
 void sweep_main(cx_handle *h, bool skip_ghosts) {
-    const bool marg = h->cfg.compute_marginals_in_sweep != 0;
+    const bool marg = h->cfg.compute_marginals_in_sweep != 0 && !h->run_skip_marg;      // (run_skip_marg: cx_sweep's loop alone sets it)
     if (h->cfg.schedule == CX_SCHED_CHAIN_SCAN) {
         // messages out of observed leaves (data) into the chains: by the scan's side pass when every free variable is on a
         // chain, by a factor phase over all slots otherwise (free variables off the chains need theirs too)
@@ -485,6 +485,12 @@ int32_t cx_chain_plan_stats(const cx_handle *h, int64_t *out8) {
     return CX_OK;
 }
 
+int32_t cx_sweep_stats(const cx_handle *h, int64_t *out4) {
+    if (!h || !out4) return CX_ERR_INVALID_ARGUMENT;
+    out4[0] = h->partner_run_entries; out4[1] = h->partner_run_fallback; out4[2] = h->sweeps_without_marginals; out4[3] = 0;
+    return CX_OK;
+}
+
 int32_t cx_chain_scan_stats(const cx_handle *h, int64_t *out4) {
     if (!h || !out4) return CX_ERR_INVALID_ARGUMENT;
     out4[0] = h->chain_onepass_state; out4[1] = h->chain_onepass_launches; out4[2] = h->batch_graph_launches; out4[3] = 0;
@@ -555,12 +561,16 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
         }
         bg->seen++;
     }
+    // marginals in the last sweep of the call only (cx_host.h: last_sweep_marginals_only) — 32 of the 376 MB a C4 sweep moved
+    const bool last_marg_only = last_sweep_marginals_only(h);
     // the sweeps of the call: their launches (issue; not when a graph replays them) and the host state they leave (always)
     bool ran = false;
     auto sweeps = [&](bool issue) {
         ran = true;
         for (int32_t s = 0; s < n_sweeps; s++) {
             h->run_slice0 = 0; h->run_nslices = 0;
+            h->run_skip_marg = last_marg_only && s + 1 < n_sweeps;
+            if (h->run_skip_marg) h->sweeps_without_marginals++;
             if (h->halo_state && h->halo_depth > 0 && h->cfg.schedule == CX_SCHED_FUSED && h->big_vars.empty()) {
                 const int j = std::min(h->sweeps_since_exchange + 1, h->halo_depth);     // this is sweep j after the exchange
                 const int L = h->halo_depth - j + 1;                                       // layers that have to run
@@ -568,7 +578,7 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
             }
             if (issue) sweep_main(h, false);
             sweep_finish(h);
-            h->run_slice0 = 0; h->run_nslices = 0;
+            h->run_slice0 = 0; h->run_nslices = 0; h->run_skip_marg = false;
             h->sweeps_since_exchange++;
         }
     };

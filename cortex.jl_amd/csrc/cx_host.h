@@ -13,6 +13,7 @@
 #include <numeric>
 
 #include "cx_internal.h"
+#include "cx_partner_runs.h"      // cx::pruns::build — partner[slot] - slot as wave-uniform runs (cx_graph_create)
 
 namespace cxh {
 
@@ -161,6 +162,16 @@ inline void from_natural(int32_t form, double2 m, double *out) {
 
 inline bool is_vmp(const cx_handle *h) {
     return h->cfg.family == CX_FAMILY_VMP_MEAN_FIELD || h->cfg.family == CX_FAMILY_VMP_STRUCTURED;
+}
+// Marginals in the LAST sweep of a cx_sweep call only (cx_api_sweep.hip: cx_sweep; cx_api_mv.hip: mv_sweep): the call is asynchronous on
+// one stream, nothing can read the marginals between its launches and each launch overwrites every entry.  Not with a halo configured:
+// those sweeps run trimmed slice ranges and a redundant row's marginal comes from whichever sweep last covered it.
+// CX_MARG_EVERY_SWEEP=1: every sweep stores them (A/B; read per call: a test runs both forms in one process).
+inline bool last_sweep_marginals_only(const cx_handle *h) {
+    const char *e = std::getenv("CX_MARG_EVERY_SWEEP");
+    return !(e && e[0] == '1') && h->cfg.compute_marginals_in_sweep == 1 &&
+           (h->cfg.schedule == CX_SCHED_FUSED || (h->cfg.schedule == CX_SCHED_FLOODING && h->cfg.dim == 1)) &&      // (dims 2 .. 4 have no flooding schedule)
+           !h->halo_state && h->recv_slots.empty() && h->send_slots.empty();
 }
 #define CX_NOT_VMP(h, name) CX_REQUIRE(h, !(h) || !cxh::is_vmp(h), CX_ERR_UNSUPPORTED, name ": not available for the variational families (their state is the set of marginals: cx_set_marginals / cx_update_marginals)")
 

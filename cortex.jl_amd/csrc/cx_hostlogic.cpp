@@ -4,6 +4,7 @@
 //
 //   cxh_plan64_*   the work plan of the chain-scan schedule for dim 64 (cx_chain64_plan.h)
 //   cxh_ref_*      CX_SCHED_REFERENCE: the default resolver's wiring, the shadow of the readiness state, the recorded and levelled calls (cx_refsched.h)
+//   cxh_flat_partner_runs  the partner-run table of the packed fused sweep (cx_partner_runs.h)
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
 //                  plain struct with cx_handle's host fields
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include "cx_chain64_plan.h"
 #include "cx_chains.h"
 #include "cx_halo_plan.h"
+#include "cx_partner_runs.h"
 #include "cx_tree_plan.h"
 #include "cx_refsched.h"
 
@@ -309,6 +311,17 @@ int32_t cxh_flat_halo(void *p, int64_t n, const int64_t *variable_ids, const int
     g->send_slots.assign(send_slots, send_slots + n_send);
     cx::haloplan::quiet_run(g);
     return CX_OK;
+}
+
+// the partner-run table of the flattened graph (cx_partner_runs.h): returns the number of entries (four per 256-slot row), copies them as
+// rows {d0, d1, split, 0} of int32 when out != NULL, *fallback = entries with split < 0
+int64_t cxh_flat_partner_runs(const void *p, int32_t *out, int64_t *fallback) {
+    const HostGraph *g = (const HostGraph *)p;
+    std::vector<cx::pruns::Entry> e;
+    const int64_t fb = cx::pruns::build(g->partner, g->slice_off, g->vinfo, g->nv, e);
+    if (fallback) *fallback = fb;
+    if (out && !e.empty()) std::memcpy(out, e.data(), e.size() * sizeof(cx::pruns::Entry));
+    return (int64_t)e.size();
 }
 
 // array `which` of the graph: returns its length, copies it as int64 (or as doubles for the floating-point ones) when out != NULL

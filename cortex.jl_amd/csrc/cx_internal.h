@@ -118,6 +118,7 @@ struct DevState {
     DevBuf<double> d_scratch;       // small reduction scratch
     int sweep_max_w = 0;            // the widest SELL slice (0: not yet computed): picks the register footprint of the fused sweep
     DevBuf<int16_t> d_partner16;    // partner[s] - s where every difference fits (kNoPartner16: none); null otherwise (cx_kernels.hip: PACK)
+    DevBuf<int32_t> d_partner_runs; // with d_partner16: {d0, d1, split, 0} per (256-slot row, wave) — cx_partner_runs.h; read by the packed k_sweep
     DevBuf<char> d_stage;           // staging for set/get/batch, in bytes (cxh::ensure_stage)
 
     // factors with more than two edges (cx_kary.hip, CX_FACTOR_GAUSS_LINEAR_N): entry = 8 * row + edge position (OUT first, then IN by
@@ -316,6 +317,8 @@ struct cx_handle : cx::DevState {
     std::vector<int32_t> trim_lo, trim_hi;   // [depth + 1]: first / last slice holding a variable of layer <= L
     int run_slice0 = 0, run_nslices = 0;     // what launch_fused covers (0 slices: everything)
     int run_excl_lo = 1, run_excl_hi = 0;    // ... minus this slice range (empty by default)
+    int64_t partner_run_entries = 0, partner_run_fallback = 0, sweeps_without_marginals = 0;      // cx_sweep_stats
+    bool run_skip_marg = false;              // cx_sweep sets it around every sweep of a call but the last: nobody can read that sweep's marginals
     int own_slice_lo = 1, own_slice_hi = 0;  // deep halo: the run of slices that hold OWNED variables only (cx_halo_set_layers); empty: none
     // RCCL exchange issued by the library (cx_comm.hip)
     struct Peer { int rank; int64_t send_off, send_count, recv_off, recv_count; };

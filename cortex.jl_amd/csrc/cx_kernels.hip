@@ -61,19 +61,26 @@ __device__ __forceinline__ void store_stream(double2 *p, double2 v) {
 //   bit 1  q is read at the LOWER slot of the factor's two: additive factors have one q for both directions, so only the lines of
 //          the lower slots are ever fetched (a line holds the k-th neighbour of 16 consecutive variables: all lower or all higher on
 //          grid-like graphs)
+//   with bit 0, partner runs (cx_partner_runs.h): the wave's entry of the row, read through a wave-uniform index on the scalar path, gives the
+//          partner as slot + d0 / d1 by lane; a piece without partner stores nothing and loads no index (every k = 0 row of a grid with
+//          priors); an entry that is not representable (split < 0) sends the whole wave down the per-lane path — a wave-uniform branch
 constexpr int kPackPartner16 = 1, kPackQLow = 2;
 constexpr int16_t kNoPartner16 = -32768;
+constexpr int32_t kNoPartnerRun = INT32_MIN;      // (cx::pruns::kNone)
+typedef int i4v __attribute__((ext_vector_type(4)));
 template <int MODE, bool STORE_V2F, bool PUSH, int PACK = 0, bool DAMP = false>
 __device__ __forceinline__ void emit(int slot, double2 o, const int32_t *__restrict__ partner, const double *__restrict__ sq,
                                      const double *__restrict__ sa, const double *__restrict__ sb, double2 *__restrict__ f2v_out,
                                      double2 *__restrict__ v2f, int nt_out = 0, const int16_t *__restrict__ partner16 = nullptr,
-                                     const double2 *__restrict__ prev = nullptr, double lam = 0.0) {
+                                     const double2 *__restrict__ prev = nullptr, double lam = 0.0, i4v run = {0, 0, -1, 0}, int lane = 0) {
     if (__builtin_isnan(o.y)) return;  // a dependency is undefined: the signal is not pending, keep stored values
     if (STORE_V2F) v2f[slot] = o;
     if (PUSH) {
         int p;
-        if (PACK & kPackPartner16) { const int dlt = partner16[slot]; p = dlt == kNoPartner16 ? -1 : slot + dlt; }
-        else p = partner[slot];
+        if (PACK & kPackPartner16) {
+            if (run.z >= 0) { const int dlt = lane < run.z ? run.x : run.y; p = dlt == kNoPartnerRun ? -1 : slot + dlt; }      // (uniform)
+            else { const int dlt = partner16[slot]; p = dlt == kNoPartner16 ? -1 : slot + dlt; }
+        } else p = partner[slot];
         if (p >= 0) {
             double2 r = factor_rule<MODE>(o, sq[(PACK & kPackQLow) ? (p < slot ? p : slot) : slot], MODE == kRuleLinear ? sa[slot] : 1.0, MODE == kRuleLinear ? sb[slot] : 0.0);
             if (DAMP && !__builtin_isnan(r.y)) r = damped(r, prev[p], lam);      // the message this one replaces: the receiving slot in the sweep's input buffer
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void k_sweep(int nv, const int32_t *__restr
                                                   const double2 *__restrict__ f2v_in, double2 *__restrict__ f2v_out,
                                                   double2 *__restrict__ v2f, double2 *__restrict__ marg, int write_marg,
                                                   int skip_ghosts, int nt, int slice_lo, int slice_hi, int excl_lo, int excl_hi,
-                                                  const int16_t *__restrict__ partner16, double lam) {
+                                                  const int16_t *__restrict__ partner16, double lam, const i4v *__restrict__ runs) {
     // the slice -> XCD mapping stays the same from sweep to sweep (a strip's messages largely live in the L2s between sweeps:
     // launching only the active slice range re-deals the slices over the XCDs and measured 10 % SLOWER); idle slices exit here.
     // [excl_lo, excl_hi]: slices another launch of the same sweep covers (the owned interior, run beside the halo exchange)
@@ -138,6 +145,17 @@ __global__ __launch_bounds__(kBlock) void k_sweep(int nv, const int32_t *__restr
             if (k < deg) in[k] = x;
         }
     }
+    // packed instances: the wave's partner-run entries of its rows, MAXW uniform 16-byte loads into scalar registers (runs == nullptr:
+    // CX_PARTNER_RUNS=0, every wave reads the per-lane differences)
+    i4v run[MAXW];
+    if (PACK & kPackPartner16) {
+        const int e0 = __builtin_amdgcn_readfirstlane((off >> kSliceShift) * 4 + (tid >> 6));
+#pragma unroll
+        for (int k = 0; k < MAXW; k++) {
+            run[k] = i4v{0, 0, -1, 0};
+            if (runs && k < W) run[k] = runs[e0 + k * 4];
+        }
+    }
     double2 out[MAXW];
     double2 acc = zero2();
 #pragma unroll
@@ -147,6 +165,7 @@ __global__ __launch_bounds__(kBlock) void k_sweep(int nv, const int32_t *__restr
 #pragma unroll
     for (int k = MAXW - 1; k >= 0; k--) { out[k] = add2(out[k], acc); acc = add2(acc, in[k]); }
 
+    // (uniform; 0 in every sweep of a cx_sweep call but the last: nobody can read d_marg between the launches of one call — cx_api_sweep.hip)
     if (write_marg) {                                    // 2: natural-parameter marginals
         const double2 mg = write_marg == 2 ? total : to_moment(total);
         if (nt & kNtMarg) store_stream(&marg[v], mg); else marg[v] = mg;
@@ -158,12 +177,14 @@ __global__ __launch_bounds__(kBlock) void k_sweep(int nv, const int32_t *__restr
     if (!fixed) {
 #pragma unroll
         for (int k = 0; k < MAXW; k++)
-            if (k < deg) emit<MODE, STORE_V2F, PUSH, PACK, DAMP>(base + k * kBlock, out[k], partner, sq, sa, sb, f2v_out, v2f, nt_out, partner16, f2v_in, lam);
+            if (k < deg) emit<MODE, STORE_V2F, PUSH, PACK, DAMP>(base + k * kBlock, out[k], partner, sq, sa, sb, f2v_out, v2f, nt_out, partner16, f2v_in, lam,
+                                                                 (PACK & kPackPartner16) ? run[k] : i4v{0, 0, -1, 0}, tid & 63);
     } else if (PUSH) {
         // separate path (not a select on the message) so that out[] never has its address taken
 #pragma unroll
         for (int k = 0; k < MAXW; k++)
-            if (k < deg) emit<MODE, false, true, PACK, DAMP>(base + k * kBlock, v2f[base + k * kBlock], partner, sq, sa, sb, f2v_out, v2f, 0, partner16, f2v_in, lam);
+            if (k < deg) emit<MODE, false, true, PACK, DAMP>(base + k * kBlock, v2f[base + k * kBlock], partner, sq, sa, sb, f2v_out, v2f, 0, partner16, f2v_in, lam,
+                                                                (PACK & kPackPartner16) ? run[k] : i4v{0, 0, -1, 0}, tid & 63);
     }
 }
 
@@ -376,9 +397,13 @@ static void launch_sweep_t(cx_handle *h, const double2 *f2v_in, double2 *f2v_out
     // Gaussian factors, every partner within 32 k slots) — bit-identical results: the same values travel, fewer bytes
     static const bool pack_on = [] { const char *e = std::getenv("CX_PACK"); return !(e && e[0] == '0'); }();
     const int nt = nt_flags(h);
+    // CX_PARTNER_RUNS=0: the packed kernel reads the per-lane 16-bit differences everywhere, as before the table (A/B; read per launch: a
+    // test runs both forms in one process)
+    const char *pr_env = std::getenv("CX_PARTNER_RUNS");
+    const i4v *runs = (pr_env && pr_env[0] == '0') ? nullptr : (const i4v *)h->d_partner_runs.get();
 #define CX_SWEEP_TAIL 0, h->stream, (int)h->nv, h->d_slice_off, h->d_vinfo, h->d_partner, sq, h->d_sa, \
                       h->d_sb, f2v_in, f2v_out, h->d_v2f, h->d_marg, write_marg ? (h->cfg.family == CX_FAMILY_NATURAL2 ? 2 : 1) : 0,             \
-                      skip_ghosts ? 1 : 0, nt, lo, hi, xlo, xhi, h->d_partner16, h->damping
+                      skip_ghosts ? 1 : 0, nt, lo, hi, xlo, xhi, h->d_partner16, h->damping, runs
 #define CX_SWEEP_ARGS dim3((unsigned)h->nslices), dim3(kBlock), CX_SWEEP_TAIL
     // the widest slice, once per graph (CX_MAXW8=1: the eight-message instance for every graph, A/B)
     if (h->sweep_max_w == 0) {

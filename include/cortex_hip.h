@@ -181,7 +181,9 @@ typedef struct cx_config {
                               block-diagonally (x, u) with u a unit random walk nobody observes: exact results for the d x d blocks,
                               payloads of d and d + d*d doubles as for any d, at the cost of the tile size                          */
     int32_t schedule;      /* CX_SCHED_*: dim 1 all five; dim 2 .. 64: CX_SCHED_FUSED, CX_SCHED_CHAIN_SCAN, CX_SCHED_TREE, CX_SCHED_REFERENCE */
-    int32_t compute_marginals_in_sweep; /* 1: every sweep also refreshes all marginals (update_marginals!).
+    int32_t compute_marginals_in_sweep; /* 1: every sweep also refreshes all marginals (update_marginals!); after cx_sweep(h, n) they are
+                                           those of its LAST sweep — under the fused and flooding schedules without a halo the earlier
+                                           sweeps of one call, whose marginals nobody can read, do not store them.
                                            2 (CX_SCHED_CHAIN_SCAN, dim 2..4; elsewhere the same as 1): on demand — a sweep leaves
                                            the chain's forward and backward sums in the order of its walks, and the pass that
                                            adds them up, converts to moment form and moves them to the marginals' place runs
@@ -362,6 +364,10 @@ int32_t cx_ref_plan_stats(const cx_handle *h, int64_t *out8);
  * sweeps between two exchanges of a deep-halo partition (cx_halo_configure_state + cx_halo_set_layers) replayed as ONE graph launch once
  * the same batch has been asked for twice — with CX_HALO_GRAPH=1 only: measured 2 - 5 % slower than the plain launches on MI355X, off by default. */
 int32_t cx_chain_scan_stats(const cx_handle *h, int64_t *out4);
+/* diagnostics of the fused sweep (additive, still ABI 8; tests): out4[0] entries of the partner-run table (four per 256-slot row; 0: the
+ * graph's partners do not fit 16-bit differences, no table), [1] those that fall back to the per-lane index, [2] sweeps of cx_sweep
+ * calls so far that stored no marginals (every sweep of a call but the last), [3] 0 */
+int32_t cx_sweep_stats(const cx_handle *h, int64_t *out4);
 /* the XCD-resident cluster (reference-order plans of many dependent stages of 1 - 16 k items — calls on loopy graphs — run as ONE launch
  * of the workgroups of one XCD behind barriers that stay in that XCD's L2): out4 = { 1 ready / 0 not prepared / -1 off
  * (CX_REF_CLUSTER=0, a device that is neither gfx942 nor gfx950, or a barrier once timed out), workgroups per launch (compute units),
