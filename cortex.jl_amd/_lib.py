@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CORTEX_HIP_LIB", os.path.join(HERE, "libcortex_hip.so"))  # override: A/B builds of the same ABI
 
 # mirrors of the #defines in include/cortex_hip.h
-ABI_VERSION = 8
+ABI_VERSION = 9
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_NOT_FOUND, ERR_UNSUPPORTED, ERR_STATE, ERR_DEVICE, ERR_NO_DEVICE, ERR_OUT_OF_MEMORY = (
     -1, -2, -3, -4, -5, -6, -7)
@@ -86,6 +86,7 @@ SIGNATURES = {
     "cx_factor_beliefs": (_i32, [_vp, _i64, _pi64, _pd]),
     "cx_factor_statistics": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pd, _pi64]),
     "cx_sample_posterior": (_i32, [_vp, _i64, C.c_uint64, _pd, _i64, _pi64, _pd, _pi64]),
+    "cx_linear_moments": (_i32, [_vp, _i64, _pi64, _pi64, _pd, _pd, _pd, _pi64]),
     "cx_predictive": (_i32, [_vp, _i32, _i64, _pi64, _pd, _pd, _pi64]),
     "cx_predictive_rows": (_i32, [_vp, _i64, _pi64, _pi64]),
     "cx_halo_configure": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64]),

@@ -391,6 +391,51 @@ class DeviceGraph:
                                                  _p(out, C.c_double) if S >= 1 else None, cnt))
         return out, dict(zip(("free", "components", "undefined", "not_positive_definite"), [int(x) for x in cnt]))
 
+    def linear_moments(self, functionals, cov=True):
+        """cx_linear_moments: the exact mean and covariance of linear functionals φ_k(x) = Σ_i w_{k,i}' x_i of the joint posterior of a
+        forest, from the stored messages.  functionals: a list of (variable_ids, weights [n_k, d] — [n_k] at dim 1 —) pairs, or the CSR
+        triple (offsets [K + 1], variable_ids [nnz], weights [nnz, d]).  Returns (mean [K], cov [K, K] or None, counts) with counts
+        "components", "failed", "nan_functionals", "free"; a functional that touches a failed component is NaN (its row and column of
+        cov too).  cov=False: the means only."""
+        d = self.dim
+        if isinstance(functionals, tuple) and len(functionals) == 3 and not isinstance(functionals[0], tuple):
+            off, ids, w = _i64(np.atleast_1d(functionals[0])), _i64(np.atleast_1d(functionals[1])), _f64(functionals[2])
+        else:
+            parts = [(_i64(np.atleast_1d(i)), _f64(x).reshape(-1, d)) for i, x in functionals]
+            for i, x in parts:
+                if len(i) != len(x):
+                    raise ValueError("a functional needs one weight vector of length dim per variable id")
+            off = _i64(np.concatenate([[0], np.cumsum([len(i) for i, _ in parts])]))
+            ids = _i64(np.concatenate([i for i, _ in parts])) if parts else _i64(np.zeros(0))
+            w = _f64(np.concatenate([x for _, x in parts])) if parts else _f64(np.zeros((0, d)))
+        if len(off) < 1:
+            raise ValueError("offsets needs at least one entry")
+        K = len(off) - 1
+        if w.size != len(ids) * d:
+            raise ValueError(f"weights must be [{len(ids)}, {d}]")
+        mean = np.zeros(K, dtype=np.float64)
+        cv = np.zeros((K, K), dtype=np.float64) if cov else None
+        cnt = (C.c_int64 * 4)()
+        self._check(self.lib.cx_linear_moments(self.h, K, _p(off, C.c_int64), _p(ids, C.c_int64) if len(ids) else None,
+                                               _p(w, C.c_double) if w.size else None, _p(mean, C.c_double) if K else None,
+                                               _p(cv, C.c_double) if cov and K else None, cnt))
+        return mean, cv, dict(zip(("components", "failed", "nan_functionals", "free"), [int(x) for x in cnt]))
+
+    def posterior_covariance(self, var_a, var_b):
+        """the d x d cross-covariance Cov(x_a, x_b) of two variables under the joint posterior of a forest: 2d unit functionals of
+        linear_moments (var_a == var_b: the marginal covariance)"""
+        d = self.dim
+        eye = np.eye(d)
+        fs = [([var_a], eye[i:i + 1]) for i in range(d)] + [([var_b], eye[i:i + 1]) for i in range(d)]
+        _, cv, _ = self.linear_moments(fs)
+        return cv[:d, d:].copy()
+
+    def contrast_variance(self, var_a, var_b):
+        """Var(1'(x_a - x_b)) under the joint posterior of a forest (dim 1: the variance of x_a - x_b): one functional of linear_moments"""
+        one = np.ones((1, self.dim))
+        _, cv, _ = self.linear_moments([([var_a, var_b], np.concatenate([one, -one]))])
+        return float(cv[0, 0])
+
     # -- halo -----------------------------------------------------------------------------------
     def halo_configure(self, send_var, send_fac, recv_var, recv_fac):
         sv, sf, rv, rf = _i64(send_var), _i64(send_fac), _i64(recv_var), _i64(recv_fac)

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define CX_ABI_VERSION 8   /* 8: cx_predictive, cx_predictive_rows (additive).  7: cx_sample_posterior (additive).  6: cx_factor_beliefs, cx_factor_statistics (additive).  5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
+#define CX_ABI_VERSION 9   /* 9: cx_linear_moments (additive).  8: cx_predictive, cx_predictive_rows (additive).  7: cx_sample_posterior (additive).  6: cx_factor_beliefs, cx_factor_statistics (additive).  5: cx_log_evidence (additive).  4: cx_config.sweeps_per_launch -> reserved, cx_tile_stats and CX_KERNEL_TILED removed.  3: CX_SCHED_REFERENCE, cx_sweep_for, cx_ref_plan_stats, cx_ref_trace, cx_set_damping.  2: cx_config.reserved became sweeps_per_launch (validated), five new item / factor kinds, state blobs "CXSTATE2" */
 
 /* status codes */
 #define CX_OK 0
@@ -665,6 +665,34 @@ int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t seed, cons
 #define CX_PREDICT_CAUSAL 1
 int32_t cx_predictive(cx_handle *h, int32_t mode, int64_t n, const int64_t *factor_ids, double *out, double *total, int64_t *counts4);
 int32_t cx_predictive_rows(cx_handle *h, int64_t cap, int64_t *factor_ids, int64_t *n_rows);
+
+/* ---- exact moments of linear functionals (ABI 9; no counterpart in the reference) ----
+ * cx_linear_moments: the mean and the covariance of K linear functionals  φ_k(x) = Σ_i w_{k,i}' x_i  of the joint posterior of a Gaussian
+ * forest, dim 1 - 4: the variance of x_i - x_j for two states far apart, of a window average of a smoothed chain, the
+ * covariance of two regional totals on a tree, the lag-k autocovariance of a smoother — what no marginal and no factor belief holds.
+ * The setting is cx_sample_posterior's: the forest of non-observed variables, rooted the same way, the same q(x), read from the STORED
+ * factor→variable messages and the data (never the marginals), after any schedule.  A draw is x = c + z⁰ + F ε (§4g), so
+ *     mean[k] = φ_k of the draw with ε = 0,      cov = W F F' W'  (W: the weights on the non-observed variables),
+ * and F' is the sampler's scan run leaf-to-root, on the device, for all K at once: exact at a fixed point on a forest (q = p there), the
+ * moments of the same q the sampler draws from elsewhere.  Nothing of size n is copied to the host.
+ * The functionals come sparse, in CSR form: functional k has the entries offsets[k] .. offsets[k + 1] - 1 (offsets[0] = 0, never
+ * decreasing) of variable_ids and of weights ([nnz][dim], row-major).  A variable named more than once within a functional counts with
+ * the sum of its weights.  An observed variable adds w' datum to the mean and nothing to cov.
+ * mean: a host array [K].  cov: NULL (the means only; the leaf-to-root scan is skipped) or a host array [K][K], symmetric by
+ * construction (one triangle is computed and mirrored).  A functional that touches a component with an undefined input, or whose root
+ * belief or a conditional precision is not positive definite (cx_sample_posterior's status), has a NaN mean and a NaN row and column
+ * of cov; the others are unaffected.  counts4 = {components, failed components, functionals made NaN, non-observed variables}.
+ * A functional's numbers do not depend on which others share the call, nor on how the call is cut into chunks of functionals; every
+ * sum is compensated and in a fixed order: two calls on one state are bit-identical.  The noise coordinates of all K functionals are
+ * kept on the device, K x (non-observed variables) x dim doubles: past 2^30, or past 2^28 partial sums (K x K per 2048 variables),
+ * the call is refused with CX_ERR_OUT_OF_MEMORY (ask for fewer functionals per call; cov == NULL has no such bound).
+ * Refused as cx_sample_posterior refuses, with the same codes (other families, dim >= 5, partitioned handles, zero-noise factors, a
+ * captured stream; a cycle among the non-observed variables is CX_ERR_UNSUPPORTED); n_functionals < 0 or above 32768, a NULL offsets,
+ * mean or counts4, NULL variable_ids or weights with entries, or offsets that do not start at 0 or decrease are
+ * CX_ERR_INVALID_ARGUMENT; an unknown id CX_ERR_NOT_FOUND.  Shares the sampler's cached plan.  Synchronous; moves no message, marginal,
+ * readiness bit or counter. */
+int32_t cx_linear_moments(cx_handle *h, int64_t n_functionals, const int64_t *offsets, const int64_t *variable_ids, const double *weights,
+                          double *mean, double *cov, int64_t *counts4);
 
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)

@@ -182,6 +182,22 @@ class Handle {
                                   out.data(), o.data()));
         return {out, o};
     }
+    // exact mean (K) and covariance (K x K, row-major; want_cov == false: empty) of K linear functionals of the joint posterior of a forest
+    // (cx_linear_moments), in CSR form: functional k has the entries offsets[k] .. offsets[k + 1] - 1 of variable_ids and weights (dim per
+    // entry).  counts: components, failed components, functionals made NaN, non-observed variables
+    struct LinearMoments { std::vector<double> mean, cov; std::array<int64_t, 4> counts{}; };
+    LinearMoments linear_moments(const std::vector<int64_t> &offsets, const std::vector<int64_t> &variable_ids, const std::vector<double> &weights,
+                                 bool want_cov = true) {
+        need(offsets.empty() ? 0 : 1, 1, "linear_moments offsets");
+        const int64_t K = (int64_t)offsets.size() - 1;
+        need(weights.size(), variable_ids.size() * (size_t)dim_, "linear_moments weights");
+        LinearMoments r;
+        r.mean.resize((size_t)K);
+        if (want_cov) r.cov.resize((size_t)(K * K));
+        check(cx_linear_moments(h_, K, offsets.data(), variable_ids.data(), weights.data(), r.mean.data(), want_cov && K ? r.cov.data() : nullptr,
+                                r.counts.data()));
+        return r;
+    }
     std::pair<int32_t, double> sweep_until(double tol, int32_t max_sweeps, int32_t check_every = 10) {
         int32_t n = 0; double r = 0;
         check(cx_sweep_until(h_, tol, max_sweeps, check_every, &n, &r));

@@ -363,6 +363,25 @@ function sample_posterior(p, n_samples::Integer; seed::Integer = 0, variable_ids
     return out, counts
 end
 
+# exact mean and covariance of K linear functionals of the joint posterior of a forest (ABI 9; dim 1 - 4), in CSR form with 0-based
+# offsets (length K + 1), variable ids (nnz) and a d x nnz weight matrix: (mean [K], cov [K x K] or nothing,
+# [components, failed, functionals made NaN, free])
+function linear_moments(p, offsets::Vector{Int64}, variable_ids::Vector{Int64}, weights::Matrix{Float64}; cov::Bool = true)
+    d = p.dim
+    K = length(offsets) - 1
+    size(weights) == (d, length(variable_ids)) || throw(ArgumentError("weights must be $d x $(length(variable_ids)), got $(size(weights))"))
+    mean = zeros(Float64, K)
+    cv = cov ? zeros(Float64, K, K) : nothing
+    counts = zeros(Int64, 4)
+    cp = cov && K > 0 ? pointer(cv) : Ptr{Float64}(C_NULL)
+    GC.@preserve cv begin
+        check(p.handle, ccall((:cx_linear_moments, lib), Int32,
+                              (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, K, offsets, variable_ids, weights, mean, cp, counts))
+    end
+    return mean, cv, counts
+end
+
 function tree_heavy_path_stats(p)      # light depths, paths, variables on no path, launches per sweep (zeros: the level schedule is in use)
     out = zeros(Int64, 4)
     check(p.handle, ccall((:cx_tree_heavy_path_stats, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), p.handle, out))
