@@ -80,7 +80,13 @@ def _oracle_rows(E):
 
 @pytest.mark.parametrize("d,T,skips", [(2, 12, (3,)), (3, 20, (2,)), (4, 30, (5,)), (64, 10, (3,)), (7, 9, (2,))])      # (round 6: dim 64, and 5 .. 63 inside it)
 def test_one_call_on_a_loopy_d_dimensional_graph(hip_lib, d, T, skips):
-    model = loopy_lgssm(T, d, seed=10 + d, skips=skips)
+    check_calls_on_a_loopy_graph(loopy_lgssm(T, d, seed=10 + d, skips=skips), 3)
+
+
+def check_calls_on_a_loopy_graph(model, n_calls):
+    """n_calls calls (new data before every call but the first): the executions in the reference's order, then every message of both
+    directions and every marginal against MvSequential (also run on the general models of tests/test_gpu_anisotropic.py)"""
+    d = model.dim
     twin = scalar_twin(model)
     E = engine_oracle_from_model(twin, trace=True)
     seq = MvSequential(model)
@@ -90,7 +96,7 @@ def test_one_call_on_a_loopy_d_dimensional_graph(hip_lib, d, T, skips):
     E.set_messages_to_variable(twin.edge_var, twin.edge_fac, np.zeros(len(twin.edge_var)), np.full(len(twin.edge_var), SEED_VARIANCE))
     for e in range(seq.g.ne):
         seq.f2v[e] = (np.zeros(d), SEED_VARIANCE * np.eye(d))
-    for call in range(3):
+    for call in range(n_calls):
         if call:      # new data: the likelihood messages become pending again, and everything downstream of them
             y = np.asarray(model.data_y) + 0.1 * call
             dev.set_messages(model.data_var, model.data_fac, L.TO_FACTOR, L.FORM_POINT, y)
@@ -118,7 +124,7 @@ def test_one_call_on_a_loopy_d_dimensional_graph(hip_lib, d, T, skips):
             assert_close(marg[i, :d], mm, 1e-8, f"d={d} call {call + 1}: marginal mean of {xv}", scale_by="max")
             assert_close(marg[i, d:].reshape(d, d), SS, 1e-8, f"d={d} call {call + 1}: marginal covariance of {xv}", scale_by="max")
     st = dev.ref_plan_stats()
-    assert st["hits"] + st["misses"] == 3 and st["executions"] == len(rows)
+    assert st["hits"] + st["misses"] == n_calls and st["executions"] == len(rows)
 
 
 @pytest.mark.parametrize("d", [2, 4, 64])
