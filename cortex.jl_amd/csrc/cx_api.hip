@@ -158,7 +158,6 @@ static int32_t upload_ptab(cx_handle *h) {
     if (h->d_ptab && h->ptab_sets < nsets) { captured_graphs_drop(h); h->d_ptab.reset(); }
     if (!h->d_ptab) { int32_t rc = dev_alloc(h, &h->d_ptab, (int64_t)(per * nsets)); if (rc != CX_OK) return rc; h->ptab_sets = nsets; }
     CX_HIP(h, hipMemcpy(h->d_ptab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    h->pot64_fresh = false;
     if (cx::is_mfma_dim(d)) {   // the wave-per-message rule kernel reads B transposed (tile rows are its contraction index)
         const size_t dd = (size_t)d * d;
         std::vector<double> bt(2 * (size_t)nsets * dd);
@@ -198,7 +197,7 @@ int32_t cx_set_factor_matrices(cx_handle *h, int64_t parameter_set, const double
         }
         if ((int64_t)h->psets.size() <= parameter_set) h->psets.resize(parameter_set + 1);
         auto &ps = h->psets[parameter_set];
-        h->param_epoch++;
+        changed(*h, Change::RuleMatrices);      // (before the set is touched: a refused Q leaves it empty, which is a change too)
         ps.assign(A, A + d * d);
         ps.insert(ps.end(), Q, Q + d * d);
         std::vector<double> chk((size_t)6 * d * d);
@@ -208,11 +207,6 @@ int32_t cx_set_factor_matrices(cx_handle *h, int64_t parameter_set, const double
         }
         if (!h->has_graph) return CX_OK;
         if (h->cfg.schedule == CX_SCHED_CHAIN_SCAN) { int32_t rc0 = mv_ensure_chain_msgs(h); if (rc0 != CX_OK) return rc0; }   // under the old tables
-        // the messages out of observed variables, N(A y, Q), are cached in both Jacobi buffers: new (A, Q) invalidates them
-        h->observed_passes_due = 2;
-        h->kary_dirty = true;             // dim 2..4 factors of more than two variables read the raw (A, Q)
-        h->point64_dirty = true;
-        h->chain_side_dirty = true;
         return upload_ptab(h);
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_set_factor_matrices: host allocation failed"); }
 }
@@ -240,6 +234,7 @@ int32_t cx_graph_create(cx_handle *h, int64_t n_edges, const int64_t *edge_var, 
             const int32_t frc = cx::flat::flatten(h, n_edges, edge_var, edge_fac, edge_role, n_factors, factor_ids, factor_kind, factor_params, fo, ferr);
             if (frc != CX_OK) return fail(h, frc, ferr);
         }
+        changed(*h, Change::GraphCreated);
         const int64_t ne = h->ne, nv = h->nv, slots = h->nslots, big_total = fo.big_total;
         const bool mv = fo.mv;
         std::vector<int32_t> &var_deg = fo.var_deg, &spdir = fo.spdir;
@@ -287,7 +282,7 @@ int32_t cx_graph_create(cx_handle *h, int64_t n_edges, const int64_t *edge_var, 
         CX_TRY(dev_alloc(h, &h->d_scratch, 4096));
         if (mv) {
             const int64_t nc = h->nc, ncs = h->ncs;
-            h->spdir = spdir; h->spdir_dirty = true;
+            h->spdir = spdir;
             CX_TRY(dev_upload(h, &h->d_spdir, spdir));
             CX_TRY(dev_alloc(h, &h->d_mv_f2v, ncs * slots)); CX_TRY(dev_alloc(h, &h->d_mv_f2v_alt, ncs * slots));
             CX_TRY(dev_alloc(h, &h->d_mv_v2f, ncs * slots)); CX_TRY(dev_alloc(h, &h->d_mv_marg, cx::is_mfma_dim(h->cfg.dim) ? 1 : ncs * h->nslices * cx::kBlock));      // pair form by variable, whole 256-blocks
@@ -319,7 +314,7 @@ int32_t cx_graph_create(cx_handle *h, int64_t n_edges, const int64_t *edge_var, 
         CX_HIP(h, hipStreamSynchronize(h->stream));
         if (h->n_kary) { if (h->slot_kary.empty()) h->slot_kary.assign(slots, -1); CX_TRY2(cx::kary_upload(h)); }
         if (h->cfg.schedule == CX_SCHED_REFERENCE) CX_TRY2(ref_build(h));      // the default resolver's wiring + the shadow of the readiness state
-        h->has_graph = true; h->offchain_marg_dirty = true;
+        h->has_graph = true;
         return CX_OK;
     } catch (const std::bad_alloc &) {
         return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_graph_create: host allocation failed");

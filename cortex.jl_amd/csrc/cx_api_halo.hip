@@ -38,13 +38,14 @@ int32_t cx_halo_configure(cx_handle *h, int64_t n_send, const int64_t *sv, const
         for (uint8_t &b : h->vinfo) b &= (uint8_t)~cx::kGhost;
         for (int32_t v : recv_vars) h->vinfo[v] |= cx::kGhost;
         h->halo_state = false;
-        h->chains_dirty = true; h->tree_dirty = true;
+        changed(*h, Change::GhostSet);
         CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
         cx::ipc_destroy(h);          // the receive areas are sized by the halo lists
         cx::reset_all(h->d_send_slots, h->d_recv_slots, h->d_send_vars, h->d_send_buf, h->d_recv_buf);      // (the caller's buffers are let go, not freed)
         if (mv_chain_block) {      // no message buffers: the stand-ins are marked, nothing else
             h->send_slots.clear(); h->recv_slots.clear();
-            h->spdir_dirty = true; h->chain_partition = true; h->work64_dirty = true;
+            h->chain_partition = true;
+            changed(*h, Change::ChainBlock);
             CX_HIP(h, hipStreamSynchronize(h->stream));
             return CX_OK;
         }
@@ -82,6 +83,7 @@ int32_t cx_halo_configure_state(cx_handle *h, int64_t n_send, const int64_t *sv,
         if (rc != CX_OK) return rc;
         if (std::any_of(h->vinfo.begin(), h->vinfo.end(), [](uint8_t b) { return (b & cx::kGhost) != 0; })) {
             for (uint8_t &b : h->vinfo) b &= (uint8_t)~cx::kGhost;
+            changed(*h, Change::GhostSet);
             CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
         }
         cx::ipc_destroy(h);          // the receive areas are sized by the halo lists

@@ -30,12 +30,10 @@ void unpad_payload(int u, int d, const double *in, double *out) {
 
 int32_t cx_set_messages(cx_handle *h, int64_t n, const int64_t *variable_ids, const int64_t *factor_ids, int32_t direction,
                         int32_t form, const double *payload) {
-    // data injection (variable→factor messages of observed variables) changes the chains' leaf messages but no marginal of a
-    // variable off the chains: those depend on stored factor→variable messages only
-    if (h) { h->chain_side_dirty = true; if (direction != CX_TO_FACTOR) h->offchain_marg_dirty = true; }
     CX_NOT_VMP(h, "cx_set_messages");
     CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_set_messages: no graph");
     CX_REQUIRE(h, direction == CX_TO_FACTOR || direction == CX_TO_VARIABLE, CX_ERR_INVALID_ARGUMENT, "cx_set_messages: bad direction");
+    changed(*h, direction == CX_TO_FACTOR ? Change::StoredToFactor : Change::StoredToVariable);
     CX_REQUIRE(h, form == CX_FORM_MOMENT || form == CX_FORM_POINT || form == CX_FORM_NATURAL, CX_ERR_INVALID_ARGUMENT, "cx_set_messages: bad form");
     CX_REQUIRE(h, !(form == CX_FORM_POINT && direction == CX_TO_VARIABLE), CX_ERR_UNSUPPORTED, "cx_set_messages: point-mass data is a variable→factor message");
     CX_REQUIRE(h, h->cfg.family == CX_FAMILY_GAUSSIAN || form == CX_FORM_NATURAL || form == CX_FORM_POINT, CX_ERR_UNSUPPORTED,
@@ -107,14 +105,8 @@ int32_t cx_set_messages(cx_handle *h, int64_t n, const int64_t *variable_ids, co
             if (rc != CX_OK) return rc;
             cx::launch_scatter(h, h->d_v2f, d_idx, d_val, n);
             if (form == CX_FORM_POINT) {
-                // a variable that carries a point-mass datum is observed: its messages are never recomputed.  New data for variables
-                // that were observed already leaves the structure (chains, tiles) as it is.
-                bool newly = false;
-                for (int64_t i = 0; i < n; i++)
-                    if (!(h->vinfo[vars[i]] & cx::kClamped)) { h->vinfo[vars[i]] |= cx::kClamped; newly = true; }
-                if (newly) {
-                    h->vinfo_epoch++;
-                    h->chains_dirty = true; h->tree_dirty = true; h->offchain_marg_dirty = true;
+                if (mark_observed(*h, vars.data(), n)) {
+                    changed(*h, Change::NewlyObserved);
                     CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
                 }
             }
@@ -178,15 +170,14 @@ int32_t cx_get_messages(cx_handle *h, int64_t n, const int64_t *variable_ids, co
 }
 
 int32_t cx_seed_messages(cx_handle *h, int32_t direction, double mean, double variance) {
-    if (h) { h->chain_side_dirty = true; h->offchain_marg_dirty = true; }
     CX_NOT_VMP(h, "cx_seed_messages");
     CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_seed_messages: no graph");
+    changed(*h, Change::Seeded);
     CX_REQUIRE(h, direction == CX_TO_FACTOR || direction == CX_TO_VARIABLE, CX_ERR_INVALID_ARGUMENT, "cx_seed_messages: bad direction");
     CX_REQUIRE(h, variance > 0.0, CX_ERR_INVALID_ARGUMENT, "cx_seed_messages: variance must be > 0");
     if (h->cfg.dim > 1) {
         CX_REQUIRE(h, direction == CX_TO_VARIABLE, CX_ERR_UNSUPPORTED, "cx_seed_messages: dim > 1 seeds factor→variable messages only");
         if (cx::is_mfma_dim(h->cfg.dim)) {
-            h->pot64_fresh = false;
             cx::mv64_launch_seed(h, h->d_mv_f2v, mean / variance, 1.0 / variance);
             cx::mv64_launch_seed(h, h->d_mv_f2v_alt, mean / variance, 1.0 / variance);
         } else {
@@ -308,9 +299,9 @@ static int32_t joint_slots(cx_handle *h, int64_t factor_id, int32_t *s_out, int3
 }
 
 static int32_t update_batch(cx_handle *h, const cx_item *items, int64_t n) {
-    if (h) { h->chain_side_dirty = true; h->offchain_marg_dirty = true; }
     CX_NOT_VMP(h, "cx_update_batch");
     CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_update_batch: no graph");
+    changed(*h, Change::BatchWrote);
     if (n == 0) return CX_OK;
     CX_REQUIRE(h, n > 0 && items, CX_ERR_INVALID_ARGUMENT, "cx_update_batch: null argument");
     if (h->cfg.dim > 1) { try { return mv_update_batch(h, items, n); } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_update_batch: host allocation failed"); } }

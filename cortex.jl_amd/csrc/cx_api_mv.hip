@@ -85,15 +85,10 @@ int32_t mv64_set_messages(cx_handle *h, int64_t n, const std::vector<int32_t> &i
         CX_HIP(h, hipMemcpyAsync(d_idx, idx.data(), n * 4, hipMemcpyHostToDevice, h->stream));
         CX_HIP(h, hipMemcpyAsync(d_val, payload, (size_t)n * d * 8, hipMemcpyHostToDevice, h->stream));
         cx::mv64_set_point(h, h->d_mv_v2f, d_idx, d_val, n);
-        bool newly = false;
-        for (int64_t i = 0; i < n; i++)
-            if (!(h->vinfo[vars[i]] & cx::kClamped)) { h->vinfo[vars[i]] |= cx::kClamped; newly = true; }
-        if (newly) {     // the work lists depend on WHICH variables are observed, not on their data
+        if (mark_observed(*h, vars.data(), n)) {
+            changed(*h, Change::NewlyObserved);
             CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
-            h->work64_dirty = true;
-            h->chains_dirty = true; h->tree_dirty = true;      // a newly observed variable leaves the chains
         }
-        h->point64_dirty = true;      // the constant messages out of the observed variables are due again
     } else {
         std::vector<double> val((size_t)n * nc);
         for (int64_t i = 0; i < n; i++) {
@@ -113,7 +108,7 @@ int32_t mv64_set_messages(cx_handle *h, int64_t n, const std::vector<int32_t> &i
         double *d_val = (double *)((char *)h->d_stage + bytes_idx);
         CX_HIP(h, hipMemcpyAsync(d_idx, idx.data(), n * 4, hipMemcpyHostToDevice, h->stream));
         CX_HIP(h, hipMemcpyAsync(d_val, val.data(), (size_t)n * nc * 8, hipMemcpyHostToDevice, h->stream));
-        if (direction == CX_TO_FACTOR) { cx::mv64_rows_scatter(h, h->d_mv_v2f, d_idx, d_val, n); h->point64_dirty = true; }
+        if (direction == CX_TO_FACTOR) cx::mv64_rows_scatter(h, h->d_mv_v2f, d_idx, d_val, n);
         else { cx::mv64_rows_scatter(h, h->d_mv_f2v, d_idx, d_val, n); cx::mv64_rows_scatter(h, h->d_mv_f2v_alt, d_idx, d_val, n); }
     }
     CX_HIP(h, hipGetLastError());
@@ -150,18 +145,9 @@ int32_t mv_set_messages(cx_handle *h, int64_t n, const int64_t *variable_ids, co
     CX_HIP(h, hipMemcpyAsync(d_val, val.data(), (size_t)n * nc * 8, hipMemcpyHostToDevice, h->stream));
     if (direction == CX_TO_FACTOR) {
         cx::mv_launch_scatter(h, h->d_mv_v2f, h->nslots, nc, h->ncs, d_idx, d_val, n);
-        h->observed_passes_due = 2;   // a stored variable→factor message changed: observed senders are refreshed
-        if (form == CX_FORM_POINT) {
-            // New data for variables that were observed already leaves the structure (observed flags, rule masks, chains) as it is:
-            // only the constant messages out of them are due again (observed_passes_due above).
-            bool newly = false;
-            for (int64_t i = 0; i < n; i++)
-                if (!(h->vinfo[vars[i]] & cx::kClamped)) { h->vinfo[vars[i]] |= cx::kClamped; newly = true; }
-            if (newly) {
-                h->chains_dirty = true; h->tree_dirty = true;      // a newly observed variable leaves the chains
-                CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
-                h->spdir_dirty = true;
-            }
+        if (form == CX_FORM_POINT && mark_observed(*h, vars.data(), n)) {
+            changed(*h, Change::NewlyObserved);
+            CX_HIP(h, hipMemcpyAsync(h->d_vinfo, h->vinfo.data(), (size_t)h->nv, hipMemcpyHostToDevice, h->stream));
         }
     } else {
         cx::mv_launch_scatter(h, h->d_mv_f2v, h->nslots, nc, h->ncs, d_idx, d_val, n);
@@ -299,7 +285,7 @@ int32_t build_work64(cx_handle *h) {
     if ((rc = dev_upload(h, &h->d_rule64_rec, rec)) != CX_OK) return rc;
     CX_HIP(h, hipStreamSynchronize(h->stream));
     h->work64_dirty = false;
-    h->point64_dirty = true;
+    h->point64_dirty = true;      // (work done: new lists, so the constant messages go out once more)
     return CX_OK;
 }
 
@@ -314,7 +300,7 @@ static int32_t mv_refresh_spdir(cx_handle *h) {
     }
     CX_HIP(h, hipMemcpy(h->d_spdir, eff.data(), eff.size() * 4, hipMemcpyHostToDevice));
     h->spdir_dirty = false;
-    h->observed_passes_due = 2;   // the data (or the set of observed variables) changed: refresh both buffers
+    h->observed_passes_due = 2;   // (work done: new masks, so the observed senders refresh both buffers)
     return CX_OK;
 }
 
@@ -393,7 +379,7 @@ int32_t mv_chain_block_maps(cx_handle *h, double *fwd, double *bwd, double *side
         bool no_root = false;
         if ((rc = cx::chain64_block_potential(h, pot.data(), sf, sl, &no_root)) != CX_OK) return rc;
         if (no_root) {      // the plan was built before the handle became a partition's: once more, with a root
-            h->chains_dirty = true;
+            h->chains_dirty = true;      // (work site: forces the rebuild of the next line)
             if ((rc = build_chains(h)) != CX_OK) return rc;
             if ((rc = cx::chain64_block_potential(h, pot.data(), sf, sl, &no_root)) != CX_OK) return rc;
             CX_REQUIRE(h, !no_root, CX_ERR_STATE, "cx_chain_block_maps: the plan has no root potential");
@@ -444,7 +430,7 @@ int32_t mv_chain_block_maps(cx_handle *h, double *fwd, double *bwd, double *side
     cx::mvc_launch_block_maps(h);
     CX_HIP(h, hipGetLastError());
     h->observed_passes_due = 0;
-    h->chain_side_dirty = true;          // the boundary messages change before the sweep proper
+    h->chain_side_dirty = true;          // (work done: the boundary messages change before the sweep proper)
     const int d = h->cfg.dim, nc = h->nc, nd = 2 * (d * (d + 1) / 2) + d * d + 2 * d;
     std::vector<double> maps((size_t)2 * (nd + 1)), side((size_t)nc * h->chain_npos);
     CX_HIP(h, hipMemcpyAsync(maps.data(), h->d_mvc_block, maps.size() * 8, hipMemcpyDeviceToHost, h->stream));
@@ -516,7 +502,6 @@ int32_t mv_ensure_prod_store(cx_handle *h) {
 }
 
 int32_t mv_update_batch(cx_handle *h, const cx_item *items, int64_t n) {
-    h->pot64_fresh = false;
     CX_REQUIRE(h, (int64_t)h->psets.size() > h->max_pset, CX_ERR_STATE, "cx_update_batch: a factor names a parameter set that was never set (cx_set_factor_matrices)");
     for (int64_t i = 0; i <= h->max_pset; i++)
         CX_REQUIRE(h, !h->psets[i].empty(), CX_ERR_STATE, "cx_update_batch: parameter set " + std::to_string(i) + " was never set (cx_set_factor_matrices)");
@@ -614,7 +599,6 @@ int32_t mv_update_batch(cx_handle *h, const cx_item *items, int64_t n) {
         cx::mv64_launch_v2f(h, (int)n1, d_s, d_v, h->d_mv_f2v);
         cx::mv64_launch_point(h, (int)n2, d_p, h->d_mv_f2v, h->d_mv_f2v);
         cx::mv64_launch_rule(h, (int)n3, d_r, h->d_mv_f2v, h->d_mv_f2v, CX_KERNEL_BATCH);
-        h->point64_dirty = true;      // a sweep recomputes the constant messages into both of its buffers
     }
     CX_HIP(h, hipGetLastError());
     CX_HIP(h, hipStreamSynchronize(h->stream));      // synchronous: the host sets readiness bits next (signal.jl:232-253)

@@ -644,7 +644,7 @@ int32_t ref_sweep(cx_handle *h, const int32_t *req, int64_t n, const uint64_t *k
     }
     h->sweeps_done++;
     h->v2f_stale = false;
-    if (cx::is_mfma_dim(h->cfg.dim)) { h->point64_dirty = true; h->pot64_fresh = false; }      // (as after a batch: a sweep of another schedule recomputes its constants)
+    changed(*h, Change::ForeignSweepRan);
     return CX_OK;
 }
 

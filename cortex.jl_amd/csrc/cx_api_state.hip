@@ -136,7 +136,6 @@ int32_t cx_state_export(cx_handle *h, void *buf, int64_t bytes) {
 }
 
 int32_t cx_state_import(cx_handle *h, const void *buf, int64_t bytes) {
-    if (h) { h->chain_side_dirty = true; h->offchain_marg_dirty = true; h->pot64_fresh = false; }
     CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_state_import: no graph");
     if (is_vmp(h)) return cx::vmp_state_import(h, buf, bytes);
     CX_REQUIRE(h, !h->in_sweep, CX_ERR_STATE, "cx_state_import: a cx_sweep_begin is still open");
@@ -171,19 +170,19 @@ int32_t cx_state_import(cx_handle *h, const void *buf, int64_t bytes) {
     }
     CX_HIP(h, hipSetDevice(h->cfg.device));
     CX_HIP(h, hipStreamSynchronize(h->stream));
+    changed(*h, Change::StateImported);      // (the blob is valid: from here on the handle's state is being replaced)
     o = (const char *)buf + sizeof hd;
     for (auto &p : parts) {
         o += sizeof(StateSection);
-        if (p.id == 1) { std::memcpy(h->vinfo.data(), o, (size_t)p.bytes); h->vinfo_epoch++; }
+        if (p.id == 1) std::memcpy(h->vinfo.data(), o, (size_t)p.bytes);
         if (p.bytes && p.dev) CX_HIP(h, hipMemcpy(p.dev, o, (size_t)p.bytes, hipMemcpyHostToDevice));
         else if (p.bytes && p.id == 7) CX_REQUIRE(h, ref_state_read(h, o, p.bytes), CX_ERR_INVALID_ARGUMENT, "cx_state_import: the readiness section does not fit this handle's wiring");
         o += p.bytes;
     }
     h->sweeps_done = hd.sweeps_done;
     h->v2f_stale = (hd.v2f_stale & 1) != 0;
-    h->offchain_marg_dirty = (hd.v2f_stale & 2) != 0;     // the marginals themselves travelled in section 5
+    h->offchain_marg_dirty = (hd.v2f_stale & 2) != 0;     // (restored, like the line above: the marginals themselves travelled in section 5)
     h->chain_msgs_stale = false; h->mvc_marg_pending = false;     // (the imported marginals are final)
-    h->spdir_dirty = h->work64_dirty = h->point64_dirty = h->chains_dirty = true; h->tree_dirty = true;   // derived from the observed flags
     h->d_prev.reset();              // residual snapshots restart
     h->d_mv_prev.reset();
     return CX_OK;

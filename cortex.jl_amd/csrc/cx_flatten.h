@@ -117,7 +117,7 @@ int32_t flatten(H *h, int64_t n_edges, const int64_t *edge_var, const int64_t *e
     h->nf = n_factors;
     h->lin_out_is_second.assign(n_factors, 0); h->fac_edges.clear();
     h->np_role.clear(); h->var_gamma.clear();
-    h->n_kary = 0; h->kary_slot.clear(); h->kary_coef.clear(); h->kary_qb.clear(); h->slot_kary.clear(); h->kary_pset.clear(); h->kary_dirty = true;
+    h->n_kary = 0; h->kary_slot.clear(); h->kary_coef.clear(); h->kary_qb.clear(); h->slot_kary.clear(); h->kary_pset.clear();
     std::vector<int32_t> edge_fix(ne);      // local factor number per CSR edge
     for (int64_t e = 0; e < ne; e++) {
         auto it = std::lower_bound(h->fac_ids.begin(), h->fac_ids.end(), h->edge_fac_id[e]);

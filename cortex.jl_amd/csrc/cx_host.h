@@ -13,6 +13,7 @@
 #include <numeric>
 
 #include "cx_internal.h"
+#include "cx_derived.h"           // cxh::changed — the one rule for what a caller's change voids
 #include "cx_partner_runs.h"      // cx::pruns::build — partner[slot] - slot as wave-uniform runs (cx_graph_create)
 
 namespace cxh {

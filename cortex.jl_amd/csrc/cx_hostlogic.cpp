@@ -4,6 +4,7 @@
 //
 //   cxh_plan64_*   the work plan of the chain-scan schedule for dim 64 (cx_chain64_plan.h)
 //   cxh_ref_*      CX_SCHED_REFERENCE: the default resolver's wiring, the shadow of the readiness state, the recorded and levelled calls (cx_refsched.h)
+//   cxh_derived_apply  the one rule for what a caller's change voids (cx_derived.h) over a plain struct with cx_handle's flags
 //   cxh_flat_partner_runs  the partner-run table of the packed fused sweep (cx_partner_runs.h)
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
 //                  plain struct with cx_handle's host fields
@@ -13,6 +14,7 @@
 
 #include "cx_chain64_plan.h"
 #include "cx_chains.h"
+#include "cx_derived.h"
 #include "cx_halo_plan.h"
 #include "cx_partner_runs.h"
 #include "cx_tree_plan.h"
@@ -80,6 +82,30 @@ void cxh_plan64_records(const void *pv, int32_t what, int64_t *out) {
     else std::memcpy(out, p->steps.data(), p->steps.size() * sizeof(cx::plan64::Step));
 }
 
+// ---- what a change voids (cx_derived.h) -----------------------------------------------------------------------------------------
+struct DerivedFlags {                    // the flags and epochs of cx_handle that cxh::changed touches, by the same names
+    cx_config cfg{};
+    bool chains_dirty, tree_dirty, spdir_dirty, work64_dirty, point64_dirty, kary_dirty, chain_side_dirty, chain_linkpar_dirty, offchain_marg_dirty;
+    int observed_passes_due;
+    bool pot64_fresh, v2f_stale, chain_msgs_stale, mvc_marg_pending;
+    uint64_t vinfo_epoch, param_epoch;
+};
+
+// flags in the order of DerivedFlags' members (16 values); returns 0, or -1 for a change that does not exist
+int32_t cxh_derived_apply(int32_t dim, int32_t change, const int64_t *in, int64_t *out) {
+    if (change < 0 || change >= (int32_t)cxh::Change::kCount) return -1;
+    DerivedFlags f;
+    f.cfg.dim = dim;
+    bool *b[] = {&f.chains_dirty, &f.tree_dirty, &f.spdir_dirty, &f.work64_dirty, &f.point64_dirty, &f.kary_dirty, &f.chain_side_dirty, &f.chain_linkpar_dirty,
+                 &f.offchain_marg_dirty, nullptr, &f.pot64_fresh, &f.v2f_stale, &f.chain_msgs_stale, &f.mvc_marg_pending};
+    for (int i = 0; i < 14; i++) if (b[i]) *b[i] = in[i] != 0;
+    f.observed_passes_due = (int)in[9]; f.vinfo_epoch = (uint64_t)in[14]; f.param_epoch = (uint64_t)in[15];
+    cxh::changed(f, (cxh::Change)change);
+    for (int i = 0; i < 14; i++) if (b[i]) out[i] = *b[i] ? 1 : 0;
+    out[9] = f.observed_passes_due; out[14] = (int64_t)f.vinfo_epoch; out[15] = (int64_t)f.param_epoch;
+    return 0;
+}
+
 // ---- the flattened graph ------------------------------------------------------------------------------------------------------
 struct HostGraph {                       // the host fields of cx_handle that cx_flatten.h / cx_chains.h touch, by the same names
     cx_config cfg{};
@@ -95,7 +121,6 @@ struct HostGraph {                       // the host fields of cx_handle that cx
     int64_t n_kary = 0;
     std::vector<int32_t> kary_slot, slot_kary, kary_pset;
     std::vector<double> kary_coef, kary_qb;
-    bool kary_dirty = true;
     // deep halo (cx_halo_plan.h)
     std::vector<int32_t> trim_lo, trim_hi, send_slots;
     int own_slice_lo = 1, own_slice_hi = 0, halo_depth = 0, ipc_quiet_lo = 1, ipc_quiet_hi = 0;

@@ -97,6 +97,8 @@ namespace cx {
 // default-constructed DevState: a member added here is freed and reset with no second mention anywhere, and the state after a reset is
 // what the initialisers below say.  Assignment goes member by member in the order written here, so the captured graphs come FIRST:
 // they hold the addresses of the buffers below and go before them.
+// The *_dirty / *_due / *_fresh flags and the epochs below and in cx_handle: WHAT raises each of them is written in one place, cx_derived.h
+// ("What a change voids"); whoever rebuilds the state a flag guards clears it where it rebuilds.
 struct DevState {
     OwnedStream capture_stream;
     GraphExec tree_graph;      // CX_SCHED_TREE: the stages of one sweep as ONE graph launch (hundreds of small launches otherwise)
@@ -291,7 +293,7 @@ struct cx_handle : cx::DevState {
     std::vector<int32_t> tree_c64_up, tree_c64_final;      // per light depth: index into tree_c64, -1 = no such scan
     int64_t chain_npos = 0, chain_nlinks = 0;
     int64_t chain_npos_linked = 0;   // dim > 1: positions [0, this) belong to paths with links; the isolated ones follow
-    bool chain_side_dirty = true;    // the leaf messages / side sums of the chain positions must be recomputed (data or rule parameters changed)
+    bool chain_side_dirty = true;    // the leaf messages / side sums of the chain positions are due (raised by: cx_derived.h)
     bool chain_partition = false;    // the handle holds a time block of a partitioned chain (cx_chain_block_maps was called)
     bool chain_covers_all = false;   // every variable that reads messages is a chain position: the scan's side pass produces all leaf messages
     uint64_t batch_epoch = 1;        // deep-halo batch graphs (DevState: batch_graph): moved on by whatever a captured batch bakes in (layers, damping, the graph itself): cxh::batch_graph_drop
@@ -343,12 +345,11 @@ struct cx_handle : cx::DevState {
     // cx_set_messages of a long list the caller repeats (an iteration re-sets its priors before every call): ids -> slots / variables / edges,
     // kept for the last lists (the ids themselves are kept and compared: a hash alone would be trusted with the device's memory)
     uint64_t set_memo_tick = 0;
-    uint64_t vinfo_epoch = 0;        // bumped whenever the observed flags of vinfo change (a cached "every free variable" request is then stale)
+    uint64_t vinfo_epoch = 0;        // the observed flags of vinfo changed (cx_derived.h); read by ref_sweep_all's cached "every free variable" request
     bool in_sweep = false;
     bool v2f_stale = false;          // fused schedule without materialisation: v2f must be recomputed before use
     bool chain_v2f_from_scan = false; // the scan also stores the variable→factor messages of the chain links (set by cx_vmp.hip on its inner handle)
-    bool offchain_marg_dirty = true; // chain scan: marginals of variables OFF the chains (observed, stand-ins) are due — they depend on
-                                     // stored factor→variable messages only, so a full variable phase runs after those were set
+    bool offchain_marg_dirty = true; // scalar chain scan: marginals of variables OFF the chains (observed, stand-ins) are due (cx_derived.h)
 
     // stores of the batched API's intermediates: ProductOfMessages nodes (variable, lo, hi) and JointMarginal nodes (factor)
     std::vector<uint8_t> lin_out_is_second;   // per factor (GAUSS_LINEAR): the OUT edge is the edge of the higher variable id
@@ -368,8 +369,7 @@ struct cx_handle : cx::DevState {
     // variational families (cx_vmp.hip): opaque state
     void *vmp = nullptr;
 
-    // cx_log_evidence (cx_evidence.hip): work lists of the graph and scratch, built on the first call (opaque); param_epoch moves on
-    // with every change of rule parameters after cx_graph_create (matrices, coefficients, edge sets), which the lists' parameter part follows
+    // moves on with every change of rule parameters (cx_derived.h: Change::Rule*); the parameter part of the evidence and learn caches follows it
     uint64_t param_epoch = 0;
 
     // profiling

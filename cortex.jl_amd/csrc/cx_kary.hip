@@ -158,8 +158,7 @@ int32_t cx_set_factor_coefficients(cx_handle *h, int64_t n, const int64_t *varia
         if (!(a[i] != 0.0) || !std::isfinite(a[i])) return fail(h, CX_ERR_INVALID_ARGUMENT, "cx_set_factor_coefficients: a coefficient must be finite and non-zero");
         h->kary_coef[en] = -a[i];
     }
-    h->kary_dirty = true; h->param_epoch++;
-    h->chain_side_dirty = true; h->offchain_marg_dirty = true;
+    changed(*h, Change::RuleCoefficients);
     return CX_OK;
 }
 

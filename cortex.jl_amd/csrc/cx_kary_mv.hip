@@ -90,7 +90,7 @@ int32_t cx_set_factor_edge_sets(cx_handle *h, int64_t n, const int64_t *variable
         h->kary_pset[en] = (int32_t)parameter_sets[i];
         h->max_pset = std::max<int64_t>(h->max_pset, parameter_sets[i]);
     }
-    h->kary_dirty = true; h->tree_dirty = true; h->param_epoch++;
+    changed(*h, Change::RuleEdgeSets);
     return CX_OK;
 }
 

@@ -225,3 +225,25 @@ class FlatGraph:
 
     def ref_scalar(self, what):
         return int(self.L.cxh_ref_scalar(self.p, {"signals": 0, "dependencies": 1, "products": 2, "hash": 3, "rounds": 4}[what]))
+
+
+# ---- cx_derived.h: what a caller's change voids ----------------------------------------------------------------------------------------
+DERIVED_FLAGS = ("chains_dirty", "tree_dirty", "spdir_dirty", "work64_dirty", "point64_dirty", "kary_dirty", "chain_side_dirty", "chain_linkpar_dirty",
+                 "offchain_marg_dirty", "observed_passes_due", "pot64_fresh", "v2f_stale", "chain_msgs_stale", "mvc_marg_pending", "vinfo_epoch", "param_epoch")
+CHANGES = ("StoredToVariable", "StoredToFactor", "NewlyObserved", "RuleMatrices", "RuleCoefficients", "RuleEdgeSets", "GhostSet", "ChainBlock", "Seeded",
+           "BatchWrote", "ForeignSweepRan", "StateImported", "GraphCreated")
+DERIVED_CLEAN = {**{f: 0 for f in DERIVED_FLAGS}, "pot64_fresh": 1}      # nothing due, the block potentials fresh, the epochs at 0
+
+
+def derived_apply(dim, change, flags=None):
+    """cxh::changed(h, change) on a handle of dimension `dim` whose flags are `flags` (default: all clean): the flags afterwards, by name"""
+    L = lib()
+    L.cxh_derived_apply.restype = C.c_int32
+    L.cxh_derived_apply.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    flags = DERIVED_CLEAN if flags is None else flags
+    a = np.array([flags[f] for f in DERIVED_FLAGS], dtype=np.int64)
+    out = np.zeros_like(a)
+    rc = int(L.cxh_derived_apply(int(dim), CHANGES.index(change) if isinstance(change, str) else int(change), a.ctypes.data, out.ctypes.data))
+    if rc != 0:
+        raise ValueError(f"no such change: {change}")
+    return dict(zip(DERIVED_FLAGS, out.tolist()))
