@@ -80,6 +80,16 @@ int32_t build_chains(cx_handle *h) {
         } else {
             if ((rc = dev_alloc(h, &h->d_chain_side, h->chain_npos)) != CX_OK) return rc;
             if ((rc = dev_alloc(h, &h->d_chain_totals, (int64_t)cx::chain_total_bytes(h->chain_nlinks))) != CX_OK) return rc;
+            // non-observed variables of degree 1 (off the chains): the slots that send into them
+            std::vector<int32_t> leaf_from;
+            for (int64_t v = 0; v < nv; v++) {
+                if ((h->vinfo[v] & (cx::kClamped | cx::kGhost)) || h->var_off[v + 1] - h->var_off[v] != 1) continue;
+                const int32_t p = h->partner[cx::slot_of_edge(h, h->var_off[v])];
+                if (p >= 0) leaf_from.push_back(p);
+            }
+            h->d_chain_leaf_from.reset();
+            h->chain_nleaf = (int64_t)leaf_from.size();
+            if (h->chain_nleaf > 0 && (rc = dev_upload(h, &h->d_chain_leaf_from, leaf_from)) != CX_OK) return rc;
         }
         CX_HIP(h, hipStreamSynchronize(h->stream));
         h->chains_dirty = false;
@@ -362,8 +372,16 @@ void sweep_main(cx_handle *h, bool skip_ghosts) {
         if (fast && marg) {
             h->v2f_stale = true;
         } else {
-            cx::launch_var_to_factor(h, h->d_f2v, marg);       // every variable→factor message + marginals
-            cx::launch_big_var_to_factor(h, h->d_f2v, marg);
+            // A non-observed variable of degree 1 next to a chain (the last state of a forecast) reads the rule of its neighbour's
+            // variable→factor message.  The factor phase above applied it to the message of the sweep BEFORE (undefined in the first
+            // sweep): the variable phase first, that rule again on what it wrote, and the marginals from the result.
+            const bool leaves = h->chain_nleaf > 0;
+            cx::launch_var_to_factor(h, h->d_f2v, marg && !leaves);       // every variable→factor message + marginals
+            cx::launch_big_var_to_factor(h, h->d_f2v, marg && !leaves);
+            if (leaves) {
+                cx::launch_push_slots(h, h->d_chain_leaf_from, h->chain_nleaf, h->d_f2v, CX_KERNEL_FACTOR_TO_VAR);
+                if (marg) { cx::launch_var_to_factor(h, h->d_f2v, true); cx::launch_big_var_to_factor(h, h->d_f2v, true); }
+            }
             h->v2f_stale = false;
             if (marg) h->offchain_marg_dirty = false;
         }

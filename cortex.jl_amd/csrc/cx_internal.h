@@ -168,6 +168,10 @@ struct DevState {
     // chain-scan schedule (cx_chain.hip)
     DevBuf<int32_t> d_chain_pos_var, d_chain_skip0, d_chain_skip1;
     DevBuf<int32_t> d_chain_link_pos, d_chain_from, d_chain_to;
+    // dim 1: the slots that send into a non-observed variable of degree 1 (a forecast's last state): it is off the chains, and the
+    // message into it is the rule applied to a variable→factor message that exists only once the scan has run (sweep_main)
+    DevBuf<int32_t> d_chain_leaf_from;
+    int64_t chain_nleaf = 0;
     DevBuf<uint8_t> d_chain_head_fwd, d_chain_head_bwd;
     DevBuf<double2> d_chain_side;
     DevBuf<char> d_chain_totals;    // bytes: the tile totals of whichever scan the dim runs

@@ -33,6 +33,33 @@ struct Rows {
     const int32_t *xoff, *xs;
 };
 
+// A cavity is a DIFFERENCE of precisions: the belief's minus the messages taken out.  Where what is left is flat — the flat message
+// behind a forecast's end, a direction no other datum informs — the difference is the rounding of its terms, a number of either sign
+// around 1e-16 of the belief's own entry.  A Cholesky pivot below kFlatPivot (64 ulp: fewer than six bits of it are left) times the
+// belief's diagonal entry is such a remainder, and the cavity improper, as with a pivot <= 0.
+constexpr double kFlatPivot = 64 * 2.220446049250313e-16;
+
+template <int D>
+__device__ __forceinline__ bool resolved(const double (&A)[D][D], const double (&ref)[D]) {
+    double L[D][D];
+#pragma unroll
+    for (int j = 0; j < D; j++) {
+        double s = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) s -= L[j][k] * L[j][k];
+        if (!(s > kFlatPivot * fmax(ref[j], 0.0))) return false;
+        L[j][j] = sqrt(s);
+#pragma unroll
+        for (int i = j + 1; i < D; i++) {
+            double t = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) t -= L[i][k] * L[j][k];
+            L[i][j] = t / L[j][j];
+        }
+    }
+    return true;
+}
+
 // the cavity of the free variable `var` behind `slot`: mean mc, covariance Sc.  0, 1 (an undefined input) or 2 (not positive definite)
 template <int D>
 __device__ __forceinline__ int cavity(const ev::Msgs &M, const Rows &R, int slot, int var, int input, double (&mc)[D], double (&Sc)[D][D]) {
@@ -59,11 +86,15 @@ __device__ __forceinline__ int cavity(const ev::Msgs &M, const Rows &R, int slot
     }
     if (!ok) return 1;
     if (flat) return 2;      // nothing is left: a flat cavity by structure, whatever the rounding of M_i minus its own terms leaves behind
-    double L[D][D], dl[D], logdet, quad;
+    double L[D][D], dl[D], ref[D], logdet, quad;
+    const double *w = M.W + (int64_t)var * Lay<D>::K + D;      // the belief's precision (free_edge)
 #pragma unroll
-    for (int i = 0; i < D; i++)
+    for (int i = 0; i < D; i++) {
+        ref[i] = w[tri<D>(i, i)];
 #pragma unroll
         for (int j = 0; j < D; j++) L[i][j] = ev::lam_at<D>(lm, i, j);
+    }
+    if (!resolved<D>(L, ref)) return 2;
     if (!ev::chol_quad<D>(L, et, logdet, quad)) return 2;
     ev::back_solve<D>(L, et, dl);
     ev::inv_lower<D>(L);

@@ -247,7 +247,10 @@ int32_t cx_edge_index(const cx_handle *h, int64_t n, const int64_t *variable_ids
                       int64_t *out_edge);
 
 /* ---- data injection / read-back --------------------------------------------------------------
- * payload: n rows of cx_payload_doubles(dim, form) doubles. */
+ * payload: n rows of cx_payload_doubles(dim, form) doubles.
+ * The variable→factor message of a non-observed variable of degree 1 (the last state of a forecast, a latent leaf) is the caller's:
+ * CX_FORM_NATURAL zeros is the flat message, which leaves the rest of the model as it is; left unset, it leaves the marginals of
+ * every other variable of its component undefined. */
 int64_t cx_payload_doubles(int32_t dim, int32_t form);
 int32_t cx_set_messages(cx_handle *h, int64_t n, const int64_t *variable_ids, const int64_t *factor_ids,
                         int32_t direction, int32_t form, const double *payload);
@@ -540,8 +543,10 @@ int32_t cx_tree_heavy_path_stats(const cx_handle *h, int64_t *out4);
  * zero throws in the user's Julia code).  An undefined value is NaN and propagates by itself, a rule whose input is not positive
  * definite leaves its output undefined or unchanged; this call counts, on the device, the stored factor→variable messages INTO
  * NON-OBSERVED variables:  out4 = { defined, undefined (UndefValue: never computed, or a dependency was undefined), defined with a
- * negative precision (dim > 1: a negative diagonal entry of the precision matrix), defined with a non-finite entry (a point mass
- * (y, +inf) of dim 1 is a value, not counted) }.  Synchronous. */
+ * negative precision (dim > 1: a diagonal entry of the precision matrix below -1e-12 times the largest diagonal entry of Q^-1 or
+ * A' Q^-1 A of the pairwise rule that sends the message — a flat message, such as the one behind a forecast's end or a long run of
+ * states without data, is the rounding of numbers of that size and is not counted; a message no pairwise rule sends is judged
+ * strictly), defined with a non-finite entry (a point mass (y, +inf) of dim 1 is a value, not counted) }.  Synchronous. */
 int32_t cx_message_health(cx_handle *h, int64_t *out4);
 
 /* ---- log-evidence (ABI 5; no counterpart in the reference: its engine computes no numbers) ----
@@ -649,7 +654,9 @@ int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t seed, cons
  * out: NULL, or a host array of counts4[0] rows of d + d^2 + 2 doubles:  ŷ[d] | S[d][d] (row-major) | log_density | maha.  A row with
  * an undefined (NaN) input is NaN; a row whose cavity or S is not positive definite — an improper predictive, such as the first
  * observation of a chain without a prior, which the Kalman decomposition also leaves out — is NaN and counted apart (a cavity from
- * which every message into the variable is taken out is improper by structure, whatever the subtraction rounds to).
+ * which every message into the variable is taken out is improper by structure, whatever the subtraction rounds to; so is one whose
+ * cavity has a Cholesky pivot below 64 ulp of the belief's own diagonal entry: what a flat message left behind, such as the one
+ * behind a forecast's end, is the rounding of the subtraction, of either sign).
  * counts4 = {rows, rows scored, rows with an undefined input, rows improper} (never NULL; a call with out == NULL sizes the array).
  * *total (may be NULL): the compensated f64 sum of log_density over the SCORED rows only, in a fixed order: two calls on one state are
  * bit-identical.  With out == NULL only the total and the counters come back (a learning loop's objective).

@@ -114,8 +114,13 @@ def predictive_from_messages(gm, f2v, opq=None, mode=LOO):
                 status = status or 2
                 continue
             try:
-                np.linalg.cholesky(lt)
+                Lc = np.linalg.cholesky(lt)
             except np.linalg.LinAlgError:
+                status = status or 2
+                continue
+            # what is left is a DIFFERENCE: a pivot below 64 ulp of the belief's own entry is the rounding of a flat remainder (the flat
+            # message behind a forecast's end), of either sign — improper, as cx_predictive has it
+            if not np.all(np.diag(Lc) ** 2 > 64 * np.finfo(float).eps * np.maximum(np.diag(M_lam[v]), 0.0)):
                 status = status or 2
                 continue
             Sc = np.linalg.inv(lt)
