@@ -308,6 +308,12 @@ int32_t cx_graph_create(cx_handle *h, int64_t n_edges, const int64_t *edge_var, 
         if (h->cfg.schedule == CX_SCHED_FUSED) {
             CX_TRY(dev_alloc(h, &h->d_f2v_alt, slots));
             CX_HIP(h, hipMemsetAsync(h->d_f2v_alt, 0xff, (size_t)slots * sizeof(double2), h->stream));
+            // a grid of additive Gaussian factors: the plan of the paired sweep (cx_lattice_plan.h; cx_api_sweep.hip: cx_sweep runs it)
+            if (h->cfg.family == CX_FAMILY_GAUSSIAN && !h->any_linear && h->n_kary == 0 && h->big_vars.empty()) {
+                const cx::lattice::Plan pl = cx::lattice::build(h->partner, h->slice_off, h->vinfo, h->nv, q.data());
+                h->pair_refused = pl.reason;
+                if (pl.ok && h->pair_abort.alloc() && h->d_pair_flag.alloc(h, 1) == CX_OK) { h->pair_H = pl.H; h->pair_W = pl.W; h->pair_block_cols = pl.block_cols; }
+            } else h->pair_refused = "not a fused scalar handle of additive Gaussian factors";
         }
 #undef CX_TRY
 #define CX_TRY2(x) do { int32_t rc2_ = (x); if (rc2_ != CX_OK) { dev_free_all(h); return rc2_; } } while (0)

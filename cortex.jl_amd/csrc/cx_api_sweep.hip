@@ -354,6 +354,46 @@ int32_t tree_sweep(cx_handle *h) {
     return CX_OK;
 }
 
+// ---- two sweeps per launch (cx_sweep_pair.hip) ----------------------------------------------------------------------
+// Whether this cx_sweep call may run pairs: what the handle is (a grid plan; nothing the pair kernel does not do — damping, factors of more
+// than two edges, big variables, halos, stored variable→factor messages, a marginal store in every sweep, per-launch profiling) and, checked
+// on the device when due, what its buffers hold.  CX_SWEEP_PAIRS=0 (read per call: a test runs both forms in one process) turns them off.
+static int32_t pairs_allowed(cx_handle *h, int32_t n_sweeps, bool last_marg_only, bool *yes) {
+    *yes = false;
+    const char *e = std::getenv("CX_SWEEP_PAIRS");
+    if (e && e[0] == '0') return CX_OK;
+    if (n_sweeps < 3 || h->pair_H == 0 || h->cfg.dim != 1 || h->cfg.family != CX_FAMILY_GAUSSIAN || h->cfg.schedule != CX_SCHED_FUSED) return CX_OK;
+    if (h->damping != 0.0 || h->any_linear || h->n_kary > 0 || !h->big_vars.empty() || h->halo_state || !h->recv_slots.empty() || !h->send_slots.empty() ||
+        h->halo_depth > 0 || h->run_excl_lo <= h->run_excl_hi || h->cfg.materialize_messages_to_factor != 0 || h->profiling || h->d_q_gamma) return CX_OK;
+    if (!(last_marg_only || h->cfg.compute_marginals_in_sweep == 0)) return CX_OK;
+    if (h->pair_check_due || (!h->pair_inputs_ok && h->sweeps_done >= h->pair_check_at)) {
+        h->pair_inputs_ok = true;
+        for (int64_t v = 0; v < h->nv && h->pair_inputs_ok; v++)      // (observed since the plan was made: cx_set_messages with point-mass data)
+            if ((h->vinfo[v] & (cx::kClamped | cx::kGhost)) || (h->vinfo[v] & cx::kDegMask) == cx::kBigDeg) h->pair_inputs_ok = false;
+        if (h->pair_inputs_ok) {
+            unsigned flag = 1;
+            CX_HIP(h, hipMemsetAsync(h->d_pair_flag, 0, sizeof(unsigned), h->stream));
+            cx::launch_pair_check(h, h->d_f2v, h->d_f2v_alt, h->d_pair_flag);
+            CX_HIP(h, hipMemcpyAsync(&flag, h->d_pair_flag, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+            CX_HIP(h, hipStreamSynchronize(h->stream));
+            h->pair_inputs_ok = flag == 0;
+        }
+        h->pair_check_due = false;
+        // a graph that is still propagating definedness sweeps plain; it is looked at again 16 sweeps on (one pass over the messages each time)
+        if (!h->pair_inputs_ok) h->pair_check_at = h->sweeps_done + 16;
+    }
+    if (!h->pair_inputs_ok) return CX_OK;
+    if (h->pair_rows == 0) {
+        // rows per segment: every workgroup of the launch resident at once at the kernel's occupancy, no second partial round (CX_PAIR_ROWS: A/B)
+        const char *re = std::getenv("CX_PAIR_ROWS");
+        cx::lattice::Plan pl;
+        pl.H = h->pair_H; pl.W = h->pair_W; pl.block_cols = h->pair_block_cols;
+        h->pair_rows = re && std::atoi(re) >= 1 ? std::atoi(re) : cx::lattice::choose_rows(pl, cx::pair_capacity_blocks(h));
+    }
+    *yes = true;
+    return CX_OK;
+}
+
 // ---- the sweep ----------------------------------------------------------------------------------------------------
 void sweep_main(cx_handle *h, bool skip_ghosts) {
     const bool marg = h->cfg.compute_marginals_in_sweep != 0 && !h->run_skip_marg;      // (run_skip_marg: cx_sweep's loop alone sets it)
@@ -505,7 +545,7 @@ int32_t cx_chain_plan_stats(const cx_handle *h, int64_t *out8) {
 
 int32_t cx_sweep_stats(const cx_handle *h, int64_t *out4) {
     if (!h || !out4) return CX_ERR_INVALID_ARGUMENT;
-    out4[0] = h->partner_run_entries; out4[1] = h->partner_run_fallback; out4[2] = h->sweeps_without_marginals; out4[3] = 0;
+    out4[0] = h->partner_run_entries; out4[1] = h->partner_run_fallback; out4[2] = h->sweeps_without_marginals; out4[3] = h->pair_launches;
     return CX_OK;
 }
 
@@ -581,11 +621,24 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
     }
     // marginals in the last sweep of the call only (cx_host.h: last_sweep_marginals_only) — 32 of the 376 MB a C4 sweep moved
     const bool last_marg_only = last_sweep_marginals_only(h);
+    // two sweeps per launch where the handle allows it (pairs_allowed): floor((n - 1) / 2) pairs, then one or two plain sweeps — the last sweep
+    // of a call is always plain, so what a caller can observe afterwards (marginals, d_f2v_alt as the last sweep's input, ensure_v2f) comes
+    // from the same code as ever.  A pair reads d_f2v and writes d_f2v_alt like one sweep, and counts as two.
+    bool pairs = false;
+    if (!bg) { const int32_t rcp = pairs_allowed(h, n_sweeps, last_marg_only, &pairs); if (rcp != CX_OK) return rcp; }
     // the sweeps of the call: their launches (issue; not when a graph replays them) and the host state they leave (always)
     bool ran = false;
     auto sweeps = [&](bool issue) {
         ran = true;
-        for (int32_t s = 0; s < n_sweeps; s++) {
+        int32_t s0 = 0;
+        for (; pairs && n_sweeps - s0 >= 3; s0 += 2) {
+            cx::launch_sweep_pair(h, h->d_f2v, h->d_f2v_alt);
+            std::swap(h->d_f2v, h->d_f2v_alt);
+            h->v2f_stale = true;
+            h->sweeps_done += 2; h->sweeps_since_exchange += 2; h->pair_launches++;
+            if (last_marg_only) h->sweeps_without_marginals += 2;
+        }
+        for (int32_t s = s0; s < n_sweeps; s++) {
             h->run_slice0 = 0; h->run_nslices = 0;
             h->run_skip_marg = last_marg_only && s + 1 < n_sweeps;
             if (h->run_skip_marg) h->sweeps_without_marginals++;

@@ -29,6 +29,13 @@ enum class Change : int32_t {
 template <class H>
 void changed(H &h, Change c) {
     const bool scalar = h.cfg.dim == 1, mfma = cx::is_mfma_dim(h.cfg.dim);
+    // the paired sweep (cx_sweep_pair.hip) relies on every variable being free, every stored message defined and the unary messages being
+    // the same in both Jacobi buffers: whatever sets messages or data, or changes which variables are observed or stand-ins, makes
+    // the check due again.  Rule parameters are read by the launch itself: they void nothing.
+    switch (c) {
+    case Change::RuleMatrices: case Change::RuleCoefficients: case Change::RuleEdgeSets: case Change::ChainBlock: case Change::kCount: break;
+    default: h.pair_check_due = true; break;
+    }
     switch (c) {
     case Change::StoredToVariable:
         // a stored message into a chain variable is part of its side sum; marginals of variables OFF the chains (observed ones,

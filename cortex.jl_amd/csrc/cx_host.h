@@ -15,6 +15,7 @@
 #include "cx_internal.h"
 #include "cx_derived.h"           // cxh::changed — the one rule for what a caller's change voids
 #include "cx_partner_runs.h"      // cx::pruns::build — partner[slot] - slot as wave-uniform runs (cx_graph_create)
+#include "cx_lattice_plan.h"      // cx::lattice::build — a grid recognised in the slot space: two sweeps per launch (cx_graph_create)
 
 namespace cxh {
 
@@ -34,6 +35,18 @@ inline bool chain_abort_take(H *h) {
     return true;
 }
 inline bool chain_abort_take(std::nullptr_t) { return false; }
+// The paired sweep (cx_sweep_pair.hip) raises its word when a launch met an undefined variable→factor message, which a pair cannot treat
+// as plain sweeps do (the slot keeps its older value).  Found the same way; the handle sweeps plainly from then on.
+constexpr const char *kPairAbortMessage = "a paired sweep launch met an undefined variable→factor message (inf - inf in a diverging model): the messages of this handle "
+                                          "are not those of plain sweeps — create the handle again and sweep with CX_SWEEP_PAIRS=0";
+template <class H>
+inline bool pair_abort_take(H *h) {
+    if (!h || !h->pair_abort.host || !*h->pair_abort.host) return false;
+    *const_cast<volatile unsigned *>(h->pair_abort.host) = 0;
+    const_cast<cx_handle *>(static_cast<const cx_handle *>(h))->pair_H = 0;
+    return true;
+}
+inline bool pair_abort_take(std::nullptr_t) { return false; }
 inline int32_t fail(cx_handle *h, int32_t code, const std::string &msg) {
     if (h) h->err = msg; else g_create_error = msg;
     return code;
@@ -47,6 +60,8 @@ inline int32_t fail(cx_handle *h, int32_t code, const std::string &msg) {
                              std::string(#call) + ": " + hipGetErrorString(e_));                 \
         if (cxh::chain_abort_take(h))                                                            \
             return cxh::fail(h, CX_ERR_DEVICE, cxh::kChainAbortMessage);                         \
+        if (cxh::pair_abort_take(h))                                                             \
+            return cxh::fail(h, CX_ERR_DEVICE, cxh::kPairAbortMessage);                          \
     } while (0)
 
 #define CX_REQUIRE(h, cond, code, msg) \

@@ -6,6 +6,7 @@
 //   cxh_ref_*      CX_SCHED_REFERENCE: the default resolver's wiring, the shadow of the readiness state, the recorded and levelled calls (cx_refsched.h)
 //   cxh_derived_apply  the one rule for what a caller's change voids (cx_derived.h) over a plain struct with cx_handle's flags
 //   cxh_flat_partner_runs  the partner-run table of the packed fused sweep (cx_partner_runs.h)
+//   cxh_flat_lattice  the grid plan of the paired sweep (cx_lattice_plan.h)
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
 //                  plain struct with cx_handle's host fields
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include "cx_chains.h"
 #include "cx_derived.h"
 #include "cx_halo_plan.h"
+#include "cx_lattice_plan.h"
 #include "cx_partner_runs.h"
 #include "cx_tree_plan.h"
 #include "cx_refsched.h"
@@ -89,6 +91,7 @@ struct DerivedFlags {                    // the flags and epochs of cx_handle th
     int observed_passes_due;
     bool pot64_fresh, v2f_stale, chain_msgs_stale, mvc_marg_pending;
     uint64_t vinfo_epoch, param_epoch;
+    bool pair_check_due = false;
 };
 
 // flags in the order of DerivedFlags' members (16 values); returns 0, or -1 for a change that does not exist
@@ -347,6 +350,32 @@ int64_t cxh_flat_partner_runs(const void *p, int32_t *out, int64_t *fallback) {
     if (fallback) *fallback = fb;
     if (out && !e.empty()) std::memcpy(out, e.data(), e.size() * sizeof(cx::pruns::Entry));
     return (int64_t)e.size();
+}
+
+// the grid plan of the flattened graph (cx_lattice_plan.h).  Returns 1 with a plan, 0 without (reason: why).  With a plan: hw4 = {H, W, strips,
+// workgroup columns}; dest (may be NULL) = [nv][4] the computed destination slot of every variable's message left, right, up, down (-1: no
+// such neighbour) and src = [nv][4] the slot it is sent from; count (may be NULL) = [nv] how many (strip, segment) waves store for the
+// variable at `rows` rows per segment; rows_for_capacity (may be NULL): in *rows_for_capacity the workgroups the device holds, out the rows chosen
+int32_t cxh_flat_lattice(const void *p, int32_t rows, int64_t *hw4, int32_t *dest, int32_t *src, int32_t *count, int64_t *rows_for_capacity, char *reason, int32_t reasonlen) {
+    const HostGraph *g = (const HostGraph *)p;
+    const cx::lattice::Plan pl = cx::lattice::build(g->partner, g->slice_off, g->vinfo, g->nv, g->fo.q.empty() ? nullptr : g->fo.q.data());
+    if (reason && reasonlen > 0) std::snprintf(reason, (size_t)reasonlen, "%s", pl.reason.c_str());
+    if (!pl.ok) return 0;
+    if (hw4) { hw4[0] = pl.H; hw4[1] = pl.W; hw4[2] = pl.strips; hw4[3] = pl.block_cols; }
+    for (int r = 0; r < pl.H && dest && src; r++)
+        for (int c = 0; c < pl.W; c++)
+            for (int d = 0; d < 4; d++) {
+                const size_t i = ((size_t)r * pl.W + c) * 4 + d;
+                dest[i] = cx::lattice::dest_slot(pl, g->slice_off.data(), r, c, d);
+                src[i] = dest[i] < 0 ? -1 : cx::lattice::slot_base(g->slice_off.data(), r * pl.W + c) + cx::lattice::source_rank(pl, r, c, d) * cx::kBlock;
+            }
+    if (count && rows >= 1) {
+        std::vector<int32_t> n;
+        cx::lattice::cover(pl, rows, n);
+        std::memcpy(count, n.data(), n.size() * 4);
+    }
+    if (rows_for_capacity) *rows_for_capacity = cx::lattice::choose_rows(pl, *rows_for_capacity);
+    return 1;
 }
 
 // array `which` of the graph: returns its length, copies it as int64 (or as doubles for the floating-point ones) when out != NULL

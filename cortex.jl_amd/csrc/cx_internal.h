@@ -81,6 +81,32 @@ private:
 struct StreamDestroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
 using OwnedStream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDestroy>;
 
+// One word of mapped host memory that a kernel raises with an ordinary store and the host reads without a copy (the paired sweep's
+// abort word): move-only, freed by reset() and by the destructor.
+struct HostWord {
+    volatile unsigned *host = nullptr;
+    unsigned *dev = nullptr;
+    HostWord() = default;
+    HostWord(HostWord &&o) noexcept : host(o.host), dev(o.dev) { o.host = nullptr; o.dev = nullptr; }
+    HostWord &operator=(HostWord &&o) noexcept {
+        if (this != &o) { reset(); host = o.host; dev = o.dev; o.host = nullptr; o.dev = nullptr; }
+        return *this;
+    }
+    ~HostWord() { reset(); }
+    void reset() { if (host) (void)hipHostFree((void *)host); host = nullptr; dev = nullptr; }
+    bool alloc() {
+        reset();
+        void *p = nullptr, *d = nullptr;
+        if (hipHostMalloc(&p, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            if (p) (void)hipHostFree(p);
+            return false;
+        }
+        host = (volatile unsigned *)p; dev = (unsigned *)d; *host = 0;
+        return true;
+    }
+};
+
 // what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample, predict, reference order): the deleter is defined there
 template <class T> struct Deleter { void operator()(T *p) const; };
 struct RefSched;      // cx_api_ref.hip
@@ -122,6 +148,16 @@ struct DevState {
     DevBuf<int16_t> d_partner16;    // partner[s] - s where every difference fits (kNoPartner16: none); null otherwise (cx_kernels.hip: PACK)
     DevBuf<int32_t> d_partner_runs; // with d_partner16: {d0, d1, split, 0} per (256-slot row, wave) — cx_partner_runs.h; read by the packed k_sweep
     DevBuf<char> d_stage;           // staging for set/get/batch, in bytes (cxh::ensure_stage)
+    // two sweeps per launch on a recognised grid (cx_lattice_plan.h, cx_sweep_pair.hip): the plan's shape (pair_H == 0: no plan), the rows
+    // per segment (0: not chosen yet), the word a launch raises when it meets an undefined message, the flag of the definedness check
+    int32_t pair_H = 0, pair_W = 0, pair_block_cols = 0, pair_rows = 0;
+    std::string pair_refused;       // why the graph has no plan
+    HostWord pair_abort;
+    DevBuf<unsigned> d_pair_flag;
+    // what pairs rely on — every variable free, every live slot of the input defined, the unary messages the same in both buffers — is
+    // checked when due (raised by: cx_derived.h) and, while it does not hold, again once pair_check_at sweeps are done
+    bool pair_check_due = true, pair_inputs_ok = false;
+    int64_t pair_check_at = 0, pair_launches = 0;
 
     // factors with more than two edges (cx_kary.hip, CX_FACTOR_GAUSS_LINEAR_N): entry = 8 * row + edge position (OUT first, then IN by
     // ascending variable id); coefficient c_e = +1 (OUT) / -a_i (IN); their slots have partner -1 (no pairwise rule touches them)
@@ -424,6 +460,10 @@ void launch_kary_link_params(cx_handle *h, int64_t link_lo, int64_t nlinks, doub
 int32_t kary_mv_upload(cx_handle *h);
 void mv_launch_kary(cx_handle *h, double *f2v_out = nullptr);
 void launch_residual(cx_handle *h, const double2 *cur, const double2 *prev, int64_t n, double *d_out);
+// two sweeps per launch on a grid (cx_sweep_pair.hip)
+int64_t pair_capacity_blocks(const cx_handle *h);
+void launch_sweep_pair(cx_handle *h, const double2 *f2v_in, double2 *f2v_out);
+void launch_pair_check(cx_handle *h, const double2 *f2v, const double2 *alt, unsigned *d_flag);
 void launch_chain_scan(cx_handle *h, double2 *f2v, bool fused_leaves, int marg_form, bool chain_v2f);
 void launch_chain_totals(cx_handle *h, double2 *f2v, bool fused_leaves, int64_t *ntiles_out);
 void launch_chain_scan_range(cx_handle *h, double2 *f2v, int64_t pos_lo, int64_t npos, int64_t link_lo, int64_t nlinks, const int32_t *skip1, bool final);

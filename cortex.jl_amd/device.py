@@ -122,10 +122,12 @@ class DeviceGraph:
         return {"state": int(out[0]), "launches": int(out[1]), "halo_batch_graph_launches": int(out[2])}
 
     def sweep_stats(self):
-        """cx_sweep_stats: the partner-run table's entries and how many of them fall back to the per-lane index; sweeps that stored no marginals"""
+        """cx_sweep_stats: the partner-run table's entries and how many of them fall back to the per-lane index; sweeps that stored no marginals; launches that ran two sweeps at once
+        (cx_sweep_pair.hip)"""
         out = (C.c_int64 * 4)()
         self._check(self.lib.cx_sweep_stats(self.h, out))
-        return {"partner_run_entries": int(out[0]), "partner_run_fallback": int(out[1]), "sweeps_without_marginals": int(out[2])}
+        return {"partner_run_entries": int(out[0]), "partner_run_fallback": int(out[1]), "sweeps_without_marginals": int(out[2]),
+                "paired_launches": int(out[3])}
 
     def edge_index(self, variable_ids, factor_ids):
         v, f = _i64(np.atleast_1d(variable_ids)), _i64(np.atleast_1d(factor_ids))

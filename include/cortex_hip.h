@@ -369,7 +369,8 @@ int32_t cx_ref_plan_stats(const cx_handle *h, int64_t *out8);
 int32_t cx_chain_scan_stats(const cx_handle *h, int64_t *out4);
 /* diagnostics of the fused sweep (additive, still ABI 8; tests): out4[0] entries of the partner-run table (four per 256-slot row; 0: the
  * graph's partners do not fit 16-bit differences, no table), [1] those that fall back to the per-lane index, [2] sweeps of cx_sweep
- * calls so far that stored no marginals (every sweep of a call but the last), [3] 0 */
+ * calls so far that stored no marginals (every sweep of a call but the last), [3] launches so far that ran two sweeps at once (grids:
+ * floor((n - 1) / 2) per cx_sweep(h, n) call; CX_SWEEP_PAIRS=0 in the environment turns them off) */
 int32_t cx_sweep_stats(const cx_handle *h, int64_t *out4);
 /* the XCD-resident cluster (reference-order plans of many dependent stages of 1 - 16 k items — calls on loopy graphs — run as ONE launch
  * of the workgroups of one XCD behind barriers that stay in that XCD's L2): out4 = { 1 ready / 0 not prepared / -1 off
