@@ -43,7 +43,11 @@ template <class H>
 inline bool pair_abort_take(H *h) {
     if (!h || !h->pair_abort.host || !*h->pair_abort.host) return false;
     *const_cast<volatile unsigned *>(h->pair_abort.host) = 0;
-    const_cast<cx_handle *>(static_cast<const cx_handle *>(h))->pair_H = 0;
+    // the launches of one call are queued together: one behind the launch that raised the word meets the same messages and raises it
+    // again, possibly after the host has taken the first.  The handle has no plan by then (only a plan allocates the word): told once
+    cx_handle *hh = const_cast<cx_handle *>(static_cast<const cx_handle *>(h));
+    if (hh->pair_H == 0) return false;
+    hh->pair_H = 0;
     return true;
 }
 inline bool pair_abort_take(std::nullptr_t) { return false; }

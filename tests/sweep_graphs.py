@@ -1,5 +1,7 @@
-"""Graphs and read-backs shared by tests/test_gpu_sweep_last_marginals.py, test_gpu_partner_runs.py and test_partner_runs_host.py:
-plain cx.synth.Model values, seeded."""
+"""Graphs and read-backs shared by tests/test_gpu_sweep_last_marginals.py, test_gpu_partner_runs.py, test_partner_runs_host.py,
+test_gpu_sweep_pairs.py, test_gpu_grid_between_calls.py and test_lattice_plan.py: plain cx.synth.Model values, seeded."""
+import dataclasses
+
 import numpy as np
 
 import cortex.jl_amd as cx
@@ -80,3 +82,99 @@ def read_back(dev, model):
     """every factor→variable message (scalars: natural form, as stored) and every marginal, float64"""
     form = L.FORM_NATURAL if model.dim == 1 else L.FORM_MOMENT
     return (dev.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE, form), dev.get_marginals(model.x_ids))
+
+
+class GridIds:
+    """the ids of cx.synth.gaussian_grid(H, W) by grid position: variable (r, c), its unary factor, the pairwise factor towards each neighbour"""
+
+    def __init__(self, H, W):
+        self.H, self.W, self.V = H, W, H * W
+
+    def var(self, r, c):
+        return 1 + r * self.W + c
+
+    def unary(self, r, c):
+        return self.var(r, c) + self.V
+
+    def factor(self, r, c, direction):
+        """the factor between (r, c) and its neighbour to the "left", "right", "up" or "down" """
+        H, W, V = self.H, self.W, self.V
+        if direction in ("left", "right"):
+            cc = c - 1 if direction == "left" else c
+            assert 0 <= cc < W - 1
+            return 2 * V + 1 + r * (W - 1) + cc
+        rr = r - 1 if direction == "up" else r
+        assert 0 <= rr < H - 1
+        return 2 * V + H * (W - 1) + 1 + rr * W + c
+
+    def pairwise_edges(self, r, c):
+        """(variable ids, factor ids) of the pairwise edges of (r, c), in the order left, right, up, down with absent directions skipped"""
+        have = [d for d, ok in (("left", c > 0), ("right", c < self.W - 1), ("up", r > 0), ("down", r < self.H - 1)) if ok]
+        return (np.full(len(have), self.var(r, c), dtype=np.int64), np.array([self.factor(r, c, d) for d in have], dtype=np.int64))
+
+
+# ---- a grid whose paired sweep meets an undefined variable→factor message in the middle of a call -------------------------------------
+# factor_rule<kRuleAdditive> divides by 1 + q w.  The factor right of (1, 1) has q = 0.5 exactly; (1, 1) has the unary message (0, -2) in natural
+# form and zeros from its four neighbours, so in sweep 1 its message into that factor is (0, -2), 1 + q w = 0 exactly and the factor sends
+# (nan, -inf) to (1, 2).  In sweep 2 the messages out of (1, 2) have precision -inf and the rule turns them into nan; sweep 3 reads those.
+UNDEFINED_MIDCALL_SHAPE = (4, 5)
+UNDEFINED_MIDCALL_SENDER = (1, 1)
+
+
+def undefined_midcall_grid():
+    """(model, set_vars, set_facs, natural payload [n, 2]): the 4 x 5 grid with the variance of one factor set to 0.5, and the messages to
+    store (CX_TO_VARIABLE, CX_FORM_NATURAL) after the usual load with a seed"""
+    H, W = UNDEFINED_MIDCALL_SHAPE
+    r, c = UNDEFINED_MIDCALL_SENDER
+    ids = GridIds(H, W)
+    m = cx.synth.gaussian_grid(H, W, seed=7)
+    fv = m.factor_var.copy()
+    fv[m.factor_ids == ids.factor(r, c, "right")] = 0.5
+    model = dataclasses.replace(m, factor_var=fv)
+    pv, pf = ids.pairwise_edges(r, c)
+    set_vars = np.concatenate([[ids.var(r, c)], pv]).astype(np.int64)
+    set_facs = np.concatenate([[ids.unary(r, c)], pf]).astype(np.int64)
+    payload = np.zeros((len(set_vars), 2))
+    payload[0] = (0.0, -2.0)
+    return model, set_vars, set_facs, payload
+
+
+def natural_form_sweeps(model, seed_variance, set_vars, set_facs, payload, n):
+    """n plain Jacobi sweeps of a model of unary and two-variable additive factors in float64 numpy, natural form (xi, w), as the device
+    defines them: a variable→factor message is the sum of the variable's OTHER messages in ascending factor id; the factor sends
+    (xi, w) / (1 + q w); the result of an undefined (nan precision) variable→factor message is not stored.  Returns per sweep
+    (messages with precision -inf, messages with nan precision, undefined variable→factor messages read), counted after / in the sweep."""
+    order = np.lexsort((model.edge_fac, model.edge_var))
+    ev, ef = model.edge_var[order], model.edge_fac[order]
+    q = dict(zip(model.factor_ids.tolist(), np.asarray(model.factor_var, dtype=np.float64).tolist()))
+    edge = {(int(v), int(f)): i for i, (v, f) in enumerate(zip(ev, ef))}
+    by_fac, by_var = {}, {}
+    for i, (v, f) in enumerate(zip(ev.tolist(), ef.tolist())):
+        by_fac.setdefault(f, []).append(i)
+        by_var.setdefault(v, []).append(i)
+    msg = np.full((len(ev), 2), np.nan)
+    for v, f, mean, var in zip(model.prior_var, model.prior_fac, model.prior_mean, model.prior_variance):
+        msg[edge[(int(v), int(f))]] = (mean / var, 1.0 / var)
+    pairwise = np.array([len(by_fac[f]) == 2 for f in ef.tolist()])
+    msg[pairwise & np.isnan(msg[:, 1])] = (0.0, 1.0 / seed_variance)
+    for v, f, p in zip(set_vars, set_facs, payload):
+        msg[edge[(int(v), int(f))]] = p
+    out = []
+    with np.errstate(all="ignore"):
+        for _ in range(n):
+            new, undefined_read = msg.copy(), 0
+            for f, es in by_fac.items():
+                if len(es) != 2:
+                    continue
+                for src, dst in (es, es[::-1]):
+                    acc = np.zeros(2)
+                    for k in by_var[int(ev[src])]:
+                        if k != src:
+                            acc = acc + msg[k]
+                    if np.isnan(acc[1]):
+                        undefined_read += 1
+                        continue
+                    new[dst] = acc * (1.0 / (1.0 + q[f] * acc[1]))
+            msg = new
+            out.append((int(np.sum(msg[:, 1] == -np.inf)), int(np.sum(np.isnan(msg[:, 1]))), undefined_read))
+    return out

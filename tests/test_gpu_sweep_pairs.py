@@ -10,7 +10,11 @@ from tests.sweep_graphs import grid_with_star, random_sparse, read_back
 
 pytestmark = pytest.mark.gpu
 
-ACCEPTED = [(2, 2), (3, 3), (5, 61), (5, 62), (5, 63), (5, 64), (7, 124), (9, 125), (20, 37), (24, 1415)]
+ACCEPTED = [(2, 2), (3, 3), (5, 61), (5, 62), (5, 63), (5, 64), (7, 124), (9, 125), (20, 37), (24, 1415),
+            (40, 2), (300, 3), (2, 300), (130, 70), (4, 248), (6, 249)]
+# 40 x 2: no lane with a left AND a right neighbour, below more than two rows; 300 x 3: many segments in one column of workgroups, three of
+# its four waves returning at once, rows in the slices 0 .. 3; 2 x 300, 130 x 70, 4 x 248: two columns of workgroups (4 x 248: four full
+# strips, exactly one); 6 x 249: the last column of workgroups holds one strip of one column
 NS = (3, 4, 5, 8)
 
 
@@ -59,10 +63,13 @@ def test_pairs_equal_single_sweeps_and_the_switch(hip_lib, monkeypatch, shape):
             d.close()
 
 
-@pytest.mark.parametrize("rows", [1, 3, 7, 64])
-@pytest.mark.parametrize("shape", [(20, 37), (9, 125)], ids=lambda s: "%dx%d" % s)
+ROWS_CASES = [(s, r) for s in ((20, 37), (9, 125)) for r in (1, 3, 7, 64)] + [(s, r) for s in ((300, 3), (6, 249)) for r in (1, 7)]
+
+
+@pytest.mark.parametrize("shape,rows", ROWS_CASES, ids=lambda x: "%dx%d" % x if isinstance(x, tuple) else str(x))
 def test_any_rows_per_segment(hip_lib, monkeypatch, shape, rows):
-    """CX_PAIR_ROWS: segments of one row (every row a halo row of two waves), odd lengths with a short last segment, one segment"""
+    """CX_PAIR_ROWS: segments of one row (every row a halo row of two waves), odd lengths with a short last segment, one segment;
+    300 x 3: 300 and 43 workgroups in the one column, 6 x 249: the one-column strip alone in its workgroups"""
     model = cx.synth.gaussian_grid(*shape, seed=11)
     monkeypatch.setenv("CX_PAIR_ROWS", str(rows))
     a, b = _device(model), _device(model)

@@ -8,9 +8,10 @@ import pytest
 
 import cortex.jl_amd as cx
 from tests.hostlogic import FlatGraph, lib
-from tests.sweep_graphs import grid_with_star
+from tests.sweep_graphs import grid_with_star, natural_form_sweeps, undefined_midcall_grid
 
-ACCEPTED = [(2, 2), (3, 3), (5, 61), (5, 62), (5, 63), (5, 64), (7, 124), (9, 125), (20, 37), (24, 1415)]
+ACCEPTED = [(2, 2), (3, 3), (5, 61), (5, 62), (5, 63), (5, 64), (7, 124), (9, 125), (20, 37), (24, 1415),
+            (40, 2), (300, 3), (2, 300), (130, 70), (4, 248), (6, 249)]
 
 
 def flat(model):
@@ -77,6 +78,10 @@ def test_rows_per_segment_fill_the_device_once():
     for capacity, want in ((1024, 4), (36, 4), (12, 12), (6, 24), (1, 24)):      # 170 / 6 / 2 / 1 / 1 segments fit: rows clamped to 4 .. 64
         *_, rows = plan(g, capacity=capacity)
         assert rows == want, (capacity, rows)
+    g = flat(cx.synth.gaussian_grid(300, 3, seed=7))        # one strip, one column of workgroups: every workgroup a segment
+    for capacity, want in ((1024, 4), (75, 4), (50, 6), (10, 30), (4, 64), (1, 64)):     # 300 rows over 1024 / 75 / 50 / 10 segments; above 64 rows: more than one round
+        *_, rows = plan(g, capacity=capacity)
+        assert rows == want, (capacity, rows)
 
 
 def _permuted_ranks():
@@ -118,3 +123,16 @@ def test_refusals_name_their_reason():
     refused(flat(_permuted_ranks()), "not in the order")
     refused(flat(grid_with_star()), "big degree")
     refused(flat(cx.synth.gaussian_grid(40, 12, seed=7, row0=8, row1=20)), "not a grid")      # a row block with its stand-in rows of degree 1
+
+
+def test_the_grid_that_goes_undefined_in_the_middle_of_a_call():
+    """tests/sweep_graphs.py: undefined_midcall_grid, which tests/test_gpu_grid_between_calls.py sweeps in pairs.  The plan takes it (a factor
+    variance of 0.5 is a variance like any other) and every input is defined; in float64 numpy, natural form, plain sweeps: sweep 1 stores
+    one message of precision -inf (1 + q w = 0), sweep 2 three undefined ones, sweep 3 reads eight undefined variable→factor messages —
+    the second launch of a paired call — and, keeping the older values, leaves every message defined again"""
+    model, sv, sf, payload = undefined_midcall_grid()
+    ok, reason, hw, *_ = plan(flat(model))
+    assert ok, reason
+    assert (hw["H"], hw["W"]) == (4, 5)
+    assert np.all(np.isfinite(payload)) and payload[0, 1] == -2.0
+    assert natural_form_sweeps(model, 1e6, sv, sf, payload, 5) == [(1, 0, 0), (0, 3, 0), (0, 0, 8), (0, 0, 0), (0, 0, 0)]
