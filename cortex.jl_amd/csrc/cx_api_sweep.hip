@@ -4,6 +4,7 @@
 #include "cx_host.h"
 #include "cx_chains.h"
 #include "cx_tree_plan.h"
+#include "cx_lattice_deep.h"
 
 using namespace cxh;
 
@@ -354,7 +355,17 @@ int32_t tree_sweep(cx_handle *h) {
     return CX_OK;
 }
 
-// ---- two sweeps per launch (cx_sweep_pair.hip) ----------------------------------------------------------------------
+// ---- two sweeps per launch (cx_sweep_pair.hip), three or four in long calls (cx_sweep_deep.hip) ------------------------------------------
+// A call of at least kDeepMinSweeps sweeps runs its sweeps before the last at depth kDeepDefault (CX_SWEEP_DEPTH=2|3|4, read per call: a
+// test runs every depth in one process).  Shorter calls decompose into pairs exactly as they did before there were deeper launches.
+constexpr int kDeepMax = 4, kDeepDefault = 4, kDeepMinSweeps = 16;
+static int deep_depth_of_call(int32_t n_sweeps) {
+    if (n_sweeps < kDeepMinSweeps) return 2;
+    const char *e = std::getenv("CX_SWEEP_DEPTH");
+    const int d = e ? std::atoi(e) : kDeepDefault;
+    return d >= 2 && d <= kDeepMax ? d : kDeepDefault;
+}
+
 // Whether this cx_sweep call may run pairs: what the handle is (a grid plan; nothing the pair kernel does not do — damping, factors of more
 // than two edges, big variables, halos, stored variable→factor messages, a marginal store in every sweep, per-launch profiling) and, checked
 // on the device when due, what its buffers hold.  CX_SWEEP_PAIRS=0 (read per call: a test runs both forms in one process) turns them off.
@@ -389,6 +400,11 @@ static int32_t pairs_allowed(cx_handle *h, int32_t n_sweeps, bool last_marg_only
         cx::lattice::Plan pl;
         pl.H = h->pair_H; pl.W = h->pair_W; pl.block_cols = h->pair_block_cols;
         h->pair_rows = re && std::atoi(re) >= 1 ? std::atoi(re) : cx::lattice::choose_rows(pl, cx::pair_capacity_blocks(h));
+        // ... and of the deep launches, here and not in the first long call: the occupancy queries stay out of a caller's timed region
+        // (CX_DEEP_ROWS: tests, A/B)
+        const char *de = std::getenv("CX_DEEP_ROWS");
+        for (int d = 3; d <= kDeepMax; d++)
+            h->deep_rows[d] = de && std::atoi(de) >= 1 ? std::atoi(de) : cx::lattice::deep::choose_rows(pl, cx::deep_capacity_blocks(h, d), d);
     }
     *yes = true;
     return CX_OK;
@@ -549,6 +565,14 @@ int32_t cx_sweep_stats(const cx_handle *h, int64_t *out4) {
     return CX_OK;
 }
 
+int32_t cx_sweep_deep_stats(const cx_handle *h, int64_t *out4) {
+    if (!h || !out4) return CX_ERR_INVALID_ARGUMENT;
+    const int d = h->pair_H ? h->deep_depth : 0;
+    out4[0] = h->deep_launches[3]; out4[1] = h->deep_launches[4]; out4[2] = d;
+    out4[3] = d == 0 ? 0 : d == 2 ? h->pair_rows : h->deep_rows[d];
+    return CX_OK;
+}
+
 int32_t cx_chain_scan_stats(const cx_handle *h, int64_t *out4) {
     if (!h || !out4) return CX_ERR_INVALID_ARGUMENT;
     out4[0] = h->chain_onepass_state; out4[1] = h->chain_onepass_launches; out4[2] = h->batch_graph_launches; out4[3] = 0;
@@ -621,22 +645,28 @@ int32_t cx_sweep(cx_handle *h, int32_t n_sweeps) {
     }
     // marginals in the last sweep of the call only (cx_host.h: last_sweep_marginals_only) — 32 of the 376 MB a C4 sweep moved
     const bool last_marg_only = last_sweep_marginals_only(h);
-    // two sweeps per launch where the handle allows it (pairs_allowed): floor((n - 1) / 2) pairs, then one or two plain sweeps — the last sweep
-    // of a call is always plain, so what a caller can observe afterwards (marginals, d_f2v_alt as the last sweep's input, ensure_v2f) comes
-    // from the same code as ever.  A pair reads d_f2v and writes d_f2v_alt like one sweep, and counts as two.
+    // several sweeps per launch where the handle allows it (pairs_allowed).  The last sweep of a call is always plain, so what a caller can
+    // observe afterwards (marginals, d_f2v_alt as the last sweep's input, ensure_v2f) comes from the same code as ever.  The n - 1 sweeps
+    // before it go greedily: launches of the call's depth D (2 below 16 sweeps: floor((n - 1) / 2) pairs) while D sweeps remain, then one
+    // launch of the remainder's depth, a plain sweep for a remainder of 1.  A launch of depth d reads d_f2v and writes d_f2v_alt like one
+    // sweep, and counts as d.
     bool pairs = false;
     if (!bg) { const int32_t rcp = pairs_allowed(h, n_sweeps, last_marg_only, &pairs); if (rcp != CX_OK) return rcp; }
+    const int depth = deep_depth_of_call(n_sweeps);
+    if (pairs) h->deep_depth = depth;
     // the sweeps of the call: their launches (issue; not when a graph replays them) and the host state they leave (always)
     bool ran = false;
     auto sweeps = [&](bool issue) {
         ran = true;
         int32_t s0 = 0;
-        for (; pairs && n_sweeps - s0 >= 3; s0 += 2) {
-            cx::launch_sweep_pair(h, h->d_f2v, h->d_f2v_alt);
+        while (pairs && n_sweeps - s0 >= 3) {
+            const int d = std::min<int32_t>(depth, n_sweeps - 1 - s0);
+            if (d == 2) { cx::launch_sweep_pair(h, h->d_f2v, h->d_f2v_alt); h->pair_launches++; }
+            else { cx::launch_sweep_deep(h, d, h->d_f2v, h->d_f2v_alt); h->deep_launches[d]++; }
             std::swap(h->d_f2v, h->d_f2v_alt);
             h->v2f_stale = true;
-            h->sweeps_done += 2; h->sweeps_since_exchange += 2; h->pair_launches++;
-            if (last_marg_only) h->sweeps_without_marginals += 2;
+            h->sweeps_done += d; h->sweeps_since_exchange += d; s0 += d;
+            if (last_marg_only) h->sweeps_without_marginals += d;
         }
         for (int32_t s = s0; s < n_sweeps; s++) {
             h->run_slice0 = 0; h->run_nslices = 0;

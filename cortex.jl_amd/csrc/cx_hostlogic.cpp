@@ -7,6 +7,7 @@
 //   cxh_derived_apply  the one rule for what a caller's change voids (cx_derived.h) over a plain struct with cx_handle's flags
 //   cxh_flat_partner_runs  the partner-run table of the packed fused sweep (cx_partner_runs.h)
 //   cxh_flat_lattice  the grid plan of the paired sweep (cx_lattice_plan.h)
+//   cxh_flat_lattice_deep  the strips, levels and rows of the deep sweep on that plan (cx_lattice_deep.h)
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
 //                  plain struct with cx_handle's host fields
 #include <cstdio>
@@ -18,6 +19,7 @@
 #include "cx_derived.h"
 #include "cx_halo_plan.h"
 #include "cx_lattice_plan.h"
+#include "cx_lattice_deep.h"
 #include "cx_partner_runs.h"
 #include "cx_tree_plan.h"
 #include "cx_refsched.h"
@@ -376,6 +378,48 @@ int32_t cxh_flat_lattice(const void *p, int32_t rows, int64_t *hw4, int32_t *des
     }
     if (rows_for_capacity) *rows_for_capacity = cx::lattice::choose_rows(pl, *rows_for_capacity);
     return 1;
+}
+
+// the deep sweep's geometry on the grid plan of the flattened graph (cx_lattice_deep.h) at depth K and `rows` rows per segment.  Returns the
+// number of (strip, segment) waves, 0 without a plan, -1 for a depth outside 2 .. 4 or rows < 1.  geom6 (may be NULL) = {owned columns per
+// wave, strips, workgroup columns, segments, the floor of choose_rows, kMaxRows}; count (may be NULL) = [nv] how many waves store for the
+// variable; rows_for_capacity as in cxh_flat_lattice, at depth K.  wave3 / level / owned (all three or none): per wave {strip, r0, r1} and, for
+// the window of rows r0 - K - 1 .. r0 + rows + K (rows + 2 K + 2 of them) by lanes -1 .. 64 (66), the highest level at which the cell is valid
+// (0: at none; the levels nest) and whether the wave stores it — by the predicates the kernel uses
+int32_t cxh_flat_lattice_deep(const void *p, int32_t K, int32_t rows, int64_t *geom6, int32_t *count, int64_t *rows_for_capacity, int32_t *wave3,
+                              int8_t *level, int8_t *owned) {
+    namespace dp = cx::lattice::deep;
+    const HostGraph *g = (const HostGraph *)p;
+    if (K < dp::kMinDepth || K > dp::kMaxDepth || rows < 1) return -1;
+    const cx::lattice::Plan pl = cx::lattice::build(g->partner, g->slice_off, g->vinfo, g->nv, g->fo.q.empty() ? nullptr : g->fo.q.data());
+    if (!pl.ok) return 0;
+    const int nseg = cx::lattice::n_segments(pl, rows), nstrips = dp::strips(pl.W, K);
+    if (geom6) { geom6[0] = dp::strip_cols(K); geom6[1] = nstrips; geom6[2] = dp::block_cols(pl.W, K); geom6[3] = nseg; geom6[4] = dp::min_rows(K); geom6[5] = cx::lattice::kMaxRows; }
+    if (count) {
+        std::vector<int32_t> n;
+        dp::cover(pl, rows, K, n);
+        std::memcpy(count, n.data(), n.size() * 4);
+    }
+    if (rows_for_capacity) *rows_for_capacity = dp::choose_rows(pl, *rows_for_capacity, K);
+    if (wave3 && level && owned) {
+        const int win = rows + 2 * K + 2;
+        size_t w = 0;
+        for (int strip = 0; strip < nstrips; strip++)
+            for (int seg = 0; seg < nseg; seg++, w++) {
+                const int r0 = seg * rows, r1 = std::min<int>(r0 + rows, pl.H);
+                wave3[3 * w] = strip; wave3[3 * w + 1] = r0; wave3[3 * w + 2] = r1;
+                for (int ri = 0; ri < win; ri++)
+                    for (int li = 0; li < 66; li++) {
+                        const int r = r0 - K - 1 + ri, lane = li - 1, c = dp::lane_col(strip, lane, K);
+                        int8_t lv = 0;
+                        for (int j = 1; j <= K; j++)
+                            if (dp::row_valid_at_level(r, r0, r1, pl.H, K, j) && dp::lane_valid_at_level(lane, c, pl.W, j)) lv = (int8_t)j;
+                        level[(w * win + ri) * 66 + li] = lv;
+                        owned[(w * win + ri) * 66 + li] = (int8_t)(r >= r0 && r < r1 && dp::lane_owned(lane, c, pl.W, K));
+                    }
+            }
+    }
+    return nstrips * nseg;
 }
 
 // array `which` of the graph: returns its length, copies it as int64 (or as doubles for the floating-point ones) when out != NULL

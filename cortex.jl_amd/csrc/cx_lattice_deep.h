@@ -1,0 +1,69 @@
+// cx_lattice_deep.h — the strips of the deep sweep (cx_sweep_deep.hip: K sweeps per launch on the grid plan of cx_lattice_plan.h), with the depth
+// K as a parameter.  Pure C++, shared by the host, the kernel and the CPU tests (cx_hostlogic.cpp: cxh_flat_lattice_deep) like the plan itself.
+//
+// Decomposition.  A wave owns strip_cols(K) = 64 - 2 (K - 1) consecutive columns and has K - 1 halo lanes on each side; a segment of R rows
+// has K - 1 halo rows at each end: the wave loads rows r0 - (K - 1) .. r1 + (K - 1) - 1 at its 64 lanes.  Level 1 is the sweep that reads
+// what was loaded, level j the j-th sweep of the launch; level K is stored, at the owned cells only.
+//
+// Validity.  A cell's level-j value depends on the loaded cells within distance j - 1 of it.  Here a cell is VALID at level j when it lies in
+// the grid and within K - j lanes and K - j rows of the owned rectangle: then everything within j - 1 of it lies within K - 1 of the owned
+// rectangle, which is what the wave loaded, or outside the grid, where a sweep reads nothing.  A cell that is not valid at a level holds
+// garbage there; it feeds only cells that are not valid one level up (a valid cell's in-grid neighbours are valid one level down), and it is
+// neither tested for an undefined message nor stored.  (Near the grid's edge a few more cells would qualify by the clipped distance; they
+// are owned by another wave, which tests them, and leaving them out keeps the rule one comparison per side.)
+#pragma once
+
+#include "cx_lattice_plan.h"
+
+namespace cx {
+namespace lattice {
+namespace deep {
+
+constexpr int kMinDepth = 2, kMaxDepth = 4;
+
+CX_LAT_HD int strip_cols(int K) { return 64 - 2 * (K - 1); }
+CX_LAT_HD int lane_col(int strip, int lane, int K) { return strip * strip_cols(K) - (K - 1) + lane; }                             // (< 0 and >= W: outside)
+CX_LAT_HD bool lane_owned(int lane, int col, int W, int K) { return lane >= K - 1 && lane <= 64 - K && col < W; }                  // (lane >= K - 1: col >= 0)
+CX_LAT_HD bool lane_valid_at_level(int lane, int col, int W, int j) { return lane >= j - 1 && lane <= 64 - j && col >= 0 && col < W; }
+// rows of segment [r0, r1) valid at level j: [row_lo, row_hi)
+CX_LAT_HD int row_lo(int r0, int K, int j) { return r0 - (K - j) > 0 ? r0 - (K - j) : 0; }
+CX_LAT_HD int row_hi(int r1, int H, int K, int j) { return r1 + (K - j) < H ? r1 + (K - j) : H; }
+CX_LAT_HD bool row_valid_at_level(int r, int r0, int r1, int H, int K, int j) { return r >= row_lo(r0, K, j) && r < row_hi(r1, H, K, j); }
+// what the wave loads: rows [load_lo, load_hi) of the grid at the lanes whose column is inside it
+CX_LAT_HD int load_lo(int r0, int K) { return row_lo(r0, K, 1); }
+CX_LAT_HD int load_hi(int r1, int H, int K) { return row_hi(r1, H, K, 1); }
+
+inline int32_t strips(int W, int K) { return (W + strip_cols(K) - 1) / strip_cols(K); }
+inline int32_t block_cols(int W, int K) { return (strips(W, K) + kStripsPerBlock - 1) / kStripsPerBlock; }
+// fewer than 4 (K - 1) rows per segment read (1 + 2 (K - 1) / R) > 1.5 times the messages: a grid too tall for one resident round runs more
+// than one round instead (cx_lattice_plan.h: kMinRows is this floor at K = 2)
+inline int min_rows(int K) { return 4 * (K - 1); }
+
+// rows per segment such that every workgroup of the launch is resident at once (capacity_blocks: workgroups the chip holds of the depth-K kernel)
+inline int choose_rows(const Plan &p, int64_t capacity_blocks, int K) {
+    const int64_t seg_max = std::max<int64_t>(1, capacity_blocks / std::max<int32_t>(1, block_cols(p.W, K)));
+    const int64_t R = (p.H + seg_max - 1) / seg_max;
+    return (int)std::min<int64_t>(kMaxRows, std::max<int64_t>(min_rows(K), R));
+}
+
+// how many (strip, segment) waves store for each variable at depth K and R rows per segment, by the kernel's own predicates (the tests want 1)
+inline void cover(const Plan &p, int R, int K, std::vector<int32_t> &count) {
+    count.assign((size_t)p.H * p.W, 0);
+    const int nseg = n_segments(p, R), bcs = block_cols(p.W, K);
+    for (int bc = 0; bc < bcs; bc++)
+        for (int seg = 0; seg < nseg; seg++)
+            for (int w = 0; w < kStripsPerBlock; w++) {
+                const int strip = bc * kStripsPerBlock + w;
+                if (strip * strip_cols(K) >= p.W) continue;
+                const int r0 = seg * R, r1 = std::min(r0 + R, (int)p.H);
+                for (int r = r0; r < r1; r++)
+                    for (int lane = 0; lane < 64; lane++) {
+                        const int c = lane_col(strip, lane, K);
+                        if (lane_owned(lane, c, p.W, K)) count[(size_t)r * p.W + c]++;
+                    }
+            }
+}
+
+}  // namespace deep
+}  // namespace lattice
+}  // namespace cx
