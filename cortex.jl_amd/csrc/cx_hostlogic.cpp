@@ -8,6 +8,7 @@
 //   cxh_flat_partner_runs  the partner-run table of the packed fused sweep (cx_partner_runs.h)
 //   cxh_flat_lattice  the grid plan of the paired sweep (cx_lattice_plan.h)
 //   cxh_flat_lattice_deep  the strips, levels and rows of the deep sweep on that plan (cx_lattice_deep.h)
+//   cxh_lattice_deep_interior  which waves of the deep sweep take the interior instance, beside what the general predicates say of them
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
 //                  plain struct with cx_handle's host fields
 #include <cstdio>
@@ -419,6 +420,36 @@ int32_t cxh_flat_lattice_deep(const void *p, int32_t K, int32_t rows, int64_t *g
                     }
             }
     }
+    return nstrips * nseg;
+}
+
+// the interior instance of the deep sweep on an H x W grid at depth K and R rows per segment (no graph needed: geometry alone).  Per wave, in
+// the order strip-major of cxh_flat_lattice_deep: pred = strip_interior && segment_interior, the kernel's choice; general = what the general
+// path would find, cell by cell: every lane 0 .. 63 (lane_col) holds a column of the grid with a left and a right neighbour, every row loaded
+// and every row of [row_lo, row_hi) at every level 1 .. K lies in the grid with a row above and a row below, and row_lo / row_hi are not
+// clipped by the grid.  Returns the number of waves, -1 for arguments out of range
+int32_t cxh_lattice_deep_interior(int32_t K, int32_t W, int32_t H, int32_t R, int8_t *pred, int8_t *general) {
+    namespace dp = cx::lattice::deep;
+    if (K < dp::kMinDepth || K > dp::kMaxDepth || W < 1 || H < 1 || R < 1) return -1;
+    const int nseg = (H + R - 1) / R, nstrips = dp::strips(W, K);
+    size_t w = 0;
+    for (int strip = 0; strip < nstrips; strip++)
+        for (int seg = 0; seg < nseg; seg++, w++) {
+            const int r0 = seg * R, r1 = std::min<int>(r0 + R, H);
+            pred[w] = (int8_t)(dp::strip_interior(strip, W, K) && dp::segment_interior(r0, r1, H, K));
+            bool all = true;
+            for (int lane = 0; lane < 64; lane++) {
+                const int c = dp::lane_col(strip, lane, K);
+                const bool colv = c >= 0 && c < W;
+                all = all && colv && c > 0 && c < W - 1;
+            }
+            for (int r = r0 - (K - 1); r <= r1 + (K - 1) - 1; r++) all = all && r >= 0 && r < H && r > 0 && r < H - 1;
+            for (int j = 1; j <= K; j++) {
+                all = all && dp::row_lo(r0, K, j) == r0 - (K - j) && dp::row_hi(r1, H, K, j) == r1 + (K - j);
+                for (int m = dp::row_lo(r0, K, j); m < dp::row_hi(r1, H, K, j); m++) all = all && m > 0 && m < H - 1;
+            }
+            general[w] = (int8_t)all;
+        }
     return nstrips * nseg;
 }
 

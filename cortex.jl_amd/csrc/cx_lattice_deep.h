@@ -10,7 +10,9 @@
 // rectangle, which is what the wave loaded, or outside the grid, where a sweep reads nothing.  A cell that is not valid at a level holds
 // garbage there; it feeds only cells that are not valid one level up (a valid cell's in-grid neighbours are valid one level down), and it is
 // neither tested for an undefined message nor stored.  (Near the grid's edge a few more cells would qualify by the clipped distance; they
-// are owned by another wave, which tests them, and leaving them out keeps the rule one comparison per side.)
+// are owned by another wave, which tests them, and leaving them out keeps the rule one comparison per side.)  Lanes 0 and 63 are valid at
+// level 1 only (K >= 2) and never owned: what a level's sideways shift delivers to them — a shuffle the lane's own value, the kernel's
+// whole-wave shift zero — is garbage of this kind, and nothing tested or stored depends on it.
 #pragma once
 
 #include "cx_lattice_plan.h"
@@ -32,6 +34,13 @@ CX_LAT_HD bool row_valid_at_level(int r, int r0, int r1, int H, int K, int j) { 
 // what the wave loads: rows [load_lo, load_hi) of the grid at the lanes whose column is inside it
 CX_LAT_HD int load_lo(int r0, int K) { return row_lo(r0, K, 1); }
 CX_LAT_HD int load_hi(int r1, int H, int K) { return row_hi(r1, H, K, 1); }
+
+// Interior waves (the kernel's second instance: no edge tests).  A strip is interior when every one of its 64 lanes holds a column of the grid
+// that has a left and a right neighbour; a segment is interior when every row it loads, r0 - (K - 1) .. r1 + (K - 1) - 1, which are all the rows
+// it touches at any level, has a row above and a row below.  For such a wave hasL, hasR, hasU, hasD and the column test are true at every lane,
+// row and level, every cell has degree 5, and row_lo / row_hi are never clipped by the grid.
+CX_LAT_HD bool strip_interior(int strip, int W, int K) { return lane_col(strip, 0, K) >= 1 && lane_col(strip, 63, K) <= W - 2; }
+CX_LAT_HD bool segment_interior(int r0, int r1, int H, int K) { return r0 - (K - 1) >= 1 && r1 + (K - 1) - 1 <= H - 2; }
 
 inline int32_t strips(int W, int K) { return (W + strip_cols(K) - 1) / strip_cols(K); }
 inline int32_t block_cols(int W, int K) { return (strips(W, K) + kStripsPerBlock - 1) / kStripsPerBlock; }

@@ -4,11 +4,22 @@
 // A wave owns 64 - 2 (K - 1) columns, with K - 1 halo lanes on each side, and streams down rows r0 - (K - 1) .. r1 + (K - 1) - 1 of its segment.
 // In the iteration of row i, level 1 works on row i as loaded, level j on row i - (j - 1), and level K stores row i - (K - 1) into the OTHER
 // buffer at the partner slots.  Level j of a row takes the unary message, the left / right inputs that level j - 1 of the same row pushed one
-// lane sideways (a wave shuffle; kept for one iteration), the up input that level j - 1 of the row above sent down (kept for two) and the
+// lane sideways (a whole-wave shift; kept for one iteration), the up input that level j - 1 of the row above sent down (kept for two) and the
 // down input that level j - 1 of the row below sends up in this very iteration.  What a row needs at every level — the unary message, the q
 // of its right and its lower factor, its first slot — is carried in registers from the one time it is loaded (K + 1 rows of them; loading
 // them again at level K was not tried: with them K = 4 still fits three waves per SIMD).  No LDS, no barrier, no atomics, no wait on another
 // workgroup; every global access is a unit-stride run of 16 B per lane.
+//
+// The loop and its loads (profiles/deep_sweep_issue.md).  The loads of row i + 1 are issued at the top of the iteration of row i and are first
+// needed at the top of the next one: between them lie all K levels of arithmetic, and no instruction there waits for a load.  That takes
+// two things.  The slice_off word of row i + 2 is loaded behind the loads of row i + 1 and kept as loaded; the row's first slot is formed
+// from it one iteration later, in front of that iteration's loads.  And the loop starts one row early, on a row of zeros, so that the first
+// row is loaded where every other row is and the loop is entered with nothing in flight.  One s_waitcnt vmcnt(0) per iteration remains, where
+// the loaded row is taken over; it also waits for level K's four stores of the iteration, which the in-order counter cannot tell apart.
+//
+// Two instances per depth, chosen per wave (wave-uniformly): a wave all of whose columns and rows have four neighbours in the grid
+// (cx_lattice_deep.h: strip_interior, segment_interior) runs the loop with every edge test folded to true; every other wave runs the
+// general loop.  The arithmetic, its order, the point-mass branch of the rule and the test for an undefined message are the same in both.
 //
 // Bit-identity with K plain sweeps.  Every level is the pair kernel's: the same leave_one_out over the fixed order unary, left, right, up,
 // down with +0 for an absent direction, the same factor_rule<kRuleAdditive>(., q, 1.0, 0.0), q of a factor read at one of its two slots.
@@ -35,8 +46,16 @@ __device__ __forceinline__ int deep_slab(int b, int nb) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
 }
 __device__ __forceinline__ double2 dsel2(bool c, double2 a, double2 b) { return make_double2(c ? a.x : b.x, c ? a.y : b.y); }
-__device__ __forceinline__ double2 dshfl_up2(double2 a) { return make_double2(__shfl_up(a.x, 1, 64), __shfl_up(a.y, 1, 64)); }
-__device__ __forceinline__ double2 dshfl_down2(double2 a) { return make_double2(__shfl_down(a.x, 1, 64), __shfl_down(a.y, 1, 64)); }
+// the value of the lane below (up) or above (down), as whole-wave DPP shifts of one dword each (v_mov_b32_dpp wave_shr:1 / wave_shl:1: no LDS
+// instruction, no wait).  Lane 0 of a shift up and lane 63 of a shift down receive 0, not their own value as with __shfl_up / __shfl_down:
+// those two lanes are valid at level 1 only and never owned (cx_lattice_deep.h), and what is shifted in feeds levels >= 2 and the stores, so
+// nothing tested or stored depends on it
+__device__ __forceinline__ int ishift_up(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
+__device__ __forceinline__ int ishift_down(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x130 /* wave_shl:1 */, 0xf, 0xf, false); }
+__device__ __forceinline__ double dshift_up(double x) { return __hiloint2double(ishift_up(__double2hiint(x)), ishift_up(__double2loint(x))); }
+__device__ __forceinline__ double dshift_down(double x) { return __hiloint2double(ishift_down(__double2hiint(x)), ishift_down(__double2loint(x))); }
+__device__ __forceinline__ double2 dshfl_up2(double2 a) { return make_double2(dshift_up(a.x), dshift_up(a.y)); }
+__device__ __forceinline__ double2 dshfl_down2(double2 a) { return make_double2(dshift_down(a.x), dshift_down(a.y)); }
 
 // k_sweep's leave-one-out sums over five inputs: out[k] = (in[0] + .. + in[k-1]) + (in[4] + .. + in[k+1])
 __device__ __forceinline__ void deep_leave_one_out(const double2 (&in)[5], double2 (&out)[5]) {
@@ -80,39 +99,46 @@ __device__ __forceinline__ bool deep_undefined(const double2 (&o)[5], bool hasL,
 
 }  // namespace
 
-// grid = block_cols * nseg workgroups; wave w of workgroup (bc, seg) owns strip 4 bc + w, rows [seg R, seg R + R)
-template <int K>
-__global__ __launch_bounds__(kBlock) void k_sweep_deep(int H, int W, int R, int nseg, const int32_t *__restrict__ slice_off, const double *__restrict__ q,
-                                                       const double2 *__restrict__ f2v_in, double2 *__restrict__ f2v_out, unsigned *__restrict__ abort_word) {
+// one wave: strip `strip`, rows [r0, r1).  INTERIOR (cx_lattice_deep.h: strip_interior and segment_interior, both wave-uniform): every lane's
+// column and every row touched lie inside the grid with all four neighbours, so the edge tests below are the constant true, every cell has
+// degree 5 and the ranks are constants; the selects on them compile to nothing.  The point-mass branch of factor_rule and the test for an
+// undefined message stay in both instances.
+template <int K, bool INTERIOR>
+__device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int W, const int32_t *__restrict__ slice_off, const double *__restrict__ q,
+                                          const double2 *__restrict__ f2v_in, double2 *__restrict__ f2v_out, unsigned *__restrict__ abort_word) {
     namespace dp = lattice::deep;
-    const int s = deep_slab(blockIdx.x, gridDim.x);
-    const int bc = s / nseg, seg = s - bc * nseg;       // consecutive segments of one column of workgroups share an XCD (their halo rows meet in its L2)
-    const int strip = bc * lattice::kStripsPerBlock + (threadIdx.x >> 6);
-    if (strip * dp::strip_cols(K) >= W) return;         // (wave-uniform: the last workgroup column may hold fewer than four strips)
     const int lane = threadIdx.x & 63;
     const int c = dp::lane_col(strip, lane, K);
-    const bool colv = c >= 0 && c < W;
-    const bool hasL = colv && c > 0, hasR = colv && c < W - 1;
+    const bool colv = INTERIOR || (c >= 0 && c < W);
+    const bool hasL = INTERIOR || (colv && c > 0), hasR = INTERIOR || (colv && c < W - 1);
     const bool own = dp::lane_owned(lane, c, W, K) && colv;
     const bool two = hasL && hasR;                      // left AND right: up / down sit one rank higher
-    const int r0 = seg * R, r1 = min(r0 + R, H);
     bool bad = false;
 
-    // rows outside the grid and lanes outside the row load nothing: zeros, q = 1 (their results are never used).  The lane's first slot of
-    // a row comes from slice_off one row earlier than the row's messages are asked for: no dependent load in front of them
-    auto load_base = [&](int r) { return (r >= 0 && r < H && colv) ? lattice::slot_base(slice_off, r * W + c) : 0; };
-    auto load_row = [&](int r, int base) {
+    // rows outside the grid and lanes outside the row load nothing: zeros, q = 1 (their results are never used).  The lane's first slot of a
+    // row is slice_off[v >> 8] + (v & 255).  The slice_off word of row i + 2 is asked for in the iteration of row i, behind the loads of row
+    // i + 1, and is kept as loaded; the sum is formed at the top of the next iteration, in front of that iteration's loads.  So no instruction
+    // between the loads of a row and the end of the arithmetic of the row before needs a loaded value (profiles/deep_sweep_issue.md: the
+    // loop's loads and waits)
+    auto in_grid = [&](int r) { return INTERIOR || (r >= 0 && r < H && colv); };
+    auto load_raw = [&](int r) { return in_grid(r) ? slice_off[(r * W + c) >> kSliceShift] : 0; };
+    auto finish_base = [&](int r, int raw) { return in_grid(r) ? raw + ((r * W + c) & (kBlock - 1)) : 0; };
+    auto zero_row = [](int base) {
         DeepRow in;
 #pragma unroll
         for (int k = 0; k < 5; k++) in.x[k] = zero2();
         in.qR = 1.0; in.qD = 1.0; in.base = base;
-        if (r >= 0 && r < H && colv) {
-            const int deg = lattice::degree(r, c, H, W);
+        return in;
+    };
+    auto load_row = [&](int r, int base) {
+        DeepRow in = zero_row(base);
+        if (in_grid(r)) {
+            const int deg = INTERIOR ? 5 : lattice::degree(r, c, H, W);
 #pragma unroll
             for (int k = 0; k < 5; k++)
                 if (k < deg) in.x[k] = deep_load_stream(&f2v_in[in.base + k * kBlock]);
-            if (hasR) in.qR = q[in.base + lattice::rank_right(c) * kBlock];
-            if (r < H - 1) in.qD = q[in.base + lattice::rank_down(r, c, W) * kBlock];
+            if (hasR) in.qR = q[in.base + (INTERIOR ? 2 : lattice::rank_right(c)) * kBlock];
+            if (INTERIOR || r < H - 1) in.qD = q[in.base + (INTERIOR ? 4 : lattice::rank_down(r, c, W)) * kBlock];
         }
         return in;
     };
@@ -131,17 +157,23 @@ __global__ __launch_bounds__(kBlock) void k_sweep_deep(int H, int W, int R, int 
     for (int j = 0; j <= K; j++) { pend[j].L = zero2(); pend[j].R = zero2(); pend[j].U = zero2(); pend[j].carry = zero2(); }
 
     const int i0 = r0 - (K - 1), i1 = r1 + (K - 1) - 1;      // rows loaded: level K reaches row r1 - 1 in the iteration of row i1
-    DeepRow cur = load_row(i0, load_base(i0));
-    int base_next = load_base(i0 + 1);
-    for (int i = i0; i <= i1; i++) {
-        DeepRow nxt = cur;
-        if (i < i1) nxt = load_row(i + 1, base_next);        // (uniform) the next row's loads are in flight while this one is worked on
-        if (i + 1 < i1) base_next = load_base(i + 2);
+    // The loop starts one row early, on a row of zeros at which no level works, so that the first row's loads are issued where every other
+    // row's are and the loop is entered with no load in flight: the compiler places its waits from what may be outstanding on any path into
+    // the loop, and a row loaded in front of the loop cost a wait behind the loads of every iteration.  The empty asm is a use of the word
+    // that the load cannot be moved behind
+    DeepRow nxt = zero_row(0);
+    int raw_next = load_raw(i0);
+    asm volatile("" : "+v"(raw_next));
+    for (int i = i0 - 1; i <= i1; i++) {
+        const DeepRow cur = nxt;                             // the one wait for loads of the iteration: in front of the next row's loads
+        const int base_next = finish_base(i + 1, raw_next);  // (the word came in behind row i's loads, one iteration ago)
+        if (i < i1) nxt = load_row(i + 1, base_next);        // (uniform) in flight until the top of the next iteration: nothing below waits for a load
+        if (i + 1 < i1) raw_next = load_raw(i + 2);
         P[0] = cur.x[0]; qR[0] = cur.qR; qD[0] = cur.qD; base[0] = cur.base;
         DeepOut e;
         e.L = zero2(); e.R = zero2(); e.up = zero2(); e.down = zero2();
-        if (i >= 0 && i < H) {                               // (uniform) level 1 of row i
-            const bool hasU = i > 0, hasD = i < H - 1;
+        if (i >= i0 && (INTERIOR || (i >= 0 && i < H))) {    // (uniform) level 1 of row i
+            const bool hasU = INTERIOR || i > 0, hasD = INTERIOR || i < H - 1;
             double2 in[5], o[5];
             const double2 xu = two ? cur.x[3] : cur.x[2];
             const double2 xd = hasU ? (two ? cur.x[4] : cur.x[3]) : xu;
@@ -162,23 +194,24 @@ __global__ __launch_bounds__(kBlock) void k_sweep_deep(int H, int W, int R, int 
             int baseL = 0, baseR = 0;
             double qL = 1.0;
             if (j == K) {                                    // (by every lane: the stores below are the owned lanes' alone)
-                baseL = __shfl_up(base[K - 1], 1, 64); baseR = __shfl_down(base[K - 1], 1, 64);
-                qL = __shfl_up(qR[K - 1], 1, 64);
+                baseL = ishift_up(base[K - 1]); baseR = ishift_down(base[K - 1]);
+                qL = dshift_up(qR[K - 1]);
             }
-            if (dp::row_valid_at_level(m, r0, r1, H, K, j)) {      // (uniform)
-                const bool mU = m > 0, mD = m < H - 1;
+            // (an interior segment's rows are never clipped by the grid: row_lo / row_hi without the clamp)
+            if (INTERIOR ? (m >= r0 - (K - j) && m < r1 + (K - j)) : dp::row_valid_at_level(m, r0, r1, H, K, j)) {      // (uniform)
+                const bool mU = INTERIOR || m > 0, mD = INTERIOR || m < H - 1;
                 double2 in[5], o[5];
                 in[0] = P[j - 1]; in[1] = pend[j].L; in[2] = pend[j].R;
                 in[3] = dsel2(mU, pend[j].U, zero2());
                 in[4] = dsel2(mD, e.up, zero2());
                 deep_leave_one_out(in, o);
-                if (dp::lane_valid_at_level(lane, c, W, j)) bad = bad || deep_undefined(o, hasL, hasR, mU, mD);
+                if (dp::lane_valid_at_level(lane, INTERIOR ? 0 : c, INTERIOR ? 1 : W, j)) bad = bad || deep_undefined(o, hasL, hasR, mU, mD);
                 if (j < K) f = deep_emit(o, hasL, hasR, qR[j - 1], qD[j], qD[j - 1]);
                 else if (own) {                              // level K of an owned row (row_valid_at_level at j = K: r0 <= m < r1): stored
-                    if (hasL) f2v_out[baseL + lattice::rank_right(c - 1) * kBlock] = factor_rule<kRuleAdditive>(o[1], qL, 1.0, 0.0);
+                    if (hasL) f2v_out[baseL + (INTERIOR ? 2 : lattice::rank_right(c - 1)) * kBlock] = factor_rule<kRuleAdditive>(o[1], qL, 1.0, 0.0);
                     if (hasR) f2v_out[baseR + lattice::rank_left() * kBlock] = factor_rule<kRuleAdditive>(o[2], qR[K - 1], 1.0, 0.0);
-                    if (mU) f2v_out[base[K] + lattice::rank_down(m - 1, c, W) * kBlock] = factor_rule<kRuleAdditive>(o[3], qD[K], 1.0, 0.0);
-                    if (mD) f2v_out[base[K - 2] + lattice::rank_up(c, W) * kBlock] = factor_rule<kRuleAdditive>(o[4], qD[K - 1], 1.0, 0.0);
+                    if (mU) f2v_out[base[K] + (INTERIOR ? 4 : lattice::rank_down(m - 1, c, W)) * kBlock] = factor_rule<kRuleAdditive>(o[3], qD[K], 1.0, 0.0);
+                    if (mD) f2v_out[base[K - 2] + (INTERIOR ? 3 : lattice::rank_up(c, W)) * kBlock] = factor_rule<kRuleAdditive>(o[4], qD[K - 1], 1.0, 0.0);
                 }
             }
             // what level j - 1 produced in this iteration waits for its row's turn at level j
@@ -190,9 +223,22 @@ __global__ __launch_bounds__(kBlock) void k_sweep_deep(int H, int W, int R, int 
             if (a < K) { P[a] = P[a - 1]; qR[a] = qR[a - 1]; }
             qD[a] = qD[a - 1]; base[a] = base[a - 1];
         }
-        cur = nxt;
     }
     if (bad) *abort_word = 1u;      // (an ordinary per-lane store)
+}
+
+// grid = block_cols * nseg workgroups; wave w of workgroup (bc, seg) owns strip 4 bc + w, rows [seg R, seg R + R)
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_sweep_deep(int H, int W, int R, int nseg, const int32_t *__restrict__ slice_off, const double *__restrict__ q,
+                                                       const double2 *__restrict__ f2v_in, double2 *__restrict__ f2v_out, unsigned *__restrict__ abort_word) {
+    namespace dp = lattice::deep;
+    const int s = deep_slab(blockIdx.x, gridDim.x);
+    const int bc = s / nseg, seg = s - bc * nseg;       // consecutive segments of one column of workgroups share an XCD (their halo rows meet in its L2)
+    const int strip = __builtin_amdgcn_readfirstlane(bc * lattice::kStripsPerBlock + (threadIdx.x >> 6));
+    if (strip * dp::strip_cols(K) >= W) return;         // (wave-uniform: the last workgroup column may hold fewer than four strips)
+    const int r0 = seg * R, r1 = min(r0 + R, H);
+    if (dp::strip_interior(strip, W, K) && dp::segment_interior(r0, r1, H, K)) deep_wave<K, true>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
+    else deep_wave<K, false>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
 }
 
 template <int K>
