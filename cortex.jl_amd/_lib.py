@@ -29,6 +29,7 @@ KERNEL_VAR_TO_FACTOR, KERNEL_FACTOR_TO_VAR, KERNEL_FUSED, KERNEL_BATCH, KERNEL_B
 KERNEL_HALO_BEGIN, KERNEL_HALO_END = 5, 6
 KERNEL_COUNT = 8
 PREDICT_LOO, PREDICT_CAUSAL = 0, 1
+CAUSAL_PREDICTED, CAUSAL_FILTERED = 0, 1
 
 
 class Config(C.Structure):
@@ -89,6 +90,7 @@ SIGNATURES = {
     "cx_linear_moments": (_i32, [_vp, _i64, _pi64, _pi64, _pd, _pd, _pd, _pi64]),
     "cx_predictive": (_i32, [_vp, _i32, _i64, _pi64, _pd, _pd, _pi64]),
     "cx_predictive_rows": (_i32, [_vp, _i64, _pi64, _pi64]),
+    "cx_causal_marginals": (_i32, [_vp, _i32, _i32, _i64, _pi64, _pd, _pi64]),
     "cx_halo_configure": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64]),
     "cx_halo_buffers": (_i32, [_vp, C.POINTER(_vp), _pi64, C.POINTER(_vp), _pi64]),
     "cx_halo_set_buffers": (_i32, [_vp, _vp, _vp]),

@@ -36,6 +36,12 @@ void changed(H &h, Change c) {
     case Change::RuleMatrices: case Change::RuleCoefficients: case Change::RuleEdgeSets: case Change::ChainBlock: case Change::kCount: break;
     default: h.pair_check_due = true; break;
     }
+    // the slot classes and the transition list of cx_causal_marginals (cx_causal.hip) follow the graph and WHICH variables are observed;
+    // messages and rule parameters are read by every call: they void nothing
+    switch (c) {
+    case Change::NewlyObserved: case Change::GhostSet: case Change::StateImported: case Change::GraphCreated: h.causal_plan_dirty = true; break;
+    default: break;
+    }
     switch (c) {
     case Change::StoredToVariable:
         // a stored message into a chain variable is part of its side sum; marginals of variables OFF the chains (observed ones,

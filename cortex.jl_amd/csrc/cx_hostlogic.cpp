@@ -94,7 +94,7 @@ struct DerivedFlags {                    // the flags and epochs of cx_handle th
     int observed_passes_due;
     bool pot64_fresh, v2f_stale, chain_msgs_stale, mvc_marg_pending;
     uint64_t vinfo_epoch, param_epoch;
-    bool pair_check_due = false;
+    bool pair_check_due = false, causal_plan_dirty = false;
 };
 
 // flags in the order of DerivedFlags' members (16 values); returns 0, or -1 for a change that does not exist

@@ -107,13 +107,14 @@ struct HostWord {
     }
 };
 
-// what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample, predict, reference order): the deleter is defined there
+// what a handle keeps behind a pointer to a type only its own file knows (evidence, learn, sample, predict, causal, reference order): the deleter is defined there
 template <class T> struct Deleter { void operator()(T *p) const; };
 struct RefSched;      // cx_api_ref.hip
 namespace ev { struct Cache; }
 namespace fs { struct Cache; }
 namespace sp { struct Plan; }
 namespace pr { struct Plan; }
+namespace cm { struct Plan; }
 
 }  // namespace cx
 
@@ -249,6 +250,10 @@ struct DevState {
     std::unique_ptr<fs::Cache, Deleter<fs::Cache>> learn;
     std::unique_ptr<sp::Plan, Deleter<sp::Plan>> sample;
     std::unique_ptr<pr::Plan, Deleter<pr::Plan>> predict;
+    // cx_causal_marginals (cx_causal.hip): the class of every slot and the transition list, with the call's scratch; the plan is due
+    // again after whatever changes the graph or the observed flags (raised by: cx_derived.h)
+    std::unique_ptr<cm::Plan, Deleter<cm::Plan>> causal;
+    bool causal_plan_dirty = true;
 };
 
 }  // namespace cx

@@ -375,6 +375,28 @@ class DeviceGraph:
                 "log_density": out[:, d + d * d].copy(), "mahalanobis": out[:, d + d * d + 1].copy(), "total": float(tot.value),
                 "counts": dict(zip(keys, [int(x) for x in cnt]))}
 
+    def causal_marginals(self, mode="filtered", lag=0, variable_ids=None):
+        """cx_causal_marginals: the causal estimates of the states beside the smoothed marginals of get_marginals, from the stored
+        messages.  mode "predicted": p(x_t | y_<t); "filtered": p(x_t | y_<=t); "filtered" with lag=L: the fixed-lag smoother
+        p(x_t | y_<=t+L) (on a forest: the data of the descendants within L transitions).  variable_ids=None: every variable in
+        ascending id.  Returns {"variable_ids", "mean" [n, d], "cov" [n, d, d], "counts"}; an observed variable's row is its datum and a
+        zero covariance, a row with an undefined input or a precision that is not positive definite is NaN (counts "undefined" /
+        "improper")."""
+        m = {"predicted": L.CAUSAL_PREDICTED, "filtered": L.CAUSAL_FILTERED}.get(mode, mode)
+        d = self.dim
+        if variable_ids is None:
+            ids, n = None, self.stats()["n_variables"]
+        else:
+            ids = _i64(np.atleast_1d(variable_ids))
+            n = len(ids)
+        out = np.zeros((n, d + d * d), dtype=np.float64)
+        cnt = (C.c_int64 * 4)()
+        self._check(self.lib.cx_causal_marginals(self.h, int(m), int(lag), n if ids is not None else 0, None if ids is None else _p(ids, C.c_int64),
+                                                 _p(out, C.c_double), cnt))
+        assert cnt[0] == n
+        return {"variable_ids": ids, "mean": out[:, :d].copy(), "cov": out[:, d:].reshape(n, d, d).copy(),
+                "counts": dict(zip(("rows", "finite", "undefined", "improper"), [int(x) for x in cnt]))}
+
     def sample_posterior(self, n_samples, seed=0, variable_ids=None, noise=None):
         """cx_sample_posterior: joint draws from p(x | data) on a forest (the simulation smoother), from the stored messages.
         Returns (samples [n_samples, n, d] for variable_ids — None: every variable in ascending id —, counts) with counts "free",

@@ -707,6 +707,46 @@ int32_t cx_predictive_rows(cx_handle *h, int64_t cap, int64_t *factor_ids, int64
 int32_t cx_linear_moments(cx_handle *h, int64_t n_functionals, const int64_t *offsets, const int64_t *variable_ids, const double *weights,
                           double *mean, double *cov, int64_t *counts4);
 
+/* ---- causal marginals of the states (added after ABI 9: a new function breaks no caller, CX_ABI_VERSION stays; no counterpart in the
+ * reference) ----
+ * cx_causal_marginals: beside the smoothed marginals of cx_get_marginals, p(x_i | all data), the estimates a real-time user reports:
+ * the one-step prediction p(x_t | y_<t), the filtered estimate p(x_t | y_<=t) and the fixed-lag smoother p(x_t | y_<=t+L), dim 1 - 4
+ * (DESIGN.md §4j), from the STORED factor→variable messages, the rule parameters and the data (never the marginals), after any schedule.
+ * Every stored message into a non-observed variable i is of one class — cx_predictive's conventions, so that the two calls agree:
+ *   U_i  upstream: the message of an opaque (caller-set) factor, or of a rule factor on which i is not a CX_ROLE_IN end
+ *   O_i  i's own observations: of a rule factor on which i is a CX_ROLE_IN end and whose CX_ROLE_OUT end is observed; of a
+ *        CX_FACTOR_GAUSS_ADDITIVE factor (dim 1) whose other end is observed, whichever id is lower
+ *   T_i  transitions onward: of a rule factor on which i is a CX_ROLE_IN end and whose CX_ROLE_OUT end is not observed
+ *        (CX_FACTOR_GAUSS_ADDITIVE has no roles: the lower variable id is `out`, as in cx_factor_beliefs and cx_predictive)
+ * and the result is a sum of messages, in natural parameters:
+ *   CX_CAUSAL_PREDICTED (lag 0)   Σ U_i
+ *   CX_CAUSAL_FILTERED, lag 0     Σ U_i + Σ O_i
+ *   CX_CAUSAL_FILTERED, lag L     Σ U_i + Σ O_i + Σ_{a in T_i} β_a^(L),  with β_a^(0) flat and, for the transition a with `out` end j,
+ *                                 β_a^(s) = the factor's sum-product rule towards i applied to Σ O_j + Σ_{a' in T_j} β_a'^(s-1):
+ *                                 the backward message that has seen only the data within L transitions downstream.
+ * On a chain with a prior or data at its start these are the Kalman predicted, filtered and fixed-lag-smoothed states (a chain of
+ * CX_FACTOR_GAUSS_ADDITIVE transitions with ids ascending in time: their reverse-time counterparts, as cx_predictive documents); on any
+ * forest at a fixed point p(x_i | every datum except those of i's descendants [+ i's own] [+ of descendants within L transitions]); on a
+ * loopy graph the same formula on the Bethe messages; with L at least the depth below i, the smoothed marginal.  The sums are sums of
+ * the messages kept, never the belief minus what is left out: nothing cancels.
+ * Rows: variable_ids == NULL: every variable in ascending id (n is ignored; cx_graph_stats gives n_variables); otherwise the n named
+ * variables in the caller's order.  out: a host array [rows][dim + dim²], mean then covariance (row-major), the moment form of
+ * cx_get_marginals.  An observed variable's row is its datum and a zero covariance.  A row that read an undefined (NaN) message is NaN; a
+ * row whose precision is not positive definite — nothing kept at all, such as the predicted first state of a chain without a prior — is
+ * improper and NaN.  counts4 = {rows, rows returned finite, rows with an undefined input, rows improper}.  A variable's numbers do not
+ * depend on which others share the call; two calls on one state are bit-identical.
+ * Cost: one pass over the messages and one thread per row; a lag L adds L passes over EVERY transition of the graph, whatever rows are
+ * asked for.  The classes and the transition list are built on the first call and again after the graph or the observed flags changed.
+ * Refused as cx_log_evidence refuses, with the same codes (other families, dim >= 5, partitioned handles, zero-noise factors, a captured
+ * stream, no graph); an unknown mode, lag < 0, lag > 0 with CX_CAUSAL_PREDICTED, a NULL out or counts4, or n < 0 with ids are
+ * CX_ERR_INVALID_ARGUMENT; an unknown id CX_ERR_NOT_FOUND; lag > 0 on a graph that holds a transition through a
+ * CX_FACTOR_GAUSS_LINEAR_N factor (a free CX_ROLE_OUT end and a free CX_ROLE_IN end: the recursion has no single predecessor there) is
+ * CX_ERR_UNSUPPORTED and names the factor — with lag 0 such factors are simply classified as above.  Synchronous; moves no message,
+ * marginal, readiness bit or counter. */
+#define CX_CAUSAL_PREDICTED 0
+#define CX_CAUSAL_FILTERED 1
+int32_t cx_causal_marginals(cx_handle *h, int32_t mode, int32_t lag, int64_t n, const int64_t *variable_ids, double *out, int64_t *counts4);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

@@ -169,6 +169,20 @@ class Handle {
         check(cx_predictive(h_, mode, (int64_t)factor_ids.size(), ids, rows && !r.rows.empty() ? r.rows.data() : nullptr, &r.total, r.counts.data()));
         return r;
     }
+    // the causal estimates of the states beside the smoothed marginals, from the stored messages (cx_causal_marginals): per row the mean (d)
+    // then the covariance (d x d, row-major); variable_ids empty: every variable in ascending id.  mode CX_CAUSAL_PREDICTED: p(x_t | y_<t);
+    // CX_CAUSAL_FILTERED: p(x_t | y_<=t), with lag L > 0 the fixed-lag smoother p(x_t | y_<=t+L).  counts: rows, finite, with an undefined
+    // input, improper (NaN rows)
+    struct CausalMarginals { std::vector<double> rows; std::array<int64_t, 4> counts{}; };
+    CausalMarginals causal_marginals(int32_t mode, int32_t lag = 0, const std::vector<int64_t> &variable_ids = {}) {
+        const int64_t n = variable_ids.empty() ? stats().n_variables : (int64_t)variable_ids.size();
+        CausalMarginals r;
+        r.rows.resize((size_t)n * (size_t)(dim_ + dim_ * dim_) + 1);      // (+ 1: never a NULL out)
+        check(cx_causal_marginals(h_, mode, lag, (int64_t)variable_ids.size(), variable_ids.empty() ? nullptr : variable_ids.data(), r.rows.data(),
+                                  r.counts.data()));
+        r.rows.resize((size_t)n * (size_t)(dim_ + dim_ * dim_));
+        return r;
+    }
     // joint posterior draws on a forest (the simulation smoother): n_samples x n x dim doubles for variable_ids (empty: every variable in
     // ascending id); noise (optional): the standard normals, n_samples x n_variables x dim in ascending id order, in place of the device's
     // Philox4x32-10 draws.  counts: free variables, components, components with an undefined input, components not positive definite
