@@ -207,8 +207,97 @@ int32_t cx_set_factor_matrices(cx_handle *h, int64_t parameter_set, const double
         }
         if (!h->has_graph) return CX_OK;
         if (h->cfg.schedule == CX_SCHED_CHAIN_SCAN) { int32_t rc0 = mv_ensure_chain_msgs(h); if (rc0 != CX_OK) return rc0; }   // under the old tables
-        return upload_ptab(h);
+        { const int32_t rc1 = upload_ptab(h); if (rc1 != CX_OK) return rc1; }
+        if (h->has_offsets) {      // the offsets' linear terms, Q^-1 b and -A' Q^-1 b, follow the tables
+            cx::mv_launch_offset_terms(h);
+            CX_HIP(h, hipGetLastError());
+        }
+        return CX_OK;
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_set_factor_matrices: host allocation failed"); }
+}
+
+// h->offsets (by factor) -> d_off_b (by slot, every slot: the arrays are small next to the messages) -> d_off_g (k_mv_offset_terms)
+static int32_t upload_offsets(cx_handle *h) {
+    const int d = h->cfg.dim;
+    const int64_t ns = h->nslots;
+    std::vector<double> bs((size_t)d * ns, 0.0);
+    for (int64_t f = 0; f < h->nf; f++)
+        for (int k = 0; k < 2; k++) {
+            const int32_t sl = h->off_fac_slots[2 * (size_t)f + k];
+            if (sl < 0) continue;
+            for (int i = 0; i < d; i++) bs[(size_t)i * ns + sl] = h->offsets[(size_t)f * d + i];
+        }
+    CX_HIP(h, hipMemcpyAsync(h->d_off_b, bs.data(), bs.size() * 8, hipMemcpyHostToDevice, h->stream));
+    cx::mv_launch_offset_terms(h);
+    CX_HIP(h, hipGetLastError());
+    CX_HIP(h, hipStreamSynchronize(h->stream));      // (bs dies here)
+    return CX_OK;
+}
+
+int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets) {
+    const std::string who = "cx_set_factor_offsets";
+    CX_REQUIRE(h, h, CX_ERR_INVALID_ARGUMENT, "null handle");
+    CX_REQUIRE(h, h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only");
+    CX_REQUIRE(h, h->cfg.dim != 1, CX_ERR_STATE, who + ": dim 1 factors carry b in their parameters (CX_FACTOR_GAUSS_LINEAR: params[2])");
+    CX_REQUIRE(h, h->cfg.dim <= 4 && !h->user_dim, CX_ERR_UNSUPPORTED, who + ": dim 2, 3 and 4 (the matrix-core dims, 5 - 64, have no offsets)");
+    CX_REQUIRE(h, h->has_graph, CX_ERR_STATE, who + ": no graph");
+    CX_REQUIRE(h, h->cfg.schedule != CX_SCHED_REFERENCE, CX_ERR_UNSUPPORTED,
+               who + ": not for CX_SCHED_REFERENCE handles or wirings (cx_graph_wire): the reference order has no d-dimensional offset to be pinned against");
+    CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
+               who + ": not for a partitioned handle (halo lists, state halos or a chain's time block)");
+    CX_REQUIRE(h, n >= 0 && (n == 0 || (factor_ids && offsets)), CX_ERR_INVALID_ARGUMENT, who + ": a negative count or a null array");
+    CX_HIP(h, hipSetDevice(h->cfg.device));
+    if (h->stream) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
+        CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
+    }
+    try {
+        const int d = h->cfg.dim;
+        // everything is checked before anything changes
+        std::vector<int64_t> fac((size_t)n);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t f = find_factor(h, factor_ids[i]);
+            if (f < 0) return fail(h, CX_ERR_NOT_FOUND, who + ": no factor " + std::to_string(factor_ids[i]));
+            if (h->fac_kind[(size_t)f] != CX_FACTOR_GAUSS_LINEAR)
+                return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(factor_ids[i]) + " is not a two-variable CX_FACTOR_GAUSS_LINEAR factor");
+            for (int k = 0; k < d; k++)
+                if (!std::isfinite(offsets[i * d + k]))
+                    return fail(h, CX_ERR_INVALID_ARGUMENT, who + ": the offset of factor " + std::to_string(factor_ids[i]) + " is not finite");
+            fac[(size_t)i] = f;
+        }
+        if (h->cfg.schedule == CX_SCHED_CHAIN_SCAN) { const int32_t rc0 = mv_ensure_chain_msgs(h); if (rc0 != CX_OK) return rc0; }   // under the old offsets
+        int32_t rc;
+        if (!h->has_offsets) {
+            // the factors' slots; per slot the rule table of the messages INTO it: what its partner sends (unmasked: an observed
+            // receiver's slot has a term too, read when it is the sender's)
+            h->off_fac_slots.assign((size_t)2 * h->nf, -1);
+            for (int64_t e = 0; e < h->ne; e++) {
+                const int64_t f = find_factor(h, h->edge_fac_id[e]);
+                if (h->fac_kind[(size_t)f] != CX_FACTOR_GAUSS_LINEAR) continue;
+                int32_t *fs = &h->off_fac_slots[2 * (size_t)f];
+                fs[fs[0] < 0 ? 0 : 1] = cx::slot_of_edge(h, e);
+            }
+            std::vector<int32_t> rt((size_t)h->nslots, -1);
+            for (int64_t f = 0; f < h->nf; f++) {
+                const int32_t s0 = h->off_fac_slots[2 * (size_t)f], s1 = h->off_fac_slots[2 * (size_t)f + 1];
+                if (s0 < 0 || s1 < 0 || h->partner[s0] != s1) { h->off_fac_slots[2 * (size_t)f] = h->off_fac_slots[2 * (size_t)f + 1] = -1; continue; }
+                rt[s0] = h->spdir[s1]; rt[s1] = h->spdir[s0];
+            }
+            CX_HIP(h, hipStreamSynchronize(h->stream));
+            captured_graphs_drop(h);      // a captured sweep names the kernels' instances without offsets
+            if ((rc = dev_upload(h, &h->d_off_rt, rt)) != CX_OK) return rc;
+            if ((rc = dev_alloc(h, &h->d_off_b, (int64_t)d * h->nslots)) != CX_OK) return rc;
+            if ((rc = dev_alloc(h, &h->d_off_g, (int64_t)d * h->nslots)) != CX_OK) return rc;
+            CX_HIP(h, hipStreamSynchronize(h->stream));      // (rt dies here)
+            h->offsets.assign((size_t)h->nf * d, 0.0);
+            h->has_offsets = true;
+        }
+        changed(*h, Change::RuleOffsets);
+        for (int64_t i = 0; i < n; i++) std::copy(offsets + i * d, offsets + (i + 1) * d, h->offsets.begin() + fac[(size_t)i] * d);
+        h->offsets_nonzero = std::any_of(h->offsets.begin(), h->offsets.end(), [](double v) { return v != 0.0; });
+        return upload_offsets(h);
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
 }
 
 

@@ -63,6 +63,8 @@ uint64_t graph_fingerprint(const cx_handle *h) {
     if (h->n_kary) { f = fnv1a(f, h->kary_slot.data(), h->kary_slot.size() * 4); f = fnv1a(f, h->kary_coef.data(), h->kary_coef.size() * 8); }
     if (h->n_kary && h->cfg.dim > 1) f = fnv1a(f, h->kary_pset.data(), h->kary_pset.size() * 4);
     if (h->user_dim) { const int32_t u = h->user_dim; f = fnv1a(f, &u, 4); }      // dim 5 .. 63 embedded in 64: the real block's size is part of the model
+    // cx_set_factor_offsets: part of the rule parameters once set (a handle without offsets keeps the fingerprint it always had)
+    if (h->has_offsets) { f = fnv1a(f, "offsets", 7); f = fnv1a(f, h->offsets.data(), h->offsets.size() * 8); }
     return f;
 }
 

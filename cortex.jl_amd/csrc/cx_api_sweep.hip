@@ -501,6 +501,7 @@ int32_t cx_chain_block_maps(cx_handle *h, double *fwd6, double *bwd6, double *si
     CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_chain_block_maps: no graph");
     CX_REQUIRE(h, h->cfg.schedule == CX_SCHED_CHAIN_SCAN, CX_ERR_STATE, "cx_chain_block_maps: chain-scan handles only");
     CX_REQUIRE(h, fwd6 && bwd6 && side_first2 && side_last2, CX_ERR_INVALID_ARGUMENT, "cx_chain_block_maps: null argument");
+    CX_REQUIRE(h, !h->has_offsets, CX_ERR_UNSUPPORTED, "cx_chain_block_maps: the handle has factor offsets (cx_set_factor_offsets), which a partition does not carry");
     if (h->cfg.dim > 1) {
         try { h->chain_partition = true; return mv_chain_block_maps(h, fwd6, bwd6, side_first2, side_last2, first_variable_id, last_variable_id, n_links); }
         catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_chain_block_maps: host allocation failed"); }

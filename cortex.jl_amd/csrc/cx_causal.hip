@@ -284,6 +284,7 @@ extern "C" int32_t cx_causal_marginals(cx_handle *h, int32_t mode, int32_t lag, 
                           : lag > 0 && mode == CX_CAUSAL_PREDICTED ? "a lag goes with CX_CAUSAL_FILTERED"
                           : variable_ids && n < 0 ? "negative count" : nullptr;
         if ((rc = cx::ev::prepare(h, "cx_causal_marginals", bad, Ep)) != CX_OK) return rc;
+        CX_REQUIRE(h, !h->offsets_nonzero, CX_ERR_UNSUPPORTED, "cx_causal_marginals: the handle has non-zero factor offsets (cx_set_factor_offsets), which this call does not implement");
         if (!h->causal) { h->causal.reset(new cx::cm::Plan()); h->causal_plan_dirty = true; }
         cx::cm::Plan &P = *h->causal;
         if (h->causal_plan_dirty) {

@@ -23,6 +23,7 @@ enum class Change : int32_t {
     ForeignSweepRan,        // a reference-order call ran: messages changed behind the back of the other schedules' constants
     StateImported,          // cx_state_import: messages, marginals and the observed flags are another handle's
     GraphCreated,           // cx_graph_create flattened a graph into the handle
+    RuleOffsets,            // cx_set_factor_offsets (dim 2..4)
     kCount
 };
 
@@ -33,7 +34,7 @@ void changed(H &h, Change c) {
     // the same in both Jacobi buffers: whatever sets messages or data, or changes which variables are observed or stand-ins, makes
     // the check due again.  Rule parameters are read by the launch itself: they void nothing.
     switch (c) {
-    case Change::RuleMatrices: case Change::RuleCoefficients: case Change::RuleEdgeSets: case Change::ChainBlock: case Change::kCount: break;
+    case Change::RuleMatrices: case Change::RuleCoefficients: case Change::RuleEdgeSets: case Change::RuleOffsets: case Change::ChainBlock: case Change::kCount: break;
     default: h.pair_check_due = true; break;
     }
     // the slot classes and the transition list of cx_causal_marginals (cx_causal.hip) follow the graph and WHICH variables are observed;
@@ -119,6 +120,13 @@ void changed(H &h, Change c) {
         h.kary_dirty = true;
         if (scalar) h.offchain_marg_dirty = true; else h.spdir_dirty = true;
         if (mfma) h.pot64_fresh = false;
+        break;
+    case Change::RuleOffsets:
+        // what RuleMatrices voids and that reads eta: the messages out of observed variables, N(A y + b, Q), cached in both Jacobi buffers;
+        // the chains' leaf messages and side sums.  Precisions, k-ary tables, the tree plan and the matrix cores' state do not see b.  (The
+        // linear terms themselves are rewritten by the entry, and again by cx_set_factor_matrices: they follow (A, Q) too.)
+        h.param_epoch++;
+        h.observed_passes_due = 2; h.chain_side_dirty = true;
         break;
     case Change::kCount: break;
     }

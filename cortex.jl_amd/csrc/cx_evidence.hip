@@ -382,6 +382,13 @@ int32_t refresh_params(cx_handle *h, Cache &C, const std::string &who) {
                 }
             o[2 * d * d] = ld;
         }
+        // the factors' offsets by pair row (cx_set_factor_offsets); none while every offset is zero: the kernels then run as without them
+        if (h->offsets_nonzero) {
+            std::vector<double> pb((size_t)C.n_pair * d);
+            for (int64_t r = 0; r < C.n_pair; r++) std::copy_n(&h->offsets[(size_t)C.pair_fac[(size_t)r] * d], d, &pb[(size_t)r * d]);
+            if ((rc = dev_upload(h, &C.d_pb, pb)) != CX_OK) return rc;
+            CX_HIP(h, hipStreamSynchronize(h->stream));      // (pb dies here)
+        } else C.d_pb.reset();
         if ((rc = C.d_ptab.ensure(h, (int64_t)tab.size())) != CX_OK) return rc;
         CX_HIP(h, hipMemcpyAsync(C.d_ptab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, h->stream));
         if ((rc = dev_upload(h, &C.d_kps, kps)) != CX_OK) return rc;

@@ -305,7 +305,8 @@ __device__ __forceinline__ void datum(const double *__restrict__ v2f, int slot, 
 
 // ---- the tables and the messages, as the kernels take them (filled by Cache::pair_tab / kary_tab and msgs_of) --------------------------
 // pair row p: rec[p] = (slot out, slot in, var out, var in) of x_out = A x_in + b + N(0, Q).  dim 1: (q, a, b) per row (pa, pb may be
-// null: a = 1, b = 0); dim > 1: the row's parameter set pset[p] in ptab = [set][A | Q⁻¹ | log det 2πQ, 0] (b = 0)
+// null: a = 1, b = 0); dim > 1: the row's parameter set pset[p] in ptab = [set][A | Q⁻¹ | log det 2πQ, 0] and its offset pb[p * d ..)
+// (cx_set_factor_offsets; pb null: b = 0)
 struct PairTab {
     const int4 *rec;
     const int32_t *pset;
@@ -348,7 +349,7 @@ __device__ __forceinline__ void pair_joint(int64_t p, const PairTab &T, const Ms
         const double *t = T.ptab + (int64_t)T.pset[p] * (2 * D * D + 2);
 #pragma unroll
         for (int i = 0; i < D; i++) {
-            bb[i] = 0.0;
+            bb[i] = T.pb ? T.pb[p * D + i] : 0.0;      // (cx_set_factor_offsets; null: no offset is non-zero)
 #pragma unroll
             for (int j = 0; j < D; j++) { A[i][j] = t[i * D + j]; Qi[i][j] = t[D * D + i * D + j]; }
         }

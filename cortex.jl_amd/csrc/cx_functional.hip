@@ -393,6 +393,7 @@ extern "C" int32_t cx_linear_moments(cx_handle *h, int64_t n_functionals, const 
             else if (K > 32768) bad = "more than 32768 functionals";
         }
         if ((rc = cx::ev::prepare(h, who, bad, Ep)) != CX_OK) return rc;
+        CX_REQUIRE(h, !h->offsets_nonzero, CX_ERR_UNSUPPORTED, who + ": the handle has non-zero factor offsets (cx_set_factor_offsets), which this call does not implement");
         cx::ev::Cache &E = *Ep;
         cx::sp::Plan *Pp = nullptr;
         if ((rc = cx::sp::plan_of(h, E, who, Pp)) != CX_OK) return rc;

@@ -98,7 +98,15 @@ struct DerivedFlags {                    // the flags and epochs of cx_handle th
 };
 
 // flags in the order of DerivedFlags' members (16 values); returns 0, or -1 for a change that does not exist
+static int32_t derived_apply(int32_t dim, int32_t change, const int64_t *in, int64_t *out);
+// the thirteen changes this entry was published with, StoredToVariable .. GraphCreated, by number; a change added since is reached by name
+// (cxh_derived_apply_offsets)
 int32_t cxh_derived_apply(int32_t dim, int32_t change, const int64_t *in, int64_t *out) {
+    if (change < 0 || change > (int32_t)cxh::Change::GraphCreated) return -1;
+    return derived_apply(dim, change, in, out);
+}
+int32_t cxh_derived_apply_offsets(int32_t dim, const int64_t *in, int64_t *out) { return derived_apply(dim, (int32_t)cxh::Change::RuleOffsets, in, out); }
+static int32_t derived_apply(int32_t dim, int32_t change, const int64_t *in, int64_t *out) {
     if (change < 0 || change >= (int32_t)cxh::Change::kCount) return -1;
     DerivedFlags f;
     f.cfg.dim = dim;

@@ -185,6 +185,11 @@ struct DevState {
     int64_t ptab_sets = 0, ptab_bt_sets = 0;      // parameter sets the device tables have room for (rewritten in place while that holds)
     DevBuf<double> d_mv_f2v, d_mv_f2v_alt, d_mv_v2f, d_mv_marg, d_mv_prev;
     int mv_max_deg = 0;             // dim 2..4: widest slice of the graph (0: not computed yet)
+    // cx_set_factor_offsets (dim 2..4): x_out = A x_in + b + N(0, Q).  Allocated by the first call, for every slot, and rewritten in place
+    // from then on (a captured sweep holds d_off_g by value): the offset of each slot's factor, [d][nslots]; the linear term it puts at
+    // the slot's end, [d][nslots] (k_mv_offset_terms, again after cx_set_factor_matrices); the rule table of the messages INTO each slot
+    DevBuf<double> d_off_b, d_off_g;
+    DevBuf<int32_t> d_off_rt;
     // d = 64 work lists (built lazily: they depend on which variables are observed)
     bool work64_dirty = true, point64_dirty = true;
     DevBuf<int32_t> d_point64_slots;
@@ -390,6 +395,11 @@ struct cx_handle : cx::DevState {
     bool ipc_fused = false;          // cx_halo_ipc_set_fused: push and unpack of an exchange as ONE launch (every neighbour pushes from another device)
     int ipc_quiet_lo = 1, ipc_quiet_hi = 0;   // the longest run of owned-only slices none of whose variables WRITES a message of the send list
                                               // (cx_halo_ipc_batch: that run of the last sweep is computed after the push); empty: none
+    // cx_set_factor_offsets was called (the sweeps then launch the kernels' OFF instances); whether any offset is non-zero; the offsets
+    // by local factor number, [nf][d]; the two slots of every factor (-1: none), built by the first call
+    bool has_offsets = false, offsets_nonzero = false;
+    std::vector<double> offsets;
+    std::vector<int32_t> off_fac_slots;
     double damping = 0.0;            // cx_set_damping: new = (1 - damping) rule + damping old (fused and flooding sweeps)
     // cx_set_messages of a long list the caller repeats (an iteration re-sets its priors before every call): ids -> slots / variables / edges,
     // kept for the last lists (the ids themselves are kept and compared: a hash alone would be trusted with the device's memory)
@@ -490,6 +500,7 @@ void mv_launch_batch_run(cx_handle *h, const int32_t *d_rec, const int64_t *d_st
 int mv_run_block();
 void mv_launch_batch(cx_handle *h, const int32_t *d_rec, int64_t n);   // cx_mvbatch.hip: 5 int32 per item (kind, index, variable, rule table, 0)
 void mv_launch_residual(cx_handle *h, const double *cur, const double *prev, int64_t n, double *d_out);
+void mv_launch_offset_terms(cx_handle *h);      // cx_set_factor_offsets: d_off_b and the rule tables -> d_off_g
 bool spd_inverse(int d, const double *S, double *out);
 // d = 64 (cx_mv64.hip): message-major layout, MFMA rule kernel
 void mv64_launch_rule(cx_handle *h, int nwork, const int32_t *d_rec, const double *f2v_in, double *f2v_out, int kernel_id);

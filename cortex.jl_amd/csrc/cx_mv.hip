@@ -48,13 +48,15 @@ constexpr int kTabLds = 8;   // parameter-set/direction pairs kept in LDS (3 d*d
 // DAMP (cx_set_damping): a result is mixed with the message it replaces — the receiving slot in the sweep's input buffer — in natural
 // form, (1 - lambda) rule + lambda old: a convex combination of positive definite precisions is positive definite.  Instances of their
 // own (one more gather and its registers), launched only while a damping factor is set.
-template <int D, int DEG, bool NT_LOADS, bool DAMP = false>
-__global__ __launch_bounds__(kBlock, DAMP ? 1 : DEG == 3 ? 3 : DEG == 4 ? 2 : 1) void k_sweep_mv(int nv, int64_t nslots, const int32_t *__restrict__ slice_off,
+// OFF (cx_set_factor_offsets): the factors' offsets b enter as the linear terms goff of the slots (cx_mv_core.h: mv_rule_off) — instances of
+// their own, launched only for a handle that has offsets.
+template <int D, int DEG, bool NT_LOADS, bool DAMP, bool OFF>
+__device__ __forceinline__ void sweep_mv_body(int nv, int64_t nslots, const int32_t *__restrict__ slice_off,
                                                      const uint8_t *__restrict__ vinfo, const int32_t *__restrict__ partner,
                                                      const int32_t *__restrict__ spdir, const double *__restrict__ ptab, int ntab,
                                                      const double *__restrict__ f2v_in, double *__restrict__ f2v_out,
                                                      const double *__restrict__ v2f, double *__restrict__ marg, int write_marg,
-                                                     int observed_only, double lam) {
+                                                     int observed_only, double lam, const double *__restrict__ goff) {
     __shared__ double tab_s[kTabLds * 3 * D * D];
     const int s = blockIdx.x;
     const int tid = threadIdx.x;
@@ -117,7 +119,9 @@ __global__ __launch_bounds__(kBlock, DAMP ? 1 : DEG == 3 ? 3 : DEG == 4 ? 2 : 1)
                 if (j < deg && j != k) msg_add<D>(o, in[j]);
         }
         if (__builtin_isnan(o.lam[0])) continue;
-        Msg<D> r = pd < nt ? mv_rule<D>(o, tab_s + pd * 3 * D * D) : mv_rule<D>(o, ptab + (int64_t)pd * 3 * D * D);
+        Msg<D> r = OFF ? (pd < nt ? mv_rule_off<D>(o, tab_s + pd * 3 * D * D, goff, nslots, slot, p)
+                                  : mv_rule_off<D>(o, ptab + (int64_t)pd * 3 * D * D, goff, nslots, slot, p))
+                       : (pd < nt ? mv_rule<D>(o, tab_s + pd * 3 * D * D) : mv_rule<D>(o, ptab + (int64_t)pd * 3 * D * D));
         if (DAMP && !__builtin_isnan(r.lam[0])) {
             const Msg<D> old = slot_load<D>(f2v_in, p);
             if (!__builtin_isnan(old.lam[0])) {
@@ -129,6 +133,27 @@ __global__ __launch_bounds__(kBlock, DAMP ? 1 : DEG == 3 ? 3 : DEG == 4 ? 2 : 1)
         }
         if (!__builtin_isnan(r.lam[0])) slot_store<D>(f2v_out, p, r);
     }
+}
+
+template <int D, int DEG, bool NT_LOADS, bool DAMP = false>
+__global__ __launch_bounds__(kBlock, DAMP ? 1 : DEG == 3 ? 3 : DEG == 4 ? 2 : 1) void k_sweep_mv(int nv, int64_t nslots, const int32_t *__restrict__ slice_off,
+                                                     const uint8_t *__restrict__ vinfo, const int32_t *__restrict__ partner,
+                                                     const int32_t *__restrict__ spdir, const double *__restrict__ ptab, int ntab,
+                                                     const double *__restrict__ f2v_in, double *__restrict__ f2v_out,
+                                                     const double *__restrict__ v2f, double *__restrict__ marg, int write_marg,
+                                                     int observed_only, double lam) {
+    sweep_mv_body<D, DEG, NT_LOADS, DAMP, false>(nv, nslots, slice_off, vinfo, partner, spdir, ptab, ntab, f2v_in, f2v_out, v2f, marg, write_marg, observed_only, lam, nullptr);
+}
+
+// the OFF instances: the incoming messages always read nontemporally, two waves per SIMD where the plain kernel has two or three
+template <int D, int DEG, bool DAMP>
+__global__ __launch_bounds__(kBlock, DAMP || DEG > 4 ? 1 : 2) void k_sweep_mv_off(int nv, int64_t nslots, const int32_t *__restrict__ slice_off,
+                                                     const uint8_t *__restrict__ vinfo, const int32_t *__restrict__ partner,
+                                                     const int32_t *__restrict__ spdir, const double *__restrict__ ptab, int ntab,
+                                                     const double *__restrict__ f2v_in, double *__restrict__ f2v_out,
+                                                     const double *__restrict__ v2f, double *__restrict__ marg, int write_marg,
+                                                     int observed_only, double lam, const double *__restrict__ goff) {
+    sweep_mv_body<D, DEG, true, DAMP, true>(nv, nslots, slice_off, vinfo, partner, spdir, ptab, ntab, f2v_in, f2v_out, v2f, marg, write_marg, observed_only, lam, goff);
 }
 
 // variable→factor messages of a list of slots, on demand (cx_get_messages): leave-one-out of the retained input buffer
@@ -155,12 +180,12 @@ __global__ __launch_bounds__(kBlock) void k_v2f_mv(int64_t n, int64_t nslots, co
 // through a segment tree of ProductOfMessages nodes (src/dependencies.jl:90-173: O(log degree) inputs per message); here every slot
 // sums the others itself — O(degree^2) loads per hub and sweep out of the caches, which is what a hub of some hundreds of neighbours
 // costs without a second kernel and a scratch array (the scalar path has the wave scans: k_big_var_to_factor).
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_big_mv(int64_t n, const int32_t *__restrict__ slots, const int32_t *__restrict__ slot_var,
+template <int D, bool OFF>
+__device__ __forceinline__ void big_mv_body(int64_t n, const int32_t *__restrict__ slots, const int32_t *__restrict__ slot_var,
                                                    const int32_t *__restrict__ vbase, const int32_t *__restrict__ vdeg, const uint8_t *__restrict__ vinfo,
                                                    const int32_t *__restrict__ partner, const int32_t *__restrict__ spdir, const double *__restrict__ ptab,
                                                    const double *__restrict__ f2v_in, double *__restrict__ f2v_out, const double *__restrict__ v2f,
-                                                   double *__restrict__ marg, int write_marg, double lam) {
+                                                   double *__restrict__ marg, int write_marg, double lam, const double *__restrict__ goff, int64_t nslots) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const int slot = slots[i], v = slot_var[i], info = vinfo[v], deg = vdeg[v], b = vbase[v];
@@ -175,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_big_mv(int64_t n, const int32_t *__r
     if (info & (kClamped | kGhost)) o = slot_load<D>(v2f, slot);      // an observed variable sends its data
     const int p = partner[slot], pd = spdir[slot];
     if (p < 0 || pd < 0 || __builtin_isnan(o.lam[0])) return;
-    Msg<D> r = mv_rule<D>(o, ptab + (int64_t)pd * 3 * D * D);
+    Msg<D> r = OFF ? mv_rule_off<D>(o, ptab + (int64_t)pd * 3 * D * D, goff, nslots, slot, p) : mv_rule<D>(o, ptab + (int64_t)pd * 3 * D * D);
     if (__builtin_isnan(r.lam[0])) return;
     if (lam != 0.0) {
         const Msg<D> old = slot_load<D>(f2v_in, p);
@@ -187,6 +212,23 @@ __global__ __launch_bounds__(kBlock) void k_big_mv(int64_t n, const int32_t *__r
         }
     }
     slot_store<D>(f2v_out, p, r);
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_big_mv(int64_t n, const int32_t *__restrict__ slots, const int32_t *__restrict__ slot_var,
+                                                   const int32_t *__restrict__ vbase, const int32_t *__restrict__ vdeg, const uint8_t *__restrict__ vinfo,
+                                                   const int32_t *__restrict__ partner, const int32_t *__restrict__ spdir, const double *__restrict__ ptab,
+                                                   const double *__restrict__ f2v_in, double *__restrict__ f2v_out, const double *__restrict__ v2f,
+                                                   double *__restrict__ marg, int write_marg, double lam) {
+    big_mv_body<D, false>(n, slots, slot_var, vbase, vdeg, vinfo, partner, spdir, ptab, f2v_in, f2v_out, v2f, marg, write_marg, lam, nullptr, 0);
+}
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_big_mv_off(int64_t n, const int32_t *__restrict__ slots, const int32_t *__restrict__ slot_var,
+                                                   const int32_t *__restrict__ vbase, const int32_t *__restrict__ vdeg, const uint8_t *__restrict__ vinfo,
+                                                   const int32_t *__restrict__ partner, const int32_t *__restrict__ spdir, const double *__restrict__ ptab,
+                                                   const double *__restrict__ f2v_in, double *__restrict__ f2v_out, const double *__restrict__ v2f,
+                                                   double *__restrict__ marg, int write_marg, double lam, const double *__restrict__ goff, int64_t nslots) {
+    big_mv_body<D, true>(n, slots, slot_var, vbase, vdeg, vinfo, partner, spdir, ptab, f2v_in, f2v_out, v2f, marg, write_marg, lam, goff, nslots);
 }
 
 // host staging <-> device.  ncs > 0: a MESSAGE buffer (block-major pairs, ncs stored doubles per slot: cx_mv_core.h);
@@ -244,6 +286,34 @@ __global__ __launch_bounds__(kBlock) void k_mv_residual(const double *__restrict
     }
 }
 
+// The linear terms of the factors' offsets (cx_set_factor_offsets), per slot: g = Q^-1 b at the OUT end of the slot's factor, -A' Q^-1 b
+// at its IN end — C b and -B b of the (P | B | C) triple of the messages INTO the slot (rt[slot]: its index, odd = the slot is the IN
+// end; -1: no pairwise rule factor, g = 0).  b: [d][nslots], the factor's offset at both of its slots.  Runs when offsets or rule
+// matrices change, never in a sweep.
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_mv_offset_terms(int64_t nslots, const int32_t *__restrict__ rt, const double *__restrict__ ptab,
+                                                            const double *__restrict__ b, double *__restrict__ g) {
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= nslots) return;
+    const int t = rt[s];
+    if (t < 0) {
+#pragma unroll
+        for (int i = 0; i < D; i++) g[(int64_t)i * nslots + s] = 0.0;
+        return;
+    }
+    const double *M = ptab + (int64_t)t * 3 * D * D + ((t & 1) ? D * D : 2 * D * D);
+    double bv[D];
+#pragma unroll
+    for (int i = 0; i < D; i++) bv[i] = b[(int64_t)i * nslots + s];
+#pragma unroll
+    for (int i = 0; i < D; i++) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; k++) a += M[i * D + k] * bv[k];
+        g[(int64_t)i * nslots + s] = (t & 1) ? -a : a;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static void prof_b(cx_handle *h, int kernel) {
     h->prof_armed = false;
@@ -280,8 +350,16 @@ void mv_launch_sweep(cx_handle *h, bool write_marg, int observed_only, double *f
     static const bool nt = [] { const char *e = getenv("CX_MV_NT"); return !(e && e[0] == '0'); }();
     // messages out of observed variables and other constant senders (observed_only passes) are functions of the data alone: never damped
     const bool damp = h->damping != 0.0 && !observed_only;
+    // a handle with offsets (cx_set_factor_offsets): the OFF instances
+    const bool off = h->has_offsets;
+    const double *goff = h->d_off_g;
 #define CX_MV(DD)                                                                      \
-    if (damp && deg8) hipLaunchKernelGGL((k_sweep_mv<DD, 8, true, true>), CX_MV_ARGS); \
+    if (off && damp && deg8) hipLaunchKernelGGL((k_sweep_mv_off<DD, 8, true>), CX_MV_ARGS, goff);  \
+    else if (off && damp) hipLaunchKernelGGL((k_sweep_mv_off<DD, 4, true>), CX_MV_ARGS, goff);     \
+    else if (off && deg8) hipLaunchKernelGGL((k_sweep_mv_off<DD, 8, false>), CX_MV_ARGS, goff);    \
+    else if (off && deg3) hipLaunchKernelGGL((k_sweep_mv_off<DD, 3, false>), CX_MV_ARGS, goff);    \
+    else if (off) hipLaunchKernelGGL((k_sweep_mv_off<DD, 4, false>), CX_MV_ARGS, goff);            \
+    else if (damp && deg8) hipLaunchKernelGGL((k_sweep_mv<DD, 8, true, true>), CX_MV_ARGS); \
     else if (damp) hipLaunchKernelGGL((k_sweep_mv<DD, 4, true, true>), CX_MV_ARGS);    \
     else if (deg8) hipLaunchKernelGGL((k_sweep_mv<DD, 8, true>), CX_MV_ARGS);          \
     else if (deg3 && nt) hipLaunchKernelGGL((k_sweep_mv<DD, 3, true>), CX_MV_ARGS);    \
@@ -302,12 +380,14 @@ void mv_launch_big(cx_handle *h, bool write_marg, double *f2v_out) {
     if (n == 0) return;
     if (!f2v_out) f2v_out = h->d_mv_f2v_alt;
     const dim3 g((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
-#define CX_MV(DD) hipLaunchKernelGGL((k_big_mv<DD>), g, b, 0, h->stream, n, h->d_big_slots, h->d_big_slot_var, h->d_vbase, h->d_var_deg, h->d_vinfo, h->d_partner, \
-                                     h->d_spdir, h->d_ptab, h->d_mv_f2v, f2v_out, h->d_mv_v2f, h->d_mv_marg, write_marg ? 1 : 0, h->damping)
+#define CX_MV_ARGS g, b, 0, h->stream, n, h->d_big_slots, h->d_big_slot_var, h->d_vbase, h->d_var_deg, h->d_vinfo, h->d_partner, h->d_spdir, h->d_ptab, h->d_mv_f2v, \
+                   f2v_out, h->d_mv_v2f, h->d_mv_marg, write_marg ? 1 : 0, h->damping
+#define CX_MV(DD) do { if (h->has_offsets) hipLaunchKernelGGL((k_big_mv_off<DD>), CX_MV_ARGS, (const double *)h->d_off_g, h->nslots); else hipLaunchKernelGGL((k_big_mv<DD>), CX_MV_ARGS); } while (0)
     if (h->cfg.dim == 2) CX_MV(2);
     else if (h->cfg.dim == 3) CX_MV(3);
     else CX_MV(4);
 #undef CX_MV
+#undef CX_MV_ARGS
 }
 
 void mv_launch_v2f(cx_handle *h, const int32_t *d_slots, const int32_t *d_vars, int64_t n, const double *f2v) {
@@ -333,6 +413,15 @@ void mv_launch_seed(cx_handle *h, double *buf, double eta, double lam) {
 }
 void mv_launch_residual(cx_handle *h, const double *cur, const double *prev, int64_t n, double *d_out) {
     hipLaunchKernelGGL(k_mv_residual, dim3(1024), dim3(kBlock), 0, h->stream, cur, prev, n, d_out);
+}
+// d_off_b (the offsets by slot) and the rule tables -> d_off_g (the slots' linear terms)
+void mv_launch_offset_terms(cx_handle *h) {
+    const dim3 g((unsigned)((h->nslots + kBlock - 1) / kBlock)), b(kBlock);
+#define CX_MV(DD) hipLaunchKernelGGL((k_mv_offset_terms<DD>), g, b, 0, h->stream, h->nslots, h->d_off_rt, h->d_ptab, h->d_off_b, h->d_off_g)
+    if (h->cfg.dim == 2) CX_MV(2);
+    else if (h->cfg.dim == 3) CX_MV(3);
+    else CX_MV(4);
+#undef CX_MV
 }
 
 // ---- small dense helpers (host) -------------------------------------------------------------------------------

@@ -228,6 +228,27 @@ __device__ __forceinline__ Msg<D> mv_rule(const Msg<D> &in, const double *__rest
     return out;
 }
 
+// ---- per-factor offsets (cx_set_factor_offsets): x_out = A x_in + b + N(0, Q) -----------------------------------------------------
+// The pairwise potential then has a linear term at each end, g_out = Q^-1 b and g_in = -A' Q^-1 b, kept per SLOT (the term of the
+// slot's factor at the slot's variable; [D][nslots], component-major; cx_mv.hip: k_mv_offset_terms).  A message from the sending end s
+// to the receiving end p keeps its precision and has  eta_p = g_p + B (Lambda_s + P)^-1 (eta_s + g_s);  an observed sender's datum
+// takes no g_s (eta_p = g_p + B y).  The kernels call these from instantiations of their own (OFF = true), launched only for a
+// handle that has offsets: the others are compiled from the code they always had.
+template <int D>
+__device__ __forceinline__ void off_add(Msg<D> &m, const double *__restrict__ g, int64_t nslots, int slot) {
+#pragma unroll
+    for (int i = 0; i < D; i++) m.eta[i] += g[(int64_t)i * nslots + slot];
+}
+
+template <int D, bool POINT = true>
+__device__ __forceinline__ Msg<D> mv_rule_off(Msg<D> in, const double *__restrict__ tab, const double *__restrict__ g, int64_t nslots, int s_slot,
+                                              int p_slot) {
+    if (!(POINT && in.lam[0] == __builtin_inf())) off_add<D>(in, g, nslots, s_slot);
+    Msg<D> out = mv_rule<D, POINT>(in, tab);
+    off_add<D>(out, g, nslots, p_slot);
+    return out;
+}
+
 // natural -> moment (mean, packed covariance) for marginals
 template <int D>
 __device__ __forceinline__ Msg<D> mv_to_moment(const Msg<D> &nat) {

@@ -26,10 +26,14 @@ namespace cx {
 
 // rec: 5 int32 per item — kind, index (slot of the signal's edge | local variable | place in the product table), local variable, rule table
 // of the sending slot (ProductOfMessages: first message of the range, 1-based), 0 (ProductOfMessages: last message of the range)
-template <int D>
+// OFF (cx_set_factor_offsets): a MessageToVariable item adds the linear terms of the factor's offset at its two ends (goff by slot:
+// cx_mv_core.h: mv_rule_off); instances of their own, launched only for a handle that has offsets
+struct OffTab { const double *g; int64_t nslots; };
+template <int D, bool OFF = false>
 __device__ __forceinline__ void batch_item_mv(int kind, int idx, int v, int tab, int hi, const int32_t *__restrict__ vbase, const uint8_t *__restrict__ vinfo, const int32_t *__restrict__ vdeg,
                                               const int32_t *__restrict__ partner, const double *__restrict__ ptab, double *__restrict__ f2v,
-                                              double *__restrict__ v2f, double *__restrict__ marg, double *__restrict__ prod, const KaryMvTab kt, const int32_t *__restrict__ list) {
+                                              double *__restrict__ v2f, double *__restrict__ marg, double *__restrict__ prod, const KaryMvTab kt, const int32_t *__restrict__ list,
+                                              const OffTab ot = OffTab{nullptr, 0}) {
     if (kind == 32) { kary_item_mv<D>(idx, kt, v2f, f2v, nullptr, 0.0); return; }      // a message out of a factor of more than two variables (index = entry of its table)
     if (kind >= 64 && kind <= 66) {      // (a node may lag behind its leaves on a graph with loops, and the reference reads the node)
         Msg<D> acc = msg_zero<D>();
@@ -53,7 +57,7 @@ __device__ __forceinline__ void batch_item_mv(int kind, int idx, int v, int tab,
         if (p < 0) return;                                  // an opaque factor's message is the caller's to set
         const Msg<D> in = slot_load<D>(v2f, p);
         if (__builtin_isnan(in.lam[0])) return;
-        const Msg<D> r = mv_rule<D>(in, ptab + (int64_t)tab * 3 * D * D);
+        const Msg<D> r = OFF ? mv_rule_off<D>(in, ptab + (int64_t)tab * 3 * D * D, ot.g, ot.nslots, p, idx) : mv_rule<D>(in, ptab + (int64_t)tab * 3 * D * D);
         if (!__builtin_isnan(r.lam[0])) slot_store<D>(f2v, idx, r);
     } else if (kind == CX_ITEM_INDIVIDUAL_MARGINAL) {
         Msg<D> total = msg_zero<D>();
@@ -76,6 +80,16 @@ __global__ __launch_bounds__(kBlock) void k_batch_mv(int64_t n, const int32_t *_
     if (i >= n) return;
     batch_item_mv<D>(rec[5 * i], rec[5 * i + 1], rec[5 * i + 2], rec[5 * i + 3], rec[5 * i + 4], vbase, vinfo, vdeg, partner, ptab, f2v, v2f, marg, prod, kt, list);
 }
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_batch_mv_off(int64_t n, const int32_t *__restrict__ rec, int64_t nslots, int nv, const int32_t *__restrict__ vbase,
+                                                         const uint8_t *__restrict__ vinfo, const int32_t *__restrict__ vdeg, const int32_t *__restrict__ partner,
+                                                         const double *__restrict__ ptab, double *__restrict__ f2v, double *__restrict__ v2f,
+                                                         double *__restrict__ marg, double *__restrict__ prod, const KaryMvTab kt, const int32_t *__restrict__ list,
+                                                         const OffTab ot) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    batch_item_mv<D, true>(rec[5 * i], rec[5 * i + 1], rec[5 * i + 2], rec[5 * i + 3], rec[5 * i + 4], vbase, vinfo, vdeg, partner, ptab, f2v, v2f, marg, prod, kt, list, ot);
+}
 
 // at most kSmallBatch items: the records are the first kernel argument (cx_batch.hip: k_batch_small)
 template <int D>
@@ -86,6 +100,17 @@ __global__ __launch_bounds__(64) void k_batch_mv_small(SmallBatch recs, int n, c
     if (i >= n) return;
     const __attribute__((address_space(4))) int32_t *rec = (const __attribute__((address_space(4))) int32_t *)__builtin_amdgcn_kernarg_segment_ptr();
     batch_item_mv<D>(rec[5 * i], rec[5 * i + 1], rec[5 * i + 2], rec[5 * i + 3], rec[5 * i + 4], vbase, vinfo, vdeg, partner, ptab, f2v, v2f, marg, prod, kt, list);
+    (void)recs;
+}
+template <int D>
+__global__ __launch_bounds__(64) void k_batch_mv_small_off(SmallBatch recs, int n, const int32_t *__restrict__ vbase, const uint8_t *__restrict__ vinfo,
+                                                           const int32_t *__restrict__ vdeg, const int32_t *__restrict__ partner, const double *__restrict__ ptab, double *__restrict__ f2v,
+                                                           double *__restrict__ v2f, double *__restrict__ marg, double *__restrict__ prod, const KaryMvTab kt, const int32_t *__restrict__ list,
+                                                           const OffTab ot) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    const __attribute__((address_space(4))) int32_t *rec = (const __attribute__((address_space(4))) int32_t *)__builtin_amdgcn_kernarg_segment_ptr();
+    batch_item_mv<D, true>(rec[5 * i], rec[5 * i + 1], rec[5 * i + 2], rec[5 * i + 3], rec[5 * i + 4], vbase, vinfo, vdeg, partner, ptab, f2v, v2f, marg, prod, kt, list, ot);
     (void)recs;
 }
 
@@ -123,24 +148,30 @@ void mv_launch_batch_run(cx_handle *h, const int32_t *d_rec, const int64_t *d_st
 void mv_launch_batch(cx_handle *h, const int32_t *d_rec, int64_t n) {
     if (n == 0) return;
     const dim3 g((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
-#define CX_MVB(DD) hipLaunchKernelGGL((k_batch_mv<DD>), g, b, 0, h->stream, n, d_rec, h->nslots, (int)h->nv, h->d_vbase, h->d_vinfo, h->d_var_deg, h->d_partner, \
-                                      h->d_ptab, h->d_mv_f2v, h->d_mv_v2f, h->d_mv_marg, h->d_mv_prod, kt, h->d_ref_list)
+#define CX_MVB_ARGS g, b, 0, h->stream, n, d_rec, h->nslots, (int)h->nv, h->d_vbase, h->d_vinfo, h->d_var_deg, h->d_partner, h->d_ptab, h->d_mv_f2v, h->d_mv_v2f, \
+                    h->d_mv_marg, h->d_mv_prod, kt, h->d_ref_list
+#define CX_MVB(DD) do { if (h->has_offsets) hipLaunchKernelGGL((k_batch_mv_off<DD>), CX_MVB_ARGS, ot); else hipLaunchKernelGGL((k_batch_mv<DD>), CX_MVB_ARGS); } while (0)
     const KaryMvTab kt{h->d_kary_slot, h->d_kary_pset, h->d_kary_aq};
+    const OffTab ot{h->d_off_g, h->nslots};
     if (h->cfg.dim == 2) CX_MVB(2);
     else if (h->cfg.dim == 3) CX_MVB(3);
     else CX_MVB(4);
 #undef CX_MVB
+#undef CX_MVB_ARGS
 }
 
 void mv_launch_batch_small(cx_handle *h, const SmallBatch &recs, int n) {
     if (n == 0) return;
-#define CX_MVB(DD) hipLaunchKernelGGL((k_batch_mv_small<DD>), dim3(1), dim3(64), 0, h->stream, recs, n, h->d_vbase, h->d_vinfo, h->d_var_deg, h->d_partner, h->d_ptab, \
-                                      h->d_mv_f2v, h->d_mv_v2f, h->d_mv_marg, h->d_mv_prod, kt, h->d_ref_list)
+#define CX_MVB_ARGS dim3(1), dim3(64), 0, h->stream, recs, n, h->d_vbase, h->d_vinfo, h->d_var_deg, h->d_partner, h->d_ptab, h->d_mv_f2v, h->d_mv_v2f, h->d_mv_marg, \
+                    h->d_mv_prod, kt, h->d_ref_list
+#define CX_MVB(DD) do { if (h->has_offsets) hipLaunchKernelGGL((k_batch_mv_small_off<DD>), CX_MVB_ARGS, ot); else hipLaunchKernelGGL((k_batch_mv_small<DD>), CX_MVB_ARGS); } while (0)
     const KaryMvTab kt{h->d_kary_slot, h->d_kary_pset, h->d_kary_aq};
+    const OffTab ot{h->d_off_g, h->nslots};
     if (h->cfg.dim == 2) CX_MVB(2);
     else if (h->cfg.dim == 3) CX_MVB(3);
     else CX_MVB(4);
 #undef CX_MVB
+#undef CX_MVB_ARGS
 }
 
 }  // namespace cx

@@ -215,6 +215,17 @@ struct SrcLink {           // the (non-constant) map of a link: side information
     __device__ __forceinline__ int flags() const { return 0; }
 };
 
+template <int D>
+struct SrcLinkOff {        // the same with the factor's offset (cx_set_factor_offsets): u already holds eta + g_s, cv = g_p — the map's affine parts (h, c)
+    const Msg<D> &u; const double *tab; const double *cv;
+    __device__ __forceinline__ double P(int a, int b) const { return tab[a * D + b] + u.lam[tri<D>(a, b)]; }
+    __device__ __forceinline__ double B(int a, int b) const { return tab[D * D + a * D + b]; }
+    __device__ __forceinline__ double C(int a, int b) const { return tab[2 * D * D + a * D + b]; }
+    __device__ __forceinline__ double h(int a) const { return u.eta[a]; }
+    __device__ __forceinline__ double c(int a) const { return cv[a]; }
+    __device__ __forceinline__ int flags() const { return 0; }
+};
+
 template <int D, class S>
 __device__ __forceinline__ void cmap_assign(CMap<D> &f, const S &s) {
     using M = CMap<D>;
@@ -449,8 +460,11 @@ __device__ __forceinline__ const double *mvc_tab(const MvcArgs &A, const double 
 
 // the composed map of a thread's K consecutive links, in the direction's order, accumulated in place: the link's own map is
 // never materialised (its B and C are the LDS tables, its P and h the tables plus the side information)
-template <int D, bool GT>
-__device__ __forceinline__ void mvc_thread_total(CMap<D> &tot, const MvcArgs &A, const double *tab_s, int l0, int64_t il0, int K, int dir) {
+// OFF (cx_set_factor_offsets): link l's map takes the offset of its factor as h += g_s, c += g_p — s the sending end (forward: the
+// left variable's slot, from_slot[l]), p the receiving end; goff: the linear terms by slot, [D][nslots] (cx_mv_core.h)
+template <int D, bool GT, bool OFF = false>
+__device__ __forceinline__ void mvc_thread_total(CMap<D> &tot, const MvcArgs &A, const double *tab_s, int l0, int64_t il0, int K, int dir,
+                                                 const double *__restrict__ goff = nullptr) {
     using M = CMap<D>;
     tot = cmap_identity<D>();
     // (the next link's loads in flight while this link's map is appended — what the walks do — measured: no gain here, 0.243 vs 0.241 ms)
@@ -460,9 +474,20 @@ __device__ __forceinline__ void mvc_thread_total(CMap<D> &tot, const MvcArgs &A,
         if (l >= A.nlinks) continue;
         const bool head = (dir > 0 ? A.head_fwd[l] : A.head_bwd[l]) != 0;
         const double *tab = mvc_tab<D, GT>(A, tab_s, dir > 0 ? A.tab_fwd[l] : A.tab_bwd[l]);
-        const Msg<D> u = dir > 0 ? slot_load<D, true>(A.side_l, (int)(il0 + (int64_t)kk * kBlock)) : mvc_side_right<D>(A, l, il0 + (int64_t)kk * kBlock, K);
+        Msg<D> u = dir > 0 ? slot_load<D, true>(A.side_l, (int)(il0 + (int64_t)kk * kBlock)) : mvc_side_right<D>(A, l, il0 + (int64_t)kk * kBlock, K);
+        double gp[OFF ? D : 1];
+        if constexpr (OFF) {
+            const int ss = dir > 0 ? A.from_slot[l] : A.to_slot[l], ps = dir > 0 ? A.to_slot[l] : A.from_slot[l];
+            off_add<D>(u, goff, A.nslots, ss);
+#pragma unroll
+            for (int i = 0; i < D; i++) gp[i] = goff[(int64_t)i * A.nslots + ps];
+        }
         if (head && A.collapse_heads) {      // the first link of a path: the constant map "rule applied to u alone"
-            const Msg<D> o = mv_rule<D, false>(u, tab);
+            Msg<D> o = mv_rule<D, false>(u, tab);
+            if constexpr (OFF) {
+#pragma unroll
+                for (int i = 0; i < D; i++) o.eta[i] += gp[i];
+            }
 #pragma unroll
             for (int i = 0; i < D; i++) {
                 tot.v[M::oH + i] = 0.0; tot.v[M::oS + i] = o.eta[i];
@@ -472,6 +497,10 @@ __device__ __forceinline__ void mvc_thread_total(CMap<D> &tot, const MvcArgs &A,
                 for (int j = i; j < D; j++) { tot.v[tri<D>(i, j)] = i == j ? 1.0 : 0.0; tot.v[M::oC + tri<D>(i, j)] = o.lam[tri<D>(i, j)]; }
             }
             tot.flags = kMapSeg;
+        } else if constexpr (OFF) {
+            const SrcLinkOff<D> link{u, tab, gp};
+            if (tot.flags & kMapIdent) cmap_assign<D>(tot, link);
+            else cmap_append<D>(tot, link);
         } else {
             const SrcLink<D> link{u, tab};
             if (tot.flags & kMapIdent) cmap_assign<D>(tot, link);
@@ -533,8 +562,8 @@ __device__ __forceinline__ CMap<D> prefix_load(const double *__restrict__ p, int
 // it in the workgroup, composed) — stored per wave; the logically last wave also stores the tile total = its carry ∘ its total,
 // at totals[dir][pos], pos in the direction's scan order (backward: tile ntiles - 1 first).  The walks put the pieces together
 // (k_mvc_apply): tile carry ∘ wave carry ∘ prefix of the previous lane.
-template <int D, bool GT>
-__global__ __launch_bounds__(kBlock, 2) void k_mvc_totals(MvcArgs A, int K, double *__restrict__ totals) {
+template <int D, bool GT, bool OFF>
+__device__ __forceinline__ void mvc_totals_body(const MvcArgs &A, int K, double *__restrict__ totals, const double *__restrict__ goff) {
     constexpr int E = CMap<D>::ND + 1, NW = kBlock / 64;
     __shared__ double tab_s[GT ? 1 : kMvcTabLds * 3 * D * D];
     __shared__ double wt[NW * E];
@@ -544,7 +573,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_mvc_totals(MvcArgs A, int K, doub
     const int lane = tid & 63, wid = tid >> 6;
     const int li = dir > 0 ? lane : 63 - lane, wl = dir > 0 ? wid : NW - 1 - wid;
     CMap<D> t;
-    mvc_thread_total<D, GT>(t, A, tab_s, (int)gid * K, (int64_t)blockIdx.x * kBlock * K + tid, K, dir);
+    mvc_thread_total<D, GT, OFF>(t, A, tab_s, (int)gid * K, (int64_t)blockIdx.x * kBlock * K + tid, K, dir, goff);
 #pragma unroll 1
     for (int d = 1; d < 64; d <<= 1) cmap_scan_step<D>(t, dir > 0 ? lane - d : lane + d, li >= d);
     prefix_store<D>(A.prefix + (size_t)blockIdx.y * E * nthreads, nthreads, gid, t);
@@ -560,6 +589,15 @@ __global__ __launch_bounds__(kBlock, 2) void k_mvc_totals(MvcArgs A, int K, doub
         const int pos = dir > 0 ? blockIdx.x : ntiles - 1 - blockIdx.x;
         if (li == 0) cmap_store<D>(totals + ((size_t)blockIdx.y * ntiles + pos) * E, carry);
     }
+}
+
+template <int D, bool GT>
+__global__ __launch_bounds__(kBlock, 2) void k_mvc_totals(MvcArgs A, int K, double *__restrict__ totals) {
+    mvc_totals_body<D, GT, false>(A, K, totals, nullptr);
+}
+template <int D, bool GT>
+__global__ __launch_bounds__(kBlock, 2) void k_mvc_totals_off(MvcArgs A, int K, double *__restrict__ totals, const double *__restrict__ goff) {
+    mvc_totals_body<D, GT, true>(A, K, totals, goff);
 }
 
 // exclusive scan of the tile totals, in place: one workgroup per direction, chunks of kBlock tiles
@@ -601,9 +639,11 @@ __device__ __forceinline__ void marg_store(double *__restrict__ marg, int64_t, i
 // stores, at the two waves per SIMD a chain of 1e6 links fills.  (The plain form, PF = false, is kept for CX_MVC_PREFETCH=0 A/B runs;
 // until round 5 it was held to 128 registers — four waves per SIMD — and carried 112 B of scratch for d = 4; a chain of 1e6 links
 // fills two waves per SIMD whatever the register count, so both forms now take what they need: 202 / 168 registers, no scratch.)
-template <int D, bool GT, bool PF>
-__global__ __launch_bounds__(kBlock, 2) void k_mvc_apply(MvcArgs A, int K, const double *__restrict__ excl, double *__restrict__ f2v,
-                                                               double *__restrict__ marg, int flags) {
+// OFF (cx_set_factor_offsets): every rule of the walks takes the linear terms of its factor's offset (g_s before, g_p after); gamma, the
+// sum a variable hears from everybody but the link, is stored before g_s goes in.
+template <int D, bool GT, bool PF, bool OFF>
+__device__ __forceinline__ void mvc_apply_body(const MvcArgs &A, int K, const double *__restrict__ excl, double *__restrict__ f2v,
+                                               double *__restrict__ marg, int flags, const double *__restrict__ goff) {
     constexpr int E = CMap<D>::ND + 1;
     using M = CMap<D>;
     __shared__ double tab_s[GT ? 1 : kMvcTabLds * 3 * D * D];
@@ -684,7 +724,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_mvc_apply(MvcArgs A, int K, const
                 head = A.head_fwd[l]; tab = A.tab_fwd[l];
             }
             if (!head) msg_add<D>(in, cur);
+            if constexpr (OFF) off_add<D>(in, goff, A.nslots, A.from_slot[l]);
             cur = mv_rule<D, false>(in, mvc_tab<D, GT>(A, tab_s, tab));
+            if constexpr (OFF) off_add<D>(cur, goff, A.nslots, A.to_slot[l]);
             slot_store<D>(A.alpha, (int)il, cur);
             if (store_msgs && !__builtin_isnan(cur.lam[0])) slot_store<D>(f2v, A.to_slot[l], cur);
         }
@@ -708,7 +750,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_mvc_apply(MvcArgs A, int K, const
             }
             if (!head) msg_add<D>(in, cur);
             slot_store<D>(A.gamma, (int)il, in);
+            if constexpr (OFF) off_add<D>(in, goff, A.nslots, A.to_slot[l]);
             cur = mv_rule<D, false>(in, mvc_tab<D, GT>(A, tab_s, tab));
+            if constexpr (OFF) off_add<D>(cur, goff, A.nslots, A.from_slot[l]);
             if (store_msgs && !__builtin_isnan(cur.lam[0])) slot_store<D>(f2v, A.from_slot[l], cur);
             if (write_marg && A.head_fwd[l]) {                        // the first variable of a path hears no alpha
                 const int p = A.link_pos[l];
@@ -718,6 +762,17 @@ __global__ __launch_bounds__(kBlock, 2) void k_mvc_apply(MvcArgs A, int K, const
             }
         }
     }
+}
+
+template <int D, bool GT, bool PF>
+__global__ __launch_bounds__(kBlock, 2) void k_mvc_apply(MvcArgs A, int K, const double *__restrict__ excl, double *__restrict__ f2v,
+                                                               double *__restrict__ marg, int flags) {
+    mvc_apply_body<D, GT, PF, false>(A, K, excl, f2v, marg, flags, nullptr);
+}
+template <int D, bool GT>
+__global__ __launch_bounds__(kBlock, 2) void k_mvc_apply_off(MvcArgs A, int K, const double *__restrict__ excl, double *__restrict__ f2v,
+                                                             double *__restrict__ marg, int flags, const double *__restrict__ goff) {
+    mvc_apply_body<D, GT, true, true>(A, K, excl, f2v, marg, flags, goff);
 }
 
 // Marginal of every link's right variable: (alpha + gamma) to moment form, then from the interleaved order of the walks to
@@ -954,6 +1009,13 @@ static void mvc_launch_t(cx_handle *h, const MvcArgs &A, int K, int flags, bool 
     const int ntiles = (int)mvc_ntiles(A.nlinks, K);
     // (the tile totals stay as k_mvc_totals left them: the walks' workgroups compose their own carry from them — also when only the
     // walks run again, scan == false)
+    if (h->has_offsets) {      // cx_set_factor_offsets: the OFF instances (the walks always in their prefetching form)
+        const double *goff = h->d_off_g;
+        if (scan) hipLaunchKernelGGL((k_mvc_totals_off<D, GT>), dim3(ntiles, 2), dim3(kBlock), 0, h->stream, A, K, h->d_mvc_totals, goff);
+        hipLaunchKernelGGL((k_mvc_apply_off<D, GT>), dim3(ntiles, 2), dim3(kBlock), 0, h->stream, A, K, h->d_mvc_totals, h->d_mv_f2v, h->d_mv_marg, flags, goff);
+        if ((flags & 1) && !(flags & 4)) mvc_marg_out_t<D>(h, A, K);
+        return;
+    }
     if (scan) hipLaunchKernelGGL((k_mvc_totals<D, GT>), dim3(ntiles, 2), dim3(kBlock), 0, h->stream, A, K, h->d_mvc_totals);
     // CX_MVC_PREFETCH=0: the walks without the next step's loads in flight (A/B)
     static const bool pf = [] { const char *e = getenv("CX_MVC_PREFETCH"); return !(e && e[0] == '0'); }();

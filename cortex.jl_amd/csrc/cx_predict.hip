@@ -210,6 +210,10 @@ __global__ __launch_bounds__(kPB) void k_pr_rows(int64_t n, Rows R, ev::PairTab 
                 } else {
                     const double *t = PT.ptab + (int64_t)PT.pset[p] * PS;
                     push<D>(t, 1.0, mc, Sc, yh, S);
+                    if (PT.pb) {      // cx_set_factor_offsets: y^ = A mu + b
+#pragma unroll
+                        for (int q = 0; q < D; q++) yh[q] += PT.pb[p * D + q];
+                    }
                     add_noise<D>(t + D * D, 0.0, S);
                 }
             }

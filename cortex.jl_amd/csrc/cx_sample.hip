@@ -44,6 +44,7 @@ extern "C" int32_t cx_sample_posterior(cx_handle *h, int64_t n_samples, uint64_t
         const char *bad = n_samples >= 1 && out && counts4 && (!variable_ids || n >= 0)
                               ? nullptr : "n_samples < 1, a null output or counts4, or a negative count with variable ids";
         if ((rc = cx::ev::prepare(h, who, bad, Ep)) != CX_OK) return rc;
+        CX_REQUIRE(h, !h->offsets_nonzero, CX_ERR_UNSUPPORTED, who + ": the handle has non-zero factor offsets (cx_set_factor_offsets), which this call does not implement");
         cx::ev::Cache &E = *Ep;
         cx::sp::Plan *Pp = nullptr;
         if ((rc = cx::sp::plan_of(h, E, who, Pp)) != CX_OK) return rc;

@@ -72,6 +72,8 @@ class DeviceGraph:
         self._check(self.lib.cx_graph_create(self.h, len(edge_var), _p(edge_var, C.c_int64), _p(edge_fac, C.c_int64),
                                              role, len(factor_ids), _p(factor_ids, C.c_int64),
                                              _p(factor_kind, C.c_int32), _p(fp, C.c_double)))
+        # kept on the host for the callers that need the factor -> parameter set map (learn.em with offsets)
+        self._factor_ids, self._factor_kind, self._factor_params = factor_ids.copy(), factor_kind.copy(), fp
 
     def set_factor_coefficients(self, variable_ids, factor_ids, a):
         """cx_set_factor_coefficients: a_i of the ROLE_IN edges of CX_FACTOR_GAUSS_LINEAR_N factors (default 1)"""
@@ -84,6 +86,20 @@ class DeviceGraph:
             raise ValueError(f"A and Q must be {self.dim}x{self.dim}")
         self._check(self.lib.cx_set_factor_matrices(self.h, int(parameter_set), _p(A, C.c_double), _p(Q, C.c_double)))
         self._n_sets = max(getattr(self, "_n_sets", 0), int(parameter_set) + 1)      # (the default n_groups of factor_statistics)
+
+    def set_factor_offsets(self, factor_ids, b):
+        """cx_set_factor_offsets (dim 2..4): the named two-variable CX_FACTOR_GAUSS_LINEAR factors become x_out = A x_in + b + N(0, Q);
+        b: [n, dim] (or [dim] for one factor).  Factors not named keep their offset (initially 0)."""
+        f = _i64(np.atleast_1d(factor_ids))
+        b = _f64(b).reshape(-1, self.dim) if len(f) else _f64(np.zeros((0, self.dim)))
+        if len(b) != len(f):
+            raise ValueError(f"b must be [{len(f)}, {self.dim}]")
+        self._check(self.lib.cx_set_factor_offsets(self.h, len(f), _p(f, C.c_int64) if len(f) else None, _p(b, C.c_double) if len(f) else None))
+
+    def linear_factors_of_set(self, parameter_set: int):
+        """the ids of the two-variable CX_FACTOR_GAUSS_LINEAR factors that name `parameter_set` (dim > 1), from what graph_create was given"""
+        lin = self._factor_kind == L.FACTOR_GAUSS_LINEAR
+        return self._factor_ids[lin & (self._factor_params[:, 0] == int(parameter_set))]
 
     def set_factor_edge_sets(self, variable_ids, factor_ids, parameter_sets):
         """cx_set_factor_edge_sets: dim 2..4, the A_i of ROLE_IN edges of CX_FACTOR_GAUSS_LINEAR_N factors by parameter set"""

@@ -73,13 +73,17 @@ def group(stats, g):
     return {k: np.asarray(v)[g] for k, v in stats.items()}
 
 
-def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q")):
+def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None):
     """EM on the parameter sets of a dim 2..4 DeviceGraph: per iteration sweep(sweeps_per_iter) → log_evidence → factor_statistics
     (one group per parameter set) → m_step → set_factor_matrices.
 
     sets: {set: (A, Q)}, the starting parameters (set on the handle here).  learn: a tuple for every set, or {set: tuple}.
     Returns (trace, params): trace[i] = log p(data) under the parameters of iteration i (n_iter + 1 values, the last under the final
     parameters) and params = {set: (A, Q)}.
+
+    offsets: None, or {set: b}: every two-variable CX_FACTOR_GAUSS_LINEAR factor of that set starts at x_out = A x_in + b + N(0, Q)
+    (DeviceGraph.set_factor_offsets; the factor → set map is what graph_create was given) and "b" may be learned for it: one b per set,
+    applied after each M-step beside (A, Q).  Then returns (trace, params, offsets) with offsets = {set: b}.
 
     The log-evidence trace is non-decreasing only where the E-step is exact: a chain-scan or tree sweep, or one reference-order
     call, on a forest.  Fused / flooding sweeps give Bethe beliefs (exact on forests only once converged) and loops give Bethe
@@ -93,6 +97,18 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q")):
     n_groups = max(params) + 1
     for s, (A, Q) in params.items():
         dev.set_factor_matrices(s, A, Q)
+    offs, facs = None, {}
+    if offsets is not None:
+        offs = {int(s): np.array(b, float).reshape(dev.dim) for s, b in offsets.items()}
+        if not set(offs) <= set(params):
+            raise ValueError("em: offsets names a set that sets does not")
+        for s, b in offs.items():
+            facs[s] = dev.linear_factors_of_set(s)
+            dev.set_factor_offsets(facs[s], np.tile(b, (len(facs[s]), 1)))
+    for s in params:
+        ls = learn.get(s, ("A", "Q")) if isinstance(learn, dict) else learn
+        if "b" in ls and offs is not None and s not in offs:
+            raise ValueError(f'em: "b" is learned for the sets that offsets names (set {s} is not one)')
     trace = []
     for it in range(n_iter + 1):
         dev.sweep(sweeps_per_iter)
@@ -105,7 +121,12 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q")):
             ls = learn.get(s, ("A", "Q")) if isinstance(learn, dict) else learn
             if not ls:
                 continue
-            new = m_step(group(stats, s), A, learn=ls)
+            new = m_step(group(stats, s), A, b=None if offs is None else offs.get(s), learn=ls)
             params[s] = (new["A"], Q if new["Q"] is None else new["Q"])
             dev.set_factor_matrices(s, *params[s])
+            if offs is not None and s in offs:
+                offs[s] = new["b"]
+                dev.set_factor_offsets(facs[s], np.tile(offs[s], (len(facs[s]), 1)))
+    if offs is not None:
+        return trace, params, offs
     return trace, params

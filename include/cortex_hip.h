@@ -87,7 +87,8 @@ extern "C" {
 #define CX_FACTOR_OPAQUE 0          /* messages only ever set by the caller (priors, unary observations) */
 #define CX_FACTOR_GAUSS_ADDITIVE 1  /* 2 edges: x_b = x_a + N(0, q)            params = {q}                */
 #define CX_FACTOR_GAUSS_LINEAR 2    /* 2 edges: x_out = a*x_in + b + N(0, q)   params = {q, a, b}          */
-                                    /* dim>1:   x_out = A x_in + N(0, Q)       params via cx_set_factor_matrices */
+                                    /* dim>1:   x_out = A x_in + b + N(0, Q)   (A, Q) via cx_set_factor_matrices; b per factor, 0 unless set
+                                                                               by cx_set_factor_offsets (dim 2 - 4) */
 #define CX_FACTOR_NORMAL_PRECISION 3 /* 3 edges: x_out ~ N(x_in, 1 / precision); roles OUT, IN, PRECISION — the :likelihood and
                                        :transition factors of test/inference_engine_tests.jl:691-715.  Variational rules only: the
                                        CX_FAMILY_VMP_* families, or CX_FAMILY_GAUSSIAN under CX_SCHED_REFERENCE with a user wiring
@@ -232,8 +233,8 @@ int32_t cx_set_stream(cx_handle *h, void *hip_stream); /* run on the caller's hi
 int32_t cx_graph_create(cx_handle *h, int64_t n_edges, const int64_t *edge_var, const int64_t *edge_fac,
                         const int32_t *edge_role, int64_t n_factors, const int64_t *factor_ids,
                         const int32_t *factor_kind, const double *factor_params);
-/* dim > 1: parameter set `parameter_set` of the linear-Gaussian factors x_out = A x_in + N(0, Q); A, Q are d x d row-major,
- * Q symmetric positive definite.  A CX_FACTOR_GAUSS_LINEAR factor names its set in factor_params[0]; its ROLE_IN edge carries
+/* dim > 1: parameter set `parameter_set` of the linear-Gaussian factors x_out = A x_in + b + N(0, Q); A, Q are d x d row-major,
+ * Q symmetric positive definite; b is the factor's own (cx_set_factor_offsets, dim 2 - 4; 0 otherwise).  A CX_FACTOR_GAUSS_LINEAR factor names its set in factor_params[0]; its ROLE_IN edge carries
  * x_in.  (The reference leaves Factor.functional_form opaque, model_engine.jl:119-122; this is what the user rule reads.) */
 int32_t cx_set_factor_matrices(cx_handle *h, int64_t parameter_set, const double *A, const double *Q);
 /* a_i of ROLE_IN edges of CX_FACTOR_GAUSS_LINEAR_N factors (finite, non-zero; default 1).  Takes effect at the next sweep. */
@@ -587,7 +588,8 @@ int32_t cx_factor_beliefs(cx_handle *h, int64_t n, const int64_t *factor_ids, do
 
 /* cx_factor_statistics: the expected sufficient statistics of EM (Shumway–Stoffer), summed per group of factors that share A, in
  * RESIDUAL coordinates r = x_out - A x_in - b under the factor's current parameters (dim 1: (a, b) of CX_FACTOR_GAUSS_LINEAR, (1, 0)
- * of CX_FACTOR_GAUSS_ADDITIVE; dim 2 - 4: the parameter set's A, b = 0).  out: n_groups rows of 1 + 2d + 3d^2 doubles,
+ * of CX_FACTOR_GAUSS_ADDITIVE; dim 2 - 4: the parameter set's A and the factor's own b — cx_set_factor_offsets, 0 unless set; factors of
+ * one group may differ in b, as they may in q at dim 1).  out: n_groups rows of 1 + 2d + 3d^2 doubles,
  *     n_g | Σ E[r] (d) | Σ E[x_in] (d) | Σ E[r r'] (d x d) | Σ E[r x_in'] (d x d) | Σ E[x_in x_in'] (d x d)     (row-major)
  * from which the M-step is  ΔA = S_rx S_xx^-1,  A' = A + ΔA,  Q' = (S_rr - ΔA S_rx') / n_g  (a Q-only update: Q' = S_rr / n_g).
  * Sums are compensated (f64) and taken in a fixed order: two calls on one state are bit-identical.
@@ -746,6 +748,32 @@ int32_t cx_linear_moments(cx_handle *h, int64_t n_functionals, const int64_t *of
 #define CX_CAUSAL_PREDICTED 0
 #define CX_CAUSAL_FILTERED 1
 int32_t cx_causal_marginals(cx_handle *h, int32_t mode, int32_t lag, int64_t n, const int64_t *variable_ids, double *out, int64_t *counts4);
+
+/* ---- per-factor offsets, dim 2 - 4 (added after ABI 9: a new function breaks no caller, CX_ABI_VERSION stays; the reference has no
+ * d-dimensional rule at all) ----
+ * cx_set_factor_offsets: the two-variable CX_FACTOR_GAUSS_LINEAR factors named become x_out = A x_in + b + N(0, Q) with b = offsets[i]
+ * (offsets: [n][dim], row-major) — a control input B u_t, a drift, an observation mean, a regression effect: whatever enters a factor as
+ * a constant.  (A, Q) stay the parameter set's.  Offsets of factors not named keep their value; the initial value is 0; a later call
+ * replaces the named factors' offsets; n == 0 changes no offset and still marks the handle as having offsets.
+ * What it does: the factor's potential gains the linear terms g_out = Q^-1 b, g_in = -A' Q^-1 b; every message from the
+ * sending end s to the receiving end p keeps its precision and has eta_p = g_p + B (Lambda_s + P)^-1 (eta_s + g_s) (an observed sender:
+ * eta_p = g_p + B y, the message N(A y + b, Q)).  Covered: CX_SCHED_FUSED (degree > 8 and damping included), CX_SCHED_CHAIN_SCAN
+ * (marginals and messages on demand included), CX_SCHED_TREE (level plans, heavy paths, the captured sweep), cx_update_batch message
+ * items, cx_residual / cx_sweep_until, and of the derived calls cx_log_evidence, cx_factor_beliefs, cx_factor_statistics (r uses the
+ * factor's own b) and cx_predictive (y^ = A mu + b).  cx_sample_posterior, cx_linear_moments and cx_causal_marginals return
+ * CX_ERR_UNSUPPORTED, naming this function, while any offset is non-zero, and work as before once all are 0 again.
+ * cx_set_factor_matrices afterwards keeps b and recomputes the linear terms.  The offsets are rule parameters: part of the checkpoint
+ * fingerprint once the function has been called (a blob taken under other offsets, or none, is refused; handles that never called it
+ * exchange blobs as before).
+ * A handle on which the function was never called launches the kernels it always launched; a handle whose offsets are all 0 computes the
+ * same numbers (==) through the offset instances of the kernels.
+ * Refused: dim 1 CX_ERR_STATE (dim 1 factors carry b in their parameters); dim 5 - 64, other families, CX_SCHED_REFERENCE handles (wired
+ * or not: the reference order has nothing to pin a d-dimensional offset against), a partitioned handle (halo lists, state halos, a
+ * chain's time block — and configuring a halo or asking for block maps on a handle that has offsets) CX_ERR_UNSUPPORTED; a factor of
+ * another kind (CX_FACTOR_GAUSS_LINEAR_N included) CX_ERR_UNSUPPORTED, naming it; an unknown id CX_ERR_NOT_FOUND; a non-finite entry,
+ * n < 0 or NULL arrays with n > 0 CX_ERR_INVALID_ARGUMENT; no graph or a captured stream CX_ERR_STATE.  A refused call changes nothing.
+ * Synchronous. */
+int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets);
 
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)

@@ -76,6 +76,12 @@ class Handle {
     void set_factor_matrices(int64_t parameter_set, const std::vector<double> &A, const std::vector<double> &Q) {
         check(cx_set_factor_matrices(h_, parameter_set, A.data(), Q.data()));
     }
+    // dim 2 - 4: the named two-variable CX_FACTOR_GAUSS_LINEAR factors become x_out = A x_in + b + N(0, Q); offsets: dim doubles per factor
+    // (cx_set_factor_offsets; factors not named keep theirs, initially 0)
+    void set_factor_offsets(const std::vector<int64_t> &factor_ids, const std::vector<double> &offsets) {
+        need(offsets.size(), factor_ids.size() * (size_t)dim_, "set_factor_offsets offsets");
+        check(cx_set_factor_offsets(h_, (int64_t)factor_ids.size(), factor_ids.empty() ? nullptr : factor_ids.data(), offsets.empty() ? nullptr : offsets.data()));
+    }
     cx_stats stats() const { cx_stats s{}; check(cx_graph_stats(h_, &s)); return s; }
     // CX_SCHED_TREE: { depth, stages, items, k-ary entries, components, messages up, messages down, marginals } of the last sweep's plan
     std::array<int64_t, 8> tree_plan_stats() const { std::array<int64_t, 8> o{}; check(cx_tree_plan_stats(h_, o.data())); return o; }

@@ -45,7 +45,7 @@ function HipProcessor(; device = 0, dim = 1, schedule = 1, marginals = 1)
 end
 
 # graph ingestion through the reference's own accessors (model_engine.jl:329-391).  Directed factors (CX_FACTOR_GAUSS_LINEAR:
-# x_out = a x_in + b + N(0, q), or x_out = A x_in + N(0, Q) for dim > 1) read the edge roles from Connection.label:
+# x_out = a x_in + b + N(0, q), or x_out = A x_in + b + N(0, Q) for dim > 1, b by set_factor_offsets!) read the edge roles from Connection.label:
 # role_of(engine, v, f) -> 0 (:out) | 1 (:in).  For dim > 1 params_of returns (parameter_set, 0, 0, 0) and the matrices of
 # every set are supplied with set_factor_matrices! BEFORE the first sweep / batch.
 function upload!(p::HipProcessor, engine::Cortex.InferenceEngine, kind_of, params_of; role_of = (engine, v, f) -> 0)
@@ -65,6 +65,14 @@ end
 set_factor_matrices!(p::HipProcessor, set, A::Matrix{Float64}, Q::Matrix{Float64}) =
     check(p.handle, ccall((:cx_set_factor_matrices, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}),
                           p.handle, set, collect(transpose(A)), collect(transpose(Q))))
+
+# dim 2 - 4: the two-variable CX_FACTOR_GAUSS_LINEAR factors `factor_ids` become x_out = A x_in + b + N(0, Q), b = column i of `offsets`
+# (d x n; cx_set_factor_offsets, added after ABI 9): a control input, a drift, an observation mean.  Factors not named keep theirs (initially 0)
+function set_factor_offsets!(p::HipProcessor, factor_ids::Vector{Int64}, offsets::Matrix{Float64})
+    size(offsets) == (p.dim, length(factor_ids)) || throw(ArgumentError("offsets must be dim x length(factor_ids)"))
+    check(p.handle, ccall((:cx_set_factor_offsets, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}),
+                          p.handle, length(factor_ids), factor_ids, offsets))
+end
 
 # where the user calls set_value!(message_to_factor(y, likelihood), datum): a Real for dim == 1, a length-d vector for dim > 1
 function set_datum!(p::HipProcessor, signal::Cortex.InferenceSignal, datum)
