@@ -16,6 +16,10 @@
 //          (k_ev_kary)  one thread per factor of 3 .. 7 variables, its joint precision (up to 28 x 28) packed in LDS
 //   k_ev_final          the per-block partial sums (compensated, f64) in a fixed order: two calls on one state are bit-identical
 // The counters travel with the partial sums (per block, then in index order): no atomics at all.
+//
+// cx_log_evidence_components: the same terms summed per connected component of the graph — the passes' term entries
+// write one term per thread, k_ev_seg / k_ev_span add them up over the terms sorted by component (a segmented scan; no atomics either).
+#include "cx_components.h"
 #include "cx_evidence_core.h"
 
 namespace cx {
@@ -24,13 +28,23 @@ namespace ev {
 constexpr int kKB = 16;        // threads per block of the k-ary pass: each thread's joint precision lives in LDS
 constexpr int kFB = 1024;      // threads of the one block of the final sum (C4: 23 k block partials)
 
+// Every pass has two entries over one body: the one cx_log_evidence launches (TERMS false: the block's Part, block_part) and the term
+// entry of cx_log_evidence_components (TERMS true: the thread's term and flag bits at its index, coalesced; the caller passes the
+// arrays offset to the pass's first term)
+template <bool TERMS>
+using PassOut = std::conditional_t<TERMS, TermOut, Part *__restrict__>;
+__device__ __forceinline__ void put_term(const TermOut &o, int64_t i, double s, double c, bool vterm, bool undef, bool npd, bool ghost) {
+    o.val[i] = s + c;
+    o.flag[i] = (uint8_t)((vterm ? kTermVar : 0u) | (undef ? kTermUndef : 0u) | (npd ? kTermNpd : 0u) | (ghost ? kTermGhost : 0u));
+}
+
 // ---- pass 1: variables ----------------------------------------------------------------------------------------------------------
 // vrec[v] = d_v (low 24 bits) | opaque mask of the SELL slots (bits 24..31); variables of the CSR tail read tail_opq[slot - tail0]
-template <int D>
+template <int D, bool TERMS = false>
 __global__ __launch_bounds__(kB) void k_ev_var(int64_t nv, const int32_t *__restrict__ vbase, const int32_t *__restrict__ vdeg,
                                                const uint8_t *__restrict__ vinfo, const int32_t *__restrict__ vrec,
                                                const uint8_t *__restrict__ tail_opq, int32_t tail0, const double *__restrict__ f2v,
-                                               double *__restrict__ W, Part *__restrict__ partial) {
+                                               double *__restrict__ W, PassOut<TERMS> partial) {
     constexpr int NT = Lay<D>::NT, K = Lay<D>::K;
     const int64_t v = (int64_t)blockIdx.x * kB + threadIdx.x;
     double s = 0.0, c = 0.0;
@@ -121,14 +135,15 @@ __global__ __launch_bounds__(kB) void k_ev_var(int64_t nv, const int32_t *__rest
             }
         }
     }
-    block_part<kB>(s, c, vterm, undef_t, npd_t, ghost, partial);
+    if constexpr (TERMS) { if (v < nv) put_term(partial, v, s, c, vterm, undef_t, npd_t, ghost); }
+    else block_part<kB>(s, c, vterm, undef_t, npd_t, ghost, partial);
 }
 
 // ---- pass 2: factors of two variables -------------------------------------------------------------------------------------------
 // x_out = A x_in + b + N(0, Q): log z_a = -½ rc'Q⁻¹rc - ½ log det 2πQ + ½ h'J⁻¹h - ½ log det J + (free entries) ½ log 2π, with J, h of
 // ev::pair_joint.  Both ends free: the 2d x 2d joint; one end observed (half the factors of a state-space chain): its d x d block
-template <int D>
-__global__ __launch_bounds__(kB) void k_ev_pair(int64_t n, PairTab tab, Msgs msg, Part *__restrict__ partial) {
+template <int D, bool TERMS = false>
+__global__ __launch_bounds__(kB) void k_ev_pair(int64_t n, PairTab tab, Msgs msg, PassOut<TERMS> partial) {
     const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
     double s = 0.0, c = 0.0;
     bool undef_t = false, npd_t = false;
@@ -158,14 +173,15 @@ __global__ __launch_bounds__(kB) void k_ev_pair(int64_t n, PairTab tab, Msgs msg
         npd_t = B.ok && !pd;
         if (B.ok && pd) neu(s, c, lz);
     }
-    block_part<kB>(s, c, 0, undef_t, npd_t, 0, partial);
+    if constexpr (TERMS) { if (i < n) put_term(partial, i, s, c, false, undef_t, npd_t, false); }
+    else block_part<kB>(s, c, 0, undef_t, npd_t, 0, partial);
 }
 
 // ---- pass 2: factors of 3 .. 7 variables ----------------------------------------------------------------------------------------
 // The joint precision over the free entries (ev::kary_joint: packed lower triangle, up to 28 x 28) and its right-hand side live in LDS,
 // thread-interleaved.
-template <int D>
-__global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, KaryTab tab, Msgs msg, Part *__restrict__ partial) {
+template <int D, bool TERMS = false>
+__global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, KaryTab tab, Msgs msg, PassOut<TERMS> partial) {
     constexpr int NP = KLay<D>::NP, NM = KLay<D>::NM;
     __shared__ double sJ[NP * kKB], sh[NM * kKB];
     const int t = threadIdx.x;
@@ -194,7 +210,8 @@ __global__ __launch_bounds__(kKB) void k_ev_kary(int64_t n, KaryTab tab, Msgs ms
         npd_t = ok && !pd;
         if (ok && pd) neu(s, c, lz);
     }
-    block_part<kKB>(s, c, 0, undef_t, npd_t, 0, partial);
+    if constexpr (TERMS) { if (f < n) put_term(partial, f, s, c, false, undef_t, npd_t, false); }
+    else block_part<kKB>(s, c, 0, undef_t, npd_t, 0, partial);
 }
 
 // ---- the partial sums and counters in index order; out = value | counters[kNCnt] (u64) ------------------------------------------
@@ -227,6 +244,141 @@ __global__ __launch_bounds__(kFB) void k_ev_final(int64_t n, const Part *__restr
     }
     if (t == 0) out[0] = ss[0] + cs[0];
     if (t < kNCnt) reinterpret_cast<unsigned long long *>(out)[1 + t] = ns[t][0];
+}
+
+// ---- the terms summed per component (cx_log_evidence_components) ---------------------------------------------------
+// The terms sorted by (component, term index) lie at the positions of comp::sort_terms, cut into tiles of kTile positions, one block
+// each.  A block reduces every run of one component inside its tile by a segmented scan (head flag: the component differs from the
+// position before; the tile's first position is a head): four positions per thread in order, the threads' aggregates by wave64
+// shuffles, the waves' through LDS.  A component of up to kTile terms lies inside one tile (its alignment) and goes straight to cval /
+// ccnt; a longer one starts a tile, is the first run of every tile it reaches, leaves one TilePart per tile, and k_ev_span adds those up
+// in tile order.  Every sum is compensated (neu) and taken in an order that the component's own terms fix (the alignment again): no
+// atomics, two calls are bit-identical, and a component's value does not depend on which others share the graph.
+constexpr int kSB = 256, kSI = 4, kTile = kSB * kSI;
+
+struct Acc {
+    double s, c;
+    unsigned long long n;      // the four counters, 16 bits each (a tile holds 1024 terms)
+};
+__device__ __forceinline__ void acc_add(Acc &a, const Acc &b) {      // a <- a + b, a's terms first
+    neu(a.s, a.c, b.s);
+    a.c += b.c;
+    a.n += b.n;
+}
+__device__ __forceinline__ Acc acc_shfl_up(const Acc &a, int off) { return {__shfl_up(a.s, off), __shfl_up(a.c, off), __shfl_up(a.n, off)}; }
+__device__ __forceinline__ void put_comp(const Acc &a, int k, double *__restrict__ cval, unsigned long long *__restrict__ ccnt) {
+    cval[k] = a.s + a.c;
+#pragma unroll
+    for (int q = 0; q < kNCnt; q++) ccnt[(int64_t)k * kNCnt + q] = (a.n >> (16 * q)) & 0xffffull;
+}
+
+// perm, key [npos], npos a multiple of kSI (the threads load four at once); -1: a position without a term
+__global__ __launch_bounds__(kSB) void k_ev_seg(int64_t npos, const int32_t *__restrict__ perm, const int32_t *__restrict__ key,
+                                                const int64_t *__restrict__ sbeg, const int64_t *__restrict__ send, const double *__restrict__ tval,
+                                                const uint8_t *__restrict__ tflag, TilePart *__restrict__ tpart, double *__restrict__ cval,
+                                                unsigned long long *__restrict__ ccnt) {
+    __shared__ Acc wv[kSB / 64];
+    __shared__ int wf[kSB / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t tile0 = (int64_t)blockIdx.x * kTile, tile1 = tile0 + kTile < npos ? tile0 + kTile : npos;
+    const int64_t p0 = tile0 + (int64_t)t * kSI;
+    int k[kSI + 1], kprev = -1;      // k[kSI]: the component of the position after the thread's (-1: no term there, -2: past the tile)
+    Acc x[kSI];
+#pragma unroll
+    for (int j = 0; j < kSI; j++) { k[j] = -2; x[j] = {0.0, 0.0, 0ull}; }
+    k[kSI] = -2;
+    if (p0 < tile1) {
+        const int4 pp = reinterpret_cast<const int4 *>(perm)[p0 / kSI], kk = reinterpret_cast<const int4 *>(key)[p0 / kSI];
+        const int pj[kSI] = {pp.x, pp.y, pp.z, pp.w}, kj[kSI] = {kk.x, kk.y, kk.z, kk.w};
+#pragma unroll
+        for (int j = 0; j < kSI; j++)
+            if (p0 + j < tile1 && kj[j] >= 0 && pj[j] >= 0) {
+                k[j] = kj[j];
+                const unsigned f = tflag[pj[j]];
+                x[j] = {tval[pj[j]], 0.0,
+                        (unsigned long long)(f & 1u) | (unsigned long long)((f >> 1) & 1u) << 16 | (unsigned long long)((f >> 2) & 1u) << 32 |
+                            (unsigned long long)((f >> 3) & 1u) << 48};
+            }
+        if (p0 > tile0) kprev = key[p0 - 1];
+        if (p0 + kSI < tile1) k[kSI] = key[p0 + kSI];
+    }
+    // the thread's aggregate: the sum of its positions after its last head (all of them without one) and whether it holds a head
+    Acc v = {0.0, 0.0, 0ull};
+    int fl = 0;
+#pragma unroll
+    for (int j = 0; j < kSI; j++) {
+        if (k[j] < 0) continue;
+        if (k[j] != (j ? k[j - 1] : kprev)) { fl = 1; v = x[j]; }
+        else acc_add(v, x[j]);
+    }
+    // inclusive segmented scan of the aggregates over the wave, then over the block's waves
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        Acc u = acc_shfl_up(v, off);
+        const int uf = __shfl_up(fl, off);
+        if (lane >= off) {
+            if (!fl) { acc_add(u, v); v = u; }
+            fl |= uf;
+        }
+    }
+    if (lane == 63) { wv[w] = v; wf[w] = fl; }
+    __syncthreads();
+    Acc carry = {0.0, 0.0, 0ull};      // the run that reaches the thread's first position from the positions before it
+    for (int i = 0; i < w; i++) {
+        if (wf[i]) carry = wv[i];
+        else acc_add(carry, wv[i]);
+    }
+    {
+        const Acc e = acc_shfl_up(v, 1);
+        const int ef = __shfl_up(fl, 1);
+        if (lane > 0) {
+            if (ef) carry = e;
+            else acc_add(carry, e);
+        }
+    }
+    // the runs that end at one of the thread's positions
+#pragma unroll
+    for (int j = 0; j < kSI; j++) {
+        if (k[j] < 0) continue;
+        if (k[j] != (j ? k[j - 1] : kprev)) carry = x[j];
+        else acc_add(carry, x[j]);
+        const int knext = p0 + j + 1 < tile1 ? k[j + 1] : -2;
+        if (knext == k[j]) continue;
+        if (sbeg[k[j]] >= tile0 && send[k[j]] <= tile1) put_comp(carry, k[j], cval, ccnt);
+        else tpart[blockIdx.x] = {carry.s, carry.c, carry.n};
+    }
+}
+
+// one wave per component of more than kTile terms: its pieces in tile order, lanes striding the tiles, then a fixed shuffle tree
+__global__ __launch_bounds__(kSB) void k_ev_span(int64_t ns, const int32_t *__restrict__ span, const int64_t *__restrict__ sbeg, const int64_t *__restrict__ send,
+                                                 const TilePart *__restrict__ tpart, double *__restrict__ cval, unsigned long long *__restrict__ ccnt) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (kSB / 64) + (threadIdx.x >> 6);
+    if (i >= ns) return;      // (the whole wave)
+    const int k = span[i];
+    const int64_t t0 = sbeg[k] / kTile, t1 = (send[k] - 1) / kTile;
+    double s = 0.0, c = 0.0;
+    unsigned long long m[kNCnt] = {0, 0, 0, 0};
+    for (int64_t tt = t0 + lane; tt <= t1; tt += 64) {
+        const TilePart p = tpart[tt];
+        neu(s, c, p.s);
+        c += p.c;
+#pragma unroll
+        for (int q = 0; q < kNCnt; q++) m[q] += (p.n >> (16 * q)) & 0xffffull;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double s2 = __shfl_down(s, off), c2 = __shfl_down(c, off);
+        neu(s, c, s2);
+        c += c2;
+#pragma unroll
+        for (int q = 0; q < kNCnt; q++) m[q] += __shfl_down(m[q], off);
+    }
+    if (lane == 0) {
+        cval[k] = s + c;
+#pragma unroll
+        for (int q = 0; q < kNCnt; q++) ccnt[(int64_t)k * kNCnt + q] = m[q];
+    }
 }
 
 // ---- host: the work lists -------------------------------------------------------------------------------------------------------
@@ -421,6 +573,65 @@ void launch(cx_handle *h, Cache &C) {
     final_sum(h, C.nb, part, C.d_out);
 }
 
+// the plan of cx_log_evidence_components: the labels, the terms sorted by (component, term index) into aligned positions, every
+// component's first and last position, the components of more than a tile, and the call's scratch
+int32_t build_components(cx_handle *h, Cache &C, const std::string &who) {
+    using namespace cxh;
+    const int64_t nv = h->nv, nf = h->nf, ne = h->ne, nt = nv + C.n_pair + C.n_kary;
+    CX_REQUIRE(h, nt < (int64_t)0x3fffffff, CX_ERR_UNSUPPORTED, who + ": more than 2^30 terms");
+    std::vector<int32_t> efac((size_t)ne);
+    for (int64_t e = 0; e < ne; e++) efac[(size_t)e] = (int32_t)find_factor(h, h->edge_fac_id[(size_t)e]);
+    C.n_comp = comp::label(nv, nf, ne, h->edge_var.data(), efac.data(), C.var_label, C.fac_label);
+    std::vector<int32_t> term_label((size_t)nt), perm, key, span;
+    std::vector<int64_t> beg, end;
+    std::copy(C.var_label.begin(), C.var_label.end(), term_label.begin());
+    C.comp_fac_terms.assign((size_t)C.n_comp, 0);
+    for (int64_t f = 0; f < nf; f++) {
+        const int32_t rp = C.row_of_fac[(size_t)f], rk = C.kary_row_of_fac[(size_t)f];
+        if (rp < 0 && rk < 0) continue;
+        term_label[(size_t)(rp >= 0 ? nv + rp : nv + C.n_pair + rk)] = C.fac_label[(size_t)f];
+        C.comp_fac_terms[(size_t)C.fac_label[(size_t)f]]++;
+    }
+    C.n_pos = comp::sort_terms(C.n_comp, term_label, kTile, kSI, perm, key, beg, end);
+    for (int64_t k = 0; k < C.n_comp; k++)
+        if (end[(size_t)k] - beg[(size_t)k] > kTile) span.push_back((int32_t)k);
+    C.n_term = nt; C.n_tile = (C.n_pos + kTile - 1) / kTile; C.n_span = (int64_t)span.size();
+    int32_t rc;
+    if ((rc = dev_upload(h, &C.d_perm, perm)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &C.d_key, key)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &C.d_sbeg, beg)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &C.d_send, end)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &C.d_span, span)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_tval, nt)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_tflag, nt)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_tpart, C.n_tile)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_cout, C.n_comp * (1 + kNCnt))) != CX_OK) return rc;
+    C.h_cout.assign((size_t)(C.n_comp * (1 + kNCnt)), 0.0);
+    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
+    C.comp_built = true;
+    return CX_OK;
+}
+
+template <int D>
+void launch_components(cx_handle *h, Cache &C) {
+    const int64_t nv = h->nv, nb_v = (nv + kB - 1) / kB, nb_p = (C.n_pair + kB - 1) / kB, nb_k = (C.n_kary + kKB - 1) / kKB;
+    const Msgs msg = msgs_of(h, C);
+    double *tv = C.d_tval;
+    uint8_t *tf = C.d_tflag;
+    if (nb_v)
+        k_ev_var<D, true><<<dim3((unsigned)nb_v), dim3(kB), 0, h->stream>>>(nv, h->d_vbase, h->d_var_deg, h->d_vinfo, C.d_vrec, C.d_tail, h->big_start,
+                                                                           f2v_of(h), C.d_W, TermOut{tv, tf});
+    if (nb_p) k_ev_pair<D, true><<<dim3((unsigned)nb_p), dim3(kB), 0, h->stream>>>(C.n_pair, C.pair_tab(), msg, TermOut{tv + nv, tf + nv});
+    if (nb_k)
+        k_ev_kary<D, true><<<dim3((unsigned)nb_k), dim3(kKB), 0, h->stream>>>(C.n_kary, C.kary_tab(), msg, TermOut{tv + nv + C.n_pair, tf + nv + C.n_pair});
+    double *cval = C.d_cout;
+    unsigned long long *ccnt = reinterpret_cast<unsigned long long *>(cval + C.n_comp);
+    if (C.n_tile)
+        k_ev_seg<<<dim3((unsigned)C.n_tile), dim3(kSB), 0, h->stream>>>(C.n_pos, C.d_perm, C.d_key, C.d_sbeg, C.d_send, C.d_tval, C.d_tflag, C.d_tpart, cval, ccnt);
+    if (C.n_span)
+        k_ev_span<<<dim3((unsigned)((C.n_span + kSB / 64 - 1) / (kSB / 64))), dim3(kSB), 0, h->stream>>>(C.n_span, C.d_span, C.d_sbeg, C.d_send, C.d_tpart, cval, ccnt);
+}
+
 }  // namespace ev
 
 template <> void Deleter<ev::Cache>::operator()(ev::Cache *C) const { delete C; }
@@ -476,4 +687,69 @@ extern "C" int32_t cx_log_evidence(cx_handle *h, double *value, int64_t *counts4
         *value = counts4[2] + counts4[3] > 0 ? kNaN : C.h_out[0];
         return CX_OK;
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence: host allocation failed"); }
+}
+
+extern "C" int32_t cx_graph_components(cx_handle *h, int64_t n, const int64_t *variable_ids, int64_t *component, int64_t *n_components) {
+    try {
+        CX_NOT_VMP(h, "cx_graph_components");
+        CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, "cx_graph_components: no graph");
+        CX_REQUIRE(h, n_components && (!variable_ids || n >= 0), CX_ERR_INVALID_ARGUMENT, "cx_graph_components: null n_components or n < 0");
+        // (the named variables are looked up first: a refused call writes nothing)
+        std::vector<int64_t> idx;
+        if (variable_ids && component)
+            for (int64_t i = 0; i < n; i++) {
+                const int64_t v = find_var(h, variable_ids[i]);
+                if (v < 0) return fail(h, CX_ERR_NOT_FOUND, "cx_graph_components: no variable " + std::to_string(variable_ids[i]));
+                idx.push_back(v);
+            }
+        // the labels of the evidence plan when a component call has built it (a handle has one graph for life), else a union-find now
+        std::vector<int32_t> mine, fl;
+        const bool planned = h->evidence && h->evidence->comp_built;
+        if (planned) *n_components = h->evidence->n_comp;
+        else {
+            std::vector<int32_t> efac((size_t)h->ne);
+            for (int64_t e = 0; e < h->ne; e++) efac[(size_t)e] = (int32_t)find_factor(h, h->edge_fac_id[(size_t)e]);
+            *n_components = cx::comp::label(h->nv, h->nf, h->ne, h->edge_var.data(), efac.data(), mine, fl);
+        }
+        const std::vector<int32_t> &vl = planned ? h->evidence->var_label : mine;
+        if (component && variable_ids) for (int64_t i = 0; i < n; i++) component[i] = vl[(size_t)idx[(size_t)i]];
+        else if (component) std::copy(vl.begin(), vl.end(), component);
+        return CX_OK;
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_graph_components: host allocation failed"); }
+}
+
+extern "C" int32_t cx_log_evidence_components(cx_handle *h, int64_t cap, double *values, int64_t *comp_counts4, int64_t *n_components, int64_t *counts4) {
+    try {
+        namespace ev = cx::ev;
+        ev::Cache *Cp = nullptr;
+        int32_t rc;
+        const char *bad = !n_components || !counts4 ? "null n_components or counts4" : cap < 0 ? "cap < 0" : cap > 0 && !values ? "cap > 0 with null values" : nullptr;
+        if ((rc = ev::prepare(h, "cx_log_evidence_components", bad, Cp, " (no variational free energy, no Beta-Bernoulli evidence)")) != CX_OK) return rc;
+        ev::Cache &C = *Cp;
+        if (!C.comp_built && (rc = ev::build_components(h, C, "cx_log_evidence_components")) != CX_OK) return rc;
+        ev::with_dim(h->cfg.dim, [&](auto D) { ev::launch_components<D()>(h, C); });
+        CX_HIP(h, hipGetLastError());
+        const int64_t nc = C.n_comp;
+        if (nc) CX_HIP(h, hipMemcpyAsync(C.h_cout.data(), C.d_cout, (size_t)(nc * (1 + ev::kNCnt)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        CX_HIP(h, hipStreamSynchronize(h->stream));
+        // the whole graph's counters are the sums of the components'
+        const double *val = C.h_cout.data();
+        const uint64_t *cnt = reinterpret_cast<const uint64_t *>(val + nc);
+        uint64_t tot[ev::kNCnt] = {0, 0, 0, 0};
+        for (int64_t k = 0; k < nc; k++)
+            for (int q = 0; q < ev::kNCnt; q++) tot[q] += cnt[k * ev::kNCnt + q];
+        CX_REQUIRE(h, tot[3] == 0, CX_ERR_UNSUPPORTED, "cx_log_evidence_components: the graph holds stand-in variables of a partition");
+        counts4[0] = C.n_pair + C.n_kary;
+        for (int q = 1; q < 4; q++) counts4[q] = (int64_t)tot[q - 1];
+        *n_components = nc;
+        for (int64_t k = 0; k < std::min(cap, nc); k++) {
+            const uint64_t *c = cnt + k * ev::kNCnt;
+            values[k] = c[1] + c[2] > 0 ? kNaN : val[k];
+            if (comp_counts4) {
+                comp_counts4[4 * k] = C.comp_fac_terms[(size_t)k];
+                for (int q = 1; q < 4; q++) comp_counts4[4 * k + q] = (int64_t)c[q - 1];
+            }
+        }
+        return CX_OK;
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence_components: host allocation failed"); }
 }

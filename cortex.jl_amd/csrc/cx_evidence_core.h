@@ -49,6 +49,19 @@ struct Part {
 // variables met (a halo handle: refused); the factor terms are known on the host
 constexpr int kNCnt = 4;
 
+// one term of cx_log_evidence_components: its flag bits, in the counters' order
+constexpr unsigned kTermVar = 1, kTermUndef = 2, kTermNpd = 4, kTermGhost = 8;
+// where the term entry of a pass writes: the term's value (the thread's compensated sum as one double) and flag bits at its term index
+struct TermOut {
+    double *val;
+    uint8_t *flag;
+};
+// the piece of one component inside one tile of the sorted term list: a compensated sum and the four counters, 16 bits each
+struct TilePart {
+    double s, c;
+    unsigned long long n;
+};
+
 // fixed-order tree over the block's threads; thread 0 writes the block's Part
 template <int NB>
 __device__ __forceinline__ void block_part(double s, double c, unsigned n0, unsigned n1, unsigned n2, unsigned n3, Part *__restrict__ out) {
@@ -546,6 +559,20 @@ struct Cache {
     DevBuf<Part> d_partial;
     DevBuf<double> d_out;
     double *h_out = nullptr;              // value | counters, pinned
+    // cx_log_evidence_components: the plan of the first component call, dropped with the cache.  Terms: index v for
+    // variable v, nv + pair row, nv + n_pair + k-ary row; sorted by (component, term index) into aligned positions
+    bool comp_built = false;
+    int64_t n_comp = 0, n_term = 0, n_pos = 0, n_tile = 0, n_span = 0;
+    std::vector<int32_t> var_label, fac_label;      // component of every variable / factor index
+    std::vector<int64_t> comp_fac_terms;            // [C] the factor terms of every component
+    DevBuf<int32_t> d_perm, d_key;        // [n_pos] the term at every position and its component (-1: none; comp::sort_terms)
+    DevBuf<int64_t> d_sbeg, d_send;       // [C] first position of every component and the one past its last
+    DevBuf<int32_t> d_span;               // [n_span] the components of more than a tile of terms
+    DevBuf<double> d_tval;                // [n_term] the terms
+    DevBuf<uint8_t> d_tflag;              // [n_term] their flag bits (kTermVar ..)
+    DevBuf<TilePart> d_tpart;             // [n_tile] the piece of the long component that reaches the tile
+    DevBuf<double> d_cout;                // [C] values | [C][kNCnt] counters (u64)
+    std::vector<double> h_cout;
     Cache() = default;
     Cache(const Cache &) = delete;
     ~Cache() { if (h_out) (void)hipHostFree(h_out); }

@@ -11,12 +11,14 @@
 //   cxh_lattice_deep_interior  which waves of the deep sweep take the interior instance, beside what the general predicates say of them
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
 //                  plain struct with cx_handle's host fields
+//   cxh_flat_components  the connected components of the flattened graph (cx_components.h)
 #include <cstdio>
 #include <cstring>
 #include <new>
 
 #include "cx_chain64_plan.h"
 #include "cx_chains.h"
+#include "cx_components.h"
 #include "cx_derived.h"
 #include "cx_halo_plan.h"
 #include "cx_lattice_plan.h"
@@ -459,6 +461,18 @@ int32_t cxh_lattice_deep_interior(int32_t K, int32_t W, int32_t H, int32_t R, in
             general[w] = (int8_t)all;
         }
     return nstrips * nseg;
+}
+
+// the connected components of the flattened graph (cx_components.h): var_label [nv] by variable index (ascending id), fac_label [nf] by
+// factor index (ascending id); either may be NULL.  Returns the number of components
+int64_t cxh_flat_components(const void *p, int64_t *var_label, int64_t *fac_label) {
+    const HostGraph *g = (const HostGraph *)p;
+    std::vector<int32_t> efac((size_t)g->ne), vl, fl;
+    for (int64_t e = 0; e < g->ne; e++) efac[(size_t)e] = (int32_t)(std::lower_bound(g->fac_ids.begin(), g->fac_ids.end(), g->edge_fac_id[(size_t)e]) - g->fac_ids.begin());
+    const int64_t C = cx::comp::label(g->nv, g->nf, g->ne, g->edge_var.data(), efac.data(), vl, fl);
+    if (var_label) std::copy(vl.begin(), vl.end(), var_label);
+    if (fac_label) std::copy(fl.begin(), fl.end(), fac_label);
+    return C;
 }
 
 // array `which` of the graph: returns its length, copies it as int64 (or as doubles for the floating-point ones) when out != NULL

@@ -313,6 +313,39 @@ class DeviceGraph:
         self._check(self.lib.cx_log_evidence(self.h, C.byref(val), out))
         return float(val.value), dict(zip(("factor_terms", "variable_terms", "undefined", "not_positive_definite"), [int(x) for x in out]))
 
+    def components(self, variable_ids=None):
+        """cx_graph_components: (labels, n_components) — the connected component of every named variable (None: every variable in
+        ascending id) of the graph as graph_create received it.  Observed variables and opaque factors are nodes like any other;
+        components are numbered by their least variable id.  Host work only."""
+        nc = C.c_int64()
+        if variable_ids is None:
+            ids, n = None, self.stats()["n_variables"]
+        else:
+            ids = _i64(np.atleast_1d(variable_ids))
+            n = len(ids)
+        out = np.zeros(n, dtype=np.int64)
+        self._check(self.lib.cx_graph_components(self.h, 0 if ids is None else n, None if ids is None else _p(ids, C.c_int64),
+                                                 _p(out, C.c_int64) if n else None, C.byref(nc)))
+        return out, int(nc.value)
+
+    def log_evidence_components(self, cap=None):
+        """cx_log_evidence_components: log p(data) of every connected component from the stored messages.  Returns (values [C],
+        comp_counts [C, 4], counts): values[k] sums the terms of log_evidence that belong to component k and is NaN when one of them
+        read an undefined message or a belief that is not positive definite (the other components keep their values); comp_counts[k]
+        = (factor terms, variable terms, undefined, not positive definite) of component k; counts is log_evidence's dict for the
+        whole graph.  cap: return the first min(cap, C) components only."""
+        nc = C.c_int64()
+        if getattr(self, "_n_components", None) is None:      # (a handle has one graph for life: counted once, host work)
+            self._check(self.lib.cx_graph_components(self.h, 0, None, None, C.byref(nc)))
+            self._n_components = int(nc.value)
+        n = self._n_components if cap is None else min(int(cap), self._n_components)
+        val = np.zeros(n, dtype=np.float64)
+        cc = np.zeros((n, 4), dtype=np.int64)
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.cx_log_evidence_components(self.h, n, _p(val, C.c_double) if n else None, _p(cc, C.c_int64) if n else None,
+                                                        C.byref(nc), out))
+        return val, cc, dict(zip(("factor_terms", "variable_terms", "undefined", "not_positive_definite"), [int(x) for x in out]))
+
     def factor_beliefs(self, factor_ids):
         """cx_factor_beliefs: the joint posterior of two-variable Gaussian factors from the stored messages, (means [n, 2d],
         covariances [n, 2d, 2d]) in the order (out, in) — ADDITIVE: the lower variable id first.  Observed entries are the datum with

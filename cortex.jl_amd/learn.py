@@ -73,7 +73,7 @@ def group(stats, g):
     return {k: np.asarray(v)[g] for k, v in stats.items()}
 
 
-def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None):
+def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_component=False):
     """EM on the parameter sets of a dim 2..4 DeviceGraph: per iteration sweep(sweeps_per_iter) → log_evidence → factor_statistics
     (one group per parameter set) → m_step → set_factor_matrices.
 
@@ -84,6 +84,10 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None):
     offsets: None, or {set: b}: every two-variable CX_FACTOR_GAUSS_LINEAR factor of that set starts at x_out = A x_in + b + N(0, Q)
     (DeviceGraph.set_factor_offsets; the factor → set map is what graph_create was given) and "b" may be learned for it: one b per set,
     applied after each M-step beside (A, Q).  Then returns (trace, params, offsets) with offsets = {set: b}.
+
+    by_component=True: the trace is an array [n_iter + 1, C], row i = DeviceGraph.log_evidence_components under the parameters of
+    iteration i, one column per connected component.  On a synth.replicas graph (replica k's sets are k * S + s) this is multi-start EM
+    in one handle: the statistics are grouped by set, so every replica is updated from its own, and its column is its own trace.
 
     The log-evidence trace is non-decreasing only where the E-step is exact: a chain-scan or tree sweep, or one reference-order
     call, on a forest.  Fused / flooding sweeps give Bethe beliefs (exact on forests only once converged) and loops give Bethe
@@ -112,8 +116,11 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None):
     trace = []
     for it in range(n_iter + 1):
         dev.sweep(sweeps_per_iter)
-        value, cnt = dev.log_evidence()
-        trace.append(value)
+        if by_component:
+            trace.append(dev.log_evidence_components()[0])
+        else:
+            value, cnt = dev.log_evidence()
+            trace.append(value)
         if it == n_iter:
             break
         stats, _ = dev.factor_statistics(n_groups=n_groups)
@@ -127,6 +134,30 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None):
             if offs is not None and s in offs:
                 offs[s] = new["b"]
                 dev.set_factor_offsets(facs[s], np.tile(offs[s], (len(facs[s]), 1)))
+    if by_component:
+        trace = np.array(trace, dtype=np.float64).reshape(n_iter + 1, -1)
     if offs is not None:
         return trace, params, offs
     return trace, params
+
+
+def profile(model, candidates, schedule=L.SCHED_TREE):
+    """The log-likelihood of one dim 2..4 model under K candidate parameter sets from ONE handle and one exact sweep: K replicas of the
+    model as one graph (synth.replicas), one component each.  candidates: a list of {set: (A, Q)}; a set a candidate does not name
+    falls back to model.psets.  schedule: an exact one for the model (SCHED_TREE, or SCHED_CHAIN_SCAN on chains).
+    Returns (loglik [K], comp_counts [K, 4]) of DeviceGraph.log_evidence_components: loglik[k] = log p(data | candidate k), NaN when
+    that replica read an undefined message or a belief that is not positive definite (comp_counts[k, 2:])."""
+    from . import synth
+    from .device import DeviceGraph
+
+    rep = synth.replicas(model, list(candidates))
+    dev = DeviceGraph(dim=model.dim, schedule=schedule)
+    try:
+        synth.load_into_device(rep, dev)
+        dev.sweep(1)
+        values, comp_counts, _ = dev.log_evidence_components()
+    finally:
+        dev.close()
+    if len(values) != len(rep.meta["replica_offset"]):
+        raise ValueError("profile: the model is not one connected component (its replicas are not the components of the graph)")
+    return values, comp_counts

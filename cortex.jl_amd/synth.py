@@ -241,6 +241,48 @@ def concat_models(models) -> Model:
                  psets=first.psets, meta={"parts": [(len(m.x_ids), o) for m, o in parts], "kind": "concat"})
 
 
+def replicas(model: Model, psets_list) -> Model:
+    """K copies of one dim 2..4 model as ONE graph of disjoint components (ids shifted past each other, as concat_models does), replica k
+    under its own parameter sets: psets_list[k] = {set: (A, Q)}, a set it does not name falls back to model.psets.  Set s of replica k
+    is renumbered k * S + s with S = 1 + the model's largest set; psets holds the K * S entries (of the sets the model has);
+    meta["replica_offset"] lists the id shifts, meta["S"] = S.  One exact sweep and DeviceGraph.log_evidence_components then give the K
+    log-likelihoods of the one series (a likelihood profile); with learn.em(by_component=True), multi-start EM in one handle."""
+    if model.dim < 2:
+        raise ValueError("replicas: dim 2..4 (dim 1 factors carry their own parameters)")
+    K = len(psets_list)
+    if K < 1:
+        raise ValueError("replicas: no parameter sets")
+    S = 1 + max(int(s) for s in model.psets)
+    step = int(max(model.edge_var.max(), model.edge_fac.max()))
+    rule = np.asarray(model.factor_kind) != L.FACTOR_OPAQUE
+    fv = np.asarray(model.factor_var, dtype=np.float64)
+
+    def sets_of(k):
+        out = fv.copy()
+        if out.ndim == 1:
+            out[rule] += k * S
+        else:
+            out[rule, 0] += k * S
+        return out
+
+    psets = {}
+    for k, ps in enumerate(psets_list):
+        unknown = set(int(s) for s in ps) - set(int(s) for s in model.psets)
+        if unknown:
+            raise ValueError(f"replicas: candidate {k} names sets the model does not have: {sorted(unknown)}")
+        for s, AQ in model.psets.items():
+            A, Q = ps.get(s, AQ)
+            psets[k * S + int(s)] = (np.array(A, dtype=np.float64), np.array(Q, dtype=np.float64))
+    offs = [k * step for k in range(K)]
+    cat = lambda f: np.concatenate([f(o) for o in offs])
+    return Model(edge_var=cat(lambda o: model.edge_var + o), edge_fac=cat(lambda o: model.edge_fac + o),
+                 factor_ids=cat(lambda o: model.factor_ids + o), factor_kind=np.concatenate([model.factor_kind] * K),
+                 factor_var=np.concatenate([sets_of(k) for k in range(K)]), x_ids=cat(lambda o: model.x_ids + o),
+                 data_var=cat(lambda o: model.data_var + o), data_fac=cat(lambda o: model.data_fac + o),
+                 data_y=np.concatenate([model.data_y] * K), dim=model.dim, edge_role=np.concatenate([model.edge_role] * K),
+                 psets=psets, meta={"kind": "replicas", "replica_offset": offs, "S": S, "K": K, "parts": [(len(model.x_ids), o) for o in offs]})
+
+
 def kary_model(n_factors: int, seed: int = 1234, tree: bool = True, k_choices=(2, 3, 4, 5, 6), observe: float = 0.0) -> Model:
     """Scalar model with linear-Gaussian factors of MORE than two edges (CX_FACTOR_GAUSS_LINEAR_N): x_out = sum_i a_i x_i + b + N(0, q),
     k in `k_choices` inputs each, plus a unary prior factor on every latent variable (message set by the caller, as the prior of

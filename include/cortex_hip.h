@@ -775,6 +775,38 @@ int32_t cx_causal_marginals(cx_handle *h, int32_t mode, int32_t lag, int64_t n, 
  * Synchronous. */
 int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets);
 
+/* ---- connected components and the log-evidence of each (added after ABI 9: a new function breaks no caller, CX_ABI_VERSION stays; no
+ * counterpart in the reference) ----
+ * One handle may hold many independent models (a panel of series, K replicas of one series under K candidate parameter sets): the
+ * connected components of the bipartite graph exactly as cx_graph_create received it.  Two variables are in one component when a path
+ * of connections joins them; observed variables and opaque factors count like any other node, so the components depend on the graph
+ * alone, not on which variables are observed — an observed variable shared by two otherwise separate models joins them into ONE
+ * component.  Components are numbered 0 .. C-1 by their least variable id, ascending; a factor belongs to the component of its
+ * variables.
+ *
+ * cx_graph_components: component[i] = the component of variable_ids[i]; variable_ids == NULL: every variable in ascending id (n is
+ * ignored; cx_graph_stats gives n_variables).  component may be NULL when only *n_components is wanted.  Host work only (a union-find
+ * over the connections per call, O(connections); a lookup once cx_log_evidence_components has built its plan on the handle); every dim
+ * (1 - 64) and schedule once a graph exists.  No graph: CX_ERR_STATE; an unknown id:
+ * CX_ERR_NOT_FOUND, naming it; a NULL n_components or n < 0 with ids: CX_ERR_INVALID_ARGUMENT; the variational families keep their
+ * graph in another form: CX_ERR_UNSUPPORTED.
+ *
+ * cx_log_evidence_components: values[k] = the sum of exactly the terms of cx_log_evidence that belong to component k — the variable
+ * terms, the centred opaque terms that travel with them, the factor terms of two-variable and k-ary factors — from the same STORED
+ * messages.  It writes the first min(cap, C) entries of values and of comp_counts4 and *n_components = C;
+ * comp_counts4 may be NULL, otherwise it is [cap][4] with the meaning of cx_log_evidence's counts4 restricted to the component;
+ * cap == 0 with NULL arrays is the sizing call.  values[k] is NaN iff component k has a term with an undefined input or a belief that
+ * is not positive definite: the other components keep their values (cx_log_evidence's one total would be NaN).  counts4 is the whole
+ * graph's, equal to what cx_log_evidence returns.  The terms are summed per component on the device, compensated and in an order that
+ * the graph alone fixes (no atomics): two calls on one state are bit-identical, a value does not depend on cap, and the sum of the
+ * values agrees with cx_log_evidence to the rounding of two orders of summation, not bit for bit.
+ * The labels, the terms sorted by component and the segment offsets are built on the first call (O(connections) on the host) and kept
+ * with cx_log_evidence's work lists.  Refused as cx_log_evidence refuses, with the same codes (other families, dim >= 5, partitioned
+ * handles, zero-noise factors, a factor without a rule, a captured stream, no graph); a NULL n_components or counts4, cap < 0, or
+ * cap > 0 with a NULL values are CX_ERR_INVALID_ARGUMENT.  Synchronous; moves no message, marginal, readiness bit or counter. */
+int32_t cx_graph_components(cx_handle *h, int64_t n, const int64_t *variable_ids, int64_t *component, int64_t *n_components);
+int32_t cx_log_evidence_components(cx_handle *h, int64_t cap, double *values, int64_t *comp_counts4, int64_t *n_components, int64_t *counts4);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

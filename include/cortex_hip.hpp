@@ -136,6 +136,31 @@ class Handle {
         check(cx_log_evidence(h_, &v, o.data()));
         return {v, o};
     }
+    // the connected component of every named variable (empty: every variable in ascending id) and the number of components; components
+    // are numbered by their least variable id (cx_graph_components)
+    std::pair<std::vector<int64_t>, int64_t> components(const std::vector<int64_t> &variable_ids = {}) {
+        const int64_t n = variable_ids.empty() ? stats().n_variables : (int64_t)variable_ids.size();
+        std::vector<int64_t> out((size_t)n + 1);      // (+ 1: never a NULL array)
+        int64_t c = 0;
+        check(cx_graph_components(h_, (int64_t)variable_ids.size(), variable_ids.empty() ? nullptr : variable_ids.data(), out.data(), &c));
+        out.resize((size_t)n);
+        return {out, c};
+    }
+    // log p(data) per connected component from the stored messages (cx_log_evidence_components): values [C] (NaN: that component has an
+    // undefined input or a belief that is not positive definite, the others keep theirs), comp_counts [C][4] and counts (the whole graph's)
+    // as log_evidence's counts
+    struct EvidenceComponents { std::vector<double> values; std::vector<std::array<int64_t, 4>> comp_counts; std::array<int64_t, 4> counts{}; };
+    EvidenceComponents log_evidence_components() {
+        EvidenceComponents r;
+        int64_t c = 0;
+        check(cx_graph_components(h_, 0, nullptr, nullptr, &c));
+        r.values.resize((size_t)c + 1);
+        r.comp_counts.resize((size_t)c + 1);
+        check(cx_log_evidence_components(h_, c, r.values.data(), r.comp_counts[0].data(), &c, r.counts.data()));
+        r.values.resize((size_t)c);
+        r.comp_counts.resize((size_t)c);
+        return r;
+    }
     // the joint posterior of two-variable Gaussian factors from the stored messages: per factor 2d means then the 2d x 2d covariance
     // (row-major), (out, in) (NaN rows: an undefined input or a belief that is not positive definite)
     std::vector<double> factor_beliefs(const std::vector<int64_t> &factor_ids) {

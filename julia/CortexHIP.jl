@@ -297,6 +297,31 @@ function log_evidence(p)
     return value[], out
 end
 
+# the connected components of the graph as cx_graph_create received it (numbered by their least variable id): (labels, C) for the named
+# variables (nothing: every variable in ascending id, n_variables of them); host work only
+function graph_components(p, n_variables::Integer, variable_ids::Union{Nothing,Vector{Int64}} = nothing)
+    n = variable_ids === nothing ? Int(n_variables) : length(variable_ids)
+    out = zeros(Int64, max(n, 1))
+    nc = Ref{Int64}(0)
+    check(p.handle, ccall((:cx_graph_components, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                          p.handle, variable_ids === nothing ? 0 : n, variable_ids === nothing ? C_NULL : variable_ids, out, nc))
+    return out[1:n], nc[]
+end
+
+# log p(data) of every connected component from the stored messages (dim 1 - 4): (values [C], counts 4 x C, whole-graph counts [4]);
+# values[k] is NaN when component k read an undefined input or a belief that is not positive definite — the others keep their values
+function log_evidence_components(p)
+    nc = Ref{Int64}(0)
+    check(p.handle, ccall((:cx_graph_components, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), p.handle, 0, C_NULL, C_NULL, nc))
+    c = nc[]
+    values = zeros(Float64, max(c, 1))
+    comp_counts = zeros(Int64, 4, max(c, 1))
+    out = zeros(Int64, 4)
+    check(p.handle, ccall((:cx_log_evidence_components, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                          p.handle, c, values, comp_counts, nc, out))
+    return values[1:c], comp_counts[:, 1:c], out
+end
+
 # the joint posterior of two-variable Gaussian factors from the stored messages (ABI 6; dim 1 - 4): a (2d + 4d^2) x n matrix, column f =
 # the 2d means then the 2d x 2d covariance (row-major, (out, in)); NaN columns: an undefined input or a belief that is not positive definite
 function factor_beliefs(p, factor_ids::Vector{Int64})
