@@ -1,0 +1,505 @@
+// cx_evidence_mfma.hip — cx_log_evidence_mfma: log p(data) of a Gaussian model at the matrix-core dims (cx_create dim 5 .. 64, internal
+// tiles of 16 / 32 / 64) from the stored factor→variable messages and the caller's data.  DESIGN.md §4e defines the quantity,
+//
+//   log Z = Σ_o c_o + Σ_a log z_a + Σ_i (1 - d_i) log z_i,
+//
+// and §4m derives the terms at these dims.  Only pairwise x_out = A x_in + N(0, Q) factors and opaque messages exist here, so every
+// term is one or two factorisations of a KD x KD matrix "table + sum of message records" by ONE WAVE, in the form of k_rule64w
+// (cx_mv64w.hip): upper tiles in registers, the 16 x 16 diagonal tiles through diag_factor, U^-T η on the vector pipe.  With
+// m_{i→a} the sum of variable i's OTHER stored messages (summed directly, as k_v2f64 does — never M_i - m_{a→i}):
+//
+//   variable (d_i != 1)       Λ = Σ all messages:                       log z_i = ½ η'Λ⁻¹η - ½ log det Λ + (d/2) log 2π
+//   opaque message            Λ_o positive definite:                    c_o = ½ log det Λ_o - ½ η_o'Λ_o⁻¹η_o - (d/2) log 2π   (else 0)
+//   factor, one end observed  S = Λ_{free→a} + C, h = η_{free→a} + B y: log z_a = -½ log det 2πQ - ½ y'P y + ½ h'S⁻¹h - ½ log det S + (d/2) log 2π
+//                             ((P, B, C) the rule table TOWARDS the free end: its (C, B y) is the message k_point64 writes)
+//   factor, both ends free    the OUT end goes first: M = Λ_{out→a} + Q⁻¹ is positive definite whenever its input is defined, a flat
+//                             leaf included; that elimination IS the rule towards IN applied to m_{out→a}, (Λ', η') = (C - B M⁻¹ B',
+//                             B M⁻¹ η_out), kept in registers; then S = Λ_{in→a} + Λ', h = η_{in→a} + η':
+//                             log z_a = -½ log det 2πQ + [½ η_out'M⁻¹η_out - ½ log det M] + [½ h'S⁻¹h - ½ log det S] + d log 2π
+//   factor, both observed     log N(y_out; A y_in, Q)
+//
+// Embedded dims (a user dim of 5 .. 15, 17 .. 31, 33 .. 63: every matrix block-diagonal, real block and identity block): a
+// block-diagonal matrix has a block-diagonal Cholesky factor, so every log-determinant is Σ_{k < user dim} 2 log U_kk, every quadratic
+// form the first `user dim` entries of U^-T η, and d above is the user's: the value is the real model's at any internal tile size.
+//
+// The terms are evaluated UNCENTRED (§4e centres dims 1 .. 4 on the belief means): ½ η'Λ⁻¹η of a term is of size (y/σ)² per component
+// and cancels between terms, so about (y/σ)² 1e-16 of absolute error per term against ~ d/2 of value: 1e-9 relative is lost for data
+// beyond ~ 3e3 √d standard deviations from the origin (an estimate from the sizes of the terms, not a measurement).
+//
+// k_evm_terms writes one (value, flags) per term at the term's index; k_evm_part folds 256 terms into an ev::Part and ev::final_sum
+// (k_ev_final, cx_evidence.hip) adds the parts in index order: no atomics, two calls on one state are bit-identical.
+// cx_log_evidence and cx_log_evidence_components keep refusing these dims (their tests pin that); routing them here is a later,
+// separate decision.
+#include "cx_evidence_core.h"
+#include "cx_mv64w_core.h"
+
+namespace cx {
+namespace evm {
+
+using namespace w64;
+
+// term record (8 int32): {kind, rule-table index, A offset, A count, B offset, B count, y0, y1}; A and B are runs of message slots in `srcs`
+//   kVar      B = every slot of the variable, y0 = d_i            kOpaque  B = the slot of the opaque message
+//   kFacFree  table 2 set + 1 (towards IN), A = the OUT variable's other slots, B = the IN variable's other slots
+//   kFacObs   table towards the free end, B = the free variable's other slots, y0 = the observed end's slot (its datum: v2f)
+//   kFacBoth  table 2 set + 1, y0 = the OUT end's slot, y1 = the IN end's slot
+constexpr int kVar = 0, kOpaque = 1, kFacFree = 2, kFacObs = 3, kFacBoth = 4;
+constexpr int kTB = 256;      // terms per block of k_evm_part
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m, 64);
+    return x;
+}
+
+// M (upper tiles) += the Λ of the message records srcs[0 .. n); wcv[j] += their η[16 j + c]
+template <int NT>
+__device__ __forceinline__ void add_sources(d4 (&M)[NT * (NT + 1) / 2], double (&wcv)[NT], const double *__restrict__ f2v, const int32_t *__restrict__ srcs, int n,
+                                            int mo, int c) {
+    constexpr int KD = 16 * NT, KM = KD + KD * KD;
+    for (int s = 0; s < n; s++) {
+        const gcdp p = (gcdp)(f2v + (int64_t)srcs[s] * KM);
+#pragma unroll
+        for (int a = 0; a < NT; a++)
+#pragma unroll
+            for (int b = a; b < NT; b++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) M[utn<NT>(a, b)][r] += p[KD + mo + tile_const_n<NT>(a, b, r)];
+#pragma unroll
+        for (int j = 0; j < NT; j++) wcv[j] += p[16 * j + c];
+    }
+}
+
+// M = U'U in place (the off-diagonal tiles become U, V_k = U_kk⁻¹ goes to Vs), then z = U^-T w on the vector pipe (rule64_body's two
+// passes).  logdet = Σ_{k < u} 2 log U_kk = -2 Σ log V_kk off the tile diagonals; quad = Σ_{k < u} z_k²; pd: every pivot below u is
+// positive and finite.  zrv: z in the row layout (lane (g, c) holds z[16 j + g + 4 r]).
+template <int NT>
+__device__ __forceinline__ void factor_solve(d4 (&M)[NT * (NT + 1) / 2], const double (&wcv)[NT], double (&zrv)[NT][4], double *S, double (*Vs)[16 * kLdT],
+                                             const int g, const int c, const int u, double &logdet, double &quad, bool &pd) {
+    double ld = 0.0;
+    bool bad = false;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (an earlier factorisation's reads of S and Vs have returned)
+#pragma unroll
+    for (int k = 0; k < NT; k++) {
+        const d4 Vk = diag_factor(M[utn<NT>(k, k)], S, g, c);
+#pragma unroll
+        for (int r = 0; r < 4; r++) Vs[k][(g + 4 * r) * kLdT + c] = Vk[r];
+        // V[i][i] sits in lane (g, c) = (i & 3, i), register i >> 2
+        const int rr = c >> 2;
+        const double dv = rr == 0 ? Vk[0] : rr == 1 ? Vk[1] : rr == 2 ? Vk[2] : Vk[3];
+        const bool on = g == (c & 3) && 16 * k + c < u, fine = dv > 0.0 && dv < __builtin_inf();
+        bad = bad || (on && !fine);
+        ld += log(on && fine ? dv : 1.0);
+#pragma unroll
+        for (int j = k + 1; j < NT; j++) M[utn<NT>(k, j)] = tts(Vk, M[utn<NT>(k, j)], d4{0.0, 0.0, 0.0, 0.0});
+#pragma unroll
+        for (int i = k + 1; i < NT; i++) {
+            const d4 nu = neg(M[utn<NT>(k, i)]);
+#pragma unroll
+            for (int j = i; j < NT; j++) M[utn<NT>(i, j)] = tts(nu, M[utn<NT>(k, j)], M[utn<NT>(i, j)]);
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    double q = 0.0;
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        double w = wcv[j];
+#pragma unroll
+        for (int k = 0; k < j; k++) {
+            double p = 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; r++) p += M[utn<NT>(k, j)][r] * zrv[k][r];
+            w -= sum_groups(p);
+        }
+        double p = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; r++) p += Vs[j][(g + 4 * r) * kLdT + c] * cv_to_rv(w, g, r);
+        const double zcv = sum_groups(p);
+#pragma unroll
+        for (int r = 0; r < 4; r++) zrv[j][r] = cv_to_rv(zcv, g, r);
+        q += (g == 0 && 16 * j + c < u) ? zcv * zcv : 0.0;
+    }
+    logdet = -2.0 * wave_sum(ld);
+    quad = wave_sum(q);
+    pd = __ballot(bad) == 0;
+}
+
+// out[a] (lane (g, c): entry 16 a + c) = (X' y)[16 a + c] for a row-major KD x KD matrix X and y in the row layout
+template <int NT>
+__device__ __forceinline__ void xty(const double *__restrict__ Xp, const double (&yrv)[NT][4], double (&out)[NT], const int mo) {
+    constexpr int KD = 16 * NT;
+    const gcdp X = (gcdp)Xp;
+#pragma unroll
+    for (int a = 0; a < NT; a++) {
+        double p = 0.0;
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) p += X[mo + tile_const_n<NT>(j, a, r)] * yrv[j][r];
+        out[a] = sum_groups(p);
+    }
+}
+// a datum (the η part of a stored variable→factor record) in both layouts
+template <int NT>
+__device__ __forceinline__ void load_y(const double *__restrict__ y, double (&yrv)[NT][4], double (&ycv)[NT], const int g, const int c) {
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        ycv[j] = y[16 * j + c];
+#pragma unroll
+        for (int r = 0; r < 4; r++) yrv[j][r] = y[16 * j + g + 4 * r];
+    }
+}
+// Σ_{k < u} a_k b_k of two vectors in the column layout (every lane group holds a copy: lane group 0 counts); the real block only, like
+// every other quadratic form here
+template <int NT>
+__device__ __forceinline__ double dot_cv(const double (&a)[NT], const double (&b)[NT], const int g, const int c, const int u) {
+    double p = 0.0;
+#pragma unroll
+    for (int j = 0; j < NT; j++) p += (g == 0 && 16 * j + c < u) ? a[j] * b[j] : 0.0;
+    return wave_sum(p);
+}
+
+// one wave per term.  ptab: [table][P | B | C], btab: [table] B' (upload_ptab); ldq[set] = log det 2πQ of the real block; u: the user's dim
+template <int NT, int WAVES_PER_SIMD>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
+void k_evm_terms(int nterm, const int32_t *__restrict__ rec, const int32_t *__restrict__ srcs, const double *__restrict__ ptab,
+                 const double *__restrict__ btab, const double *__restrict__ ldq, const double *__restrict__ f2v,
+                 const double *__restrict__ v2f, const int u, double *__restrict__ tval, uint8_t *__restrict__ tflag) {
+    constexpr int KD = 16 * NT, KM = KD + KD * KD, NU = NT * (NT + 1) / 2;
+    __shared__ double S[16 * kLdT];
+    __shared__ double Vs[NT][16 * kLdT];
+    // Workgroups go to the eight XCDs in turn, each with an L2 of its own: XCD x takes the x-th eighth of the terms in index order, so
+    // that terms next to each other in the list — the host sorts them by variable: they share most of their message records — run at
+    // about the same time behind ONE L2
+    const int per = (nterm + 7) >> 3, w = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if (w >= nterm) return;
+    const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, mo = g * KD + c;
+    const int32_t *t = rec + 8 * (int64_t)w;
+    const int kind = t[0], tab_i = t[1], a_off = t[2], a_n = t[3], b_off = t[4], b_n = t[5], y0 = t[6], y1 = t[7];
+    const double *tab = ptab + (int64_t)(tab_i < 0 ? 0 : tab_i) * 3 * KD * KD;
+    const double *bt = btab + (int64_t)(tab_i < 0 ? 0 : tab_i) * KD * KD;
+    const double hl2pi = 0.5 * u * ev::kLog2Pi;
+
+    if (kind == kFacBoth) {      // log N(y_o; A y_i, Q): r'Q⁻¹r = y_o'Q⁻¹y_o - 2 y_o'(Q⁻¹A y_i) + y_i'(A'Q⁻¹A) y_i from the table towards IN
+        double orv[NT][4], ocv[NT], irv[NT][4], icv[NT], po[NT], bi[NT], ci[NT];
+        load_y<NT>(v2f + (int64_t)y0 * KM, orv, ocv, g, c);
+        load_y<NT>(v2f + (int64_t)y1 * KM, irv, icv, g, c);
+        xty<NT>(tab, orv, po, mo);                       // Q⁻¹ y_o (P is symmetric)
+        xty<NT>(tab + KD * KD, irv, bi, mo);             // B' y_i = Q⁻¹A y_i
+        xty<NT>(tab + 2 * KD * KD, irv, ci, mo);         // C y_i
+        const double q = dot_cv<NT>(ocv, po, g, c, u) - 2.0 * dot_cv<NT>(ocv, bi, g, c, u) + dot_cv<NT>(icv, ci, g, c, u);
+        const bool undef = __builtin_isnan(q);
+        if (lane == 0) { tval[w] = undef ? 0.0 : -0.5 * ldq[tab_i >> 1] - 0.5 * q; tflag[w] = undef ? ev::kTermUndef : 0; }
+        return;
+    }
+
+    d4 Sm[NU];
+    double hcv[NT], zrv[NT][4];
+#pragma unroll
+    for (int i = 0; i < NU; i++) Sm[i] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < NT; j++) hcv[j] = 0.0;
+    double cst = 0.0;      // what the term holds besides ½ h'S⁻¹h - ½ log det S of the last factorisation
+    bool pd_a = true, undef_a = false;      // the first factorisation of a factor with two free ends: positive definite; its inputs undefined
+    if (kind == kFacFree) {
+        // the rule towards IN on m_{out→a} (rule64_body's passes), its message left in Sm / hcv
+        d4 M[NU];
+        double wcv[NT];
+#pragma unroll
+        for (int j = 0; j < NT; j++) wcv[j] = 0.0;
+#pragma unroll
+        for (int a = 0; a < NT; a++)
+#pragma unroll
+            for (int b = a; b < NT; b++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) M[utn<NT>(a, b)][r] = ((gcdp)tab)[mo + tile_const_n<NT>(a, b, r)];
+        add_sources<NT>(M, wcv, f2v, srcs + a_off, a_n, mo, c);
+        undef_a = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
+        double ld1, q1;
+        factor_solve<NT>(M, wcv, zrv, S, Vs, g, c, u, ld1, q1, pd_a);
+        cst = -0.5 * ldq[tab_i >> 1] + 0.5 * q1 - 0.5 * ld1 + 2.0 * hl2pi;
+        // z waits in LDS between its solve and its use (η' = Yt' z), not in 8 NT registers across the matrix solve (rule64_body: Z_IN_LDS)
+        __shared__ double ZS[KD];
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) ZS[16 * j + g + 4 * r] = zrv[j][r];      // (the 16 lanes of a group write one value to one place)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // Yt = U^-T B', one block column at a time
+        d4 Y[NT][NT];
+#pragma unroll
+        for (int b = 0; b < NT; b++) {
+            asm volatile("" ::: "memory");      // (one block column of B' in flight at a time)
+#pragma unroll
+            for (int j = 0; j < NT; j++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) Y[j][b][r] = ((gcdp)bt)[mo + tile_const_n<NT>(j, b, r)];
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                d4 Vj;
+#pragma unroll
+                for (int r = 0; r < 4; r++) Vj[r] = Vs[j][(g + 4 * r) * kLdT + c];
+                Y[j][b] = tts(Vj, Y[j][b], d4{0.0, 0.0, 0.0, 0.0});
+#pragma unroll
+                for (int jj = j + 1; jj < NT; jj++) Y[jj][b] = tts(neg(M[utn<NT>(j, jj)]), Y[j][b], Y[jj][b]);
+            }
+        }
+        // Λ' = C - Yt'Yt (upper tiles), η' = Yt' z
+#pragma unroll
+        for (int a = 0; a < NT; a++) {
+#pragma unroll
+            for (int b = a; b < NT; b++) {
+                asm volatile("" ::: "memory");      // (one tile of C in flight at a time: hoisted together they cost 80 registers at NT = 4)
+                d4 G = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int j = 0; j < NT; j++) G = tts(Y[j][a], Y[j][b], G);
+#pragma unroll
+                for (int r = 0; r < 4; r++) Sm[utn<NT>(a, b)][r] = ((gcdp)tab)[2 * KD * KD + mo + tile_const_n<NT>(a, b, r)] - G[r];
+            }
+            double p = 0.0;
+#pragma unroll
+            for (int j = 0; j < NT; j++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) p += Y[j][a][r] * ZS[16 * j + g + 4 * r];
+            hcv[a] = sum_groups(p);
+        }
+    } else if (kind == kFacObs) {      // (kVar, kOpaque: S and h start at zero)
+        double yrv[NT][4], ycv[NT], py[NT];
+        load_y<NT>(v2f + (int64_t)y0 * KM, yrv, ycv, g, c);
+        xty<NT>(tab, yrv, py, mo);                       // P y
+        xty<NT>(bt, yrv, hcv, mo);                       // B y
+        cst = -0.5 * ldq[tab_i >> 1] - 0.5 * dot_cv<NT>(ycv, py, g, c, u) + hl2pi;
+#pragma unroll
+        for (int a = 0; a < NT; a++)
+#pragma unroll
+            for (int b = a; b < NT; b++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) Sm[utn<NT>(a, b)][r] = ((gcdp)tab)[2 * KD * KD + mo + tile_const_n<NT>(a, b, r)];
+    }
+    add_sources<NT>(Sm, hcv, f2v, srcs + b_off, b_n, mo, c);
+    // Undefined: an INPUT is NaN (whole messages are NaN together; a NaN datum reaches hcv and cst).  A first factorisation that is not
+    // positive definite also leaves NaN in Λ', η' and cst: that term is "not positive definite", so with two free ends the inputs of the
+    // second stage are looked at themselves (Λ[0][0] and η[0] of every source record), not through Sm
+    bool undef = undef_a;
+    if (kind == kFacFree) {
+        for (int s = 0; s < b_n; s++) {
+            const double *p = f2v + (int64_t)srcs[b_off + s] * KM;
+            undef = undef || __builtin_isnan(p[0]) || __builtin_isnan(p[KD]);
+        }
+    } else undef = __builtin_isnan(bcast(Sm[0][0], 0)) || __builtin_isnan(bcast(hcv[0], 0)) || __builtin_isnan(cst);
+    double ld, q;
+    bool pd;
+    factor_solve<NT>(Sm, hcv, zrv, S, Vs, g, c, u, ld, q, pd);
+    if (lane != 0) return;
+    double val;
+    unsigned fl = 0;
+    if (kind == kOpaque) {
+        val = (!undef && pd) ? 0.5 * ld - 0.5 * q - hl2pi : 0.0;      // improper (a flat forecast end) or undefined: no constant
+    } else {
+        const bool npd = !undef && !(pd && pd_a);
+        if (kind == kVar) { val = (double)(1 - y0) * (0.5 * q - 0.5 * ld + hl2pi); fl = ev::kTermVar; }
+        else val = cst + 0.5 * q - 0.5 * ld;
+        fl |= (undef ? ev::kTermUndef : 0u) | (npd ? ev::kTermNpd : 0u);
+        if (undef || npd) val = 0.0;
+    }
+    tval[w] = val;
+    tflag[w] = (uint8_t)fl;
+}
+
+// 256 terms -> one ev::Part (fixed-order tree); ev::final_sum adds the parts in index order
+__global__ __launch_bounds__(kTB) void k_evm_part(int nterm, const double *__restrict__ tval, const uint8_t *__restrict__ tflag, ev::Part *__restrict__ part) {
+    const int i = blockIdx.x * kTB + threadIdx.x;
+    const double s = i < nterm ? tval[i] : 0.0;
+    const unsigned f = i < nterm ? tflag[i] : 0u;
+    ev::block_part<kTB>(s, 0.0, (f & ev::kTermVar) ? 1u : 0u, (f & ev::kTermUndef) ? 1u : 0u, (f & ev::kTermNpd) ? 1u : 0u, 0u, part);
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------------
+// The term lists follow the graph and WHICH variables are observed (vinfo_epoch: cx_derived.h), the log-det table the rule parameters
+// (param_epoch); messages and data are read by every call
+struct Cache {
+    bool built = false;
+    uint64_t vinfo_epoch = 0, param_epoch = ~0ull;
+    int64_t n_term = 0, n_fac = 0, nb = 0, unsupported_fac = -1;
+    DevBuf<int32_t> d_rec, d_srcs;
+    DevBuf<double> d_ldq, d_tval, d_out;
+    DevBuf<uint8_t> d_tflag;
+    DevBuf<ev::Part> d_part;
+    std::vector<double> h_out;
+};
+
+static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
+    using namespace cxh;
+    const int64_t nv = h->nv, ne = h->ne, nf = h->nf;
+    std::vector<int32_t> efac((size_t)ne), fe1((size_t)nf, -1), fe2((size_t)nf, -1), nfe((size_t)nf, 0);
+    for (int64_t e = 0; e < ne; e++) {
+        const int64_t f = find_factor(h, h->edge_fac_id[e]);
+        efac[e] = (int32_t)f;
+        if (fe1[f] < 0) fe1[f] = (int32_t)e; else if (fe2[f] < 0) fe2[f] = (int32_t)e;
+        nfe[f]++;
+    }
+    // the terms in the order made, and the variable each is filed under: the list is sorted by it (stable), so that a variable's term,
+    // the terms of its factors and those of its neighbours — which read the same message records — are next to each other
+    std::vector<int32_t> made, key, srcs;
+    auto term = [&](int32_t file_under, int kind, int tab, int ao, int an, int bo, int bn, int y0, int y1) {
+        const int32_t r[8] = {kind, tab, ao, an, bo, bn, y0, y1};
+        made.insert(made.end(), r, r + 8);
+        key.push_back(file_under);
+    };
+    // the slots of variable v but `skip`, in ascending neighbour order (k_v2f64's): (offset, count) in srcs
+    auto others = [&](int32_t v, int32_t skip, int &off, int &n) {
+        off = (int)srcs.size();
+        for (int32_t e = h->var_off[v]; e < h->var_off[v + 1]; e++) {
+            const int32_t s = slot_of_edge(h, e);
+            if (s != skip) srcs.push_back(s);
+        }
+        n = (int)srcs.size() - off;
+    };
+    C.unsupported_fac = -1;
+    for (int64_t v = 0; v < nv; v++) {
+        if (h->vinfo[v] & (kClamped | kGhost)) continue;
+        int di = 0;
+        for (int32_t e = h->var_off[v]; e < h->var_off[v + 1]; e++) {
+            if (h->fac_kind[efac[e]] != CX_FACTOR_OPAQUE) { di++; continue; }
+            const int off = (int)srcs.size();
+            srcs.push_back(slot_of_edge(h, e));
+            term((int32_t)v, kOpaque, -1, 0, 0, off, 1, 0, 0);
+        }
+        if (di == 1) continue;
+        int off, n;
+        others((int32_t)v, -1, off, n);
+        term((int32_t)v, kVar, -1, 0, 0, off, n, di, 0);
+    }
+    C.n_fac = 0;
+    for (int64_t f = 0; f < nf; f++) {
+        if (h->fac_kind[f] == CX_FACTOR_OPAQUE) continue;
+        if (h->fac_kind[f] != CX_FACTOR_GAUSS_LINEAR || nfe[f] != 2) { if (C.unsupported_fac < 0) C.unsupported_fac = h->fac_ids[f]; continue; }
+        const int32_t s1 = slot_of_edge(h, fe1[f]), s2 = slot_of_edge(h, fe2[f]);
+        int32_t so = s1, si = s2, vo = h->edge_var[fe1[f]], vi = h->edge_var[fe2[f]];
+        if ((h->spdir[s1] & 1) == 0) { std::swap(so, si); std::swap(vo, vi); }      // spdir[in slot] = 2 set (the message it sends goes forward)
+        const int set = h->spdir[si] >> 1;
+        const bool oo = (h->vinfo[vo] & kClamped) != 0, oi = (h->vinfo[vi] & kClamped) != 0;
+        int ao = 0, an = 0, bo = 0, bn = 0;
+        if (oo && oi) term(std::min(vo, vi), kFacBoth, 2 * set + 1, 0, 0, 0, 0, so, si);
+        else if (oo) { others(vi, si, bo, bn); term(vi, kFacObs, 2 * set + 1, 0, 0, bo, bn, so, 0); }      // towards IN
+        else if (oi) { others(vo, so, bo, bn); term(vo, kFacObs, 2 * set, 0, 0, bo, bn, si, 0); }          // towards OUT
+        else { others(vo, so, ao, an); others(vi, si, bo, bn); term(std::min(vo, vi), kFacFree, 2 * set + 1, ao, an, bo, bn, 0, 0); }
+        C.n_fac++;
+    }
+    C.n_term = (int64_t)key.size();
+    std::vector<int32_t> order((size_t)C.n_term), rec;
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[(size_t)a] < key[(size_t)b]; });
+    rec.reserve(made.size());
+    for (int32_t i : order) rec.insert(rec.end(), made.begin() + 8 * (size_t)i, made.begin() + 8 * (size_t)i + 8);
+    CX_REQUIRE(h, C.n_term < (int64_t)0x7fffffff && (int64_t)srcs.size() < (int64_t)0x7fffffff, CX_ERR_UNSUPPORTED, who + ": more than 2^31 terms");
+    C.nb = (C.n_term + kTB - 1) / kTB;
+    int32_t rc;
+    if ((rc = dev_upload(h, &C.d_rec, rec)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &C.d_srcs, srcs)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_tval, C.n_term)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_tflag, C.n_term)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_part, C.nb)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &C.d_out, 1 + ev::kNCnt)) != CX_OK) return rc;
+    C.h_out.assign(1 + ev::kNCnt, 0.0);
+    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
+    C.built = true;
+    C.vinfo_epoch = h->vinfo_epoch;
+    C.param_epoch = ~0ull;
+    return CX_OK;
+}
+
+// log det 2πQ of the real block of every parameter set (Q symmetric positive definite: cx_set_factor_matrices checks it)
+static int32_t refresh_params(cx_handle *h, Cache &C) {
+    if (C.param_epoch == h->param_epoch) return CX_OK;
+    const int d = h->cfg.dim, u = h->user_dim ? h->user_dim : d;
+    std::vector<double> ldq(std::max<size_t>(h->psets.size(), 1), cxh::kNaN), L((size_t)u * u);
+    for (size_t s = 0; s < h->psets.size(); s++) {
+        if (h->psets[s].empty()) continue;
+        const double *Q = h->psets[s].data() + (size_t)d * d;
+        double ld = u * ev::kLog2Pi;
+        for (int j = 0; j < u; j++) {
+            double t = Q[(size_t)j * d + j];
+            for (int k = 0; k < j; k++) t -= L[(size_t)j * u + k] * L[(size_t)j * u + k];
+            L[(size_t)j * u + j] = std::sqrt(t); ld += std::log(t);
+            for (int i = j + 1; i < u; i++) {
+                double x = 0.5 * (Q[(size_t)i * d + j] + Q[(size_t)j * d + i]);
+                for (int k = 0; k < j; k++) x -= L[(size_t)i * u + k] * L[(size_t)j * u + k];
+                L[(size_t)i * u + j] = x / L[(size_t)j * u + j];
+            }
+        }
+        ldq[s] = ld;
+    }
+    int32_t rc;
+    if ((rc = C.d_ldq.ensure(h, (int64_t)ldq.size())) != CX_OK) return rc;
+    CX_HIP(h, hipMemcpyAsync(C.d_ldq, ldq.data(), ldq.size() * 8, hipMemcpyHostToDevice, h->stream));
+    CX_HIP(h, hipStreamSynchronize(h->stream));
+    C.param_epoch = h->param_epoch;
+    return CX_OK;
+}
+
+static void launch(cx_handle *h, Cache &C) {
+    const int n = (int)C.n_term, u = h->user_dim ? h->user_dim : h->cfg.dim;
+    if (n) {
+        // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch
+        const unsigned grid = 8u * (unsigned)((n + 7) / 8);      // (k_evm_terms: an eighth of the terms per XCD)
+#define CX_T(N, W)                                                                                                                                      \
+    hipLaunchKernelGGL((k_evm_terms<N, W>), dim3(grid), dim3(64), 0, h->stream, n, C.d_rec, C.d_srcs, h->d_ptab, h->d_ptab_bt, C.d_ldq, h->d_mv_f2v, \
+                       h->d_mv_v2f, u, C.d_tval, C.d_tflag)
+        if (h->cfg.dim == 16) CX_T(1, 4);
+        else if (h->cfg.dim == 32) CX_T(2, 3);
+        else CX_T(4, 2);      // (4 x 4 tiles: 256 registers, and only with one block of B' / one tile of C in flight in the two-free-ends pass)
+#undef CX_T
+        hipLaunchKernelGGL(k_evm_part, dim3((unsigned)C.nb), dim3(kTB), 0, h->stream, n, C.d_tval, C.d_tflag, C.d_part);
+    }
+    ev::final_sum(h, n ? C.nb : 0, C.d_part, C.d_out);
+}
+
+}  // namespace evm
+
+template <> void Deleter<evm::Cache>::operator()(evm::Cache *C) const { delete C; }
+
+}  // namespace cx
+
+using namespace cxh;
+
+extern "C" int32_t cx_log_evidence_mfma(cx_handle *h, double *value, int64_t *counts4) {
+    try {
+        namespace evm = cx::evm;
+        const std::string who = "cx_log_evidence_mfma";
+        CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only (no variational free energy, no Beta-Bernoulli evidence)");
+        CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
+        CX_REQUIRE(h, value && counts4, CX_ERR_INVALID_ARGUMENT, who + ": null argument");
+        CX_REQUIRE(h, cx::is_mfma_dim(h->cfg.dim), CX_ERR_UNSUPPORTED, who + ": the matrix-core dims, 5 .. 64 (dim 1, 2, 3 and 4: cx_log_evidence)");
+        // (a user wiring, cx_graph_wire, cannot exist here: it is refused at these dims)
+        CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
+                   who + ": not for a partitioned handle (halo lists, state halos or a chain's time block: its terms would need owners)");
+        CX_HIP(h, hipSetDevice(h->cfg.device));
+        if (h->stream) {
+            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+            CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
+            CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
+        }
+        int32_t rc;
+        if ((rc = mv_check_psets(h)) != CX_OK) return rc;
+        CX_REQUIRE(h, h->d_ptab && h->d_ptab_bt && h->d_mv_f2v, CX_ERR_STATE, who + ": the rule tables are not on the device (cx_set_factor_matrices)");
+        if (h->evidence_mfma && h->evidence_mfma->vinfo_epoch != h->vinfo_epoch) h->evidence_mfma.reset();      // other variables are observed
+        if (!h->evidence_mfma) h->evidence_mfma.reset(new evm::Cache());
+        evm::Cache &C = *h->evidence_mfma;
+        if (!C.built && (rc = evm::build(h, C, who)) != CX_OK) { h->evidence_mfma.reset(); return rc; }
+        if (C.unsupported_fac >= 0)
+            return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(C.unsupported_fac) + " is no two-variable CX_FACTOR_GAUSS_LINEAR factor and no opaque message");
+        if ((rc = evm::refresh_params(h, C)) != CX_OK) return rc;
+        if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
+        evm::launch(h, C);
+        CX_HIP(h, hipGetLastError());
+        CX_HIP(h, hipMemcpyAsync(C.h_out.data(), C.d_out, (1 + cx::ev::kNCnt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        CX_HIP(h, hipStreamSynchronize(h->stream));
+        uint64_t cnt[cx::ev::kNCnt];
+        std::memcpy(cnt, C.h_out.data() + 1, sizeof(cnt));
+        counts4[0] = C.n_fac;
+        for (int k = 1; k < 4; k++) counts4[k] = (int64_t)cnt[k - 1];
+        *value = counts4[2] + counts4[3] > 0 ? kNaN : C.h_out[0];
+        return CX_OK;
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence_mfma: host allocation failed"); }
+}

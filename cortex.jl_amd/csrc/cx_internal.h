@@ -111,6 +111,7 @@ struct HostWord {
 template <class T> struct Deleter { void operator()(T *p) const; };
 struct RefSched;      // cx_api_ref.hip
 namespace ev { struct Cache; }
+namespace evm { struct Cache; }
 namespace fs { struct Cache; }
 namespace sp { struct Plan; }
 namespace pr { struct Plan; }
@@ -252,6 +253,8 @@ struct DevState {
     // cx_factor_statistics (cx_learn.hip): the grouping's work lists and scratch; cx_sample_posterior (cx_sample.hip): the forest
     // plan, the links and the per-call scratch; cx_predictive (cx_predict.hip): the rows of the last (mode, factor_ids) and their scratch
     std::unique_ptr<ev::Cache, Deleter<ev::Cache>> evidence;
+    // cx_log_evidence_mfma (cx_evidence_mfma.hip): the term lists of the matrix-core dims, the log-det table and the call's scratch
+    std::unique_ptr<evm::Cache, Deleter<evm::Cache>> evidence_mfma;
     std::unique_ptr<fs::Cache, Deleter<fs::Cache>> learn;
     std::unique_ptr<sp::Plan, Deleter<sp::Plan>> sample;
     std::unique_ptr<pr::Plan, Deleter<pr::Plan>> predict;

@@ -313,6 +313,15 @@ class DeviceGraph:
         self._check(self.lib.cx_log_evidence(self.h, C.byref(val), out))
         return float(val.value), dict(zip(("factor_terms", "variable_terms", "undefined", "not_positive_definite"), [int(x) for x in out]))
 
+    def log_evidence_mfma(self):
+        """cx_log_evidence_mfma: log_evidence at the matrix-core dims (a handle created with dim 5 .. 64) — (value, counts) with the
+        keys of log_evidence.  One wave per term on the f64 matrix cores; a dim embedded in the next tile size gives the real model's
+        value.  log_evidence itself keeps refusing these dims."""
+        val = C.c_double()
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.cx_log_evidence_mfma(self.h, C.byref(val), out))
+        return float(val.value), dict(zip(("factor_terms", "variable_terms", "undefined", "not_positive_definite"), [int(x) for x in out]))
+
     def components(self, variable_ids=None):
         """cx_graph_components: (labels, n_components) — the connected component of every named variable (None: every variable in
         ascending id) of the graph as graph_create received it.  Observed variables and opaque factors are nodes like any other;

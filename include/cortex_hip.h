@@ -807,6 +807,37 @@ int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids
 int32_t cx_graph_components(cx_handle *h, int64_t n, const int64_t *variable_ids, int64_t *component, int64_t *n_components);
 int32_t cx_log_evidence_components(cx_handle *h, int64_t cap, double *values, int64_t *comp_counts4, int64_t *n_components, int64_t *counts4);
 
+/* ---- log-evidence at the matrix-core dims (added after ABI 9: a new function breaks no caller, CX_ABI_VERSION stays; no counterpart
+ * in the reference) ----
+ * log p(data) of a CX_FAMILY_GAUSSIAN model at the matrix-core dims (cx_create dim 5 .. 64), from the STORED factor→variable
+ * messages and the caller's data: the formula, the meaning of counts4 and the NaN rule of cx_log_evidence,
+ *     log Z = sum_o c_o + sum_a log z_a + sum_i (1 - d_i) log z_i,
+ * counts4 = {factor terms, variable terms (d_i != 1), terms with an undefined input, terms whose belief is not positive definite},
+ * *value NaN iff counts4[2] + counts4[3] > 0.  Exact on forests at a fixed point, the Bethe estimate on loops; after every schedule
+ * these dims accept (fused, chain scan, tree, reference order).  Only two-variable CX_FACTOR_GAUSS_LINEAR factors and opaque messages
+ * exist at these dims.  Every term is one or two Cholesky factorisations of a "rule table + sum of message records" matrix by one
+ * wave on the f64 matrix cores: a leave-one-out message is the sum of the variable's OTHER stored messages (never a
+ * difference), a factor with two free ends eliminates its OUT end first (positive definite whenever the input is defined, a flat leaf
+ * included) and keeps the resulting message in registers, an opaque message that is not positive definite (a flat forecast end)
+ * contributes 0 and counts as no failure.  counts4[2] counts terms with a NaN input (a message record or a datum), counts4[3] terms
+ * whose inputs are defined and one of whose factorisations meets a non-positive pivot — the first one of a factor with two free ends
+ * included.  A dim of 5 .. 15, 17 .. 31 or 33 .. 63 runs embedded in the next tile size (cx_create): every log-determinant and
+ * quadratic form is restricted to the real block and d is the caller's, so the value is the real model's at any internal tile size.
+ * The terms are evaluated around the origin, NOT centred on the belief means as cx_log_evidence's are: about 1e-9 relative is lost once
+ * the data lie some 3e3 sqrt(d) standard deviations from the origin (an estimate from the size of the terms that cancel, not a
+ * measurement).  The terms are summed in an order the graph alone fixes (no atomics): two calls on one state are bit-identical.
+ * The term lists are built on the first call (O(connections) on the host) and kept until other variables are observed; log det 2 pi Q
+ * per parameter set follows cx_set_factor_matrices.  MI355X (profiles/evidence_mfma.md, session of 2026-10-19): T = 1e5 chains after
+ * one chain-scan sweep, median of 30 calls: 4.68 ms at d = 64 (config C5), 1.51 ms at d = 32, 0.73 ms at d = 16 — 1.16, 1.36 and 1.65
+ * times one fused sweep of the same model (4.05, 1.11, 0.44 ms): the call factors 4 T matrices where that sweep factors 2 T.
+ * cx_log_evidence and cx_log_evidence_components keep returning CX_ERR_UNSUPPORTED at these dims exactly as before; routing them here
+ * is a later, separate decision.
+ * Refused: NULL value or counts4 CX_ERR_INVALID_ARGUMENT; no graph or a captured stream CX_ERR_STATE; a handle created with dim 1 - 4
+ * (use cx_log_evidence), other families, a factor of another kind, partitioned handles (halo lists, state halos, a chain's time
+ * block) CX_ERR_UNSUPPORTED; wired handles (cx_graph_wire) cannot exist at these dims.  Synchronous; moves no message, marginal,
+ * readiness bit or counter. */
+int32_t cx_log_evidence_mfma(cx_handle *h, double *value, int64_t *counts4);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

@@ -136,6 +136,12 @@ class Handle {
         check(cx_log_evidence(h_, &v, o.data()));
         return {v, o};
     }
+    // the same at the matrix-core dims, 5 .. 64 (cx_log_evidence_mfma): one wave per term on the f64 matrix cores
+    std::pair<double, std::array<int64_t, 4>> log_evidence_mfma() {
+        double v = 0; std::array<int64_t, 4> o{};
+        check(cx_log_evidence_mfma(h_, &v, o.data()));
+        return {v, o};
+    }
     // the connected component of every named variable (empty: every variable in ascending id) and the number of components; components
     // are numbered by their least variable id (cx_graph_components)
     std::pair<std::vector<int64_t>, int64_t> components(const std::vector<int64_t> &variable_ids = {}) {

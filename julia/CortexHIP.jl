@@ -297,6 +297,14 @@ function log_evidence(p)
     return value[], out
 end
 
+# the same at the matrix-core dims (cx_create dim 5 - 64; cx_log_evidence_mfma): one wave per term on the f64 matrix cores
+function log_evidence_mfma(p)
+    value = Ref{Float64}(0.0)
+    out = zeros(Int64, 4)
+    check(p.handle, ccall((:cx_log_evidence_mfma, lib), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}), p.handle, value, out))
+    return value[], out
+end
+
 # the connected components of the graph as cx_graph_create received it (numbered by their least variable id): (labels, C) for the named
 # variables (nothing: every variable in ascending id, n_variables of them); host work only
 function graph_components(p, n_variables::Integer, variable_ids::Union{Nothing,Vector{Int64}} = nothing)
