@@ -359,10 +359,19 @@ class DeviceGraph:
         """cx_factor_beliefs: the joint posterior of two-variable Gaussian factors from the stored messages, (means [n, 2d],
         covariances [n, 2d, 2d]) in the order (out, in) — ADDITIVE: the lower variable id first.  Observed entries are the datum with
         zero rows and columns; a factor with an undefined input (or a belief that is not positive definite) reads as NaN."""
+        return self._factor_beliefs(self.lib.cx_factor_beliefs, factor_ids)
+
+    def factor_beliefs_mfma(self, factor_ids):
+        """cx_factor_beliefs_mfma: factor_beliefs at the matrix-core dims (a handle created with dim 5 .. 64), two-variable
+        CX_FACTOR_GAUSS_LINEAR factors — the same shapes, order and NaN rule; d is the dim the handle was created with, whatever tile
+        size it runs in.  factor_beliefs itself keeps refusing these dims."""
+        return self._factor_beliefs(self.lib.cx_factor_beliefs_mfma, factor_ids)
+
+    def _factor_beliefs(self, call, factor_ids):
         f = _i64(np.atleast_1d(factor_ids))
         n2 = 2 * self.dim
         out = np.zeros((len(f), n2 + n2 * n2), dtype=np.float64)
-        self._check(self.lib.cx_factor_beliefs(self.h, len(f), _p(f, C.c_int64), _p(out, C.c_double)))
+        self._check(call(self.h, len(f), _p(f, C.c_int64), _p(out, C.c_double)))
         return out[:, :n2].copy(), out[:, n2:].reshape(len(f), n2, n2).copy()
 
     def factor_statistics(self, factor_ids=None, groups=None, n_groups=None):
@@ -370,6 +379,15 @@ class DeviceGraph:
         (dim 2..4): one group per parameter set (n_groups default: the sets given to set_factor_matrices).  Returns ({"n" [G],
         "sum_r" [G, d], "sum_x" [G, d], "S_rr", "S_rx", "S_xx" [G, d, d]}, counts) with counts "factors", "groups", "undefined",
         "not_positive_definite"; a group's arrays (n excepted) are NaN when one of its factors is undefined or not positive definite."""
+        return self._factor_statistics(self.lib.cx_factor_statistics, factor_ids, groups, n_groups)
+
+    def factor_statistics_mfma(self, factor_ids=None, groups=None, n_groups=None):
+        """cx_factor_statistics_mfma: factor_statistics at the matrix-core dims (a handle created with dim 5 .. 64) — the same
+        arguments, dict keys, shapes, counts and NaN rule, r = x_out - A x_in (no offsets exist there).  One wave per factor on the f64
+        matrix cores; sums in a fixed order, bit-identical across calls.  factor_statistics itself keeps refusing these dims."""
+        return self._factor_statistics(self.lib.cx_factor_statistics_mfma, factor_ids, groups, n_groups)
+
+    def _factor_statistics(self, call, factor_ids, groups, n_groups):
         d = self.dim
         if factor_ids is None:
             if groups is not None:
@@ -388,8 +406,8 @@ class DeviceGraph:
         ns = 1 + 2 * d + 3 * d * d
         out = np.zeros((max(int(n_groups), 0), ns), dtype=np.float64)
         cnt = (C.c_int64 * 4)()
-        self._check(self.lib.cx_factor_statistics(self.h, n, None if f is None else _p(f, C.c_int64), None if g is None else _p(g, C.c_int64),
-                                                  int(n_groups), _p(out, C.c_double) if out.size else None, cnt))
+        self._check(call(self.h, n, None if f is None else _p(f, C.c_int64), None if g is None else _p(g, C.c_int64),
+                         int(n_groups), _p(out, C.c_double) if out.size else None, cnt))
         G = len(out)
         o = 1 + 2 * d
         stats = {"n": out[:, 0].copy(), "sum_r": out[:, 1:1 + d].copy(), "sum_x": out[:, 1 + d:o].copy(),

@@ -75,7 +75,8 @@ def group(stats, g):
 
 def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_component=False):
     """EM on the parameter sets of a dim 2..4 DeviceGraph: per iteration sweep(sweeps_per_iter) → log_evidence → factor_statistics
-    (one group per parameter set) → m_step → set_factor_matrices.
+    (one group per parameter set) → m_step → set_factor_matrices.  On a handle of dim 5..64 the same loop runs on log_evidence_mfma and
+    factor_statistics_mfma; offsets= and by_component=True raise ValueError there (neither exists at these dims).
 
     sets: {set: (A, Q)}, the starting parameters (set on the handle here).  learn: a tuple for every set, or {set: tuple}.
     Returns (trace, params): trace[i] = log p(data) under the parameters of iteration i (n_iter + 1 values, the last under the final
@@ -94,6 +95,11 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_
     statistics: the iteration is then a generalised EM without that guarantee."""
     if dev.dim < 2:
         raise ValueError("em: dim 2..4 (dim 1 has per-factor parameters: call factor_statistics with explicit groups and m_step)")
+    mfma = dev.dim >= 5      # the matrix-core dims: log_evidence_mfma and factor_statistics_mfma
+    if mfma and offsets is not None:
+        raise ValueError("em: offsets= at dim 5..64: these dims have no per-factor offsets (set_factor_offsets is dim 2..4)")
+    if mfma and by_component:
+        raise ValueError("em: by_component=True at dim 5..64: log_evidence_components does not exist at these dims (log_evidence_mfma gives the total)")
     if dev.schedule not in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE):
         warnings.warn("em: the log-evidence is guaranteed non-decreasing only under an exact E-step (chain scan, tree, reference order on "
                       "a forest)", RuntimeWarning, stacklevel=2)
@@ -119,11 +125,11 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_
         if by_component:
             trace.append(dev.log_evidence_components()[0])
         else:
-            value, cnt = dev.log_evidence()
+            value, cnt = dev.log_evidence_mfma() if mfma else dev.log_evidence()
             trace.append(value)
         if it == n_iter:
             break
-        stats, _ = dev.factor_statistics(n_groups=n_groups)
+        stats, _ = (dev.factor_statistics_mfma if mfma else dev.factor_statistics)(n_groups=n_groups)
         for s, (A, Q) in params.items():
             ls = learn.get(s, ("A", "Q")) if isinstance(learn, dict) else learn
             if not ls:

@@ -838,6 +838,42 @@ int32_t cx_log_evidence_components(cx_handle *h, int64_t cap, double *values, in
  * readiness bit or counter. */
 int32_t cx_log_evidence_mfma(cx_handle *h, double *value, int64_t *counts4);
 
+/* ---- factor beliefs and EM statistics at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
+ * cx_factor_beliefs_mfma / cx_factor_statistics_mfma: cx_factor_beliefs and cx_factor_statistics for a handle created with dim 5 .. 64 —
+ * the same contract, row layouts, roles (out, in), grouping rules, counts and NaN rule (see there and DESIGN.md §4f), with d the
+ * CALLER's dim: a belief row is 2d + (2d)^2 doubles, a statistics row 1 + 2d + 3d^2.  A dim embedded in the next tile size (5 .. 15 in
+ * 16, 17 .. 31 in 32, 33 .. 63 in 64, or one forced by CX_MFMA_DIM) returns the real block only, with the real model's values at any
+ * internal tile size.  Covered: the two-variable CX_FACTOR_GAUSS_LINEAR factor with either, both or none of its ends observed; opaque
+ * messages are part of each variable's sum.  There are no offsets at these dims: r = x_out - A x_in.  They read what
+ * cx_log_evidence_mfma reads (the STORED factor→variable messages and the data; a leave-one-out message is the sum of the variable's
+ * other messages, never a difference), work after every schedule, are exact on forests at a fixed point and give the Bethe factor
+ * beliefs elsewhere.  One wave per factor on the f64 matrix cores: OUT is eliminated first, IN's marginal follows, and
+ * the statistics are formed in residual coordinates directly (K = M^-1 Λ_out A), so that a flat OUT leaf gives Cov(r) = Q to rounding.
+ * A factor with a NaN input record or datum is undefined; one whose inputs are defined and one of whose two factorisations meets a
+ * non-positive pivot is not positive definite: its belief row is NaN, in the statistics it is counted in counts4[2] / counts4[3] and
+ * its group's row is NaN (n_g excepted).
+ * Grouping of cx_factor_statistics_mfma: factor_ids == NULL (and groups == NULL; n is ignored): one group per parameter set, every
+ * two-variable CX_FACTOR_GAUSS_LINEAR factor counts, n_groups must exceed the largest set in use, and a factor of any other kind but
+ * an opaque message is CX_ERR_UNSUPPORTED (naming it).  factor_ids, groups (length n): cx_factor_statistics' rules — one parameter set
+ * per group and a factor listed twice CX_ERR_INVALID_ARGUMENT, an unknown id CX_ERR_NOT_FOUND, a factor of another kind
+ * CX_ERR_UNSUPPORTED, group -1 skips.
+ * Sums: the factors sorted by group, then factor index, are cut into partials of ceil(factors / W) factors of one group, W = 1024 at an
+ * internal dim of 64 and 2048 below; one wave adds a partial's factors in order, a second kernel a group's partials in order; plain
+ * f64, no atomics.  The cut depends on the grouping alone: two calls on one state of one handle are bit-identical (another handle
+ * holding the same factors among others may cut elsewhere).  The lists of the last grouping are cached (an O(n) comparison on the host
+ * for the same arrays) and rebuilt when other variables are observed; new rule parameters re-upload the A table only.
+ * Device workspace: at most W wave workspaces of 6 KD^2 + 4 KD doubles (KD the internal dim) and one row of 2d + 3d^2 doubles per
+ * partial, at most W + n_groups of them — at most 305 MB plus n_groups rows of 99,328 B at KD = d = 64 (1024 x 198,656 B of wave
+ * workspaces, 1024 x 99,328 B of rows), 154 MB at 32, 39 MB at 16, whatever the number of factors.
+ * cx_factor_beliefs_mfma works through its list W factors at a time.
+ * Refused as cx_log_evidence_mfma refuses, each text naming the function: other families, a handle created with dim 1 - 4 (use
+ * cx_factor_beliefs / cx_factor_statistics), partitioned handles CX_ERR_UNSUPPORTED; no graph, a captured stream, rule tables not on
+ * the device CX_ERR_STATE; NULL arguments CX_ERR_INVALID_ARGUMENT.  cx_factor_beliefs and cx_factor_statistics keep refusing these
+ * dims.  Synchronous; they move no message, marginal, readiness bit or counter. */
+int32_t cx_factor_beliefs_mfma(cx_handle *h, int64_t n, const int64_t *factor_ids, double *out);
+int32_t cx_factor_statistics_mfma(cx_handle *h, int64_t n, const int64_t *factor_ids, const int64_t *groups, int64_t n_groups, double *out,
+                                  int64_t *counts4);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

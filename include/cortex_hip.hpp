@@ -186,6 +186,24 @@ class Handle {
                                    out.data(), o.data()));
         return {out, o};
     }
+    // the two above at the matrix-core dims, 5 .. 64 (cx_factor_beliefs_mfma, cx_factor_statistics_mfma): the same layouts with d the dim
+    // the handle was created with; one wave per factor on the f64 matrix cores
+    std::vector<double> factor_beliefs_mfma(const std::vector<int64_t> &factor_ids) {
+        std::vector<double> out(factor_ids.size() * (size_t)(2 * dim_ + 4 * dim_ * dim_) + 1);      // (+ 1: never a NULL array)
+        check(cx_factor_beliefs_mfma(h_, (int64_t)factor_ids.size(), factor_ids.data(), out.data()));
+        out.pop_back();
+        return out;
+    }
+    std::pair<std::vector<double>, std::array<int64_t, 4>> factor_statistics_mfma(const std::vector<int64_t> &factor_ids, const std::vector<int64_t> &groups,
+                                                                                  int64_t n_groups) {
+        need(groups.size(), factor_ids.size(), "factor_statistics_mfma groups");
+        std::vector<double> out((size_t)n_groups * (size_t)(1 + 2 * dim_ + 3 * dim_ * dim_));
+        std::array<int64_t, 4> o{};
+        const bool by_set = factor_ids.empty();
+        check(cx_factor_statistics_mfma(h_, (int64_t)factor_ids.size(), by_set ? nullptr : factor_ids.data(), by_set ? nullptr : groups.data(), n_groups,
+                                        out.data(), o.data()));
+        return {out, o};
+    }
     // the predictive score of every datum that a Gaussian rule factor generates, from the stored messages (cx_predictive): per row ŷ (d), S
     // (d x d, row-major), log density, squared standardised residual; factor_ids empty: every row in ascending factor id (`ids` names them).
     // mode CX_PREDICT_LOO: given all other data; CX_PREDICT_CAUSAL: given the data of the inputs' ancestors (a chain: the Kalman innovations,

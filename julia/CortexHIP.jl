@@ -356,6 +356,29 @@ function factor_statistics(p, factor_ids::Union{Nothing, Vector{Int64}}, groups:
     return out, counts
 end
 
+# the two above at the matrix-core dims (cx_create dim 5 - 64; cx_factor_beliefs_mfma, cx_factor_statistics_mfma): the same layouts with
+# d = p.dim, one wave per factor on the f64 matrix cores
+function factor_beliefs_mfma(p, factor_ids::Vector{Int64})
+    d = p.dim
+    out = zeros(Float64, 2d + 4d * d, length(factor_ids))
+    check(p.handle, ccall((:cx_factor_beliefs_mfma, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}), p.handle, length(factor_ids), factor_ids, out))
+    return out
+end
+
+function factor_statistics_mfma(p, factor_ids::Union{Nothing, Vector{Int64}}, groups::Union{Nothing, Vector{Int64}}, n_groups::Integer)
+    d = p.dim
+    out = zeros(Float64, 1 + 2d + 3d * d, n_groups)
+    counts = zeros(Int64, 4)
+    n = factor_ids === nothing ? 0 : length(factor_ids)
+    fp = factor_ids === nothing ? Ptr{Int64}(C_NULL) : pointer(factor_ids)
+    gp = groups === nothing ? Ptr{Int64}(C_NULL) : pointer(groups)
+    GC.@preserve factor_ids groups begin
+        check(p.handle, ccall((:cx_factor_statistics_mfma, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, n, fp, gp, n_groups, out, counts))
+    end
+    return out, counts
+end
+
 # the predictive score of every datum that a Gaussian rule factor generates, from the stored messages (ABI 8; dim 1 - 4): mode :loo (given
 # all other data) or :causal (given the data of the inputs' ancestors; a chain: the Kalman innovations, total = log_evidence).
 # (factor ids, a (d + d^2 + 2) x n matrix — column f = ŷ | S (row-major) | log density | squared standardised residual —, total, [rows,
