@@ -401,10 +401,10 @@ static int32_t pairs_allowed(cx_handle *h, int32_t n_sweeps, bool last_marg_only
         pl.H = h->pair_H; pl.W = h->pair_W; pl.block_cols = h->pair_block_cols;
         h->pair_rows = re && std::atoi(re) >= 1 ? std::atoi(re) : cx::lattice::choose_rows(pl, cx::pair_capacity_blocks(h));
         // ... and of the deep launches, here and not in the first long call: the occupancy queries stay out of a caller's timed region
-        // (CX_DEEP_ROWS: tests, A/B)
+        // (CX_DEEP_ROWS: tests, A/B).  Under the packed map of the deep launches: the fewest rows at which the launch they make is resident
         const char *de = std::getenv("CX_DEEP_ROWS");
         for (int d = 3; d <= kDeepMax; d++)
-            h->deep_rows[d] = de && std::atoi(de) >= 1 ? std::atoi(de) : cx::lattice::deep::choose_rows(pl, cx::deep_capacity_blocks(h, d), d);
+            h->deep_rows[d] = de && std::atoi(de) >= 1 ? std::atoi(de) : cx::lattice::deep::choose_rows_packed(pl, cx::deep_capacity_blocks(h, d), d);
     }
     *yes = true;
     return CX_OK;

@@ -9,6 +9,8 @@
 //   cxh_flat_lattice  the grid plan of the paired sweep (cx_lattice_plan.h)
 //   cxh_flat_lattice_deep  the strips, levels and rows of the deep sweep on that plan (cx_lattice_deep.h)
 //   cxh_lattice_deep_interior  which waves of the deep sweep take the interior instance, beside what the general predicates say of them
+//   cxh_lattice_deep_packed  the packed map of the deep sweep: the (strip, segment) of every wave of every workgroup, and their count
+//   cxh_lattice_deep_rows_packed  the rows per segment chosen under that map
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
 //                  plain struct with cx_handle's host fields
 //   cxh_flat_components  the connected components of the flattened graph (cx_components.h)
@@ -461,6 +463,30 @@ int32_t cxh_lattice_deep_interior(int32_t K, int32_t W, int32_t H, int32_t R, in
             general[w] = (int8_t)all;
         }
     return nstrips * nseg;
+}
+
+// the packed map of the deep sweep on a grid W wide at depth K with nseg segments (geometry alone).  Returns packed_blocks, the workgroups of the
+// launch, -1 for arguments out of range.  wave2 (may be NULL) = [n_blocks][4]{strip, segment} of wave w of workgroup `slab` by packed_wave,
+// {-1, -1} for a wave without work; n_blocks may exceed the count (the test looks beyond it)
+int32_t cxh_lattice_deep_packed(int32_t K, int32_t W, int32_t nseg, int32_t n_blocks, int32_t *wave2) {
+    namespace dp = cx::lattice::deep;
+    if (K < dp::kMinDepth || K > dp::kMaxDepth || W < 1 || nseg < 1 || n_blocks < 0) return -1;
+    for (int slab = 0; wave2 && slab < n_blocks; slab++)
+        for (int w = 0; w < cx::lattice::kStripsPerBlock; w++) {
+            int strip = -1, seg = -1;
+            const bool work = dp::packed_wave(slab, w, W, nseg, K, &strip, &seg);
+            wave2[(slab * 4 + w) * 2] = work ? strip : -1; wave2[(slab * 4 + w) * 2 + 1] = work ? seg : -1;
+        }
+    return dp::packed_blocks(W, nseg, K);
+}
+
+// the rows per segment that choose_rows_packed gives an H x W grid at depth K on a device that holds `capacity` workgroups; -1: out of range
+int32_t cxh_lattice_deep_rows_packed(int32_t K, int32_t H, int32_t W, int64_t capacity) {
+    namespace dp = cx::lattice::deep;
+    if (K < dp::kMinDepth || K > dp::kMaxDepth || W < 1 || H < 1 || capacity < 1) return -1;
+    cx::lattice::Plan pl;
+    pl.H = H; pl.W = W;
+    return dp::choose_rows_packed(pl, capacity, K);
 }
 
 // the connected components of the flattened graph (cx_components.h): var_label [nv] by variable index (ascending id), fac_label [nf] by

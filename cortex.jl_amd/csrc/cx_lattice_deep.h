@@ -42,9 +42,32 @@ CX_LAT_HD int load_hi(int r1, int H, int K) { return row_hi(r1, H, K, 1); }
 CX_LAT_HD bool strip_interior(int strip, int W, int K) { return lane_col(strip, 0, K) >= 1 && lane_col(strip, 63, K) <= W - 2; }
 CX_LAT_HD bool segment_interior(int r0, int r1, int H, int K) { return r0 - (K - 1) >= 1 && r1 + (K - 1) - 1 <= H - 2; }
 
-inline int32_t strips(int W, int K) { return (W + strip_cols(K) - 1) / strip_cols(K); }
+CX_LAT_HD int32_t strips(int W, int K) { return (W + strip_cols(K) - 1) / strip_cols(K); }
 inline int32_t block_cols(int W, int K) { return (strips(W, K) + kStripsPerBlock - 1) / kStripsPerBlock; }
-// fewer than 4 (K - 1) rows per segment read (1 + 2 (K - 1) / R) > 1.5 times the messages: a grid too tall for one resident round runs more
+
+// The packed map: which (strip, segment) wave w of workgroup `slab` runs, on nseg segments.  A full workgroup column bc (four strips) holds one
+// workgroup per segment, column by column: wave w runs strip 4 bc + w.  A last column of s < 4 strips would leave 4 - s waves of every
+// workgroup without work; there a workgroup takes floor(4 / s) consecutive segments, from seg0 on: wave w runs strip 4 bc + w mod s of
+// segment seg0 + w div s.  False: the wave has no work (w div s beyond floor(4 / s), a segment beyond the last, a slab beyond packed_blocks)
+CX_LAT_HD bool packed_wave(int slab, int w, int W, int nseg, int K, int *strip, int *seg) {
+    const int full = strips(W, K) / kStripsPerBlock, s = strips(W, K) - full * kStripsPerBlock;
+    if (slab < full * nseg) {
+        const int bc = slab / nseg;
+        *strip = bc * kStripsPerBlock + w; *seg = slab - bc * nseg;
+        return true;
+    }
+    if (s == 0) return false;
+    const int per = kStripsPerBlock / s, seg0 = (slab - full * nseg) * per;
+    *strip = full * kStripsPerBlock + w % s; *seg = seg0 + w / s;
+    return w / s < per && *seg < nseg;
+}
+// the workgroups of a launch under the packed map: the slabs that hold a wave with work
+CX_LAT_HD int32_t packed_blocks(int W, int nseg, int K) {
+    const int full = strips(W, K) / kStripsPerBlock, s = strips(W, K) - full * kStripsPerBlock;
+    if (s == 0) return full * nseg;
+    const int per = kStripsPerBlock / s;
+    return full * nseg + (nseg + per - 1) / per;
+}// fewer than 4 (K - 1) rows per segment read (1 + 2 (K - 1) / R) > 1.5 times the messages: a grid too tall for one resident round runs more
 // than one round instead (cx_lattice_plan.h: kMinRows is this floor at K = 2)
 inline int min_rows(int K) { return 4 * (K - 1); }
 
@@ -53,6 +76,14 @@ inline int choose_rows(const Plan &p, int64_t capacity_blocks, int K) {
     const int64_t seg_max = std::max<int64_t>(1, capacity_blocks / std::max<int32_t>(1, block_cols(p.W, K)));
     const int64_t R = (p.H + seg_max - 1) / seg_max;
     return (int)std::min<int64_t>(kMaxRows, std::max<int64_t>(min_rows(K), R));
+}
+
+// the same under the packed map: the fewest rows, not below min_rows(K), at which the packed launch is resident (never more than choose_rows:
+// packing only takes workgroups away)
+inline int choose_rows_packed(const Plan &p, int64_t capacity_blocks, int K) {
+    for (int R = min_rows(K); R < kMaxRows; R++)
+        if (packed_blocks(p.W, n_segments(p, R), K) <= capacity_blocks) return R;
+    return kMaxRows;
 }
 
 // how many (strip, segment) waves store for each variable at depth K and R rows per segment, by the kernel's own predicates (the tests want 1)

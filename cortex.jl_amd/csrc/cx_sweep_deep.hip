@@ -16,10 +16,18 @@
 // from it one iteration later, in front of that iteration's loads.  And the loop starts one row early, on a row of zeros, so that the first
 // row is loaded where every other row is and the loop is entered with nothing in flight.  One s_waitcnt vmcnt(0) per iteration remains, where
 // the loaded row is taken over; it also waits for level K's four stores of the iteration, which the in-order counter cannot tell apart.
+// (Issued in every iteration outside every branch, as buffer stores with an offset beyond the buffer where nothing is to be stored, they
+// make that wait a vmcnt(4) and stay in flight over it; on the card that was not faster, three waves per SIMD cover the wait already:
+// profiles/deep_sweep_stores.md.)
 //
 // Two instances per depth, chosen per wave (wave-uniformly): a wave all of whose columns and rows have four neighbours in the grid
 // (cx_lattice_deep.h: strip_interior, segment_interior) runs the loop with every edge test folded to true; every other wave runs the
 // general loop.  The arithmetic, its order, the point-mass branch of the rule and the test for an undefined message are the same in both.
+//
+// Waves to workgroups (cx_lattice_deep.h: packed_wave).  Four adjacent strips of one segment make a workgroup.  Where the last workgroup
+// column has s < 4 strips, a workgroup takes floor(4 / s) consecutive segments of it instead, so that no wave slot of a resident workgroup
+// stays empty: on the flagship grid at K = 4 (25 strips) that is a ninth of the slots, and it lets the launch be resident at 12 rows per
+// segment instead of 13 (choose_rows_packed; profiles/deep_sweep_stores.md).  Which wave runs which (strip, segment) changes no stored bit.
 //
 // Bit-identity with K plain sweeps.  Every level is the pair kernel's: the same leave_one_out over the fixed order unary, left, right, up,
 // down with +0 for an absent direction, the same factor_rule<kRuleAdditive>(., q, 1.0, 0.0), q of a factor read at one of its two slots.
@@ -227,15 +235,17 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
     if (bad) *abort_word = 1u;      // (an ordinary per-lane store)
 }
 
-// grid = block_cols * nseg workgroups; wave w of workgroup (bc, seg) owns strip 4 bc + w, rows [seg R, seg R + R)
+// grid = packed_blocks workgroups (cx_lattice_deep.h: the packed map).  Wave w of workgroup (bc, seg) of a full workgroup column owns strip
+// 4 bc + w, rows [seg R, seg R + R); in a last column of s < 4 strips a workgroup holds floor(4 / s) consecutive segments, wave w strip
+// 4 bc + w mod s of segment seg0 + w div s, and a wave beyond them returns at once
 template <int K>
 __global__ __launch_bounds__(kBlock) void k_sweep_deep(int H, int W, int R, int nseg, const int32_t *__restrict__ slice_off, const double *__restrict__ q,
                                                        const double2 *__restrict__ f2v_in, double2 *__restrict__ f2v_out, unsigned *__restrict__ abort_word) {
     namespace dp = lattice::deep;
-    const int s = deep_slab(blockIdx.x, gridDim.x);
-    const int bc = s / nseg, seg = s - bc * nseg;       // consecutive segments of one column of workgroups share an XCD (their halo rows meet in its L2)
-    const int strip = __builtin_amdgcn_readfirstlane(bc * lattice::kStripsPerBlock + (threadIdx.x >> 6));
-    if (strip * dp::strip_cols(K) >= W) return;         // (wave-uniform: the last workgroup column may hold fewer than four strips)
+    // consecutive slabs are consecutive segments of one column of workgroups and share an XCD (their halo rows meet in its L2)
+    const int s = deep_slab(blockIdx.x, gridDim.x), w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int strip, seg;
+    if (!dp::packed_wave(s, w, W, nseg, K, &strip, &seg)) return;      // (wave-uniform)
     const int r0 = seg * R, r1 = min(r0 + R, H);
     if (dp::strip_interior(strip, W, K) && dp::segment_interior(r0, r1, H, K)) deep_wave<K, true>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
     else deep_wave<K, false>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
@@ -255,7 +265,7 @@ int64_t deep_capacity_blocks(const cx_handle *h, int depth) { return depth == 3 
 
 void launch_sweep_deep(cx_handle *h, int depth, const double2 *f2v_in, double2 *f2v_out) {
     const int R = h->deep_rows[depth], nseg = (h->pair_H + R - 1) / R;
-    const dim3 grid((unsigned)(lattice::deep::block_cols(h->pair_W, depth) * nseg));
+    const dim3 grid((unsigned)lattice::deep::packed_blocks(h->pair_W, nseg, depth));
     if (depth == 3)
         hipLaunchKernelGGL(k_sweep_deep<3>, grid, dim3(kBlock), 0, h->stream, h->pair_H, h->pair_W, R, nseg, h->d_slice_off, h->d_q, f2v_in, f2v_out, h->pair_abort.dev);
     else
