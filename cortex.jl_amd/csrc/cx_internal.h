@@ -116,6 +116,7 @@ namespace lm { struct Cache; }
 namespace fs { struct Cache; }
 namespace sp { struct Plan; }
 namespace pr { struct Plan; }
+namespace prm { struct Plan; }
 namespace cm { struct Plan; }
 
 }  // namespace cx
@@ -261,6 +262,8 @@ struct DevState {
     std::unique_ptr<fs::Cache, Deleter<fs::Cache>> learn;
     std::unique_ptr<sp::Plan, Deleter<sp::Plan>> sample;
     std::unique_ptr<pr::Plan, Deleter<pr::Plan>> predict;
+    // cx_predictive_mfma (cx_predict_mfma.hip): the rows of the last (mode, factor_ids) at the matrix-core dims, the [A' | Q] table and the call's scratch
+    std::unique_ptr<prm::Plan, Deleter<prm::Plan>> predict_mfma;
     // cx_causal_marginals (cx_causal.hip): the class of every slot and the transition list, with the call's scratch; the plan is due
     // again after whatever changes the graph or the observed flags (raised by: cx_derived.h)
     std::unique_ptr<cm::Plan, Deleter<cm::Plan>> causal;

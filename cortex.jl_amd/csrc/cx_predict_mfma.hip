@@ -1,0 +1,486 @@
+// cx_predict_mfma.hip — cx_predictive_mfma and cx_predictive_rows_mfma: cx_predictive at the matrix-core dims (cx_create dim
+// 5 .. 64, internal tiles of 16 / 32 / 64): for every observation y that a two-variable rule factor y = A x + N(0, Q) generates from a
+// non-observed x, the predictive distribution of that datum given other data, its log score and its squared standardised residual, from
+// the stored factor→variable messages.  DESIGN.md §4o derives it; nothing here is a difference of messages:
+//
+//   cavity       Λc = Σ kept Λ, ηc = Σ kept η over x's stored messages the mode keeps (LOO: all but the row's own; CAUSAL: also not those
+//                from rule factors on which x is the IN end), summed directly as cx_log_evidence_mfma sums its leave-one-out messages
+//   Λc = U'U,    z = U^-T ηc,   Z = U^-T A'   (k_evm_terms' block-column solve with A' in place of B')
+//   S = Q + Z'Z, ŷ = Z'z        (its Gram and vector passes with + for -)
+//   e = y - ŷ,   S = Us'Us,  w = Us^-T e,  maha = Σ_{k < u} w_k²,  log_density = -½ (u log 2π + log det S + maha)
+//
+// One wave per row in the form of k_evm_terms (cx_evidence_mfma.hip): upper tiles in registers, the 16 x 16 diagonal tiles through
+// diag_factor, z parked in LDS across the matrix solve.  A row is UNDEFINED when a stored message into x (kept or not) or the datum holds
+// NaN, and otherwise IMPROPER when nothing is kept (flat by structure: no factorisation), when a pivot below u of Λc or S is not positive
+// and finite, or when a pivot of Λc is at or below kFlat times the same diagonal entry of the sum of ALL stored messages into x: a
+// message whose information is flat reaches the sum as the rounding of C - Yt'Yt, a number of either sign that must not pass for a
+// cavity (cx_predict.hip: kFlatPivot).
+//
+// Embedded dims (a user dim u below the tile size KD): every matrix is block-diagonal, real block and padding block.  The padding block
+// of a SUM OF MESSAGES may be zero (no rule table is added here, unlike cx_log_evidence_mfma's factor terms), and Z'Z runs over every
+// row of Z: the identity is added to the padding diagonal of Λc before it is factored, which leaves the real block as it is.
+//
+// k_prm_rows writes (log_density, status) per row at the row's index and, when asked, the row's u + u² + 2 doubles; k_prm_part folds 256
+// rows into an ev::Part and ev::final_sum adds the parts in index order: no atomics, two calls on one state are bit-identical, and the
+// total does not depend on how the payload is cut into chunks.
+#include "cx_evidence_core.h"
+#include "cx_evidence_mfma_core.h"
+
+namespace cx {
+namespace prm {
+
+using namespace w64;
+using evm::add_sources;
+using evm::factor_solve;
+using evm::wave_sum;
+
+constexpr int kTB = 256;                              // rows per block of k_prm_part
+constexpr int64_t kRowBufBytes = (int64_t)32 << 20;   // the device row buffer: the payload goes to the host a chunk at a time
+constexpr int kScored = 0, kUndefined = 1, kImproper = 2;
+
+// row record (8 int32): {parameter set, the slot of the datum (the OUT end's), kept offset, kept count, excluded offset, excluded count, 0, 0};
+// kept and excluded are runs of message slots in `srcs`.  ttab: [set][A' | Q] at the internal dim.  One wave per row, rows [row0, row0 + n);
+// out: null, or n rows of u + u² + 2 doubles (row row0 first).
+template <int NT, int WAVES_PER_SIMD>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
+void k_prm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t *__restrict__ srcs, const double *__restrict__ ttab,
+                const double *__restrict__ f2v, const double *__restrict__ v2f, const int u, const double k_flat, double *__restrict__ rval,
+                uint8_t *__restrict__ rflag, double *__restrict__ out) {
+    constexpr int KD = 16 * NT, KM = KD + KD * KD, NU = NT * (NT + 1) / 2;
+    __shared__ double S[16 * kLdT];
+    __shared__ double Vs[NT][16 * kLdT];
+    __shared__ double ZS[KD];
+    if ((int)blockIdx.x >= n) return;
+    const int w = row0 + (int)blockIdx.x;
+    const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, mo = g * KD + c, rr = c >> 2;
+    const bool diag_lane = g == (c & 3);      // entry [i][i] of a diagonal tile sits in lane (g, c) = (i & 3, i), register i >> 2
+    const int32_t *t = rec + 8 * (int64_t)w;
+    const int set = t[0], yslot = t[1], k_off = t[2], k_n = t[3], x_off = t[4], x_n = t[5];
+    const double *tab = ttab + (int64_t)set * 2 * KD * KD;
+    const int no = u + u * u + 2;
+    double *o = out ? out + (int64_t)blockIdx.x * no : nullptr;
+    const double nan = __builtin_nan("");
+
+    // every store of the payload's matrix part: the same lane writes the same address whether it carries a value or NaN
+    auto put_s = [&](int a, int b, int r, double v) {
+        const int row = 16 * a + g + 4 * r, col = 16 * b + c;
+        if (row < u && col < u) o[u + row * u + col] = v;
+    };
+    auto unscored = [&](int status) {
+        if (o) {
+#pragma unroll
+            for (int j = 0; j < NT; j++)
+                if (g == 0 && 16 * j + c < u) o[16 * j + c] = nan;
+#pragma unroll
+            for (int a = 0; a < NT; a++)
+#pragma unroll
+                for (int b = 0; b < NT; b++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) put_s(a, b, r, nan);
+            if (lane == 0) { o[u + u * u] = nan; o[u + u * u + 1] = nan; }
+        }
+        if (lane == 0) { rval[w] = 0.0; rflag[w] = (uint8_t)status; }
+    };
+
+    // ---- the cavity's sums, the belief's diagonal, what is undefined --------------------------------------------------------------
+    d4 M[NU];
+    double wcv[NT];
+#pragma unroll
+    for (int i = 0; i < NU; i++) M[i] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < NT; j++) wcv[j] = 0.0;
+    add_sources<NT>(M, wcv, f2v, srcs + k_off, k_n, mo, c);
+    bool undef = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
+    bool ynan = false;
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        ynan = ynan || (16 * j + c < u && __builtin_isnan(v2f[(int64_t)yslot * KM + 16 * j + c]));      // (the datum is read again where it is used)
+        // the identity on the padding diagonal
+        const bool pad = diag_lane && 16 * j + c >= u;
+#pragma unroll
+        for (int r = 0; r < 4; r++) M[utn<NT>(j, j)][r] += (pad && r == rr) ? 1.0 : 0.0;
+    }
+    undef = undef || __ballot(ynan) != 0;
+    for (int s = 0; s < x_n; s++) {
+        const double *p = f2v + (int64_t)srcs[x_off + s] * KM;
+        undef = undef || __builtin_isnan(p[0]) || __builtin_isnan(p[KD]);
+    }
+    if (undef) { unscored(kUndefined); return; }
+    if (k_n == 0) { unscored(kImproper); return; }      // nothing is kept: flat by structure
+
+    // ---- Λc = U'U, z = U^-T ηc; the flat-pivot rule off the tile diagonals of V = U^-1 ------------------------------------------------
+    double zrv[NT][4], ld1, q1;
+    bool pd1;
+    factor_solve<NT>(M, wcv, zrv, S, Vs, g, c, u, ld1, q1, pd1);
+    // ref: the diagonal of the sum of ALL stored messages into x (kept and excluded are adjacent runs of srcs), lane c entry 16 k + c
+    bool flat = false;
+#pragma unroll
+    for (int k = 0; k < NT; k++) {
+        double ref = 0.0;
+        for (int s = 0; s < k_n + x_n; s++) ref += f2v[(int64_t)srcs[k_off + s] * KM + KD + (16 * k + c) * (KD + 1)];
+        const double v = Vs[k][c * kLdT + c], piv = 1.0 / (v * v);      // V_kk = 1 / U_kk
+        flat = flat || (16 * k + c < u && !(piv > k_flat * fmax(ref, 0.0)));
+    }
+    if (!pd1 || __ballot(flat) != 0) { unscored(kImproper); return; }
+#pragma unroll
+    for (int j = 0; j < NT; j++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) ZS[16 * j + g + 4 * r] = zrv[j][r];      // (the 16 lanes of a group write one value to one place)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    // ---- Z = U^-T A', one block column at a time ------------------------------------------------------------------------------------
+    d4 Y[NT][NT];
+#pragma unroll
+    for (int b = 0; b < NT; b++) {
+        asm volatile("" ::: "memory");      // (one block column of A' in flight at a time)
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) Y[j][b][r] = ((gcdp)tab)[mo + tile_const_n<NT>(j, b, r)];
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            d4 Vj;
+#pragma unroll
+            for (int r = 0; r < 4; r++) Vj[r] = Vs[j][(g + 4 * r) * kLdT + c];
+            Y[j][b] = tts(Vj, Y[j][b], d4{0.0, 0.0, 0.0, 0.0});
+#pragma unroll
+            for (int jj = j + 1; jj < NT; jj++) Y[jj][b] = tts(neg(M[utn<NT>(j, jj)]), Y[j][b], Y[jj][b]);
+        }
+    }
+    // ---- S = Q + Z'Z (upper tiles), ŷ = Z'z, e = y - ŷ ----------------------------------------------------------------------------
+    d4 Sm[NU];
+    double ecv[NT];
+#pragma unroll
+    for (int a = 0; a < NT; a++) {
+#pragma unroll
+        for (int b = a; b < NT; b++) {
+            asm volatile("" ::: "memory");      // (one tile of Q in flight at a time)
+            d4 G = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < NT; j++) G = tts(Y[j][a], Y[j][b], G);
+#pragma unroll
+            for (int r = 0; r < 4; r++) Sm[utn<NT>(a, b)][r] = ((gcdp)tab)[KD * KD + mo + tile_const_n<NT>(a, b, r)] + G[r];
+        }
+        double p = 0.0;
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) p += Y[j][a][r] * ZS[16 * j + g + 4 * r];
+        const double yh = sum_groups(p);
+        ecv[a] = v2f[(int64_t)yslot * KM + 16 * a + c] - yh;
+        if (o && g == 0 && 16 * a + c < u) o[16 * a + c] = yh;
+    }
+    // the payload's S before the factorisation takes the tiles: the upper tiles as they are, the lower ones turned through LDS
+    if (o) {
+#pragma unroll
+        for (int a = 0; a < NT; a++)
+#pragma unroll
+            for (int b = a; b < NT; b++) {
+                const d4 D = Sm[utn<NT>(a, b)];
+                if (b > a) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) put_s(a, b, r, D[r]);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the previous tile's reads have returned
+#pragma unroll
+                for (int r = 0; r < 4; r++) S[(g + 4 * r) * kLdT + c] = D[r];
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                // (a diagonal tile: the mean of the two triangles, so that S is symmetric to the last bit)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const double tr = S[c * kLdT + g + 4 * r];
+                    put_s(b, a, r, b > a ? tr : 0.5 * (D[r] + tr));
+                }
+            }
+    }
+    // ---- the score -------------------------------------------------------------------------------------------------------------------
+    // The lane's coordinates anew: with the two factorisations in one straight line hipcc keeps what the first derives from (g, c) — the
+    // sixteen (k == c) selects of diag_factor among them, 32 registers — for the second, across the matrix solve, and spills at NT = 4
+    int g2 = g, c2 = c;
+    asm volatile("" : "+v"(g2), "+v"(c2));
+    double wrv[NT][4], ld2, maha;
+    bool pd2;
+    factor_solve<NT>(Sm, ecv, wrv, S, Vs, g2, c2, u, ld2, maha, pd2);
+    if (!pd2) { unscored(kImproper); return; }
+    if (lane != 0) return;
+    const double val = -0.5 * (u * ev::kLog2Pi + ld2 + maha);
+    if (o) { o[u + u * u] = val; o[u + u * u + 1] = maha; }
+    rval[w] = val;
+    rflag[w] = (uint8_t)kScored;
+}
+
+// 256 rows -> one ev::Part (fixed-order tree); ev::final_sum adds the parts in index order
+__global__ __launch_bounds__(kTB) void k_prm_part(int n, const double *__restrict__ rval, const uint8_t *__restrict__ rflag, ev::Part *__restrict__ part) {
+    const int i = blockIdx.x * kTB + threadIdx.x;
+    const double s = i < n ? rval[i] : 0.0;
+    const int f = i < n ? (int)rflag[i] : -1;
+    ev::block_part<kTB>(s, 0.0, f == kScored, f == kUndefined, f == kImproper, 0u, part);
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------------
+// The rows follow the mode, the caller's ids, the graph and WHICH variables are observed (vinfo_epoch: cx_derived.h), the [A' | Q] table
+// the rule parameters (param_epoch); messages and data are read by every call
+struct Plan {
+    bool valid = false, explicit_ids = false;
+    int32_t mode = 0;
+    std::vector<int64_t> ids;
+    uint64_t vinfo_epoch = 0, tab_epoch = ~0ull;
+    int64_t n_rows = 0, nb = 0;
+    DevBuf<int32_t> d_rec, d_srcs;
+    DevBuf<double> d_tab, d_rval, d_rows, d_out;
+    DevBuf<uint8_t> d_rflag;
+    DevBuf<ev::Part> d_part;
+    std::vector<double> h_out;
+};
+
+// what the graph says about the two-variable rule factors: by factor index the slots and variables of (out, in) and the parameter set
+struct Pairs {
+    std::vector<int32_t> so, si, vo, vi, set;      // so < 0: no two-variable CX_FACTOR_GAUSS_LINEAR factor
+    int64_t unsupported_fac = -1;
+};
+
+static void pairs_of(const cx_handle *h, Pairs &P) {
+    using namespace cxh;
+    const int64_t ne = h->ne, nf = h->nf;
+    std::vector<int32_t> fe1((size_t)nf, -1), fe2((size_t)nf, -1), nfe((size_t)nf, 0);
+    for (int64_t e = 0; e < ne; e++) {
+        const int64_t f = find_factor(h, h->edge_fac_id[e]);
+        if (fe1[f] < 0) fe1[f] = (int32_t)e; else if (fe2[f] < 0) fe2[f] = (int32_t)e;
+        nfe[f]++;
+    }
+    P.so.assign((size_t)nf, -1); P.si.assign((size_t)nf, -1); P.vo.assign((size_t)nf, -1); P.vi.assign((size_t)nf, -1); P.set.assign((size_t)nf, -1);
+    P.unsupported_fac = -1;
+    for (int64_t f = 0; f < nf; f++) {
+        if (h->fac_kind[f] == CX_FACTOR_OPAQUE) continue;
+        if (h->fac_kind[f] != CX_FACTOR_GAUSS_LINEAR || nfe[f] != 2) { if (P.unsupported_fac < 0) P.unsupported_fac = h->fac_ids[f]; continue; }
+        const int32_t s1 = slot_of_edge(h, fe1[f]), s2 = slot_of_edge(h, fe2[f]);
+        int32_t so = s1, si = s2, vo = h->edge_var[fe1[f]], vi = h->edge_var[fe2[f]];
+        if ((h->spdir[s1] & 1) == 0) { std::swap(so, si); std::swap(vo, vi); }      // spdir[in slot] = 2 set (the message it sends goes forward)
+        P.so[f] = so; P.si[f] = si; P.vo[f] = vo; P.vi[f] = vi; P.set[f] = h->spdir[si] >> 1;
+    }
+}
+
+// a row: the OUT end observed, the IN end not
+static bool is_row(const cx_handle *h, const Pairs &P, int64_t f) {
+    return P.so[f] >= 0 && (h->vinfo[P.vo[f]] & kClamped) != 0 && (h->vinfo[P.vi[f]] & kClamped) == 0;
+}
+
+static const char *kNotARow = " is not a row: a two-variable CX_FACTOR_GAUSS_LINEAR factor whose CX_ROLE_OUT end is observed and whose CX_ROLE_IN end is not";
+
+// the factor indices of the rows, checked: the caller's, in the caller's order, or every row in ascending factor id
+static int32_t list_rows(cx_handle *h, const Pairs &P, const std::string &who, int64_t n, const int64_t *ids, std::vector<int64_t> &fac) {
+    using namespace cxh;
+    fac.clear();
+    if (!ids) {
+        for (int64_t f = 0; f < h->nf; f++) if (is_row(h, P, f)) fac.push_back(f);
+        return CX_OK;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t f = find_factor(h, ids[i]);
+        if (f < 0) return fail(h, CX_ERR_NOT_FOUND, who + ": no factor " + std::to_string(ids[i]));
+        if (!is_row(h, P, f)) return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(ids[i]) + kNotARow);
+        fac.push_back(f);
+    }
+    return CX_OK;
+}
+
+static int32_t build_plan(cx_handle *h, const Pairs &P, Plan &L, int32_t mode, const std::vector<int64_t> &fac, const std::string &who) {
+    using namespace cxh;
+    const int64_t n = (int64_t)fac.size();
+    // CX_PREDICT_CAUSAL: the slots on which a variable is the IN end of a rule factor (cx_predict.hip: build_plan)
+    std::vector<uint8_t> in_slot((size_t)h->nslots, 0);
+    if (mode == CX_PREDICT_CAUSAL)
+        for (int64_t f = 0; f < h->nf; f++) if (P.si[f] >= 0) in_slot[(size_t)P.si[f]] = 1;
+    std::vector<int32_t> rec((size_t)n * 8, 0), srcs;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t f = fac[(size_t)i];
+        const int32_t x = P.vi[f], own = P.si[f];
+        int32_t *r = &rec[(size_t)i * 8];
+        r[0] = P.set[f]; r[1] = P.so[f];
+        // x's slots in ascending neighbour order (k_v2f64's): the kept run, then the excluded one
+        r[2] = (int32_t)srcs.size();
+        for (int32_t e = h->var_off[x]; e < h->var_off[x + 1]; e++) {
+            const int32_t s = slot_of_edge(h, e);
+            if (s != own && !in_slot[(size_t)s]) srcs.push_back(s);
+        }
+        r[3] = (int32_t)srcs.size() - r[2];
+        r[4] = (int32_t)srcs.size();
+        for (int32_t e = h->var_off[x]; e < h->var_off[x + 1]; e++) {
+            const int32_t s = slot_of_edge(h, e);
+            if (s == own || in_slot[(size_t)s]) srcs.push_back(s);
+        }
+        r[5] = (int32_t)srcs.size() - r[4];
+        CX_REQUIRE(h, (int64_t)srcs.size() < (int64_t)0x7fffff00, CX_ERR_UNSUPPORTED, who + ": more than 2^31 inputs");
+    }
+    CX_REQUIRE(h, n < (int64_t)0x7fffff00, CX_ERR_UNSUPPORTED, who + ": more than 2^31 rows");
+    L.valid = false;
+    L.n_rows = n;
+    L.nb = (n + kTB - 1) / kTB;
+    if (srcs.empty()) srcs.push_back(0);      // (never read: no row names a slot)
+    int32_t rc;
+    if ((rc = dev_upload(h, &L.d_rec, rec)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &L.d_srcs, srcs)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &L.d_rval, std::max<int64_t>(n, 1))) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &L.d_rflag, std::max<int64_t>(n, 1))) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &L.d_part, std::max<int64_t>(L.nb, 1))) != CX_OK) return rc;
+    if (!L.d_out && (rc = dev_alloc(h, &L.d_out, 1 + ev::kNCnt)) != CX_OK) return rc;
+    L.h_out.assign(1 + ev::kNCnt, 0.0);
+    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
+    return CX_OK;
+}
+
+// [set][A' | Q] at the internal dim (blockdiag(A, I)', blockdiag(Q, I) for an embedded one: cx_set_factor_matrices)
+static int32_t refresh_tab(cx_handle *h, Plan &L) {
+    if (L.tab_epoch == h->param_epoch && L.d_tab) return CX_OK;
+    const size_t d = (size_t)h->cfg.dim, dd = d * d, ns = std::max<size_t>(h->psets.size(), 1);
+    std::vector<double> tb(ns * 2 * dd, cxh::kNaN);
+    for (size_t s = 0; s < h->psets.size(); s++) {
+        if (h->psets[s].empty()) continue;
+        const double *A = h->psets[s].data(), *Q = A + dd;
+        for (size_t r = 0; r < d; r++)
+            for (size_t c = 0; c < d; c++) {
+                tb[s * 2 * dd + c * d + r] = A[r * d + c];
+                tb[s * 2 * dd + dd + r * d + c] = 0.5 * (Q[r * d + c] + Q[c * d + r]);
+            }
+    }
+    int32_t rc;
+    if ((rc = L.d_tab.ensure(h, (int64_t)tb.size())) != CX_OK) return rc;
+    CX_HIP(h, hipMemcpyAsync(L.d_tab, tb.data(), tb.size() * 8, hipMemcpyHostToDevice, h->stream));
+    CX_HIP(h, hipStreamSynchronize(h->stream));
+    L.tab_epoch = h->param_epoch;
+    return CX_OK;
+}
+
+// rows [row0, row0 + n) (d_rows: their payload, or null)
+static void launch_rows(cx_handle *h, Plan &L, int64_t row0, int64_t n, double *d_rows) {
+    if (!n) return;
+    const int u = h->user_dim ? h->user_dim : h->cfg.dim;
+    // a message that carries no information arrives as the rounding of u-term sums (the measured remainders)
+    const double k_flat = 64.0 * u * 2.220446049250313e-16;
+#define CX_R(N, W)                                                                                                                                   \
+    hipLaunchKernelGGL((k_prm_rows<N, W>), dim3((unsigned)n), dim3(64), 0, h->stream, (int)row0, (int)n, L.d_rec, L.d_srcs, L.d_tab, h->d_mv_f2v, \
+                       h->d_mv_v2f, u, k_flat, L.d_rval, L.d_rflag, d_rows)
+    // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch
+    if (h->cfg.dim == 16) CX_R(1, 4);
+    else if (h->cfg.dim == 32) CX_R(2, 3);
+    else CX_R(4, 2);
+#undef CX_R
+}
+
+// the refusals of cx_log_evidence_mfma under this call's name
+static int32_t prepare(cx_handle *h, const std::string &who, const char *bad_args) {
+    using namespace cxh;
+    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only (the variational and Beta-Bernoulli families have no Gaussian predictive)");
+    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
+    CX_REQUIRE(h, !bad_args, CX_ERR_INVALID_ARGUMENT, who + ": " + (bad_args ? bad_args : ""));
+    CX_REQUIRE(h, cx::is_mfma_dim(h->cfg.dim), CX_ERR_UNSUPPORTED, who + ": the matrix-core dims, 5 .. 64 (dim 1, 2, 3 and 4: cx_predictive)");
+    CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
+               who + ": not for a partitioned handle (halo lists, state halos or a chain's time block: its rows would need owners)");
+    CX_HIP(h, hipSetDevice(h->cfg.device));
+    if (h->stream) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
+        CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
+    }
+    // (mv_check_psets' conditions under this call's name; behind them the tables are on the device: the check below is a guard)
+    CX_REQUIRE(h, (int64_t)h->psets.size() > h->max_pset, CX_ERR_STATE, who + ": a factor names a parameter set that was never set (cx_set_factor_matrices)");
+    for (int64_t i = 0; i <= h->max_pset; i++)
+        CX_REQUIRE(h, !h->psets[i].empty(), CX_ERR_STATE, who + ": parameter set " + std::to_string(i) + " was never set (cx_set_factor_matrices)");
+    CX_REQUIRE(h, h->d_ptab && h->d_ptab_bt && h->d_mv_f2v && h->d_mv_v2f, CX_ERR_STATE, who + ": the rule tables are not on the device (cx_set_factor_matrices)");
+    return CX_OK;
+}
+
+// the pairs of the graph (O(connections) on the host: for a new request only), refused when a factor of another kind exists
+static int32_t checked_pairs(cx_handle *h, const std::string &who, Pairs &P) {
+    using namespace cxh;
+    pairs_of(h, P);
+    if (P.unsupported_fac >= 0)
+        return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(P.unsupported_fac) + " is no two-variable CX_FACTOR_GAUSS_LINEAR factor and no opaque message");
+    return CX_OK;
+}
+
+}  // namespace prm
+
+template <> void Deleter<prm::Plan>::operator()(prm::Plan *P) const { delete P; }
+
+}  // namespace cx
+
+using namespace cxh;
+
+extern "C" int32_t cx_predictive_rows_mfma(cx_handle *h, int64_t cap, int64_t *factor_ids, int64_t *n_rows) {
+    try {
+        namespace prm = cx::prm;
+        const std::string who = "cx_predictive_rows_mfma";
+        prm::Pairs P;
+        int32_t rc;
+        const char *bad = n_rows && cap >= 0 && (cap == 0 || factor_ids) ? nullptr : "null argument or negative capacity";
+        if ((rc = prm::prepare(h, who, bad)) != CX_OK) return rc;
+        if ((rc = prm::checked_pairs(h, who, P)) != CX_OK) return rc;
+        std::vector<int64_t> fac;
+        if ((rc = prm::list_rows(h, P, who, 0, nullptr, fac)) != CX_OK) return rc;
+        *n_rows = (int64_t)fac.size();
+        for (int64_t i = 0; i < std::min<int64_t>(cap, *n_rows); i++) factor_ids[i] = h->fac_ids[(size_t)fac[(size_t)i]];
+        return CX_OK;
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_predictive_rows_mfma: host allocation failed"); }
+}
+
+extern "C" int32_t cx_predictive_mfma(cx_handle *h, int32_t mode, int64_t n, const int64_t *factor_ids, double *out, double *total, int64_t *counts4) {
+    try {
+        namespace prm = cx::prm;
+        const std::string who = "cx_predictive_mfma";
+        int32_t rc;
+        const char *bad = !counts4 ? "counts4 is null"
+                          : mode != CX_PREDICT_LOO && mode != CX_PREDICT_CAUSAL ? "mode is CX_PREDICT_LOO or CX_PREDICT_CAUSAL"
+                          : factor_ids && n < 0 ? "negative count" : nullptr;
+        {
+            if ((rc = prm::prepare(h, who, bad)) != CX_OK) return rc;
+            if (h->predict_mfma && h->predict_mfma->vinfo_epoch != h->vinfo_epoch) h->predict_mfma.reset();      // other variables are observed
+            if (!h->predict_mfma) h->predict_mfma.reset(new prm::Plan());
+            prm::Plan &L = *h->predict_mfma;
+            const bool same = L.valid && L.mode == mode && L.explicit_ids == (factor_ids != nullptr) &&
+                              (!factor_ids || ((int64_t)L.ids.size() == n && std::equal(factor_ids, factor_ids + n, L.ids.begin())));
+            if (!same) {
+                L.valid = false;
+                prm::Pairs P;
+                if ((rc = prm::checked_pairs(h, who, P)) != CX_OK) return rc;
+                std::vector<int64_t> fac;
+                if ((rc = prm::list_rows(h, P, who, n, factor_ids, fac)) != CX_OK) return rc;
+                if ((rc = prm::build_plan(h, P, L, mode, fac, who)) != CX_OK) return rc;
+                L.mode = mode;
+                L.explicit_ids = factor_ids != nullptr;
+                L.ids.assign(factor_ids, factor_ids ? factor_ids + n : factor_ids);
+                L.vinfo_epoch = h->vinfo_epoch;
+                L.valid = true;
+            }
+        }
+        prm::Plan &L = *h->predict_mfma;
+        if ((rc = prm::refresh_tab(h, L)) != CX_OK) return rc;
+        if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
+        const int u = h->user_dim ? h->user_dim : h->cfg.dim;
+        const int64_t no = (int64_t)u + (int64_t)u * u + 2, nr = L.n_rows;
+        if (out && nr) {
+            // the payload a chunk at a time through a bounded device buffer; the (value, status) arrays cover every row
+            const int64_t chunk = std::min<int64_t>(nr, std::max<int64_t>(1, prm::kRowBufBytes / (no * 8)));
+            if ((rc = L.d_rows.ensure(h, chunk * no)) != CX_OK) return rc;
+            for (int64_t r0 = 0; r0 < nr; r0 += chunk) {
+                const int64_t m = std::min(chunk, nr - r0);
+                prm::launch_rows(h, L, r0, m, L.d_rows.get());
+                CX_HIP(h, hipGetLastError());
+                CX_HIP(h, hipMemcpyAsync(out + r0 * no, L.d_rows, (size_t)(m * no) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            }
+        } else {
+            prm::launch_rows(h, L, 0, nr, nullptr);
+        }
+        if (nr) hipLaunchKernelGGL(prm::k_prm_part, dim3((unsigned)L.nb), dim3(prm::kTB), 0, h->stream, (int)nr, L.d_rval, L.d_rflag, L.d_part);
+        cx::ev::final_sum(h, nr ? L.nb : 0, L.d_part, L.d_out);
+        CX_HIP(h, hipGetLastError());
+        CX_HIP(h, hipMemcpyAsync(L.h_out.data(), L.d_out, (1 + cx::ev::kNCnt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        CX_HIP(h, hipStreamSynchronize(h->stream));
+        uint64_t cnt[cx::ev::kNCnt];
+        std::memcpy(cnt, L.h_out.data() + 1, sizeof(cnt));
+        counts4[0] = nr;
+        for (int k = 1; k < 4; k++) counts4[k] = (int64_t)cnt[k - 1];
+        if (total) *total = L.h_out[0];
+        return CX_OK;
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_predictive_mfma: host allocation failed"); }
+}

@@ -417,11 +417,18 @@ class DeviceGraph:
 
     def predictive_rows(self):
         """cx_predictive_rows: the factor ids of the rows predictive(factor_ids=None) scores, ascending"""
+        return self._predictive_rows(self.lib.cx_predictive_rows)
+
+    def predictive_rows_mfma(self):
+        """cx_predictive_rows_mfma: the factor ids of the rows predictive_mfma(factor_ids=None) scores, ascending"""
+        return self._predictive_rows(self.lib.cx_predictive_rows_mfma)
+
+    def _predictive_rows(self, call):
         n = C.c_int64()
-        self._check(self.lib.cx_predictive_rows(self.h, 0, None, C.byref(n)))
+        self._check(call(self.h, 0, None, C.byref(n)))
         ids = np.zeros(n.value, dtype=np.int64)
         if n.value:
-            self._check(self.lib.cx_predictive_rows(self.h, n.value, _p(ids, C.c_int64), C.byref(n)))
+            self._check(call(self.h, n.value, _p(ids, C.c_int64), C.byref(n)))
         return ids
 
     def predictive(self, mode="loo", factor_ids=None, rows=True):
@@ -431,6 +438,16 @@ class DeviceGraph:
         factor_ids=None: every row in ascending factor id.  Returns {"factor_ids", "mean" [n, d], "cov" [n, d, d], "log_density" [n],
         "mahalanobis" [n], "total", "counts"}; a row with an undefined input or an improper predictive is NaN (counts "undefined" /
         "improper"), "total" sums the scored rows only.  rows=False: the total and the counts alone (the arrays are None)."""
+        return self._predictive(self.lib.cx_predictive, self.lib.cx_predictive_rows, mode, factor_ids, rows)
+
+    def predictive_mfma(self, mode="loo", factor_ids=None, rows=True):
+        """cx_predictive_mfma: predictive at the matrix-core dims (a handle created with dim 5 .. 64) — the same arguments, dict keys,
+        shapes, counts and NaN rule; d is the dim the handle was created with, whatever tile size it runs in.  A row is a two-variable
+        CX_FACTOR_GAUSS_LINEAR factor whose OUT end alone is observed.  One wave per row on the f64 matrix cores; the total is
+        bit-identical across calls and between rows=False and rows=True.  predictive itself keeps refusing these dims."""
+        return self._predictive(self.lib.cx_predictive_mfma, self.lib.cx_predictive_rows_mfma, mode, factor_ids, rows)
+
+    def _predictive(self, call, rows_call, mode, factor_ids, rows):
         m = {"loo": L.PREDICT_LOO, "causal": L.PREDICT_CAUSAL}.get(mode, mode)
         d = self.dim
         f = None if factor_ids is None else _i64(np.atleast_1d(factor_ids))
@@ -439,13 +456,13 @@ class DeviceGraph:
         tot, cnt = C.c_double(), (C.c_int64 * 4)()
         keys = ("rows", "scored", "undefined", "improper")
         if not rows:
-            self._check(self.lib.cx_predictive(self.h, int(m), n, pf, None, C.byref(tot), cnt))
+            self._check(call(self.h, int(m), n, pf, None, C.byref(tot), cnt))
             return {"factor_ids": f, "mean": None, "cov": None, "log_density": None, "mahalanobis": None, "total": float(tot.value),
                     "counts": dict(zip(keys, [int(x) for x in cnt]))}
         if f is None:
-            f = self.predictive_rows()
+            f = self._predictive_rows(rows_call)
         out = np.zeros((len(f), d + d * d + 2), dtype=np.float64)
-        self._check(self.lib.cx_predictive(self.h, int(m), n, pf, _p(out, C.c_double) if out.size else None, C.byref(tot), cnt))
+        self._check(call(self.h, int(m), n, pf, _p(out, C.c_double) if out.size else None, C.byref(tot), cnt))
         assert cnt[0] == len(out)
         return {"factor_ids": f, "mean": out[:, :d].copy(), "cov": out[:, d:d + d * d].reshape(len(f), d, d).copy(),
                 "log_density": out[:, d + d * d].copy(), "mahalanobis": out[:, d + d * d + 1].copy(), "total": float(tot.value),

@@ -874,6 +874,39 @@ int32_t cx_factor_beliefs_mfma(cx_handle *h, int64_t n, const int64_t *factor_id
 int32_t cx_factor_statistics_mfma(cx_handle *h, int64_t n, const int64_t *factor_ids, const int64_t *groups, int64_t n_groups, double *out,
                                   int64_t *counts4);
 
+/* ---- predictive scores of the data at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
+ * cx_predictive_mfma / cx_predictive_rows_mfma: cx_predictive and cx_predictive_rows for a handle created with dim 5 .. 64 — the same
+ * contract, modes (CX_PREDICT_LOO, CX_PREDICT_CAUSAL), row order, row layout, counts4 = {rows, scored, undefined, improper}, NaN rule and
+ * total (see there and DESIGN.md §4h), with d the CALLER's dim: a row of `out` is d + d^2 + 2 doubles,
+ *     y^[d] | S[d][d] (row-major, full and symmetric) | log_density | maha.
+ * A dim embedded in the next tile size (5 .. 15 in 16, 17 .. 31 in 32, 33 .. 63 in 64, or one forced by CX_MFMA_DIM) returns the real
+ * block only, with the real model's values at any internal tile size.
+ * A ROW at these dims is a two-variable CX_FACTOR_GAUSS_LINEAR factor  y = A x + N(0, Q)  whose CX_ROLE_OUT end is observed and whose
+ * CX_ROLE_IN end is not: the likelihood factors of a state-space model, and the transition into a clamped state.  A datum on the
+ * CX_ROLE_IN end stays out of scope, as at dim 1 - 4.  Opaque messages are part of a variable's sums.  factor_ids == NULL scores every
+ * row in ascending factor id (cx_predictive_rows_mfma names them), otherwise the n named factors in the caller's order: an unknown id is
+ * CX_ERR_NOT_FOUND, a factor that is not a row CX_ERR_UNSUPPORTED (naming it).
+ * One wave per row on the f64 matrix cores, nothing a difference of messages: the cavity is the SUM of the stored
+ * messages into x that the mode keeps (LOO: all but the row's own; CAUSAL: also none from a rule factor on which x is the CX_ROLE_IN end),
+ * Λc = U'U, Z = U^-T A', S = Q + Z'Z, y^ = Z' U^-T ηc, then S = Us'Us for the score; log-determinant and quadratic form over the real
+ * block.  A row is undefined when a stored message into x (kept or not) or the datum holds NaN; otherwise improper when nothing is kept
+ * (flat by structure, such as the first observation of a chain without a prior under CX_PREDICT_CAUSAL), when a pivot of Λc or S is not
+ * positive and finite, or when a pivot of Λc is at or below 64 d ulp of the same diagonal entry of the sum of ALL stored messages into x
+ * (a message that carries no information — the one behind a leading gap, or a forecast's end — is stored as the rounding of a
+ * difference, of either sign: it must not pass for a cavity).  A row that is not scored is all NaN.
+ * *total (may be NULL): the sum of log_density over the scored rows, folded 256 rows at a time in index order (no atomics): two calls on
+ * one state are bit-identical, rows and total, and the total with out == NULL is bit-identical to the one with rows.  The payload is
+ * large (33,296 B per row at d = 64): it passes through a device buffer of at most 32 MiB, launched and copied a chunk at a time.
+ * The rows of the last (mode, factor_ids) are cached (an O(n) comparison on the host for the same request) and rebuilt when the graph or
+ * the observed flags change; the [A' | Q] table follows cx_set_factor_matrices.  MI355X: profiles/predictive_mfma.md.
+ * cx_predictive and cx_predictive_rows keep returning CX_ERR_UNSUPPORTED at these dims exactly as before.
+ * Refused as cx_log_evidence_mfma refuses, each text naming the function: other families, a handle created with dim 1 - 4 (use
+ * cx_predictive), partitioned handles, a factor of another kind CX_ERR_UNSUPPORTED; no graph, a captured stream, rule tables not on the
+ * device CX_ERR_STATE; an unknown mode, a NULL counts4 or n < 0 with ids CX_ERR_INVALID_ARGUMENT.  Synchronous; moves no message,
+ * marginal, readiness bit or counter. */
+int32_t cx_predictive_mfma(cx_handle *h, int32_t mode, int64_t n, const int64_t *factor_ids, double *out, double *total, int64_t *counts4);
+int32_t cx_predictive_rows_mfma(cx_handle *h, int64_t cap, int64_t *factor_ids, int64_t *n_rows);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

@@ -224,6 +224,22 @@ class Handle {
         check(cx_predictive(h_, mode, (int64_t)factor_ids.size(), ids, rows && !r.rows.empty() ? r.rows.data() : nullptr, &r.total, r.counts.data()));
         return r;
     }
+    // the same at the matrix-core dims, 5 .. 64 (cx_predictive_mfma): one wave per row on the f64 matrix cores; a row is a two-variable
+    // CX_FACTOR_GAUSS_LINEAR factor whose OUT end alone is observed, its d + d² + 2 doubles in the caller's dim
+    Predictive predictive_mfma(int32_t mode, const std::vector<int64_t> &factor_ids = {}, bool rows = true) {
+        Predictive r;
+        r.ids = factor_ids;
+        const int64_t *ids = factor_ids.empty() ? nullptr : factor_ids.data();
+        if (rows && factor_ids.empty()) {
+            int64_t n = 0;
+            check(cx_predictive_rows_mfma(h_, 0, nullptr, &n));
+            r.ids.resize((size_t)n);
+            if (n) check(cx_predictive_rows_mfma(h_, n, r.ids.data(), &n));
+        }
+        if (rows) r.rows.resize(r.ids.size() * (size_t)(dim_ + dim_ * dim_ + 2));
+        check(cx_predictive_mfma(h_, mode, (int64_t)factor_ids.size(), ids, rows && !r.rows.empty() ? r.rows.data() : nullptr, &r.total, r.counts.data()));
+        return r;
+    }
     // the causal estimates of the states beside the smoothed marginals, from the stored messages (cx_causal_marginals): per row the mean (d)
     // then the covariance (d x d, row-major); variable_ids empty: every variable in ascending id.  mode CX_CAUSAL_PREDICTED: p(x_t | y_<t);
     // CX_CAUSAL_FILTERED: p(x_t | y_<=t), with lag L > 0 the fixed-lag smoother p(x_t | y_<=t+L).  counts: rows, finite, with an undefined

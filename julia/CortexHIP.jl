@@ -405,6 +405,30 @@ function predictive(p; mode::Symbol = :loo, factor_ids::Union{Nothing, Vector{In
     return ids, out, total[], counts
 end
 
+# the same at the matrix-core dims (cx_create dim 5 - 64; cx_predictive_mfma, cx_predictive_rows_mfma): one wave per row on the f64 matrix
+# cores; a row is a two-variable CX_FACTOR_GAUSS_LINEAR factor whose OUT end alone is observed, d the dim the handle was created with
+function predictive_mfma(p; mode::Symbol = :loo, factor_ids::Union{Nothing, Vector{Int64}} = nothing, rows::Bool = true)
+    d = p.dim
+    m = mode === :loo ? Int32(0) : mode === :causal ? Int32(1) : throw(ArgumentError("mode is :loo or :causal"))
+    ids = factor_ids
+    if ids === nothing && rows
+        n = Ref{Int64}(0)
+        check(p.handle, ccall((:cx_predictive_rows_mfma, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), p.handle, 0, C_NULL, n))
+        ids = zeros(Int64, n[])
+        check(p.handle, ccall((:cx_predictive_rows_mfma, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), p.handle, n[], ids, n))
+    end
+    out = zeros(Float64, d + d * d + 2, rows ? length(ids) : 0)
+    total = Ref{Float64}(0.0)
+    counts = zeros(Int64, 4)
+    fp = factor_ids === nothing ? Ptr{Int64}(C_NULL) : pointer(factor_ids)
+    op = rows && length(out) > 0 ? pointer(out) : Ptr{Float64}(C_NULL)
+    GC.@preserve factor_ids out begin
+        check(p.handle, ccall((:cx_predictive_mfma, lib), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, m, factor_ids === nothing ? 0 : length(factor_ids), fp, op, total, counts))
+    end
+    return ids, out, total[], counts
+end
+
 # the causal estimates of the states beside the smoothed marginals, from the stored messages (added after ABI 9; dim 1 - 4): mode :predicted
 # (p(x_t | y_<t)) or :filtered (p(x_t | y_<=t); with lag = L > 0 the fixed-lag smoother p(x_t | y_<=t+L)).  A (d + d^2) x n matrix — column i =
 # mean | covariance (row-major) of variable_ids[i]; nothing: every variable in ascending id — and [rows, finite, undefined, improper]
