@@ -118,6 +118,7 @@ namespace sp { struct Plan; }
 namespace pr { struct Plan; }
 namespace prm { struct Plan; }
 namespace cm { struct Plan; }
+namespace cmm { struct Plan; }
 
 }  // namespace cx
 
@@ -264,6 +265,9 @@ struct DevState {
     std::unique_ptr<pr::Plan, Deleter<pr::Plan>> predict;
     // cx_predictive_mfma (cx_predict_mfma.hip): the rows of the last (mode, factor_ids) at the matrix-core dims, the [A' | Q] table and the call's scratch
     std::unique_ptr<prm::Plan, Deleter<prm::Plan>> predict_mfma;
+    // cx_causal_marginals_mfma (cx_causal_mfma.hip): the rows of the last (mode, lag > 0 or not, variable_ids) at the matrix-core dims, the
+    // transition entries of the fixed-lag recursion and the call's scratch (the β buffers among it, allocated by the first call with a lag)
+    std::unique_ptr<cmm::Plan, Deleter<cmm::Plan>> causal_mfma;
     // cx_causal_marginals (cx_causal.hip): the class of every slot and the transition list, with the call's scratch; the plan is due
     // again after whatever changes the graph or the observed flags (raised by: cx_derived.h)
     std::unique_ptr<cm::Plan, Deleter<cm::Plan>> causal;

@@ -25,6 +25,7 @@
 // total does not depend on how the payload is cut into chunks.
 #include "cx_evidence_core.h"
 #include "cx_evidence_mfma_core.h"
+#include "cx_pairs_mfma.h"
 
 namespace cx {
 namespace prm {
@@ -233,33 +234,6 @@ struct Plan {
     std::vector<double> h_out;
 };
 
-// what the graph says about the two-variable rule factors: by factor index the slots and variables of (out, in) and the parameter set
-struct Pairs {
-    std::vector<int32_t> so, si, vo, vi, set;      // so < 0: no two-variable CX_FACTOR_GAUSS_LINEAR factor
-    int64_t unsupported_fac = -1;
-};
-
-static void pairs_of(const cx_handle *h, Pairs &P) {
-    using namespace cxh;
-    const int64_t ne = h->ne, nf = h->nf;
-    std::vector<int32_t> fe1((size_t)nf, -1), fe2((size_t)nf, -1), nfe((size_t)nf, 0);
-    for (int64_t e = 0; e < ne; e++) {
-        const int64_t f = find_factor(h, h->edge_fac_id[e]);
-        if (fe1[f] < 0) fe1[f] = (int32_t)e; else if (fe2[f] < 0) fe2[f] = (int32_t)e;
-        nfe[f]++;
-    }
-    P.so.assign((size_t)nf, -1); P.si.assign((size_t)nf, -1); P.vo.assign((size_t)nf, -1); P.vi.assign((size_t)nf, -1); P.set.assign((size_t)nf, -1);
-    P.unsupported_fac = -1;
-    for (int64_t f = 0; f < nf; f++) {
-        if (h->fac_kind[f] == CX_FACTOR_OPAQUE) continue;
-        if (h->fac_kind[f] != CX_FACTOR_GAUSS_LINEAR || nfe[f] != 2) { if (P.unsupported_fac < 0) P.unsupported_fac = h->fac_ids[f]; continue; }
-        const int32_t s1 = slot_of_edge(h, fe1[f]), s2 = slot_of_edge(h, fe2[f]);
-        int32_t so = s1, si = s2, vo = h->edge_var[fe1[f]], vi = h->edge_var[fe2[f]];
-        if ((h->spdir[s1] & 1) == 0) { std::swap(so, si); std::swap(vo, vi); }      // spdir[in slot] = 2 set (the message it sends goes forward)
-        P.so[f] = so; P.si[f] = si; P.vo[f] = vo; P.vi[f] = vi; P.set[f] = h->spdir[si] >> 1;
-    }
-}
-
 // a row: the OUT end observed, the IN end not
 static bool is_row(const cx_handle *h, const Pairs &P, int64_t f) {
     return P.so[f] >= 0 && (h->vinfo[P.vo[f]] & kClamped) != 0 && (h->vinfo[P.vi[f]] & kClamped) == 0;
@@ -365,38 +339,6 @@ static void launch_rows(cx_handle *h, Plan &L, int64_t row0, int64_t n, double *
     else if (h->cfg.dim == 32) CX_R(2, 3);
     else CX_R(4, 2);
 #undef CX_R
-}
-
-// the refusals of cx_log_evidence_mfma under this call's name
-static int32_t prepare(cx_handle *h, const std::string &who, const char *bad_args) {
-    using namespace cxh;
-    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only (the variational and Beta-Bernoulli families have no Gaussian predictive)");
-    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
-    CX_REQUIRE(h, !bad_args, CX_ERR_INVALID_ARGUMENT, who + ": " + (bad_args ? bad_args : ""));
-    CX_REQUIRE(h, cx::is_mfma_dim(h->cfg.dim), CX_ERR_UNSUPPORTED, who + ": the matrix-core dims, 5 .. 64 (dim 1, 2, 3 and 4: cx_predictive)");
-    CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
-               who + ": not for a partitioned handle (halo lists, state halos or a chain's time block: its rows would need owners)");
-    CX_HIP(h, hipSetDevice(h->cfg.device));
-    if (h->stream) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
-        CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
-    }
-    // (mv_check_psets' conditions under this call's name; behind them the tables are on the device: the check below is a guard)
-    CX_REQUIRE(h, (int64_t)h->psets.size() > h->max_pset, CX_ERR_STATE, who + ": a factor names a parameter set that was never set (cx_set_factor_matrices)");
-    for (int64_t i = 0; i <= h->max_pset; i++)
-        CX_REQUIRE(h, !h->psets[i].empty(), CX_ERR_STATE, who + ": parameter set " + std::to_string(i) + " was never set (cx_set_factor_matrices)");
-    CX_REQUIRE(h, h->d_ptab && h->d_ptab_bt && h->d_mv_f2v && h->d_mv_v2f, CX_ERR_STATE, who + ": the rule tables are not on the device (cx_set_factor_matrices)");
-    return CX_OK;
-}
-
-// the pairs of the graph (O(connections) on the host: for a new request only), refused when a factor of another kind exists
-static int32_t checked_pairs(cx_handle *h, const std::string &who, Pairs &P) {
-    using namespace cxh;
-    pairs_of(h, P);
-    if (P.unsupported_fac >= 0)
-        return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(P.unsupported_fac) + " is no two-variable CX_FACTOR_GAUSS_LINEAR factor and no opaque message");
-    return CX_OK;
 }
 
 }  // namespace prm

@@ -475,6 +475,18 @@ class DeviceGraph:
         ascending id.  Returns {"variable_ids", "mean" [n, d], "cov" [n, d, d], "counts"}; an observed variable's row is its datum and a
         zero covariance, a row with an undefined input or a precision that is not positive definite is NaN (counts "undefined" /
         "improper")."""
+        return self._causal_marginals(self.lib.cx_causal_marginals, mode, lag, variable_ids)
+
+    def causal_marginals_mfma(self, mode="filtered", lag=0, variable_ids=None):
+        """cx_causal_marginals_mfma: causal_marginals at the matrix-core dims (a handle created with dim 5 .. 64) — the same arguments,
+        dict keys, shapes, counts and NaN rule; d is the dim the handle was created with, whatever tile size it runs in.  One wave per
+        row on the f64 matrix cores; a lag L adds L launches over every transition with two free ends and, on its first use, the β
+        workspace (cortex_hip.h states its size).  A row is also improper when a pivot of its precision is at rounding level of the
+        sum of all stored messages into the variable (the state behind a leading gap, predicted).  causal_marginals itself keeps
+        refusing these dims."""
+        return self._causal_marginals(self.lib.cx_causal_marginals_mfma, mode, lag, variable_ids)
+
+    def _causal_marginals(self, call, mode, lag, variable_ids):
         m = {"predicted": L.CAUSAL_PREDICTED, "filtered": L.CAUSAL_FILTERED}.get(mode, mode)
         d = self.dim
         if variable_ids is None:
@@ -484,8 +496,7 @@ class DeviceGraph:
             n = len(ids)
         out = np.zeros((n, d + d * d), dtype=np.float64)
         cnt = (C.c_int64 * 4)()
-        self._check(self.lib.cx_causal_marginals(self.h, int(m), int(lag), n if ids is not None else 0, None if ids is None else _p(ids, C.c_int64),
-                                                 _p(out, C.c_double), cnt))
+        self._check(call(self.h, int(m), int(lag), n if ids is not None else 0, None if ids is None else _p(ids, C.c_int64), _p(out, C.c_double), cnt))
         assert cnt[0] == n
         return {"variable_ids": ids, "mean": out[:, :d].copy(), "cov": out[:, d:].reshape(n, d, d).copy(),
                 "counts": dict(zip(("rows", "finite", "undefined", "improper"), [int(x) for x in cnt]))}

@@ -907,6 +907,49 @@ int32_t cx_factor_statistics_mfma(cx_handle *h, int64_t n, const int64_t *factor
 int32_t cx_predictive_mfma(cx_handle *h, int32_t mode, int64_t n, const int64_t *factor_ids, double *out, double *total, int64_t *counts4);
 int32_t cx_predictive_rows_mfma(cx_handle *h, int64_t cap, int64_t *factor_ids, int64_t *n_rows);
 
+/* ---- causal marginals of the states at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
+ * cx_causal_marginals_mfma: cx_causal_marginals for a handle created with dim 5 .. 64 — the same contract, modes (CX_CAUSAL_PREDICTED
+ * with lag 0, CX_CAUSAL_FILTERED with lag >= 0), row order (variable_ids == NULL: every variable in ascending id, n ignored; otherwise
+ * the n named variables in the caller's order), counts4 = {rows, finite, undefined, improper} and NaN rule (see there and DESIGN.md
+ * §4j), with d the CALLER's dim: a row of `out` is d + d^2 doubles, mean[d] | cov[d][d] (row-major, full, symmetric to the last bit).
+ * An observed variable's row is its datum and a zero covariance (one without a connection has no stored datum: its row is NaN and counted
+ * undefined, as cx_causal_marginals returns it; cx_graph_create makes no such variable).  A dim embedded in the next tile size (5 .. 15 in 16, 17 .. 31 in 32,
+ * 33 .. 63 in 64, or one forced by CX_MFMA_DIM) returns the real block only, with the real model's values at any internal tile size.
+ * The classes are cx_causal_marginals', restricted to what these dims hold (two-variable CX_FACTOR_GAUSS_LINEAR factors and opaque
+ * messages; a factor of another kind is CX_ERR_UNSUPPORTED, naming it) — cx_predictive_mfma's conventions, so that the two calls agree:
+ *   U_i  opaque messages, and messages from factors on which i is the CX_ROLE_OUT end
+ *   O_i  messages from factors on which i is the CX_ROLE_IN end and whose OUT end is observed
+ *   T_i  messages from factors on which i is the CX_ROLE_IN end and whose OUT end is not observed
+ *   predicted = Σ U_i,   filtered = Σ U_i + Σ O_i,   lag L = Σ U_i + Σ O_i + Σ_{a in T_i} β_a^(L),
+ * β_a^(0) flat, β_a^(s) = the factor's own sum-product rule towards i applied to Σ O_j + Σ_{a' in T_j} β_a'^(s-1), j the OUT end of a:
+ * sums of the messages kept, never the belief minus something.
+ * One wave per item on the f64 matrix cores.  The backward pass is launched L times, one wave per T entry,
+ * double-buffered over β (no launch reads what it writes): the wave-per-message rule of the sweeps on the sending slot's tables, with
+ * j's O messages and the previous β of j's T entries as its sources.  An entry that no datum can have reached after s steps (the host
+ * plan knows its distance to the nearest datum downstream) stores β^(s) as exact zeros — the rule would leave the rounding of a
+ * difference, a "precision" of either sign — so a state behind the last datum returns the same bits at every lag; where the rule meets
+ * a NaN input or a matrix that is not positive definite, β is NaN and every row that sums it is undefined.  The output kernel sums the
+ * kept records of a row in ascending neighbour order, Λ = U'U, cov = (U^-T)'(U^-T), mean = (U^-T)' U^-T η.  A row is undefined when a
+ * stored message into i (kept or not) or a summed β holds NaN; otherwise improper when nothing is kept, when a pivot is not positive and
+ * finite, or when a pivot is at or below 64 d ulp of the same diagonal entry of the sum of ALL stored messages into i
+ * (cx_predictive_mfma's flat-pivot rule: a message that carries no information is stored as the rounding of a difference, and alone in
+ * the predicted sum — the state behind a leading gap — it must not pass for a prediction).  Statuses are folded 256 rows at a time in
+ * index order (no atomics): two calls on one state are bit-identical, and a variable's numbers do not depend on which others share the
+ * call.  The payload passes through a device buffer of at most 32 MiB, launched and copied a chunk at a time.
+ * Cost: one wave per row; a lag L adds L launches over EVERY transition with two free ends, whatever rows are asked for.
+ * Device workspace: with lag > 0, (1 for lag 1, otherwise 2) x (T entries) x (KD + KD²) doubles for β, KD the internal dim — 33,280 B
+ * per entry and buffer at KD = 64: 6.7 GB for both at 1e5 transitions, 2.1 GB at KD = 32, 0.44 GB at KD = 16; allocated by the first
+ * call with a lag and kept, growing only, until the handle's graph goes — also across a change of the observed flags, which rebuilds
+ * the lists alone (a failed allocation is CX_ERR_OUT_OF_MEMORY); plus one record per variable with more than three sources.
+ * The rows of the last (mode, lag > 0 or not, variable_ids) and the T entries are cached (an O(n) comparison on the host for the same
+ * request) and rebuilt when the observed flags change; rule tables, messages and data are read by every call.  MI355X:
+ * profiles/causal_marginals_mfma.md.  cx_causal_marginals keeps returning CX_ERR_UNSUPPORTED at these dims exactly as before.
+ * Refused as cx_predictive_mfma refuses, each text naming the function: other families, a handle created with dim 1 - 4 (use
+ * cx_causal_marginals), partitioned handles, a factor of another kind (a guard: cx_graph_create admits none at these dims) CX_ERR_UNSUPPORTED; no graph, a
+ * captured stream, parameter sets never set CX_ERR_STATE; an unknown mode, lag < 0, lag > 0 with CX_CAUSAL_PREDICTED, a NULL out or counts4, or n < 0 with ids
+ * CX_ERR_INVALID_ARGUMENT; an unknown id CX_ERR_NOT_FOUND.  Synchronous; moves no message, marginal, readiness bit or counter. */
+int32_t cx_causal_marginals_mfma(cx_handle *h, int32_t mode, int32_t lag, int64_t n, const int64_t *variable_ids, double *out, int64_t *counts4);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

@@ -254,6 +254,17 @@ class Handle {
         r.rows.resize((size_t)n * (size_t)(dim_ + dim_ * dim_));
         return r;
     }
+    // the same at the matrix-core dims, 5 .. 64 (cx_causal_marginals_mfma): one wave per row on the f64 matrix cores, rows of d + d² doubles
+    // in the caller's dim; a lag L adds L launches over every transition with two free ends and, on its first use, the β workspace
+    CausalMarginals causal_marginals_mfma(int32_t mode, int32_t lag = 0, const std::vector<int64_t> &variable_ids = {}) {
+        const int64_t n = variable_ids.empty() ? stats().n_variables : (int64_t)variable_ids.size();
+        CausalMarginals r;
+        r.rows.resize((size_t)n * (size_t)(dim_ + dim_ * dim_) + 1);      // (+ 1: never a NULL out)
+        check(cx_causal_marginals_mfma(h_, mode, lag, (int64_t)variable_ids.size(), variable_ids.empty() ? nullptr : variable_ids.data(), r.rows.data(),
+                                       r.counts.data()));
+        r.rows.resize((size_t)n * (size_t)(dim_ + dim_ * dim_));
+        return r;
+    }
     // joint posterior draws on a forest (the simulation smoother): n_samples x n x dim doubles for variable_ids (empty: every variable in
     // ascending id); noise (optional): the standard normals, n_samples x n_variables x dim in ascending id order, in place of the device's
     // Philox4x32-10 draws.  counts: free variables, components, components with an undefined input, components not positive definite

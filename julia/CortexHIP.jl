@@ -448,6 +448,24 @@ function causal_marginals(p; mode::Symbol = :filtered, lag::Integer = 0, variabl
     return out[:, 1:n], counts
 end
 
+# the same at the matrix-core dims (cx_create dim 5 - 64; cx_causal_marginals_mfma): one wave per row on the f64 matrix cores, d the dim the
+# handle was created with; a lag L adds L launches over every transition with two free ends and, on its first use, the β workspace
+function causal_marginals_mfma(p; mode::Symbol = :filtered, lag::Integer = 0, variable_ids::Union{Nothing, Vector{Int64}} = nothing)
+    d = p.dim
+    m = mode === :predicted ? Int32(0) : mode === :filtered ? Int32(1) : throw(ArgumentError("mode is :predicted or :filtered"))
+    st = zeros(Int64, 9)                                                  # cx_stats: n_variables first
+    check(p.handle, ccall((:cx_graph_stats, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), p.handle, st))
+    n = variable_ids === nothing ? Int(st[1]) : length(variable_ids)
+    out = zeros(Float64, d + d * d, max(n, 1))
+    counts = zeros(Int64, 4)
+    ip = variable_ids === nothing ? Ptr{Int64}(C_NULL) : pointer(variable_ids)
+    GC.@preserve variable_ids begin
+        check(p.handle, ccall((:cx_causal_marginals_mfma, lib), Int32, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, m, Int32(lag), variable_ids === nothing ? 0 : n, ip, out, counts))
+    end
+    return out[:, 1:n], counts
+end
+
 # joint posterior draws on a forest, the simulation smoother (ABI 7; dim 1 - 4): a d x n x n_samples array (column-major: sample s of
 # variable i is out[:, i, s]) for variable_ids (nothing: every variable in ascending id), and [free, components, undefined, not pd].
 # noise (optional): the standard normals, a d x n_variables x n_samples array in ascending id order, in place of the device's Philox4x32-10
