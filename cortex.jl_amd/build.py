@@ -96,6 +96,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), hdr_t):
             return obj
         extra = ["-DCX_C64_STAMPS=1"] if (src == "cx_mv64chain.hip" and os.environ.get("CX_BUILD_STAMPS")) else []      # lab build: phase stamps
+        if src == "cx_sweep_deep.hip" and os.environ.get("CX_BUILD_DEEP_STAMPS"):      # lab build: per-wave stamps (tools/lab/deep_sweep_stamps.py)
+            extra = ["-DCX_DEEP_STAMPS=" + os.environ["CX_BUILD_DEEP_STAMPS"]]
         cmd = [_hipcc()] + flags + extra + ["-c", path, "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -9,6 +9,7 @@
 //   cxh_flat_lattice  the grid plan of the paired sweep (cx_lattice_plan.h)
 //   cxh_flat_lattice_deep  the strips, levels and rows of the deep sweep on that plan (cx_lattice_deep.h)
 //   cxh_lattice_deep_interior  which waves of the deep sweep take the interior instance, beside what the general predicates say of them
+//   cxh_lattice_deep_classes  which of the three instances (general, interior, column-edge) every wave of the deep sweep takes
 //   cxh_lattice_deep_packed  the packed map of the deep sweep: the (strip, segment) of every wave of every workgroup, and their count
 //   cxh_lattice_deep_rows_packed  the rows per segment chosen under that map
 //   cxh_flat_*     cx_graph_create's flattening (cx_flatten.h) and CX_SCHED_CHAIN_SCAN's chain decomposition (cx_chains.h) over a
@@ -461,6 +462,36 @@ int32_t cxh_lattice_deep_interior(int32_t K, int32_t W, int32_t H, int32_t R, in
                 for (int m = dp::row_lo(r0, K, j); m < dp::row_hi(r1, H, K, j); m++) all = all && m > 0 && m < H - 1;
             }
             general[w] = (int8_t)all;
+        }
+    return nstrips * nseg;
+}
+
+// the instance each wave of the deep sweep takes on an H x W grid at depth K and R rows per segment (geometry alone), in the order strip-major
+// of cxh_flat_lattice_deep: cls = wave_class, the kernel's choice (0 general, 1 interior, 2 column-edge), with column_edge checked against it;
+// rows_ok / cols_ok = what the general path would find, cell by cell: every row loaded and every row of [row_lo, row_hi) at every level lies in
+// 1 .. H - 2 with row_lo / row_hi not clipped by the grid; every lane 0 .. 63 holds a column in 1 .. W - 2.  Returns the number of waves, -1 for
+// arguments out of range, -2 if column_edge and wave_class disagree
+int32_t cxh_lattice_deep_classes(int32_t K, int32_t W, int32_t H, int32_t R, int8_t *cls, int8_t *rows_ok, int8_t *cols_ok) {
+    namespace dp = cx::lattice::deep;
+    if (K < dp::kMinDepth || K > dp::kMaxDepth || W < 1 || H < 1 || R < 1) return -1;
+    const int nseg = (H + R - 1) / R, nstrips = dp::strips(W, K);
+    size_t w = 0;
+    for (int strip = 0; strip < nstrips; strip++)
+        for (int seg = 0; seg < nseg; seg++, w++) {
+            const int r0 = seg * R, r1 = std::min<int>(r0 + R, H);
+            cls[w] = (int8_t)dp::wave_class(strip, r0, r1, H, W, K);
+            if (dp::column_edge(strip, r0, r1, H, W, K) != (cls[w] == dp::kWaveColumnEdge)) return -2;
+            bool rows = true, cols = true;
+            for (int lane = 0; lane < 64; lane++) {
+                const int c = dp::lane_col(strip, lane, K);
+                cols = cols && c >= 1 && c <= W - 2;
+            }
+            for (int r = r0 - (K - 1); r <= r1 + (K - 1) - 1; r++) rows = rows && r >= 1 && r <= H - 2;
+            for (int j = 1; j <= K; j++) {
+                rows = rows && dp::row_lo(r0, K, j) == r0 - (K - j) && dp::row_hi(r1, H, K, j) == r1 + (K - j);
+                for (int m = dp::row_lo(r0, K, j); m < dp::row_hi(r1, H, K, j); m++) rows = rows && m >= 1 && m <= H - 2;
+            }
+            rows_ok[w] = (int8_t)rows; cols_ok[w] = (int8_t)cols;
         }
     return nstrips * nseg;
 }

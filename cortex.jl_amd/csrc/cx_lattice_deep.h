@@ -42,6 +42,17 @@ CX_LAT_HD int load_hi(int r1, int H, int K) { return row_hi(r1, H, K, 1); }
 CX_LAT_HD bool strip_interior(int strip, int W, int K) { return lane_col(strip, 0, K) >= 1 && lane_col(strip, 63, K) <= W - 2; }
 CX_LAT_HD bool segment_interior(int r0, int r1, int H, int K) { return r0 - (K - 1) >= 1 && r1 + (K - 1) - 1 <= H - 2; }
 
+// The three instances of the kernel, by wave.  A column-edge wave has an interior segment and a strip that is not: every row it touches at
+// any level lies in 1 .. H - 2, so every row test is true and what is left to test (the lane's column, its left and right neighbour) does not
+// change over the wave's row loop.  On a grid narrower than a strip both edge columns lie in the one strip.  Every other wave that is not
+// interior — the top and bottom segments, whatever the strip — is general.
+constexpr int kWaveGeneral = 0, kWaveInterior = 1, kWaveColumnEdge = 2;
+CX_LAT_HD bool column_edge(int strip, int r0, int r1, int H, int W, int K) { return segment_interior(r0, r1, H, K) && !strip_interior(strip, W, K); }
+CX_LAT_HD int wave_class(int strip, int r0, int r1, int H, int W, int K) {
+    if (!segment_interior(r0, r1, H, K)) return kWaveGeneral;
+    return strip_interior(strip, W, K) ? kWaveInterior : kWaveColumnEdge;
+}
+
 CX_LAT_HD int32_t strips(int W, int K) { return (W + strip_cols(K) - 1) / strip_cols(K); }
 inline int32_t block_cols(int W, int K) { return (strips(W, K) + kStripsPerBlock - 1) / kStripsPerBlock; }
 

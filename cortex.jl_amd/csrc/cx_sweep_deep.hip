@@ -20,9 +20,14 @@
 // make that wait a vmcnt(4) and stay in flight over it; on the card that was not faster, three waves per SIMD cover the wait already:
 // profiles/deep_sweep_stores.md.)
 //
-// Two instances per depth, chosen per wave (wave-uniformly): a wave all of whose columns and rows have four neighbours in the grid
-// (cx_lattice_deep.h: strip_interior, segment_interior) runs the loop with every edge test folded to true; every other wave runs the
-// general loop.  The arithmetic, its order, the point-mass branch of the rule and the test for an undefined message are the same in both.
+// Three instances per depth, chosen per wave (wave-uniformly; cx_lattice_deep.h: wave_class).  INTERIOR: a wave all of whose columns and rows
+// have four neighbours in the grid (strip_interior, segment_interior) runs the loop with every edge test folded to true.  COLUMN-EDGE: a
+// wave of an interior segment whose strip holds the grid's first or last column (both, on a grid narrower than a strip): every row it
+// touches at any level lies in 1 .. H - 2, so every row test is folded to true, and what depends on the lane — whether its column lies in
+// the grid and has a left and a right neighbour, the ranks of its loads, of qR / qD and of the four stores — is the same for every row and
+// is formed once in front of the loop; its loads are issued without a branch like the interior loop's, each direction from its own rank.
+// GENERAL: every other wave, the top and bottom segments.  921 / 891 / 1,144 instructions per row at K = 4 (profiles/deep_sweep_edges.md).
+// The arithmetic, its order, the point-mass branch of the rule and the test for an undefined message are the same in all three.
 //
 // Waves to workgroups (cx_lattice_deep.h: packed_wave).  Four adjacent strips of one segment make a workgroup.  Where the last workgroup
 // column has s < 4 strips, a workgroup takes floor(4 / s) consecutive segments of it instead, so that no wave slot of a resident workgroup
@@ -75,7 +80,7 @@ __device__ __forceinline__ void deep_leave_one_out(const double2 (&in)[5], doubl
     for (int k = 4; k >= 0; k--) { out[k] = add2(out[k], acc); acc = add2(acc, in[k]); }
 }
 
-struct DeepRow {          // one grid row as loaded: the five ranks, the q of the right and the lower factor, the lane's first slot
+struct DeepRow {          // one grid row as loaded: the five ranks (a column-edge wave: by direction), the q of the right and the lower factor, the lane's first slot
     double2 x[5];
     double qR, qD;
     int base;
@@ -107,20 +112,31 @@ __device__ __forceinline__ bool deep_undefined(const double2 (&o)[5], bool hasL,
 
 }  // namespace
 
-// one wave: strip `strip`, rows [r0, r1).  INTERIOR (cx_lattice_deep.h: strip_interior and segment_interior, both wave-uniform): every lane's
-// column and every row touched lie inside the grid with all four neighbours, so the edge tests below are the constant true, every cell has
-// degree 5 and the ranks are constants; the selects on them compile to nothing.  The point-mass branch of factor_rule and the test for an
-// undefined message stay in both instances.
-template <int K, bool INTERIOR>
+// one wave: strip `strip`, rows [r0, r1).  ROWS (cx_lattice_deep.h: segment_interior) and COLS (strip_interior), both wave-uniform: every
+// row touched, resp. every lane's column, lies inside the grid with both neighbours in that direction, so the edge tests of that direction
+// below are the constant true and the selects on them compile to nothing.  With both every cell has degree 5 and the ranks are constants.
+// With ROWS alone (a column-edge wave) nothing that is tested depends on the row: colv, hasL, hasR and the rank offsets of the loads and
+// the stores are per-lane constants of the whole loop, formed once in front of it.  The point-mass branch of factor_rule and
+// the test for an undefined message stay in every instance.
+template <int K, bool ROWS, bool COLS>
 __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int W, const int32_t *__restrict__ slice_off, const double *__restrict__ q,
                                           const double2 *__restrict__ f2v_in, double2 *__restrict__ f2v_out, unsigned *__restrict__ abort_word) {
     namespace dp = lattice::deep;
     const int lane = threadIdx.x & 63;
     const int c = dp::lane_col(strip, lane, K);
-    const bool colv = INTERIOR || (c >= 0 && c < W);
-    const bool hasL = INTERIOR || (colv && c > 0), hasR = INTERIOR || (colv && c < W - 1);
+    const bool colv = COLS || (c >= 0 && c < W);
+    const bool hasL = COLS || (colv && c > 0), hasR = COLS || (colv && c < W - 1);
     const bool own = dp::lane_owned(lane, c, W, K) && colv;
     const bool two = hasL && hasR;                      // left AND right: up / down sit one rank higher
+    // the ranks that do not depend on the row (ROWS: none does), as slot offsets: the right, the upper and the lower factor of the lane's
+    // column, and the right factor of the column to its left (level K's store to the left)
+    const int offR = (COLS ? 2 : lattice::rank_right(c)) * kBlock, offU = (COLS ? 3 : lattice::rank_up(c, W)) * kBlock;
+    const int offRofL = (COLS ? 2 : lattice::rank_right(c - 1)) * kBlock;
+    // A column-edge wave (EDGE) loads every row at every lane without a branch, as the interior instance does, each direction from its own
+    // rank: x[1 .. 4] = left, right, up, down.  A direction the lane's column has not is loaded from rank 0 and replaced by +0 at level 1; a
+    // lane outside the row reads variable 0 (a corner of the grid: ranks 0 .. 2), and nothing tested or stored depends on what it holds
+    constexpr bool EDGE = ROWS && !COLS;
+    const int ldL = hasL ? lattice::rank_left() * kBlock : 0, ldR = hasR ? offR : 0, ldU = colv ? offU : 0, ldD = colv ? offU + kBlock : 0;
     bool bad = false;
 
     // rows outside the grid and lanes outside the row load nothing: zeros, q = 1 (their results are never used).  The lane's first slot of a
@@ -128,9 +144,9 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
     // i + 1, and is kept as loaded; the sum is formed at the top of the next iteration, in front of that iteration's loads.  So no instruction
     // between the loads of a row and the end of the arithmetic of the row before needs a loaded value (profiles/deep_sweep_issue.md: the
     // loop's loads and waits)
-    auto in_grid = [&](int r) { return INTERIOR || (r >= 0 && r < H && colv); };
-    auto load_raw = [&](int r) { return in_grid(r) ? slice_off[(r * W + c) >> kSliceShift] : 0; };
-    auto finish_base = [&](int r, int raw) { return in_grid(r) ? raw + ((r * W + c) & (kBlock - 1)) : 0; };
+    auto in_grid = [&](int r) { return (ROWS || (r >= 0 && r < H)) && colv; };
+    auto load_raw = [&](int r) { return EDGE ? slice_off[(colv ? r * W + c : 0) >> kSliceShift] : in_grid(r) ? slice_off[(r * W + c) >> kSliceShift] : 0; };
+    auto finish_base = [&](int r, int raw) { return EDGE ? raw + ((colv ? r * W + c : 0) & (kBlock - 1)) : in_grid(r) ? raw + ((r * W + c) & (kBlock - 1)) : 0; };
     auto zero_row = [](int base) {
         DeepRow in;
 #pragma unroll
@@ -140,13 +156,18 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
     };
     auto load_row = [&](int r, int base) {
         DeepRow in = zero_row(base);
-        if (in_grid(r)) {
-            const int deg = INTERIOR ? 5 : lattice::degree(r, c, H, W);
+        if (EDGE) {
+            in.x[0] = deep_load_stream(&f2v_in[in.base]);
+            in.x[1] = deep_load_stream(&f2v_in[in.base + ldL]); in.x[2] = deep_load_stream(&f2v_in[in.base + ldR]);
+            in.x[3] = deep_load_stream(&f2v_in[in.base + ldU]); in.x[4] = deep_load_stream(&f2v_in[in.base + ldD]);
+            in.qR = q[in.base + ldR]; in.qD = q[in.base + ldD];
+        } else if (in_grid(r)) {
+            const int deg = COLS ? 5 : lattice::degree(r, c, H, W);
 #pragma unroll
             for (int k = 0; k < 5; k++)
                 if (k < deg) in.x[k] = deep_load_stream(&f2v_in[in.base + k * kBlock]);
-            if (hasR) in.qR = q[in.base + (INTERIOR ? 2 : lattice::rank_right(c)) * kBlock];
-            if (INTERIOR || r < H - 1) in.qD = q[in.base + (INTERIOR ? 4 : lattice::rank_down(r, c, W)) * kBlock];
+            if (hasR) in.qR = q[in.base + offR];
+            if (ROWS || r < H - 1) in.qD = q[in.base + (ROWS ? offU + kBlock : lattice::rank_down(r, c, W) * kBlock)];
         }
         return in;
     };
@@ -180,16 +201,16 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
         P[0] = cur.x[0]; qR[0] = cur.qR; qD[0] = cur.qD; base[0] = cur.base;
         DeepOut e;
         e.L = zero2(); e.R = zero2(); e.up = zero2(); e.down = zero2();
-        if (i >= i0 && (INTERIOR || (i >= 0 && i < H))) {    // (uniform) level 1 of row i
-            const bool hasU = INTERIOR || i > 0, hasD = INTERIOR || i < H - 1;
+        if (i >= i0 && (ROWS || (i >= 0 && i < H))) {        // (uniform) level 1 of row i
+            const bool hasU = ROWS || i > 0, hasD = ROWS || i < H - 1;
             double2 in[5], o[5];
             const double2 xu = two ? cur.x[3] : cur.x[2];
             const double2 xd = hasU ? (two ? cur.x[4] : cur.x[3]) : xu;
             in[0] = cur.x[0];
             in[1] = dsel2(hasL, cur.x[1], zero2());
-            in[2] = dsel2(hasR, hasL ? cur.x[2] : cur.x[1], zero2());
-            in[3] = dsel2(hasU && colv, xu, zero2());
-            in[4] = dsel2(hasD && colv, xd, zero2());
+            in[2] = dsel2(hasR, EDGE || hasL ? cur.x[2] : cur.x[1], zero2());
+            in[3] = EDGE ? cur.x[3] : dsel2(hasU && colv, xu, zero2());
+            in[4] = EDGE ? cur.x[4] : dsel2(hasD && colv, xd, zero2());
             deep_leave_one_out(in, o);
             bad = bad || deep_undefined(o, hasL, hasR, colv && hasU, colv && hasD);
             e = deep_emit(o, hasL, hasR, cur.qR, qD[1], cur.qD);
@@ -206,20 +227,20 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
                 qL = dshift_up(qR[K - 1]);
             }
             // (an interior segment's rows are never clipped by the grid: row_lo / row_hi without the clamp)
-            if (INTERIOR ? (m >= r0 - (K - j) && m < r1 + (K - j)) : dp::row_valid_at_level(m, r0, r1, H, K, j)) {      // (uniform)
-                const bool mU = INTERIOR || m > 0, mD = INTERIOR || m < H - 1;
+            if (ROWS ? (m >= r0 - (K - j) && m < r1 + (K - j)) : dp::row_valid_at_level(m, r0, r1, H, K, j)) {      // (uniform)
+                const bool mU = ROWS || m > 0, mD = ROWS || m < H - 1;
                 double2 in[5], o[5];
                 in[0] = P[j - 1]; in[1] = pend[j].L; in[2] = pend[j].R;
                 in[3] = dsel2(mU, pend[j].U, zero2());
                 in[4] = dsel2(mD, e.up, zero2());
                 deep_leave_one_out(in, o);
-                if (dp::lane_valid_at_level(lane, INTERIOR ? 0 : c, INTERIOR ? 1 : W, j)) bad = bad || deep_undefined(o, hasL, hasR, mU, mD);
+                if (dp::lane_valid_at_level(lane, COLS ? 0 : c, COLS ? 1 : W, j)) bad = bad || deep_undefined(o, hasL, hasR, mU, mD);
                 if (j < K) f = deep_emit(o, hasL, hasR, qR[j - 1], qD[j], qD[j - 1]);
                 else if (own) {                              // level K of an owned row (row_valid_at_level at j = K: r0 <= m < r1): stored
-                    if (hasL) f2v_out[baseL + (INTERIOR ? 2 : lattice::rank_right(c - 1)) * kBlock] = factor_rule<kRuleAdditive>(o[1], qL, 1.0, 0.0);
+                    if (hasL) f2v_out[baseL + offRofL] = factor_rule<kRuleAdditive>(o[1], qL, 1.0, 0.0);
                     if (hasR) f2v_out[baseR + lattice::rank_left() * kBlock] = factor_rule<kRuleAdditive>(o[2], qR[K - 1], 1.0, 0.0);
-                    if (mU) f2v_out[base[K] + (INTERIOR ? 4 : lattice::rank_down(m - 1, c, W)) * kBlock] = factor_rule<kRuleAdditive>(o[3], qD[K], 1.0, 0.0);
-                    if (mD) f2v_out[base[K - 2] + (INTERIOR ? 3 : lattice::rank_up(c, W)) * kBlock] = factor_rule<kRuleAdditive>(o[4], qD[K - 1], 1.0, 0.0);
+                    if (mU) f2v_out[base[K] + (ROWS ? offU + kBlock : lattice::rank_down(m - 1, c, W) * kBlock)] = factor_rule<kRuleAdditive>(o[3], qD[K], 1.0, 0.0);
+                    if (mD) f2v_out[base[K - 2] + offU] = factor_rule<kRuleAdditive>(o[4], qD[K - 1], 1.0, 0.0);
                 }
             }
             // what level j - 1 produced in this iteration waits for its row's turn at level j
@@ -235,6 +256,15 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
     if (bad) *abort_word = 1u;      // (an ordinary per-lane store)
 }
 
+#ifdef CX_DEEP_STAMPS
+// lab build (CX_BUILD_DEEP_STAMPS=1 python -m cortex.jl_amd.build --force; tools/lab/deep_sweep_stamps.py): every working wave of every launch
+// leaves one record of 8 words at slot 4 blockIdx + wave, overwriting the launch before: the 100 MHz clock at entry and exit, the shader clock
+// at both, HW_ID | XCC_ID << 32, strip | segment << 32, 1 + instance (0 general, 1 interior, 2 column-edge), blockIdx.  Never defined in the
+// shipped library
+constexpr int kDeepStampWaves = 4096;
+__device__ unsigned long long cx_deep_stamps[kDeepStampWaves * 8];
+#endif
+
 // grid = packed_blocks workgroups (cx_lattice_deep.h: the packed map).  Wave w of workgroup (bc, seg) of a full workgroup column owns strip
 // 4 bc + w, rows [seg R, seg R + R); in a last column of s < 4 strips a workgroup holds floor(4 / s) consecutive segments, wave w strip
 // 4 bc + w mod s of segment seg0 + w div s, and a wave beyond them returns at once
@@ -247,9 +277,41 @@ __global__ __launch_bounds__(kBlock) void k_sweep_deep(int H, int W, int R, int 
     int strip, seg;
     if (!dp::packed_wave(s, w, W, nseg, K, &strip, &seg)) return;      // (wave-uniform)
     const int r0 = seg * R, r1 = min(r0 + R, H);
-    if (dp::strip_interior(strip, W, K) && dp::segment_interior(r0, r1, H, K)) deep_wave<K, true>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
-    else deep_wave<K, false>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
+#ifdef CX_DEEP_STAMPS
+    const unsigned long long st_wall = wall_clock64(), st_clk = __builtin_amdgcn_s_memtime();
+#endif
+    int cls = dp::wave_class(strip, r0, r1, H, W, K);                  // (wave-uniform)
+#if defined(CX_DEEP_STAMPS) && CX_DEEP_STAMPS == 2                     // (lab: the stamps of the dispatch before the column-edge instance)
+    if (cls == dp::kWaveColumnEdge) cls = dp::kWaveGeneral;
+#endif
+    if (cls == dp::kWaveInterior) deep_wave<K, true, true>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
+    else if (cls == dp::kWaveColumnEdge) deep_wave<K, true, false>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
+    else deep_wave<K, false, false>(strip, r0, r1, H, W, slice_off, q, f2v_in, f2v_out, abort_word);
+#ifdef CX_DEEP_STAMPS
+    const unsigned long long en_clk = __builtin_amdgcn_s_memtime(), en_wall = wall_clock64();
+    const unsigned hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));       // HW_REG_HW_ID, all bits
+    const unsigned xcc = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));      // HW_REG_XCC_ID, bits 0 .. 3
+    const int slot = (int)blockIdx.x * 4 + w;
+    if ((threadIdx.x & 63) == 0 && slot < kDeepStampWaves) {           // (ordinary vector stores of one lane)
+        unsigned long long *rec = cx_deep_stamps + (size_t)slot * 8;
+        rec[0] = st_wall; rec[1] = en_wall; rec[2] = st_clk; rec[3] = en_clk;
+        rec[4] = (unsigned long long)hw | (unsigned long long)xcc << 32;
+        rec[5] = (unsigned long long)(unsigned)strip | (unsigned long long)(unsigned)seg << 32;
+        rec[6] = 1ull + (unsigned long long)cls; rec[7] = blockIdx.x;
+    }
+#endif
 }
+
+#ifdef CX_DEEP_STAMPS
+// the records of the last launch, then cleared (a wave without work leaves zeros); returns the number of records copied
+extern "C" __attribute__((visibility("default"))) int32_t cx_lab_deep_stamps(unsigned long long *out, int32_t max_waves) {
+    const int n = max_waves < kDeepStampWaves ? max_waves : kDeepStampWaves;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out, HIP_SYMBOL(cx_deep_stamps), (size_t)n * 64) != hipSuccess) return -1;
+    static unsigned long long zeros[kDeepStampWaves * 8];
+    if (hipMemcpyToSymbol(HIP_SYMBOL(cx_deep_stamps), zeros, sizeof zeros) != hipSuccess) return -1;
+    return n;
+}
+#endif
 
 template <int K>
 static int64_t deep_capacity(const cx_handle *h) {
