@@ -19,23 +19,20 @@
 //                 an observed row is its datum and zeros.  Statuses as there: UNDEFINED when a stored message into i (kept or not)
 //                 or a summed β holds NaN, otherwise IMPROPER when nothing is kept, a pivot below u is not positive and finite, or a
 //                 pivot is at or below kFlat times the same diagonal entry of the sum of ALL stored messages into i
-//   k_cmm_part    256 row statuses -> one ev::Part; ev::final_sum adds the parts in index order: no atomics
+//   the row statuses are folded 256 to one ev::Part (cx_mfma_reader.h); ev::final_sum adds the parts in index order: no atomics
 #include <algorithm>
 #include <climits>
 
-#include "cx_evidence_core.h"
 #include "cx_evidence_mfma_core.h"
-#include "cx_pairs_mfma.h"
+#include "cx_mfma_reader.h"
 
 namespace cx {
 namespace cmm {
 
 using namespace w64;
-using evm::factor_solve;
+using evm::add_records, evm::any_nan_record, evm::factor_solve, evm::flat_pivot, evm::pad_identity, evm::park_z, evm::solve_identity_cols, evm::store_symmetric;
 
-constexpr int kTB = 256;                              // rows per block of k_cmm_part
-constexpr int64_t kRowBufBytes = (int64_t)32 << 20;   // the device row buffer: the payload goes to the host a chunk at a time
-constexpr int kFinite = 0, kUndefined = 1, kImproper = 2;
+constexpr int kFinite = mfr::kRowOk, kUndefined = mfr::kRowUndefined, kImproper = mfr::kRowImproper;
 constexpr int32_t kNone = -1;                         // a source: e >= 0 the stored message of slot e, e <= -2 the β of T entry -2 - e
 constexpr int32_t kNever = INT_MAX;                   // a T entry that no datum reaches
 
@@ -119,8 +116,7 @@ void k_cmm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
     __shared__ double ZS[KD];
     if ((int)blockIdx.x >= n) return;
     const int w = row0 + (int)blockIdx.x;
-    const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, mo = g * KD + c, rr = c >> 2;
-    const bool diag_lane = g == (c & 3);      // entry [i][i] of a diagonal tile sits in lane (g, c) = (i & 3, i), register i >> 2
+    const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, mo = g * KD + c;
     const int32_t *t = rec + 8 * (int64_t)w;
     const int observed = t[0], yslot = t[1], k_off = t[2], k_n = t[3], a_off = t[4], a_n = t[5];
     double *o = out + (int64_t)blockIdx.x * (u + u * u);
@@ -165,29 +161,10 @@ void k_cmm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
     for (int i = 0; i < NU; i++) M[i] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int j = 0; j < NT; j++) wcv[j] = 0.0;
-    for (int s = 0; s < k_n; s++) {
-        const gcdp p = (gcdp)record_of(srcs[k_off + s], f2v, beta, zero, KM);
-#pragma unroll
-        for (int a = 0; a < NT; a++)
-#pragma unroll
-            for (int b = a; b < NT; b++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) M[utn<NT>(a, b)][r] += p[KD + mo + tile_const_n<NT>(a, b, r)];
-#pragma unroll
-        for (int j = 0; j < NT; j++) wcv[j] += p[16 * j + c];
-    }
+    add_records<NT>(M, wcv, k_n, [&](int s) { return record_of(srcs[k_off + s], f2v, beta, zero, KM); }, mo, c);
     bool undef = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
-#pragma unroll
-    for (int j = 0; j < NT; j++) {
-        // the identity on the padding diagonal of an embedded dim: a sum of messages may be zero there
-        const bool pad = diag_lane && 16 * j + c >= u;
-#pragma unroll
-        for (int r = 0; r < 4; r++) M[utn<NT>(j, j)][r] += (pad && r == rr) ? 1.0 : 0.0;
-    }
-    for (int s = 0; s < a_n; s++) {
-        const double *p = f2v + (int64_t)srcs[a_off + s] * KM;
-        undef = undef || __builtin_isnan(p[0]) || __builtin_isnan(p[KD]);
-    }
+    pad_identity<NT>(M, g, c, u);
+    undef = any_nan_record<NT>(undef, f2v, srcs + a_off, a_n);
     if (undef) { unscored(kUndefined); return; }
     if (k_n == 0) { unscored(kImproper); return; }      // nothing is kept: flat by structure
 
@@ -195,39 +172,12 @@ void k_cmm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
     double zrv[NT][4], ld, q;
     bool pd;
     factor_solve<NT>(M, wcv, zrv, S, Vs, g, c, u, ld, q, pd);
-    bool flat = false;
-#pragma unroll
-    for (int k = 0; k < NT; k++) {
-        double ref = 0.0;      // the diagonal of the sum of ALL stored messages into the variable, lane c entry 16 k + c
-        for (int s = 0; s < a_n; s++) ref += f2v[(int64_t)srcs[a_off + s] * KM + KD + (16 * k + c) * (KD + 1)];
-        const double v = Vs[k][c * kLdT + c], piv = 1.0 / (v * v);      // V_kk = 1 / U_kk
-        flat = flat || (16 * k + c < u && !(piv > k_flat * fmax(ref, 0.0)));
-    }
-    if (!pd || __ballot(flat) != 0) { unscored(kImproper); return; }
-#pragma unroll
-    for (int j = 0; j < NT; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) ZS[16 * j + g + 4 * r] = zrv[j][r];      // (the 16 lanes of a group write one value to one place)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (!pd || __ballot(flat_pivot<NT>(Vs, f2v, srcs + a_off, a_n, c, u, k_flat)) != 0) { unscored(kImproper); return; }
+    park_z<NT>(ZS, zrv, g);
 
-    // ---- Z = U^-T: block column b of the identity through the forward substitution; Z is lower block triangular, tiles (j, b), j >= b ----
+    // ---- Z = U^-T: the identity through the forward substitution; Z is lower block triangular, tiles (j, b), j >= b ------------------------
     d4 Y[NT][NT];
-#pragma unroll
-    for (int b = 0; b < NT; b++) {
-#pragma unroll
-        for (int j = b; j < NT; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) Y[j][b][r] = (j == b && g + 4 * r == c) ? 1.0 : 0.0;
-#pragma unroll
-        for (int j = b; j < NT; j++) {
-            d4 Vj;
-#pragma unroll
-            for (int r = 0; r < 4; r++) Vj[r] = Vs[j][(g + 4 * r) * kLdT + c];
-            Y[j][b] = tts(Vj, Y[j][b], d4{0.0, 0.0, 0.0, 0.0});
-#pragma unroll
-            for (int jj = j + 1; jj < NT; jj++) Y[jj][b] = tts(neg(M[utn<NT>(j, jj)]), Y[j][b], Y[jj][b]);
-        }
-    }
+    solve_identity_cols<NT>(Y, M, Vs, g, c);
     // ---- cov = Z'Z, mean = Z'z: the upper tiles as they are, the lower ones turned through LDS, a diagonal tile the mean of its two
     //      triangles, so that the covariance is symmetric to the last bit ---------------------------------------------------------------
 #pragma unroll
@@ -236,52 +186,31 @@ void k_cmm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
         for (int b = a; b < NT; b++) {
             d4 D = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int j = b; j < NT; j++) D = tts(Y[j][a], Y[j][b], D);
-            if (b > a) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) put_s(a, b, r, D[r]);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the previous tile's reads have returned
-#pragma unroll
-            for (int r = 0; r < 4; r++) S[(g + 4 * r) * kLdT + c] = D[r];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const double tr = S[c * kLdT + g + 4 * r];
-                put_s(b, a, r, b > a ? tr : 0.5 * (D[r] + tr));
-            }
+            for (int j = b; j < NT; j++) D = tts(Y[a][j], Y[b][j], D);      // (Z'Z over the block triangle: its own loop, not gram_pass)
+            store_symmetric(D, a, b, S, put_s, g, c);
         }
         double p = 0.0;
 #pragma unroll
         for (int j = a; j < NT; j++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) p += Y[j][a][r] * ZS[16 * j + g + 4 * r];
+            for (int r = 0; r < 4; r++) p += Y[a][j][r] * ZS[16 * j + g + 4 * r];
         put_m(a, sum_groups(p));
     }
     if (lane == 0) rflag[w] = (uint8_t)kFinite;
-}
-
-// 256 rows -> one ev::Part (fixed-order tree); ev::final_sum adds the parts in index order
-__global__ __launch_bounds__(kTB) void k_cmm_part(int n, const uint8_t *__restrict__ rflag, ev::Part *__restrict__ part) {
-    const int i = blockIdx.x * kTB + threadIdx.x;
-    const int f = i < n ? (int)rflag[i] : -1;
-    ev::block_part<kTB>(0.0, 0.0, f == kFinite, f == kUndefined, f == kImproper, 0u, part);
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
 // The rows follow the mode, whether there is a lag, the caller's ids, the graph and WHICH variables are observed (vinfo_epoch:
 // cx_derived.h); the T entries the graph and the observed flags.  Rule tables, messages and data are read by every call
 struct Plan {
-    bool valid = false, explicit_ids = false, lagged = false;
-    int32_t mode = 0;
-    std::vector<int64_t> ids;
+    mfr::RequestKey key;      // tag: 2 mode + (a lag or none)
     uint64_t vinfo_epoch = 0;
-    int64_t n_rows = 0, nb = 0, n_t = 0, n_pre = 0;
+    int64_t n_rows = 0, n_t = 0, n_pre = 0;
     DevBuf<int32_t> d_rec, d_srcs, d_trec, d_prec, d_psrcs;
-    DevBuf<double> d_beta[2], d_pre, d_rows, d_out;
+    DevBuf<double> d_beta[2], d_pre, d_rows;
     DevBuf<uint8_t> d_rflag;
     DevBuf<ev::Part> d_part;
-    std::vector<double> h_out;
+    mfr::Totals totals;
 };
 
 // the variable indices of the rows: the caller's, in the caller's order, or every variable in ascending id
@@ -300,12 +229,11 @@ static int32_t list_rows(cx_handle *h, const std::string &who, int64_t n, const 
     return CX_OK;
 }
 
-static int32_t build_plan(cx_handle *h, const prm::Pairs &P, Plan &L, int32_t mode, bool lagged, const std::vector<int32_t> &var, const std::string &who) {
+static int32_t build_plan(cx_handle *h, const mfr::Pairs &P, Plan &L, int32_t mode, bool lagged, const std::vector<int32_t> &var, const std::string &who) {
     using namespace cxh;
     constexpr uint8_t kU = 0, kO = 1, kT = 2;
     const int64_t n = (int64_t)var.size(), km = (int64_t)h->cfg.dim * (h->cfg.dim + 1);
     auto obs = [&](int32_t v) { return (h->vinfo[(size_t)v] & kClamped) != 0; };
-    L.valid = false;
     // the class of every slot into a non-observed variable; the T entries in the order of the variable they gather from (the OUT end)
     std::vector<uint8_t> cls((size_t)std::max<int64_t>(h->nslots, 1), kU);
     struct Entry { int32_t si, so, vo, vi; };
@@ -380,14 +308,12 @@ static int32_t build_plan(cx_handle *h, const prm::Pairs &P, Plan &L, int32_t mo
             else if (c == kT && lagged) srcs.push_back(-2 - tidx[(size_t)s]);
         }
         r[3] = (int32_t)srcs.size() - r[2];
-        r[4] = (int32_t)srcs.size();
-        for (int32_t e = h->var_off[x]; e < h->var_off[x + 1]; e++) srcs.push_back(slot_of_edge(h, e));
-        r[5] = (int32_t)srcs.size() - r[4];
+        const mfr::Run all = mfr::other_slots(h, x, -1, srcs);
+        r[4] = all.off; r[5] = all.n;
         CX_REQUIRE(h, (int64_t)srcs.size() < (int64_t)0x7fffff00, CX_ERR_UNSUPPORTED, who + ": more than 2^31 inputs");
     }
     CX_REQUIRE(h, n < (int64_t)0x7fffff00, CX_ERR_UNSUPPORTED, who + ": more than 2^31 rows");
     L.n_rows = n;
-    L.nb = (n + kTB - 1) / kTB;
     L.n_t = nt;
     L.n_pre = (int64_t)prec.size() / 2;
     if (srcs.empty()) srcs.push_back(0);      // (never read: no row names a source)
@@ -399,9 +325,7 @@ static int32_t build_plan(cx_handle *h, const prm::Pairs &P, Plan &L, int32_t mo
     if ((rc = dev_upload(h, &L.d_psrcs, psrcs)) != CX_OK) return rc;
     if ((rc = L.d_pre.ensure(h, L.n_pre * km)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &L.d_rflag, std::max<int64_t>(n, 1))) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &L.d_part, std::max<int64_t>(L.nb, 1))) != CX_OK) return rc;
-    if (!L.d_out && (rc = dev_alloc(h, &L.d_out, 1 + ev::kNCnt)) != CX_OK) return rc;
-    L.h_out.assign(1 + ev::kNCnt, 0.0);
+    if ((rc = dev_alloc(h, &L.d_part, std::max<int64_t>((n + mfr::kTB - 1) / mfr::kTB, 1))) != CX_OK) return rc;
     CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
     return CX_OK;
 }
@@ -413,16 +337,14 @@ static const double *launch_back(cx_handle *h, Plan &L, int32_t lag) {
     const double *f2v = h->d_mv_f2v, *zero = h->d_zero_msg;
     for (int32_t s = 1; s <= lag; s++) {
         double *next = L.d_beta[(s - 1) & 1];
-#define CX_P(N) hipLaunchKernelGGL((k_cmm_presum<N>), dim3((unsigned)L.n_pre), dim3(64), 0, h->stream, (int)L.n_pre, L.d_prec, L.d_psrcs, f2v, beta, zero, L.d_pre)
-#define CX_B(N, W)                                                                                                                                  \
-    hipLaunchKernelGGL((k_cmm_back<N, W>), dim3((unsigned)L.n_t), dim3(64), 0, h->stream, (int)L.n_t, (int)s, L.d_trec, h->d_ptab, h->d_ptab_bt, zero, \
-                       f2v, L.d_pre, beta, next)
-        // waves per SIMD: k_rule64w's, whose body this is (the register counts)
-        if (h->cfg.dim == 16) { if (L.n_pre) CX_P(1); CX_B(1, 4); }
-        else if (h->cfg.dim == 32) { if (L.n_pre) CX_P(2); CX_B(2, 4); }
-        else { if (L.n_pre) CX_P(4); CX_B(4, 2); }
-#undef CX_P
-#undef CX_B
+        mfr::for_tiles(h->cfg.dim, [&](auto tiles) {
+            // waves per SIMD: k_rule64w's, whose body this is (the register counts)
+            constexpr int NT = decltype(tiles)::value, W = NT == 4 ? 2 : 4;
+            if (L.n_pre)
+                hipLaunchKernelGGL((k_cmm_presum<NT>), dim3((unsigned)L.n_pre), dim3(64), 0, h->stream, (int)L.n_pre, L.d_prec, L.d_psrcs, f2v, beta, zero, L.d_pre);
+            hipLaunchKernelGGL((k_cmm_back<NT, W>), dim3((unsigned)L.n_t), dim3(64), 0, h->stream, (int)L.n_t, (int)s, L.d_trec, h->d_ptab, h->d_ptab_bt, zero,
+                               f2v, L.d_pre, beta, next);
+        });
         beta = next;
     }
     return beta;
@@ -431,17 +353,14 @@ static const double *launch_back(cx_handle *h, Plan &L, int32_t lag) {
 // rows [row0, row0 + n) into d_rows
 static void launch_rows(cx_handle *h, Plan &L, int64_t row0, int64_t n, const double *beta, double *d_rows) {
     if (!n) return;
-    const int u = h->user_dim ? h->user_dim : h->cfg.dim;
-    // a message that carries no information arrives as the rounding of u-term sums (the measured remainders)
-    const double k_flat = 64.0 * u * 2.220446049250313e-16;
-#define CX_R(N, W)                                                                                                                                  \
-    hipLaunchKernelGGL((k_cmm_rows<N, W>), dim3((unsigned)n), dim3(64), 0, h->stream, (int)row0, (int)n, L.d_rec, L.d_srcs, h->d_mv_f2v, h->d_mv_v2f, \
-                       beta, h->d_zero_msg, u, k_flat, L.d_rflag, d_rows)
-    // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch
-    if (h->cfg.dim == 16) CX_R(1, 4);
-    else if (h->cfg.dim == 32) CX_R(2, 3);
-    else CX_R(4, 2);
-#undef CX_R
+    const int u = mfr::user_dim(h);
+    const double k_flat = mfr::flat_pivot_factor(h);
+    mfr::for_tiles(h->cfg.dim, [&](auto nt) {
+        // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch
+        constexpr int NT = decltype(nt)::value, W = NT == 1 ? 4 : NT == 2 ? 3 : 2;
+        hipLaunchKernelGGL((k_cmm_rows<NT, W>), dim3((unsigned)n), dim3(64), 0, h->stream, (int)row0, (int)n, L.d_rec, L.d_srcs, h->d_mv_f2v, h->d_mv_v2f,
+                           beta, h->d_zero_msg, u, k_flat, L.d_rflag, d_rows);
+    });
 }
 
 }  // namespace cmm
@@ -455,6 +374,7 @@ using namespace cxh;
 extern "C" int32_t cx_causal_marginals_mfma(cx_handle *h, int32_t mode, int32_t lag, int64_t n, const int64_t *variable_ids, double *out, int64_t *counts4) {
     try {
         namespace cmm = cx::cmm;
+        namespace mfr = cx::mfr;
         const std::string who = "cx_causal_marginals_mfma";
         int32_t rc;
         const char *bad = !out || !counts4 ? "null argument"
@@ -462,58 +382,39 @@ extern "C" int32_t cx_causal_marginals_mfma(cx_handle *h, int32_t mode, int32_t 
                           : lag < 0 ? "negative lag"
                           : lag > 0 && mode == CX_CAUSAL_PREDICTED ? "a lag goes with CX_CAUSAL_FILTERED"
                           : variable_ids && n < 0 ? "negative count" : nullptr;
-        if ((rc = cx::prm::prepare(h, who, bad, "cx_causal_marginals", "marginals of this kind")) != CX_OK) return rc;
+        if ((rc = mfr::prepare(h, who, bad, {"cx_causal_marginals", "the variational and Beta-Bernoulli families have no Gaussian marginals of this kind", "rows"})) != CX_OK)
+            return rc;
         if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
         if (!h->causal_mfma) h->causal_mfma.reset(new cmm::Plan());
         cmm::Plan &L = *h->causal_mfma;
         // other variables are observed: the lists are built again, the β and row buffers stay (a user who clamps a state between two
         // calls does not pay for gigabytes freed and allocated anew)
-        if (L.vinfo_epoch != h->vinfo_epoch) L.valid = false;
-        const bool same = L.valid && L.mode == mode && L.lagged == (lag > 0) && L.explicit_ids == (variable_ids != nullptr) &&
-                          (!variable_ids || ((int64_t)L.ids.size() == n && std::equal(variable_ids, variable_ids + n, L.ids.begin())));
-        if (!same) {
-            L.valid = false;
-            cx::prm::Pairs P;
+        if (L.vinfo_epoch != h->vinfo_epoch) L.key.valid = false;
+        const int64_t tag = 2 * (int64_t)mode + (lag > 0);
+        if (!L.key.matches(tag, n, variable_ids)) {
+            L.key.valid = false;
+            mfr::Pairs P;
             // (a guard: cx_graph_create lets nothing but two-variable CX_FACTOR_GAUSS_LINEAR factors and opaque ones into a handle of
             // these dims, so no graph built through the API reaches this refusal)
-            if ((rc = cx::prm::checked_pairs(h, who, P)) != CX_OK) return rc;
+            if ((rc = mfr::checked_pairs(h, who, P)) != CX_OK) return rc;
             std::vector<int32_t> var;
             if ((rc = cmm::list_rows(h, who, n, variable_ids, var)) != CX_OK) return rc;
             if ((rc = cmm::build_plan(h, P, L, mode, lag > 0, var, who)) != CX_OK) return rc;
-            L.mode = mode;
-            L.lagged = lag > 0;
-            L.explicit_ids = variable_ids != nullptr;
-            L.ids.assign(variable_ids, variable_ids ? variable_ids + n : variable_ids);
+            L.key.remember(tag, n, variable_ids);
             L.vinfo_epoch = h->vinfo_epoch;
-            L.valid = true;
         }
-        const int u = h->user_dim ? h->user_dim : h->cfg.dim;
-        const int64_t no = (int64_t)u + (int64_t)u * u, nr = L.n_rows, km = (int64_t)h->cfg.dim * (h->cfg.dim + 1);
+        const int u = mfr::user_dim(h);
+        const int64_t km = (int64_t)h->cfg.dim * (h->cfg.dim + 1);
         // β: allocated by the first call with a lag, one buffer for lag 1 and two beyond
         if (lag > 0 && L.n_t)
             for (int k = 0; k < std::min<int32_t>(lag, 2); k++) if ((rc = L.d_beta[k].ensure(h, L.n_t * km)) != CX_OK) return rc;
         const double *beta = cmm::launch_back(h, L, lag);
         CX_HIP(h, hipGetLastError());
-        if (nr) {
-            // the payload a chunk at a time through a bounded device buffer; the status array covers every row
-            const int64_t chunk = std::min<int64_t>(nr, std::max<int64_t>(1, cmm::kRowBufBytes / (no * 8)));
-            if ((rc = L.d_rows.ensure(h, chunk * no)) != CX_OK) return rc;
-            for (int64_t r0 = 0; r0 < nr; r0 += chunk) {
-                const int64_t m = std::min(chunk, nr - r0);
-                cmm::launch_rows(h, L, r0, m, beta, L.d_rows.get());
-                CX_HIP(h, hipGetLastError());
-                CX_HIP(h, hipMemcpyAsync(out + r0 * no, L.d_rows, (size_t)(m * no) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            }
-            hipLaunchKernelGGL(cmm::k_cmm_part, dim3((unsigned)L.nb), dim3(cmm::kTB), 0, h->stream, (int)nr, L.d_rflag, L.d_part);
-        }
-        cx::ev::final_sum(h, nr ? L.nb : 0, L.d_part, L.d_out);
-        CX_HIP(h, hipGetLastError());
-        CX_HIP(h, hipMemcpyAsync(L.h_out.data(), L.d_out, (1 + cx::ev::kNCnt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        CX_HIP(h, hipStreamSynchronize(h->stream));
-        uint64_t cnt[cx::ev::kNCnt];
-        std::memcpy(cnt, L.h_out.data() + 1, sizeof(cnt));
-        counts4[0] = nr;
-        for (int k = 1; k < 4; k++) counts4[k] = (int64_t)cnt[k - 1];
-        return CX_OK;
+        // the payload a chunk at a time through a bounded device buffer; the status array covers every row
+        if ((rc = mfr::stream_rows(h, L.n_rows, (int64_t)u + (int64_t)u * u, L.d_rows, out,
+                                   [&](int64_t r0, int64_t m, double *d) { cmm::launch_rows(h, L, r0, m, beta, d); })) != CX_OK)
+            return rc;
+        double none;
+        return L.totals.read_rows(h, L.n_rows, nullptr, L.d_rflag, L.d_part, counts4, &none);
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_causal_marginals_mfma: host allocation failed"); }
 }

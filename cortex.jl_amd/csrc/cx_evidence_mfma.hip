@@ -30,8 +30,8 @@
 // (k_ev_final, cx_evidence.hip) adds the parts in index order: no atomics, two calls on one state are bit-identical.
 // cx_log_evidence and cx_log_evidence_components keep refusing these dims (their tests pin that); routing them here is a later,
 // separate decision.
-#include "cx_evidence_core.h"
 #include "cx_evidence_mfma_core.h"
+#include "cx_mfma_reader.h"
 
 namespace cx {
 namespace evm {
@@ -94,86 +94,33 @@ void k_evm_terms(int nterm, const int32_t *__restrict__ rec, const int32_t *__re
         double wcv[NT];
 #pragma unroll
         for (int j = 0; j < NT; j++) wcv[j] = 0.0;
-#pragma unroll
-        for (int a = 0; a < NT; a++)
-#pragma unroll
-            for (int b = a; b < NT; b++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) M[utn<NT>(a, b)][r] = ((gcdp)tab)[mo + tile_const_n<NT>(a, b, r)];
+        load_upper<NT>(M, [&](int k) { return ((gcdp)tab)[mo + k]; });
         add_sources<NT>(M, wcv, f2v, srcs + a_off, a_n, mo, c);
         undef_a = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
         double ld1, q1;
         factor_solve<NT>(M, wcv, zrv, S, Vs, g, c, u, ld1, q1, pd_a);
         cst = -0.5 * ldq[tab_i >> 1] + 0.5 * q1 - 0.5 * ld1 + 2.0 * hl2pi;
-        // z waits in LDS between its solve and its use (η' = Yt' z), not in 8 NT registers across the matrix solve (rule64_body: Z_IN_LDS)
         __shared__ double ZS[KD];
-#pragma unroll
-        for (int j = 0; j < NT; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) ZS[16 * j + g + 4 * r] = zrv[j][r];      // (the 16 lanes of a group write one value to one place)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // Yt = U^-T B', one block column at a time
+        park_z<NT>(ZS, zrv, g);
+        // Yt = U^-T B', then Λ' = C - Yt'Yt (upper tiles), η' = Yt' z
         d4 Y[NT][NT];
-#pragma unroll
-        for (int b = 0; b < NT; b++) {
-            asm volatile("" ::: "memory");      // (one block column of B' in flight at a time)
-#pragma unroll
-            for (int j = 0; j < NT; j++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) Y[j][b][r] = ((gcdp)bt)[mo + tile_const_n<NT>(j, b, r)];
-#pragma unroll
-            for (int j = 0; j < NT; j++) {
-                d4 Vj;
-#pragma unroll
-                for (int r = 0; r < 4; r++) Vj[r] = Vs[j][(g + 4 * r) * kLdT + c];
-                Y[j][b] = tts(Vj, Y[j][b], d4{0.0, 0.0, 0.0, 0.0});
-#pragma unroll
-                for (int jj = j + 1; jj < NT; jj++) Y[jj][b] = tts(neg(M[utn<NT>(j, jj)]), Y[j][b], Y[jj][b]);
-            }
-        }
-        // Λ' = C - Yt'Yt (upper tiles), η' = Yt' z
-#pragma unroll
-        for (int a = 0; a < NT; a++) {
-#pragma unroll
-            for (int b = a; b < NT; b++) {
-                asm volatile("" ::: "memory");      // (one tile of C in flight at a time: hoisted together they cost 80 registers at NT = 4)
-                d4 G = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int j = 0; j < NT; j++) G = tts(Y[j][a], Y[j][b], G);
-#pragma unroll
-                for (int r = 0; r < 4; r++) Sm[utn<NT>(a, b)][r] = ((gcdp)tab)[2 * KD * KD + mo + tile_const_n<NT>(a, b, r)] - G[r];
-            }
-            double p = 0.0;
-#pragma unroll
-            for (int j = 0; j < NT; j++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) p += Y[j][a][r] * ZS[16 * j + g + 4 * r];
-            hcv[a] = sum_groups(p);
-        }
+        solve_block_cols<NT, false>(Y, M, Vs, [&](int k) { return ((gcdp)bt)[mo + k]; }, g, c);
+        gram_pass<NT, -1>(Sm, Y, ZS, [&](int k) { return ((gcdp)tab)[2 * KD * KD + mo + k]; }, [&](int a, double v) { hcv[a] = v; }, g);
     } else if (kind == kFacObs) {      // (kVar, kOpaque: S and h start at zero)
         double yrv[NT][4], ycv[NT], py[NT];
         load_y<NT>(v2f + (int64_t)y0 * KM, yrv, ycv, g, c);
         xty<NT>(tab, yrv, py, mo);                       // P y
         xty<NT>(bt, yrv, hcv, mo);                       // B y
         cst = -0.5 * ldq[tab_i >> 1] - 0.5 * dot_cv<NT>(ycv, py, g, c, u) + hl2pi;
-#pragma unroll
-        for (int a = 0; a < NT; a++)
-#pragma unroll
-            for (int b = a; b < NT; b++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) Sm[utn<NT>(a, b)][r] = ((gcdp)tab)[2 * KD * KD + mo + tile_const_n<NT>(a, b, r)];
+        load_upper<NT>(Sm, [&](int k) { return ((gcdp)tab)[2 * KD * KD + mo + k]; });
     }
     add_sources<NT>(Sm, hcv, f2v, srcs + b_off, b_n, mo, c);
     // Undefined: an INPUT is NaN (whole messages are NaN together; a NaN datum reaches hcv and cst).  A first factorisation that is not
     // positive definite also leaves NaN in Λ', η' and cst: that term is "not positive definite", so with two free ends the inputs of the
     // second stage are looked at themselves (Λ[0][0] and η[0] of every source record), not through Sm
     bool undef = undef_a;
-    if (kind == kFacFree) {
-        for (int s = 0; s < b_n; s++) {
-            const double *p = f2v + (int64_t)srcs[b_off + s] * KM;
-            undef = undef || __builtin_isnan(p[0]) || __builtin_isnan(p[KD]);
-        }
-    } else undef = __builtin_isnan(bcast(Sm[0][0], 0)) || __builtin_isnan(bcast(hcv[0], 0)) || __builtin_isnan(cst);
+    if (kind == kFacFree) undef = any_nan_record<NT>(undef, f2v, srcs + b_off, b_n);
+    else undef = __builtin_isnan(bcast(Sm[0][0], 0)) || __builtin_isnan(bcast(hcv[0], 0)) || __builtin_isnan(cst);
     double ld, q;
     bool pd;
     factor_solve<NT>(Sm, hcv, zrv, S, Vs, g, c, u, ld, q, pd);
@@ -206,71 +153,53 @@ __global__ __launch_bounds__(kTB) void k_evm_part(int nterm, const double *__res
 // (param_epoch); messages and data are read by every call
 struct Cache {
     bool built = false;
-    uint64_t vinfo_epoch = 0, param_epoch = ~0ull;
+    uint64_t vinfo_epoch = 0;
     int64_t n_term = 0, n_fac = 0, nb = 0, unsupported_fac = -1;
     DevBuf<int32_t> d_rec, d_srcs;
-    DevBuf<double> d_ldq, d_tval, d_out;
+    mfr::ParamTable ldq;
+    DevBuf<double> d_tval;
     DevBuf<uint8_t> d_tflag;
     DevBuf<ev::Part> d_part;
-    std::vector<double> h_out;
+    mfr::Totals totals;
 };
 
 static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
     using namespace cxh;
-    const int64_t nv = h->nv, ne = h->ne, nf = h->nf;
-    std::vector<int32_t> efac((size_t)ne), fe1((size_t)nf, -1), fe2((size_t)nf, -1), nfe((size_t)nf, 0);
-    for (int64_t e = 0; e < ne; e++) {
-        const int64_t f = find_factor(h, h->edge_fac_id[e]);
-        efac[e] = (int32_t)f;
-        if (fe1[f] < 0) fe1[f] = (int32_t)e; else if (fe2[f] < 0) fe2[f] = (int32_t)e;
-        nfe[f]++;
-    }
+    using mfr::Run;
+    mfr::Pairs P;
+    mfr::pairs_of(h, P);
     // the terms in the order made, and the variable each is filed under: the list is sorted by it (stable), so that a variable's term,
     // the terms of its factors and those of its neighbours — which read the same message records — are next to each other
     std::vector<int32_t> made, key, srcs;
-    auto term = [&](int32_t file_under, int kind, int tab, int ao, int an, int bo, int bn, int y0, int y1) {
-        const int32_t r[8] = {kind, tab, ao, an, bo, bn, y0, y1};
+    auto term = [&](int32_t file_under, int kind, int tab, Run a, Run b, int y0, int y1) {
+        const int32_t r[8] = {kind, tab, a.off, a.n, b.off, b.n, y0, y1};
         made.insert(made.end(), r, r + 8);
         key.push_back(file_under);
     };
-    // the slots of variable v but `skip`, in ascending neighbour order (k_v2f64's): (offset, count) in srcs
-    auto others = [&](int32_t v, int32_t skip, int &off, int &n) {
-        off = (int)srcs.size();
-        for (int32_t e = h->var_off[v]; e < h->var_off[v + 1]; e++) {
-            const int32_t s = slot_of_edge(h, e);
-            if (s != skip) srcs.push_back(s);
-        }
-        n = (int)srcs.size() - off;
-    };
-    C.unsupported_fac = -1;
-    for (int64_t v = 0; v < nv; v++) {
+    C.unsupported_fac = P.unsupported_fac;
+    for (int64_t v = 0; v < h->nv; v++) {
         if (h->vinfo[v] & (kClamped | kGhost)) continue;
         int di = 0;
         for (int32_t e = h->var_off[v]; e < h->var_off[v + 1]; e++) {
-            if (h->fac_kind[efac[e]] != CX_FACTOR_OPAQUE) { di++; continue; }
-            const int off = (int)srcs.size();
+            if (h->fac_kind[P.efac[e]] != CX_FACTOR_OPAQUE) { di++; continue; }
             srcs.push_back(slot_of_edge(h, e));
-            term((int32_t)v, kOpaque, -1, 0, 0, off, 1, 0, 0);
+            term((int32_t)v, kOpaque, -1, {}, {(int32_t)srcs.size() - 1, 1}, 0, 0);
         }
         if (di == 1) continue;
-        int off, n;
-        others((int32_t)v, -1, off, n);
-        term((int32_t)v, kVar, -1, 0, 0, off, n, di, 0);
+        term((int32_t)v, kVar, -1, {}, mfr::other_slots(h, (int32_t)v, -1, srcs), di, 0);
     }
     C.n_fac = 0;
-    for (int64_t f = 0; f < nf; f++) {
-        if (h->fac_kind[f] == CX_FACTOR_OPAQUE) continue;
-        if (h->fac_kind[f] != CX_FACTOR_GAUSS_LINEAR || nfe[f] != 2) { if (C.unsupported_fac < 0) C.unsupported_fac = h->fac_ids[f]; continue; }
-        const int32_t s1 = slot_of_edge(h, fe1[f]), s2 = slot_of_edge(h, fe2[f]);
-        int32_t so = s1, si = s2, vo = h->edge_var[fe1[f]], vi = h->edge_var[fe2[f]];
-        if ((h->spdir[s1] & 1) == 0) { std::swap(so, si); std::swap(vo, vi); }      // spdir[in slot] = 2 set (the message it sends goes forward)
-        const int set = h->spdir[si] >> 1;
+    for (int64_t f = 0; f < h->nf; f++) {
+        if (P.so[f] < 0) continue;
+        const int32_t so = P.so[f], si = P.si[f], vo = P.vo[f], vi = P.vi[f], set = P.set[f];
         const bool oo = (h->vinfo[vo] & kClamped) != 0, oi = (h->vinfo[vi] & kClamped) != 0;
-        int ao = 0, an = 0, bo = 0, bn = 0;
-        if (oo && oi) term(std::min(vo, vi), kFacBoth, 2 * set + 1, 0, 0, 0, 0, so, si);
-        else if (oo) { others(vi, si, bo, bn); term(vi, kFacObs, 2 * set + 1, 0, 0, bo, bn, so, 0); }      // towards IN
-        else if (oi) { others(vo, so, bo, bn); term(vo, kFacObs, 2 * set, 0, 0, bo, bn, si, 0); }          // towards OUT
-        else { others(vo, so, ao, an); others(vi, si, bo, bn); term(std::min(vo, vi), kFacFree, 2 * set + 1, ao, an, bo, bn, 0, 0); }
+        if (oo && oi) term(std::min(vo, vi), kFacBoth, 2 * set + 1, {}, {}, so, si);
+        else if (oo) term(vi, kFacObs, 2 * set + 1, {}, mfr::other_slots(h, vi, si, srcs), so, 0);      // towards IN
+        else if (oi) term(vo, kFacObs, 2 * set, {}, mfr::other_slots(h, vo, so, srcs), si, 0);          // towards OUT
+        else {
+            const Run a = mfr::other_slots(h, vo, so, srcs);
+            term(std::min(vo, vi), kFacFree, 2 * set + 1, a, mfr::other_slots(h, vi, si, srcs), 0, 0);
+        }
         C.n_fac++;
     }
     C.n_term = (int64_t)key.size();
@@ -287,20 +216,17 @@ static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
     if ((rc = dev_alloc(h, &C.d_tval, C.n_term)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &C.d_tflag, C.n_term)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &C.d_part, C.nb)) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &C.d_out, 1 + ev::kNCnt)) != CX_OK) return rc;
-    C.h_out.assign(1 + ev::kNCnt, 0.0);
     CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
     C.built = true;
     C.vinfo_epoch = h->vinfo_epoch;
-    C.param_epoch = ~0ull;
     return CX_OK;
 }
 
 // log det 2πQ of the real block of every parameter set (Q symmetric positive definite: cx_set_factor_matrices checks it)
-static int32_t refresh_params(cx_handle *h, Cache &C) {
-    if (C.param_epoch == h->param_epoch) return CX_OK;
-    const int d = h->cfg.dim, u = h->user_dim ? h->user_dim : d;
-    std::vector<double> ldq(std::max<size_t>(h->psets.size(), 1), cxh::kNaN), L((size_t)u * u);
+static void fill_ldq(const cx_handle *h, std::vector<double> &ldq) {
+    const int d = h->cfg.dim, u = mfr::user_dim(h);
+    ldq.assign(std::max<size_t>(h->psets.size(), 1), cxh::kNaN);
+    std::vector<double> L((size_t)u * u);
     for (size_t s = 0; s < h->psets.size(); s++) {
         if (h->psets[s].empty()) continue;
         const double *Q = h->psets[s].data() + (size_t)d * d;
@@ -317,29 +243,20 @@ static int32_t refresh_params(cx_handle *h, Cache &C) {
         }
         ldq[s] = ld;
     }
-    int32_t rc;
-    if ((rc = C.d_ldq.ensure(h, (int64_t)ldq.size())) != CX_OK) return rc;
-    CX_HIP(h, hipMemcpyAsync(C.d_ldq, ldq.data(), ldq.size() * 8, hipMemcpyHostToDevice, h->stream));
-    CX_HIP(h, hipStreamSynchronize(h->stream));
-    C.param_epoch = h->param_epoch;
-    return CX_OK;
 }
 
 static void launch(cx_handle *h, Cache &C) {
-    const int n = (int)C.n_term, u = h->user_dim ? h->user_dim : h->cfg.dim;
-    if (n) {
-        // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch
-        const unsigned grid = 8u * (unsigned)((n + 7) / 8);      // (k_evm_terms: an eighth of the terms per XCD)
-#define CX_T(N, W)                                                                                                                                      \
-    hipLaunchKernelGGL((k_evm_terms<N, W>), dim3(grid), dim3(64), 0, h->stream, n, C.d_rec, C.d_srcs, h->d_ptab, h->d_ptab_bt, C.d_ldq, h->d_mv_f2v, \
-                       h->d_mv_v2f, u, C.d_tval, C.d_tflag)
-        if (h->cfg.dim == 16) CX_T(1, 4);
-        else if (h->cfg.dim == 32) CX_T(2, 3);
-        else CX_T(4, 2);      // (4 x 4 tiles: 256 registers, and only with one block of B' / one tile of C in flight in the two-free-ends pass)
-#undef CX_T
-        hipLaunchKernelGGL(k_evm_part, dim3((unsigned)C.nb), dim3(kTB), 0, h->stream, n, C.d_tval, C.d_tflag, C.d_part);
-    }
-    ev::final_sum(h, n ? C.nb : 0, C.d_part, C.d_out);
+    const int n = (int)C.n_term, u = mfr::user_dim(h);
+    if (!n) return;
+    const unsigned grid = 8u * (unsigned)((n + 7) / 8);      // (k_evm_terms: an eighth of the terms per XCD)
+    mfr::for_tiles(h->cfg.dim, [&](auto nt) {
+        // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch.
+        // 4 x 4 tiles: 256 registers, and only with one block of B' / one tile of C in flight in the two-free-ends pass
+        constexpr int NT = decltype(nt)::value, W = NT == 1 ? 4 : NT == 2 ? 3 : 2;
+        hipLaunchKernelGGL((k_evm_terms<NT, W>), dim3(grid), dim3(64), 0, h->stream, n, C.d_rec, C.d_srcs, h->d_ptab, h->d_ptab_bt, C.ldq.d, h->d_mv_f2v,
+                           h->d_mv_v2f, u, C.d_tval, C.d_tflag);
+    });
+    hipLaunchKernelGGL(k_evm_part, dim3((unsigned)C.nb), dim3(kTB), 0, h->stream, n, C.d_tval, C.d_tflag, C.d_part);
 }
 
 }  // namespace evm
@@ -353,40 +270,21 @@ using namespace cxh;
 extern "C" int32_t cx_log_evidence_mfma(cx_handle *h, double *value, int64_t *counts4) {
     try {
         namespace evm = cx::evm;
+        namespace mfr = cx::mfr;
         const std::string who = "cx_log_evidence_mfma";
-        CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only (no variational free energy, no Beta-Bernoulli evidence)");
-        CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
-        CX_REQUIRE(h, value && counts4, CX_ERR_INVALID_ARGUMENT, who + ": null argument");
-        CX_REQUIRE(h, cx::is_mfma_dim(h->cfg.dim), CX_ERR_UNSUPPORTED, who + ": the matrix-core dims, 5 .. 64 (dim 1, 2, 3 and 4: cx_log_evidence)");
-        // (a user wiring, cx_graph_wire, cannot exist here: it is refused at these dims)
-        CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
-                   who + ": not for a partitioned handle (halo lists, state halos or a chain's time block: its terms would need owners)");
-        CX_HIP(h, hipSetDevice(h->cfg.device));
-        if (h->stream) {
-            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-            CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
-            CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
-        }
         int32_t rc;
-        if ((rc = mv_check_psets(h)) != CX_OK) return rc;
-        CX_REQUIRE(h, h->d_ptab && h->d_ptab_bt && h->d_mv_f2v, CX_ERR_STATE, who + ": the rule tables are not on the device (cx_set_factor_matrices)");
+        if ((rc = mfr::prepare(h, who, value && counts4 ? nullptr : "null argument", {"cx_log_evidence", "no variational free energy, no Beta-Bernoulli evidence", "terms"})) != CX_OK)
+            return rc;
         if (h->evidence_mfma && h->evidence_mfma->vinfo_epoch != h->vinfo_epoch) h->evidence_mfma.reset();      // other variables are observed
         if (!h->evidence_mfma) h->evidence_mfma.reset(new evm::Cache());
         evm::Cache &C = *h->evidence_mfma;
         if (!C.built && (rc = evm::build(h, C, who)) != CX_OK) { h->evidence_mfma.reset(); return rc; }
-        if (C.unsupported_fac >= 0)
-            return fail(h, CX_ERR_UNSUPPORTED, who + ": factor " + std::to_string(C.unsupported_fac) + " is no two-variable CX_FACTOR_GAUSS_LINEAR factor and no opaque message");
-        if ((rc = evm::refresh_params(h, C)) != CX_OK) return rc;
+        if (C.unsupported_fac >= 0) return mfr::refuse_factor(h, who, C.unsupported_fac);
+        if ((rc = C.ldq.refresh(h, [&](std::vector<double> &t) { evm::fill_ldq(h, t); })) != CX_OK) return rc;
         if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
         evm::launch(h, C);
-        CX_HIP(h, hipGetLastError());
-        CX_HIP(h, hipMemcpyAsync(C.h_out.data(), C.d_out, (1 + cx::ev::kNCnt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        CX_HIP(h, hipStreamSynchronize(h->stream));
-        uint64_t cnt[cx::ev::kNCnt];
-        std::memcpy(cnt, C.h_out.data() + 1, sizeof(cnt));
-        counts4[0] = C.n_fac;
-        for (int k = 1; k < 4; k++) counts4[k] = (int64_t)cnt[k - 1];
-        *value = counts4[2] + counts4[3] > 0 ? kNaN : C.h_out[0];
+        if ((rc = C.totals.read(h, C.nb, C.d_part, C.n_fac, counts4, value)) != CX_OK) return rc;
+        if (counts4[2] + counts4[3] > 0) *value = kNaN;
         return CX_OK;
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence_mfma: host allocation failed"); }
 }

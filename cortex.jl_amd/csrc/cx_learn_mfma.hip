@@ -34,8 +34,8 @@
 // Device workspace: at most W = max_waves(KD) wave workspaces of 6 KD² + 4 KD doubles (W = 1024 at KD = 64, 2048 below), and one row of
 // 2d + 3d² doubles per partial, at most W + n_groups of them: it does not grow with the number of factors (KD = 64: 198,656 B + 99,328 B each,
 // 305 MB plus n_groups rows at most; KD = 32: 154 MB; KD = 16: 39 MB).  cx_factor_beliefs_mfma goes through its list W factors at a time.
-#include "cx_host.h"
 #include "cx_evidence_mfma_core.h"
+#include "cx_mfma_reader.h"
 
 namespace cx {
 namespace lm {
@@ -127,15 +127,7 @@ __device__ __forceinline__ void solve_cols(const d4 (&M)[NT * (NT + 1) / 2], dou
         for (int j = 0; j < NT; j++)
 #pragma unroll
             for (int r = 0; r < 4; r++) Y[j][r] = IDENT ? ((j == b && g + 4 * r == c) ? 1.0 : 0.0) : X.ld(mo, tile_const_n<NT>(j, b, r));
-#pragma unroll
-        for (int j = IDENT ? b : 0; j < NT; j++) {      // (U^-T is lower triangular: the tiles above the diagonal stay zero)
-            d4 Vj;
-#pragma unroll
-            for (int r = 0; r < 4; r++) Vj[r] = Vs[j][(g + 4 * r) * kLdT + c];
-            Y[j] = tts(Vj, Y[j], d4{0.0, 0.0, 0.0, 0.0});
-#pragma unroll
-            for (int jj = j + 1; jj < NT; jj++) Y[jj] = tts(neg(M[utn<NT>(j, jj)]), Y[j], Y[jj]);
-        }
+        evm::solve_col<NT>(Y, M, Vs, IDENT ? b : 0, g, c);      // (U^-T is lower triangular: the tiles above the diagonal stay zero)
 #pragma unroll
         for (int j = 0; j < NT; j++)
 #pragma unroll
@@ -212,12 +204,7 @@ void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32
                 double wcv[NT];
 #pragma unroll
                 for (int j = 0; j < NT; j++) wcv[j] = 0.0;
-#pragma unroll
-                for (int a = 0; a < NT; a++)
-#pragma unroll
-                    for (int b = a; b < NT; b++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) M[utn<NT>(a, b)][r] = tabP.ld(mo, tile_const_n<NT>(a, b, r));
+                evm::load_upper<NT>(M, [&](int k) { return tabP.ld(mo, k); });
                 evm::add_sources<NT>(M, wcv, f2v_, srcs + a_off, a_n, mo, c);
                 undef = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
                 if (STATS) {      // Λ_o whole, for K = M⁻¹ Λ_o A
@@ -273,11 +260,7 @@ void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32
 #pragma unroll
                         for (int r = 0; r < 4; r++) Sm[utn<NT>(a, b)][r] = tabC.ld(mo, tile_const_n<NT>(a, b, r)) - G[r];
                     }
-                if (!oo)      // (a first factorisation that failed left NaN in Λ', η': the inputs are looked at themselves)
-                    for (int s = 0; s < b_n; s++) {
-                        const double *pr = f2v_ + (int64_t)srcs[b_off + s] * KM;
-                        undef = undef || __builtin_isnan(pr[0]) || __builtin_isnan(pr[KD]);
-                    }
+                if (!oo) undef = evm::any_nan_record<NT>(undef, f2v_, srcs + b_off, b_n);      // (a first factorisation that failed left NaN in Λ', η')
                 evm::add_sources<NT>(Sm, hcv, f2v_, srcs + b_off, b_n, mo, c);
                 if (oo) undef = undef || __builtin_isnan(bcast(Sm[0][0], 0)) || __builtin_isnan(bcast(hcv[0], 0));
                 evm::factor_solve<NT>(Sm, hcv, zrv, S, Vs, g, c, u, ld, q, pd);
@@ -360,15 +343,15 @@ __global__ __launch_bounds__(256) void k_lm_reduce(const int na, const int32_t *
 // is fixed by the graph) and are kept until another grouping replaces them or the records are rebuilt: an EM loop uploads them once
 struct Cache {
     bool built = false;
-    uint64_t vinfo_epoch = 0, atab_epoch = ~0ull;
+    uint64_t vinfo_epoch = 0;
     std::vector<int32_t> kind, set;      // by factor index: -1 not covered (kind -2: an opaque message), else the record's flags; its parameter set
     int64_t unsupported_fac = -1;
     DevBuf<int32_t> d_rec, d_srcs;
-    DevBuf<double> d_atab, d_ws;
+    mfr::ParamTable atab;
+    DevBuf<double> d_ws;
     // the grouping
-    bool g_valid = false, g_explicit = false;
-    int64_t g_n_groups = 0, n_items = 0, n_part = 0, n_wave = 0;
-    std::vector<int64_t> g_ids, g_groups;
+    mfr::RequestKey group_key;      // tag: n_groups; the ids and their groups
+    int64_t n_items = 0, n_part = 0, n_wave = 0;
     std::vector<int64_t> group_n;             // factors of every group
     std::vector<int32_t> part_group, h_meta;
     std::vector<double> h_rows;
@@ -381,43 +364,21 @@ struct Cache {
 
 static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
     using namespace cxh;
-    const int64_t ne = h->ne, nf = h->nf;
-    std::vector<int32_t> efac((size_t)ne), fe1((size_t)nf, -1), fe2((size_t)nf, -1), nfe((size_t)nf, 0);
-    for (int64_t e = 0; e < ne; e++) {
-        const int64_t f = find_factor(h, h->edge_fac_id[e]);
-        efac[e] = (int32_t)f;
-        if (fe1[f] < 0) fe1[f] = (int32_t)e; else if (fe2[f] < 0) fe2[f] = (int32_t)e;
-        nfe[f]++;
-    }
+    const int64_t nf = h->nf;
+    mfr::Pairs P;
+    mfr::pairs_of(h, P);
     std::vector<int32_t> rec((size_t)nf * 8, -1), srcs;
-    // the slots of variable v but `skip`, in ascending neighbour order (k_v2f64's): (offset, count) in srcs
-    auto others = [&](int32_t v, int32_t skip, int32_t &off, int32_t &n) {
-        off = (int32_t)srcs.size();
-        for (int32_t e = h->var_off[v]; e < h->var_off[v + 1]; e++) {
-            const int32_t s = slot_of_edge(h, e);
-            if (s != skip) srcs.push_back(s);
-        }
-        n = (int32_t)srcs.size() - off;
-    };
     C.kind.assign((size_t)nf, -1);
-    C.set.assign((size_t)nf, -1);
-    C.unsupported_fac = -1;
+    C.set = P.set;
+    C.unsupported_fac = P.unsupported_fac;
     for (int64_t f = 0; f < nf; f++) {
-        if (h->fac_kind[f] == CX_FACTOR_OPAQUE) { C.kind[f] = -2; continue; }
-        if (h->fac_kind[f] != CX_FACTOR_GAUSS_LINEAR || nfe[f] != 2) { if (C.unsupported_fac < 0) C.unsupported_fac = h->fac_ids[f]; continue; }
-        const int32_t s1 = slot_of_edge(h, fe1[f]), s2 = slot_of_edge(h, fe2[f]);
-        int32_t so = s1, si = s2, vo = h->edge_var[fe1[f]], vi = h->edge_var[fe2[f]];
-        if ((h->spdir[s1] & 1) == 0) { std::swap(so, si); std::swap(vo, vi); }      // spdir[in slot] = 2 set (the message it sends goes forward)
-        const bool oo = (h->vinfo[vo] & kClamped) != 0, oi = (h->vinfo[vi] & kClamped) != 0;
-        int32_t *r = &rec[(size_t)f * 8];
-        r[0] = (oo ? 1 : 0) | (oi ? 2 : 0);
-        r[1] = h->spdir[si] >> 1;
-        r[2] = r[3] = r[4] = r[5] = 0;
-        if (!oo) others(vo, so, r[2], r[3]);
-        if (!oi) others(vi, si, r[4], r[5]);
-        r[6] = so; r[7] = si;
+        if (h->fac_kind[f] == CX_FACTOR_OPAQUE) C.kind[f] = -2;
+        if (P.so[f] < 0) continue;
+        const bool oo = (h->vinfo[P.vo[f]] & kClamped) != 0, oi = (h->vinfo[P.vi[f]] & kClamped) != 0;
+        const mfr::Run a = oo ? mfr::Run{} : mfr::other_slots(h, P.vo[f], P.so[f], srcs), b = oi ? mfr::Run{} : mfr::other_slots(h, P.vi[f], P.si[f], srcs);
+        const int32_t r[8] = {(oo ? 1 : 0) | (oi ? 2 : 0), P.set[f], a.off, a.n, b.off, b.n, P.so[f], P.si[f]};
+        std::copy(r, r + 8, &rec[(size_t)f * 8]);
         C.kind[f] = r[0];
-        C.set[f] = r[1];
     }
     CX_REQUIRE(h, nf < (int64_t)0x0fffffff && (int64_t)srcs.size() < (int64_t)0x7fffffff, CX_ERR_UNSUPPORTED, who + ": more than 2^28 factors");
     int32_t rc;
@@ -426,55 +387,32 @@ static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
     CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
     C.built = true;
     C.vinfo_epoch = h->vinfo_epoch;
-    C.g_valid = false;
+    C.group_key.valid = false;
     return CX_OK;
 }
 
 // [set][A | A'] at the internal dim (blockdiag(A, I) for an embedded one: cx_set_factor_matrices)
-static int32_t refresh_atab(cx_handle *h, Cache &C) {
-    if (C.atab_epoch == h->param_epoch && C.d_atab) return CX_OK;
+static void fill_atab(const cx_handle *h, std::vector<double> &at) {
     const size_t d = (size_t)h->cfg.dim, dd = d * d, ns = std::max<size_t>(h->psets.size(), 1);
-    std::vector<double> at(ns * 2 * dd, cxh::kNaN);
+    at.assign(ns * 2 * dd, cxh::kNaN);
     for (size_t s = 0; s < h->psets.size(); s++) {
         if (h->psets[s].empty()) continue;
         const double *A = h->psets[s].data();
         for (size_t r = 0; r < d; r++)
             for (size_t c = 0; c < d; c++) { at[s * 2 * dd + r * d + c] = A[r * d + c]; at[s * 2 * dd + dd + c * d + r] = A[r * d + c]; }
     }
-    int32_t rc;
-    if ((rc = C.d_atab.ensure(h, (int64_t)at.size())) != CX_OK) return rc;
-    CX_HIP(h, hipMemcpyAsync(C.d_atab, at.data(), at.size() * 8, hipMemcpyHostToDevice, h->stream));
-    CX_HIP(h, hipStreamSynchronize(h->stream));
-    C.atab_epoch = h->param_epoch;
-    return CX_OK;
 }
 
-// the refusals of cx_log_evidence_mfma, the cache and its factor records
+// the refusals of a reader (cx_mfma_reader.h), the cache and its factor records
 static int32_t prepare(cx_handle *h, const std::string &who, const char *small_dims, const char *bad_args, Cache *&out) {
     using namespace cxh;
-    CX_REQUIRE(h, !h || h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only (the variational and Beta-Bernoulli families have no Gaussian factor beliefs)");
-    CX_REQUIRE(h, h && h->has_graph, CX_ERR_STATE, who + ": no graph");
-    CX_REQUIRE(h, !bad_args, CX_ERR_INVALID_ARGUMENT, who + ": " + (bad_args ? bad_args : ""));
-    CX_REQUIRE(h, cx::is_mfma_dim(h->cfg.dim), CX_ERR_UNSUPPORTED, who + ": the matrix-core dims, 5 .. 64 (dim 1, 2, 3 and 4: " + small_dims + ")");
-    CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
-               who + ": not for a partitioned handle (halo lists, state halos or a chain's time block: its factors would need owners)");
-    CX_HIP(h, hipSetDevice(h->cfg.device));
-    if (h->stream) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        CX_HIP(h, hipStreamIsCapturing(h->stream, &st));
-        CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
-    }
     int32_t rc;
-    // (mv_check_psets' conditions under this call's name; behind them the tables are on the device: the check below is a guard)
-    CX_REQUIRE(h, (int64_t)h->psets.size() > h->max_pset, CX_ERR_STATE, who + ": a factor names a parameter set that was never set (cx_set_factor_matrices)");
-    for (int64_t i = 0; i <= h->max_pset; i++)
-        CX_REQUIRE(h, !h->psets[i].empty(), CX_ERR_STATE, who + ": parameter set " + std::to_string(i) + " was never set (cx_set_factor_matrices)");
-    CX_REQUIRE(h, h->d_ptab && h->d_ptab_bt && h->d_mv_f2v && h->d_mv_v2f, CX_ERR_STATE, who + ": the rule tables are not on the device (cx_set_factor_matrices)");
+    if ((rc = mfr::prepare(h, who, bad_args, {small_dims, "the variational and Beta-Bernoulli families have no Gaussian factor beliefs", "factors"})) != CX_OK) return rc;
     if (h->learn_mfma && h->learn_mfma->vinfo_epoch != h->vinfo_epoch) h->learn_mfma.reset();      // other variables are observed
     if (!h->learn_mfma) h->learn_mfma.reset(new Cache());
     Cache &C = *h->learn_mfma;
     if (!C.built && (rc = build(h, C, who)) != CX_OK) { h->learn_mfma.reset(); return rc; }
-    if ((rc = refresh_atab(h, C)) != CX_OK) return rc;
+    if ((rc = C.atab.refresh(h, [&](std::vector<double> &t) { fill_atab(h, t); })) != CX_OK) return rc;
     if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
     out = &C;
     return CX_OK;
@@ -489,7 +427,7 @@ static int32_t assign_groups(cx_handle *h, const Cache &C, const std::string &wh
     const int64_t nf = h->nf;
     grp.assign((size_t)nf, -1);
     if (!ids) {
-        if (C.unsupported_fac >= 0) return fail(h, CX_ERR_UNSUPPORTED, who + ": " + no_pair(C.unsupported_fac) + " and no opaque message");
+        if (C.unsupported_fac >= 0) return mfr::refuse_factor(h, who, C.unsupported_fac);
         for (int64_t f = 0; f < nf; f++) {
             if (C.kind[f] < 0) continue;
             if (C.set[f] >= n_groups)
@@ -556,14 +494,12 @@ static int32_t build_lists(cx_handle *h, Cache &C, const std::vector<int32_t> &g
 
 template <bool STATS>
 static void launch(cx_handle *h, Cache &C, int nwave, const int32_t *wbeg, const int32_t *pbeg, const int32_t *items, double *out) {
-    const int u = h->user_dim ? h->user_dim : h->cfg.dim;
-#define CX_T(N, W)                                                                                                                                    \
-    hipLaunchKernelGGL((k_lm_factors<N, STATS, W>), dim3((unsigned)nwave), dim3(64), 0, h->stream, nwave, wbeg, pbeg, items, C.d_rec, C.d_srcs, h->d_ptab, \
-                       h->d_ptab_bt, C.d_atab, h->d_mv_f2v, h->d_mv_v2f, u, C.d_ws, C.d_acc, C.d_meta, out)
-    if (h->cfg.dim == 16) CX_T(1, 2);
-    else if (h->cfg.dim == 32) CX_T(2, 2);
-    else CX_T(4, 1);      // (4 x 4 tiles at two waves per SIMD: 7 to 11 registers spilled, so one)
-#undef CX_T
+    const int u = mfr::user_dim(h);
+    mfr::for_tiles(h->cfg.dim, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value, W = NT == 4 ? 1 : 2;      // (4 x 4 tiles at two waves per SIMD: 7 to 11 registers spilled, so one)
+        hipLaunchKernelGGL((k_lm_factors<NT, STATS, W>), dim3((unsigned)nwave), dim3(64), 0, h->stream, nwave, wbeg, pbeg, items, C.d_rec, C.d_srcs, h->d_ptab,
+                           h->d_ptab_bt, C.atab.d, h->d_mv_f2v, h->d_mv_v2f, u, C.d_ws, C.d_acc, C.d_meta, out);
+    });
 }
 
 }  // namespace lm
@@ -591,7 +527,7 @@ extern "C" int32_t cx_factor_beliefs_mfma(cx_handle *h, int64_t n, const int64_t
             if (C.kind[(size_t)f] < 0) return fail(h, CX_ERR_UNSUPPORTED, who + ": " + lm::no_pair(factor_ids[i]));
             items[(size_t)i] = (int32_t)f;
         }
-        const int d = h->cfg.dim, u = h->user_dim ? h->user_dim : d;
+        const int d = h->cfg.dim, u = cx::mfr::user_dim(h);
         const int64_t nb = 2 * u + 4 * (int64_t)u * u, chunk = std::min<int64_t>(n, lm::max_waves(d));
         if ((rc = C.d_bitems.ensure(h, chunk)) != CX_OK || (rc = C.d_bout.ensure(h, chunk * nb)) != CX_OK || (rc = C.d_ws.ensure(h, chunk * lm::ws_doubles(d))) != CX_OK) return rc;
         for (int64_t at = 0; at < n; at += chunk) {
@@ -619,20 +555,13 @@ extern "C" int32_t cx_factor_statistics_mfma(cx_handle *h, int64_t n, const int6
                               : nullptr;
         if ((rc = lm::prepare(h, who, "cx_factor_statistics", bad, Cp)) != CX_OK) return rc;
         lm::Cache &C = *Cp;
-        const int d = h->cfg.dim, u = h->user_dim ? h->user_dim : d, na = 2 * u + 3 * u * u, ns = 1 + na;
-        const bool same = C.g_valid && C.g_n_groups == n_groups && C.g_explicit == (factor_ids != nullptr) &&
-                          (!factor_ids || ((int64_t)C.g_ids.size() == n && std::equal(factor_ids, factor_ids + n, C.g_ids.begin()) &&
-                                           std::equal(groups, groups + n, C.g_groups.begin())));
-        if (!same) {
-            C.g_valid = false;
+        const int d = h->cfg.dim, u = cx::mfr::user_dim(h), na = 2 * u + 3 * u * u, ns = 1 + na;
+        if (!C.group_key.matches(n_groups, n, factor_ids, groups)) {
+            C.group_key.valid = false;
             std::vector<int32_t> grp;
             if ((rc = lm::assign_groups(h, C, who, n, factor_ids, groups, n_groups, grp)) != CX_OK) return rc;
             if ((rc = lm::build_lists(h, C, grp, n_groups, na)) != CX_OK) return rc;
-            C.g_explicit = factor_ids != nullptr;
-            C.g_ids.assign(factor_ids, factor_ids ? factor_ids + n : factor_ids);
-            C.g_groups.assign(groups, groups ? groups + n : groups);
-            C.g_n_groups = n_groups;
-            C.g_valid = true;
+            C.group_key.remember(n_groups, n, factor_ids, groups);
         }
         std::fill(out, out + n_groups * ns, 0.0);
         for (int k = 0; k < 4; k++) counts4[k] = 0;

@@ -20,24 +20,20 @@
 // of a SUM OF MESSAGES may be zero (no rule table is added here, unlike cx_log_evidence_mfma's factor terms), and Z'Z runs over every
 // row of Z: the identity is added to the padding diagonal of Λc before it is factored, which leaves the real block as it is.
 //
-// k_prm_rows writes (log_density, status) per row at the row's index and, when asked, the row's u + u² + 2 doubles; k_prm_part folds 256
+// k_prm_rows writes (log_density, status) per row at the row's index and, when asked, the row's u + u² + 2 doubles; mfr::k_status_part folds 256
 // rows into an ev::Part and ev::final_sum adds the parts in index order: no atomics, two calls on one state are bit-identical, and the
 // total does not depend on how the payload is cut into chunks.
-#include "cx_evidence_core.h"
 #include "cx_evidence_mfma_core.h"
-#include "cx_pairs_mfma.h"
+#include "cx_mfma_reader.h"
 
 namespace cx {
 namespace prm {
 
 using namespace w64;
-using evm::add_sources;
-using evm::factor_solve;
-using evm::wave_sum;
+using evm::add_sources, evm::any_nan_record, evm::factor_solve, evm::flat_pivot, evm::gram_pass, evm::pad_identity, evm::park_z, evm::solve_block_cols, evm::store_symmetric;
 
-constexpr int kTB = 256;                              // rows per block of k_prm_part
-constexpr int64_t kRowBufBytes = (int64_t)32 << 20;   // the device row buffer: the payload goes to the host a chunk at a time
-constexpr int kScored = 0, kUndefined = 1, kImproper = 2;
+using mfr::Pairs;
+constexpr int kScored = mfr::kRowOk, kUndefined = mfr::kRowUndefined, kImproper = mfr::kRowImproper;
 
 // row record (8 int32): {parameter set, the slot of the datum (the OUT end's), kept offset, kept count, excluded offset, excluded count, 0, 0};
 // kept and excluded are runs of message slots in `srcs`.  ttab: [set][A' | Q] at the internal dim.  One wave per row, rows [row0, row0 + n);
@@ -53,8 +49,7 @@ void k_prm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
     __shared__ double ZS[KD];
     if ((int)blockIdx.x >= n) return;
     const int w = row0 + (int)blockIdx.x;
-    const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, mo = g * KD + c, rr = c >> 2;
-    const bool diag_lane = g == (c & 3);      // entry [i][i] of a diagonal tile sits in lane (g, c) = (i & 3, i), register i >> 2
+    const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, mo = g * KD + c;
     const int32_t *t = rec + 8 * (int64_t)w;
     const int set = t[0], yslot = t[1], k_off = t[2], k_n = t[3], x_off = t[4], x_n = t[5];
     const double *tab = ttab + (int64_t)set * 2 * KD * KD;
@@ -94,18 +89,9 @@ void k_prm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
     bool undef = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
     bool ynan = false;
 #pragma unroll
-    for (int j = 0; j < NT; j++) {
-        ynan = ynan || (16 * j + c < u && __builtin_isnan(v2f[(int64_t)yslot * KM + 16 * j + c]));      // (the datum is read again where it is used)
-        // the identity on the padding diagonal
-        const bool pad = diag_lane && 16 * j + c >= u;
-#pragma unroll
-        for (int r = 0; r < 4; r++) M[utn<NT>(j, j)][r] += (pad && r == rr) ? 1.0 : 0.0;
-    }
-    undef = undef || __ballot(ynan) != 0;
-    for (int s = 0; s < x_n; s++) {
-        const double *p = f2v + (int64_t)srcs[x_off + s] * KM;
-        undef = undef || __builtin_isnan(p[0]) || __builtin_isnan(p[KD]);
-    }
+    for (int j = 0; j < NT; j++) ynan = ynan || (16 * j + c < u && __builtin_isnan(v2f[(int64_t)yslot * KM + 16 * j + c]));      // (the datum is read again where it is used)
+    pad_identity<NT>(M, g, c, u);
+    undef = any_nan_record<NT>(undef || __ballot(ynan) != 0, f2v, srcs + x_off, x_n);
     if (undef) { unscored(kUndefined); return; }
     if (k_n == 0) { unscored(kImproper); return; }      // nothing is kept: flat by structure
 
@@ -113,86 +99,26 @@ void k_prm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
     double zrv[NT][4], ld1, q1;
     bool pd1;
     factor_solve<NT>(M, wcv, zrv, S, Vs, g, c, u, ld1, q1, pd1);
-    // ref: the diagonal of the sum of ALL stored messages into x (kept and excluded are adjacent runs of srcs), lane c entry 16 k + c
-    bool flat = false;
-#pragma unroll
-    for (int k = 0; k < NT; k++) {
-        double ref = 0.0;
-        for (int s = 0; s < k_n + x_n; s++) ref += f2v[(int64_t)srcs[k_off + s] * KM + KD + (16 * k + c) * (KD + 1)];
-        const double v = Vs[k][c * kLdT + c], piv = 1.0 / (v * v);      // V_kk = 1 / U_kk
-        flat = flat || (16 * k + c < u && !(piv > k_flat * fmax(ref, 0.0)));
-    }
-    if (!pd1 || __ballot(flat) != 0) { unscored(kImproper); return; }
-#pragma unroll
-    for (int j = 0; j < NT; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) ZS[16 * j + g + 4 * r] = zrv[j][r];      // (the 16 lanes of a group write one value to one place)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // against the diagonal of the sum of ALL stored messages into x (kept and excluded are adjacent runs of srcs)
+    if (!pd1 || __ballot(flat_pivot<NT>(Vs, f2v, srcs + k_off, k_n + x_n, c, u, k_flat)) != 0) { unscored(kImproper); return; }
+    park_z<NT>(ZS, zrv, g);
 
     // ---- Z = U^-T A', one block column at a time ------------------------------------------------------------------------------------
     d4 Y[NT][NT];
-#pragma unroll
-    for (int b = 0; b < NT; b++) {
-        asm volatile("" ::: "memory");      // (one block column of A' in flight at a time)
-#pragma unroll
-        for (int j = 0; j < NT; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) Y[j][b][r] = ((gcdp)tab)[mo + tile_const_n<NT>(j, b, r)];
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            d4 Vj;
-#pragma unroll
-            for (int r = 0; r < 4; r++) Vj[r] = Vs[j][(g + 4 * r) * kLdT + c];
-            Y[j][b] = tts(Vj, Y[j][b], d4{0.0, 0.0, 0.0, 0.0});
-#pragma unroll
-            for (int jj = j + 1; jj < NT; jj++) Y[jj][b] = tts(neg(M[utn<NT>(j, jj)]), Y[j][b], Y[jj][b]);
-        }
-    }
+    solve_block_cols<NT, false>(Y, M, Vs, [&](int k) { return ((gcdp)tab)[mo + k]; }, g, c);
     // ---- S = Q + Z'Z (upper tiles), ŷ = Z'z, e = y - ŷ ----------------------------------------------------------------------------
     d4 Sm[NU];
     double ecv[NT];
-#pragma unroll
-    for (int a = 0; a < NT; a++) {
-#pragma unroll
-        for (int b = a; b < NT; b++) {
-            asm volatile("" ::: "memory");      // (one tile of Q in flight at a time)
-            d4 G = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int j = 0; j < NT; j++) G = tts(Y[j][a], Y[j][b], G);
-#pragma unroll
-            for (int r = 0; r < 4; r++) Sm[utn<NT>(a, b)][r] = ((gcdp)tab)[KD * KD + mo + tile_const_n<NT>(a, b, r)] + G[r];
-        }
-        double p = 0.0;
-#pragma unroll
-        for (int j = 0; j < NT; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) p += Y[j][a][r] * ZS[16 * j + g + 4 * r];
-        const double yh = sum_groups(p);
+    gram_pass<NT, 1>(Sm, Y, ZS, [&](int k) { return ((gcdp)tab)[KD * KD + mo + k]; }, [&](int a, double yh) {
         ecv[a] = v2f[(int64_t)yslot * KM + 16 * a + c] - yh;
         if (o && g == 0 && 16 * a + c < u) o[16 * a + c] = yh;
-    }
-    // the payload's S before the factorisation takes the tiles: the upper tiles as they are, the lower ones turned through LDS
+    }, g);
+    // the payload's S before the factorisation takes the tiles
     if (o) {
 #pragma unroll
         for (int a = 0; a < NT; a++)
 #pragma unroll
-            for (int b = a; b < NT; b++) {
-                const d4 D = Sm[utn<NT>(a, b)];
-                if (b > a) {
-#pragma unroll
-                    for (int r = 0; r < 4; r++) put_s(a, b, r, D[r]);
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the previous tile's reads have returned
-#pragma unroll
-                for (int r = 0; r < 4; r++) S[(g + 4 * r) * kLdT + c] = D[r];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                // (a diagonal tile: the mean of the two triangles, so that S is symmetric to the last bit)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const double tr = S[c * kLdT + g + 4 * r];
-                    put_s(b, a, r, b > a ? tr : 0.5 * (D[r] + tr));
-                }
-            }
+            for (int b = a; b < NT; b++) store_symmetric(Sm[utn<NT>(a, b)], a, b, S, put_s, g, c);
     }
     // ---- the score -------------------------------------------------------------------------------------------------------------------
     // The lane's coordinates anew: with the two factorisations in one straight line hipcc keeps what the first derives from (g, c) — the
@@ -210,28 +136,19 @@ void k_prm_rows(int row0, int n, const int32_t *__restrict__ rec, const int32_t 
     rflag[w] = (uint8_t)kScored;
 }
 
-// 256 rows -> one ev::Part (fixed-order tree); ev::final_sum adds the parts in index order
-__global__ __launch_bounds__(kTB) void k_prm_part(int n, const double *__restrict__ rval, const uint8_t *__restrict__ rflag, ev::Part *__restrict__ part) {
-    const int i = blockIdx.x * kTB + threadIdx.x;
-    const double s = i < n ? rval[i] : 0.0;
-    const int f = i < n ? (int)rflag[i] : -1;
-    ev::block_part<kTB>(s, 0.0, f == kScored, f == kUndefined, f == kImproper, 0u, part);
-}
-
 // ---- host -------------------------------------------------------------------------------------------------------------------------
 // The rows follow the mode, the caller's ids, the graph and WHICH variables are observed (vinfo_epoch: cx_derived.h), the [A' | Q] table
 // the rule parameters (param_epoch); messages and data are read by every call
 struct Plan {
-    bool valid = false, explicit_ids = false;
-    int32_t mode = 0;
-    std::vector<int64_t> ids;
-    uint64_t vinfo_epoch = 0, tab_epoch = ~0ull;
-    int64_t n_rows = 0, nb = 0;
+    mfr::RequestKey key;      // tag: the mode
+    uint64_t vinfo_epoch = 0;
+    int64_t n_rows = 0;
     DevBuf<int32_t> d_rec, d_srcs;
-    DevBuf<double> d_tab, d_rval, d_rows, d_out;
+    mfr::ParamTable tab;
+    DevBuf<double> d_rval, d_rows;
     DevBuf<uint8_t> d_rflag;
     DevBuf<ev::Part> d_part;
-    std::vector<double> h_out;
+    mfr::Totals totals;
 };
 
 // a row: the OUT end observed, the IN end not
@@ -239,6 +156,7 @@ static bool is_row(const cx_handle *h, const Pairs &P, int64_t f) {
     return P.so[f] >= 0 && (h->vinfo[P.vo[f]] & kClamped) != 0 && (h->vinfo[P.vi[f]] & kClamped) == 0;
 }
 
+static const mfr::Words kWords = {"cx_predictive", "the variational and Beta-Bernoulli families have no Gaussian predictive", "rows"};
 static const char *kNotARow = " is not a row: a two-variable CX_FACTOR_GAUSS_LINEAR factor whose CX_ROLE_OUT end is observed and whose CX_ROLE_IN end is not";
 
 // the factor indices of the rows, checked: the caller's, in the caller's order, or every row in ascending factor id
@@ -271,43 +189,30 @@ static int32_t build_plan(cx_handle *h, const Pairs &P, Plan &L, int32_t mode, c
         const int32_t x = P.vi[f], own = P.si[f];
         int32_t *r = &rec[(size_t)i * 8];
         r[0] = P.set[f]; r[1] = P.so[f];
-        // x's slots in ascending neighbour order (k_v2f64's): the kept run, then the excluded one
-        r[2] = (int32_t)srcs.size();
-        for (int32_t e = h->var_off[x]; e < h->var_off[x + 1]; e++) {
-            const int32_t s = slot_of_edge(h, e);
-            if (s != own && !in_slot[(size_t)s]) srcs.push_back(s);
-        }
-        r[3] = (int32_t)srcs.size() - r[2];
-        r[4] = (int32_t)srcs.size();
-        for (int32_t e = h->var_off[x]; e < h->var_off[x + 1]; e++) {
-            const int32_t s = slot_of_edge(h, e);
-            if (s == own || in_slot[(size_t)s]) srcs.push_back(s);
-        }
-        r[5] = (int32_t)srcs.size() - r[4];
+        // x's slots: the kept run, then the excluded one
+        const auto kept = [&](int32_t s) { return s != own && !in_slot[(size_t)s]; };
+        const mfr::Run k = mfr::slots_where(h, x, srcs, kept), ex = mfr::slots_where(h, x, srcs, [&](int32_t s) { return !kept(s); });
+        r[2] = k.off; r[3] = k.n; r[4] = ex.off; r[5] = ex.n;
         CX_REQUIRE(h, (int64_t)srcs.size() < (int64_t)0x7fffff00, CX_ERR_UNSUPPORTED, who + ": more than 2^31 inputs");
     }
     CX_REQUIRE(h, n < (int64_t)0x7fffff00, CX_ERR_UNSUPPORTED, who + ": more than 2^31 rows");
-    L.valid = false;
     L.n_rows = n;
-    L.nb = (n + kTB - 1) / kTB;
+    const int64_t nb = (n + mfr::kTB - 1) / mfr::kTB;
     if (srcs.empty()) srcs.push_back(0);      // (never read: no row names a slot)
     int32_t rc;
     if ((rc = dev_upload(h, &L.d_rec, rec)) != CX_OK) return rc;
     if ((rc = dev_upload(h, &L.d_srcs, srcs)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &L.d_rval, std::max<int64_t>(n, 1))) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &L.d_rflag, std::max<int64_t>(n, 1))) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &L.d_part, std::max<int64_t>(L.nb, 1))) != CX_OK) return rc;
-    if (!L.d_out && (rc = dev_alloc(h, &L.d_out, 1 + ev::kNCnt)) != CX_OK) return rc;
-    L.h_out.assign(1 + ev::kNCnt, 0.0);
+    if ((rc = dev_alloc(h, &L.d_part, std::max<int64_t>(nb, 1))) != CX_OK) return rc;
     CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
     return CX_OK;
 }
 
 // [set][A' | Q] at the internal dim (blockdiag(A, I)', blockdiag(Q, I) for an embedded one: cx_set_factor_matrices)
-static int32_t refresh_tab(cx_handle *h, Plan &L) {
-    if (L.tab_epoch == h->param_epoch && L.d_tab) return CX_OK;
+static void fill_tab(const cx_handle *h, std::vector<double> &tb) {
     const size_t d = (size_t)h->cfg.dim, dd = d * d, ns = std::max<size_t>(h->psets.size(), 1);
-    std::vector<double> tb(ns * 2 * dd, cxh::kNaN);
+    tb.assign(ns * 2 * dd, cxh::kNaN);
     for (size_t s = 0; s < h->psets.size(); s++) {
         if (h->psets[s].empty()) continue;
         const double *A = h->psets[s].data(), *Q = A + dd;
@@ -317,28 +222,19 @@ static int32_t refresh_tab(cx_handle *h, Plan &L) {
                 tb[s * 2 * dd + dd + r * d + c] = 0.5 * (Q[r * d + c] + Q[c * d + r]);
             }
     }
-    int32_t rc;
-    if ((rc = L.d_tab.ensure(h, (int64_t)tb.size())) != CX_OK) return rc;
-    CX_HIP(h, hipMemcpyAsync(L.d_tab, tb.data(), tb.size() * 8, hipMemcpyHostToDevice, h->stream));
-    CX_HIP(h, hipStreamSynchronize(h->stream));
-    L.tab_epoch = h->param_epoch;
-    return CX_OK;
 }
 
 // rows [row0, row0 + n) (d_rows: their payload, or null)
 static void launch_rows(cx_handle *h, Plan &L, int64_t row0, int64_t n, double *d_rows) {
     if (!n) return;
-    const int u = h->user_dim ? h->user_dim : h->cfg.dim;
-    // a message that carries no information arrives as the rounding of u-term sums (the measured remainders)
-    const double k_flat = 64.0 * u * 2.220446049250313e-16;
-#define CX_R(N, W)                                                                                                                                   \
-    hipLaunchKernelGGL((k_prm_rows<N, W>), dim3((unsigned)n), dim3(64), 0, h->stream, (int)row0, (int)n, L.d_rec, L.d_srcs, L.d_tab, h->d_mv_f2v, \
-                       h->d_mv_v2f, u, k_flat, L.d_rval, L.d_rflag, d_rows)
-    // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch
-    if (h->cfg.dim == 16) CX_R(1, 4);
-    else if (h->cfg.dim == 32) CX_R(2, 3);
-    else CX_R(4, 2);
-#undef CX_R
+    const int u = mfr::user_dim(h);
+    const double k_flat = mfr::flat_pivot_factor(h);
+    mfr::for_tiles(h->cfg.dim, [&](auto nt) {
+        // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch
+        constexpr int NT = decltype(nt)::value, W = NT == 1 ? 4 : NT == 2 ? 3 : 2;
+        hipLaunchKernelGGL((k_prm_rows<NT, W>), dim3((unsigned)n), dim3(64), 0, h->stream, (int)row0, (int)n, L.d_rec, L.d_srcs, L.tab.d, h->d_mv_f2v,
+                           h->d_mv_v2f, u, k_flat, L.d_rval, L.d_rflag, d_rows);
+    });
 }
 
 }  // namespace prm
@@ -353,11 +249,11 @@ extern "C" int32_t cx_predictive_rows_mfma(cx_handle *h, int64_t cap, int64_t *f
     try {
         namespace prm = cx::prm;
         const std::string who = "cx_predictive_rows_mfma";
-        prm::Pairs P;
+        cx::mfr::Pairs P;
         int32_t rc;
         const char *bad = n_rows && cap >= 0 && (cap == 0 || factor_ids) ? nullptr : "null argument or negative capacity";
-        if ((rc = prm::prepare(h, who, bad)) != CX_OK) return rc;
-        if ((rc = prm::checked_pairs(h, who, P)) != CX_OK) return rc;
+        if ((rc = cx::mfr::prepare(h, who, bad, prm::kWords)) != CX_OK) return rc;
+        if ((rc = cx::mfr::checked_pairs(h, who, P)) != CX_OK) return rc;
         std::vector<int64_t> fac;
         if ((rc = prm::list_rows(h, P, who, 0, nullptr, fac)) != CX_OK) return rc;
         *n_rows = (int64_t)fac.size();
@@ -369,60 +265,37 @@ extern "C" int32_t cx_predictive_rows_mfma(cx_handle *h, int64_t cap, int64_t *f
 extern "C" int32_t cx_predictive_mfma(cx_handle *h, int32_t mode, int64_t n, const int64_t *factor_ids, double *out, double *total, int64_t *counts4) {
     try {
         namespace prm = cx::prm;
+        namespace mfr = cx::mfr;
         const std::string who = "cx_predictive_mfma";
         int32_t rc;
         const char *bad = !counts4 ? "counts4 is null"
                           : mode != CX_PREDICT_LOO && mode != CX_PREDICT_CAUSAL ? "mode is CX_PREDICT_LOO or CX_PREDICT_CAUSAL"
                           : factor_ids && n < 0 ? "negative count" : nullptr;
-        {
-            if ((rc = prm::prepare(h, who, bad)) != CX_OK) return rc;
-            if (h->predict_mfma && h->predict_mfma->vinfo_epoch != h->vinfo_epoch) h->predict_mfma.reset();      // other variables are observed
-            if (!h->predict_mfma) h->predict_mfma.reset(new prm::Plan());
-            prm::Plan &L = *h->predict_mfma;
-            const bool same = L.valid && L.mode == mode && L.explicit_ids == (factor_ids != nullptr) &&
-                              (!factor_ids || ((int64_t)L.ids.size() == n && std::equal(factor_ids, factor_ids + n, L.ids.begin())));
-            if (!same) {
-                L.valid = false;
-                prm::Pairs P;
-                if ((rc = prm::checked_pairs(h, who, P)) != CX_OK) return rc;
-                std::vector<int64_t> fac;
-                if ((rc = prm::list_rows(h, P, who, n, factor_ids, fac)) != CX_OK) return rc;
-                if ((rc = prm::build_plan(h, P, L, mode, fac, who)) != CX_OK) return rc;
-                L.mode = mode;
-                L.explicit_ids = factor_ids != nullptr;
-                L.ids.assign(factor_ids, factor_ids ? factor_ids + n : factor_ids);
-                L.vinfo_epoch = h->vinfo_epoch;
-                L.valid = true;
-            }
-        }
+        if ((rc = mfr::prepare(h, who, bad, prm::kWords)) != CX_OK) return rc;
+        if (h->predict_mfma && h->predict_mfma->vinfo_epoch != h->vinfo_epoch) h->predict_mfma.reset();      // other variables are observed
+        if (!h->predict_mfma) h->predict_mfma.reset(new prm::Plan());
         prm::Plan &L = *h->predict_mfma;
-        if ((rc = prm::refresh_tab(h, L)) != CX_OK) return rc;
-        if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
-        const int u = h->user_dim ? h->user_dim : h->cfg.dim;
-        const int64_t no = (int64_t)u + (int64_t)u * u + 2, nr = L.n_rows;
-        if (out && nr) {
-            // the payload a chunk at a time through a bounded device buffer; the (value, status) arrays cover every row
-            const int64_t chunk = std::min<int64_t>(nr, std::max<int64_t>(1, prm::kRowBufBytes / (no * 8)));
-            if ((rc = L.d_rows.ensure(h, chunk * no)) != CX_OK) return rc;
-            for (int64_t r0 = 0; r0 < nr; r0 += chunk) {
-                const int64_t m = std::min(chunk, nr - r0);
-                prm::launch_rows(h, L, r0, m, L.d_rows.get());
-                CX_HIP(h, hipGetLastError());
-                CX_HIP(h, hipMemcpyAsync(out + r0 * no, L.d_rows, (size_t)(m * no) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            }
-        } else {
-            prm::launch_rows(h, L, 0, nr, nullptr);
+        if (!L.key.matches(mode, n, factor_ids)) {
+            L.key.valid = false;
+            mfr::Pairs P;
+            if ((rc = mfr::checked_pairs(h, who, P)) != CX_OK) return rc;
+            std::vector<int64_t> fac;
+            if ((rc = prm::list_rows(h, P, who, n, factor_ids, fac)) != CX_OK) return rc;
+            if ((rc = prm::build_plan(h, P, L, mode, fac, who)) != CX_OK) return rc;
+            L.key.remember(mode, n, factor_ids);
+            L.vinfo_epoch = h->vinfo_epoch;
         }
-        if (nr) hipLaunchKernelGGL(prm::k_prm_part, dim3((unsigned)L.nb), dim3(prm::kTB), 0, h->stream, (int)nr, L.d_rval, L.d_rflag, L.d_part);
-        cx::ev::final_sum(h, nr ? L.nb : 0, L.d_part, L.d_out);
-        CX_HIP(h, hipGetLastError());
-        CX_HIP(h, hipMemcpyAsync(L.h_out.data(), L.d_out, (1 + cx::ev::kNCnt) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        CX_HIP(h, hipStreamSynchronize(h->stream));
-        uint64_t cnt[cx::ev::kNCnt];
-        std::memcpy(cnt, L.h_out.data() + 1, sizeof(cnt));
-        counts4[0] = nr;
-        for (int k = 1; k < 4; k++) counts4[k] = (int64_t)cnt[k - 1];
-        if (total) *total = L.h_out[0];
+        if ((rc = L.tab.refresh(h, [&](std::vector<double> &t) { prm::fill_tab(h, t); })) != CX_OK) return rc;
+        if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
+        const int u = mfr::user_dim(h);
+        const int64_t nr = L.n_rows;
+        // the payload a chunk at a time through a bounded device buffer; the (value, status) arrays cover every row
+        if (out) rc = mfr::stream_rows(h, nr, (int64_t)u + (int64_t)u * u + 2, L.d_rows, out, [&](int64_t r0, int64_t m, double *d) { prm::launch_rows(h, L, r0, m, d); });
+        else prm::launch_rows(h, L, 0, nr, nullptr);
+        if (rc != CX_OK) return rc;
+        double sum;
+        if ((rc = L.totals.read_rows(h, nr, L.d_rval, L.d_rflag, L.d_part, counts4, &sum)) != CX_OK) return rc;
+        if (total) *total = sum;
         return CX_OK;
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_predictive_mfma: host allocation failed"); }
 }
