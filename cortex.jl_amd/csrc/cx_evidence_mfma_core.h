@@ -1,6 +1,6 @@
 // cx_evidence_mfma_core.h — the wave kit of the readers of the stored messages at the matrix-core dims: cx_evidence_mfma.hip
 // (cx_log_evidence_mfma), cx_learn_mfma.hip (cx_factor_beliefs_mfma, cx_factor_statistics_mfma), cx_predict_mfma.hip (cx_predictive_mfma)
-// and cx_causal_mfma.hip (cx_causal_marginals_mfma).  Sums of message records into upper tiles, the scan for NaN records, the blocked
+// and cx_causal_mfma.hip (cx_causal_marginals_mfma); cx_sample_mfma.hip (cx_sample_posterior_mfma) factors and solves with it.  Sums of message records into upper tiles, the scan for NaN records, the blocked
 // Cholesky with its vector solve, the block-column solve U^-T X, the pass S = T ± Y'Y with h = Y'z, the identity on the padding diagonal,
 // the flat-pivot rule, the symmetric store through LDS, X'y, a datum in both vector layouts.  All on the helpers of cx_mv64w_core.h;
 // every helper is inlined into its caller and launches nothing.  The compiler fences (the empty asm that keeps one block column or one

@@ -119,6 +119,7 @@ namespace pr { struct Plan; }
 namespace prm { struct Plan; }
 namespace cm { struct Plan; }
 namespace cmm { struct Plan; }
+namespace spm { struct Plan; }
 
 }  // namespace cx
 
@@ -268,6 +269,9 @@ struct DevState {
     // cx_causal_marginals_mfma (cx_causal_mfma.hip): the rows of the last (mode, lag > 0 or not, variable_ids) at the matrix-core dims, the
     // transition entries of the fixed-lag recursion and the call's scratch (the β buffers among it, allocated by the first call with a lag)
     std::unique_ptr<cmm::Plan, Deleter<cmm::Plan>> causal_mfma;
+    // cx_sample_posterior_mfma (cx_sample_mfma.hip): the forest plan of cx_sample_core.h with the link records of the matrix-core dims,
+    // the link workspace (2 KD² + KD doubles per free variable: it stays across a rebuild of the plan) and the call's scratch
+    std::unique_ptr<spm::Plan, Deleter<spm::Plan>> sample_mfma;
     // cx_causal_marginals (cx_causal.hip): the class of every slot and the transition list, with the call's scratch; the plan is due
     // again after whatever changes the graph or the observed flags (raised by: cx_derived.h)
     std::unique_ptr<cm::Plan, Deleter<cm::Plan>> causal;

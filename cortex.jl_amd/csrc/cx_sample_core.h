@@ -1,7 +1,8 @@
 // cx_sample_core.h — what cx_sample_posterior (cx_sample.hip) and cx_linear_moments (cx_functional.hip) share: the forest plan (heavy
 // paths by light depth, positions, tiles), the links of every position (k_sp_cond, k_sp_cond_kary), the status pass (k_sp_flag) and the
 // forward blocked scan (k_sp_compose, k_sp_walk).  One plan per handle (cx_handle::sample), whichever entry builds it first.  The
-// derivation is DESIGN.md §4g; the adjoint of the scan is §4i.
+// derivation is DESIGN.md §4g; the adjoint of the scan is §4i.  The forest part of the plan (build_forest) and the status pass also serve
+// cx_sample_posterior_mfma (cx_sample_mfma.hip, §4r), which has its own links and scan on the matrix cores.
 #pragma once
 #include "cx_evidence_core.h"
 #include "cx_tree_plan.h"
@@ -434,18 +435,37 @@ struct Depth {
 };
 
 // the plan's device side; a rebuild starts from a default-constructed one
-struct PlanDev {
-    DevBuf<int32_t> d_pos_var, d_var_pos, d_comp, d_cpos, d_cbeg, d_dslot;
-    DevBuf<int32_t> d_roots, d_klink, d_xoff, d_xvar;
-    DevBuf<int4> d_plink, d_top;
-    DevBuf<int2> d_rng;
-    DevBuf<double> d_link, d_xblk;
+// The forest part of a plan — rooting, heavy paths by light depth, positions, tile levels, components and their chunks of the status
+// pass, the slot of every datum — never looks at the dim or at the kind of a factor: cx_sample_posterior / cx_linear_moments (the plan
+// below) and cx_sample_posterior_mfma (cx_sample_mfma.hip) build it with build_forest and keep it in these three parts
+struct ForestDims {
+    int64_t npos = 0, n_comp = 0, n_root = 0, n_chunk = 0;
+    std::vector<Depth> depths;
+    std::vector<int64_t> level_cap;           // per level (index 1 ..): the most items any depth has there
+};
+// the host side: the variable tree (parent variable, parent factor and component of every free variable; order: parents before
+// children) and what goes to the device
+struct Forest {
+    std::vector<int32_t> order, vpar, vfac, vcomp, pos_var, var_pos, roots, pcomp, cpos, cbeg, ccb, dslot;
+    std::vector<int4> top;
+    std::vector<int2> rngs;
+};
+struct ForestDev {
+    DevBuf<int32_t> d_pos_var, d_var_pos, d_comp, d_cpos, d_cbeg, d_dslot, d_roots;
     DevBuf<int32_t> d_ccb;                    // per component: its chunks of the status pass
+    DevBuf<int4> d_top;
+    DevBuf<int2> d_rng;
+    DevBuf<uint8_t> d_st, d_cflag, d_cpart;
+};
+
+struct PlanDev : ForestDev {
+    DevBuf<int32_t> d_klink, d_xoff, d_xvar;
+    DevBuf<int4> d_plink;
+    DevBuf<double> d_link, d_xblk;
     // the scan run leaf-to-root (cx_functional.hip): per position the heads of the light paths that hang on it (d_att_off, d_att_head)
     // and the extra blocks that read its ε, as (position of the earlier sibling, entry of d_xblk) (d_xt_off, d_xt_ent)
     DevBuf<int32_t> d_att_off, d_att_head, d_xt_off;
     DevBuf<int2> d_xt_ent;
-    DevBuf<uint8_t> d_st, d_cflag, d_cpart;
     // per call, grown on demand: z, the level buffers, the caller's noise, the requested variables, the output
     DevBuf<double> d_Z, d_noise, d_out;
     std::vector<DevBuf<double>> d_Gc, d_oc, d_carry;      // per level
@@ -459,19 +479,18 @@ struct PlanDev {
     DevBuf<double2> d_fcpart;
 };
 
-struct Plan : PlanDev {
+struct Plan : PlanDev, ForestDims {
     bool valid = false;
     int64_t nv = -1, ne = -1;
     std::vector<uint8_t> vinfo;               // what the plan was built for (the observed flags)
-    int64_t npos = 0, n_comp = 0, n_root = 0, n_plink = 0, n_klink = 0, n_xent = 0, n_chunk = 0;
-    std::vector<Depth> depths;
-    std::vector<int64_t> level_cap;           // per level (index 1 ..): the most items any depth has there
+    int64_t n_plink = 0, n_klink = 0, n_xent = 0;
     std::vector<uint8_t> h_cflag;
 };
 
-inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string &who) {
+// the forest of the free variables of h, cut into tiles of `tile` items: P's dims and F
+inline int32_t build_forest(cx_handle *h, ForestDims &P, Forest &F, const std::string &who, const int tile = kTile) {
     using namespace cxh;
-    const int64_t nv = h->nv, nf = h->nf;
+    const int64_t nv = h->nv;
     treeplan::Rooted R;
     std::string err;
     int32_t rc = treeplan::root_forest(h, R, err, true);
@@ -488,9 +507,9 @@ inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::
                                                "): no sampler is defined on a loopy graph");
     }
     auto is_free = [&](int32_t v) { return !(h->vinfo[v] & (kClamped | kGhost)); };
-    // (E.pair, E.krec: the pair rows (out slot, in slot, out var, in var) and k-ary rows (slots | vars) of cx_evidence.hip, on the host)
     // the variable tree: parent variable and parent factor of every free variable (members: parents before children)
-    std::vector<int32_t> vpar((size_t)nv, -1), vfac((size_t)nv, -1), vcomp((size_t)nv, -1), order;
+    std::vector<int32_t> &vpar = F.vpar, &vfac = F.vfac, &vcomp = F.vcomp, &order = F.order;
+    vpar.assign((size_t)nv, -1); vfac.assign((size_t)nv, -1); vcomp.assign((size_t)nv, -1); order.clear();
     int32_t comp = -1;
     for (int32_t n : R.members) {
         if (n >= nv) continue;
@@ -521,9 +540,10 @@ inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::
         for (int32_t v : order) if (vpar[v] >= 0) kid[at[vpar[v]]++] = v;
     }
     // paths by light depth: heads of depth l + 1 are the light children of the variables on the paths of depth l
-    std::vector<int32_t> pos_var, var_pos((size_t)nv, -1), roots;
-    std::vector<int4> top;
-    std::vector<int2> rngs;
+    std::vector<int32_t> &pos_var = F.pos_var, &var_pos = F.var_pos, &roots = F.roots;
+    std::vector<int4> &top = F.top;
+    std::vector<int2> &rngs = F.rngs;
+    pos_var.clear(); var_pos.assign((size_t)nv, -1); roots.clear(); top.clear(); rngs.clear();
     P.depths.clear();
     P.level_cap.assign(1, 0);
     std::vector<int32_t> heads;
@@ -544,16 +564,16 @@ inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::
             ppar.push_back(vpar[hd] < 0 ? -1 : var_pos[vpar[hd]]);
             if (vpar[hd] < 0) roots.push_back(b);
         }
-        // tile levels until every path has at most kTile items
+        // tile levels until every path has at most `tile` items
         int64_t longest = 0;
         for (const int2 &r : pr) longest = std::max<int64_t>(longest, r.y - r.x);
-        while (longest > kTile) {
+        while (longest > tile) {
             std::vector<int2> up;
             const int64_t off = (int64_t)rngs.size();
             longest = 0;
             for (int2 &r : pr) {
                 const int32_t b = (int32_t)up.size();
-                for (int32_t a = r.x; a < r.y; a += kTile) { rngs.push_back(make_int2(a, std::min<int32_t>(a + kTile, r.y))); up.push_back(rngs.back()); }
+                for (int32_t a = r.x; a < r.y; a += tile) { rngs.push_back(make_int2(a, std::min<int32_t>(a + tile, r.y))); up.push_back(rngs.back()); }
                 r = make_int2(b, (int32_t)up.size());
                 longest = std::max<int64_t>(longest, r.y - r.x);
             }
@@ -576,7 +596,60 @@ inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::
     for (int64_t v = 0; v < nv; v++)      // (every variable is on an edge, so root_forest places every free one: the gather relies on it)
         if (is_free((int32_t)v) && var_pos[v] < 0) return fail(h, CX_ERR_STATE, who + ": variable " + std::to_string(h->var_ids[v]) + " is on no factor");
     P.n_root = (int64_t)roots.size();
+    // components: their positions, contiguous, in chunks of at most kFlagChunk
+    std::vector<int32_t> coff((size_t)P.n_comp + 1, 0), &cpos = F.cpos, &pcomp = F.pcomp, &cbeg = F.cbeg, &ccb = F.ccb;
+    cpos.assign((size_t)P.npos, 0); pcomp.assign((size_t)P.npos, 0); cbeg.clear(); ccb.clear();
+    for (int64_t q = 0; q < P.npos; q++) { pcomp[q] = vcomp[pos_var[q]]; coff[pcomp[q] + 1]++; }
+    for (int64_t c = 0; c < P.n_comp; c++) coff[c + 1] += coff[c];
+    {
+        std::vector<int32_t> at(coff.begin(), coff.end() - 1);
+        for (int64_t q = 0; q < P.npos; q++) cpos[at[pcomp[q]]++] = (int32_t)q;
+    }
+    for (int64_t c = 0; c < P.n_comp; c++) {
+        ccb.push_back((int32_t)cbeg.size());
+        for (int32_t a = coff[c]; a < coff[c + 1]; a += kFlagChunk) cbeg.push_back(a);
+    }
+    ccb.push_back((int32_t)cbeg.size());
+    P.n_chunk = (int64_t)cbeg.size();
+    cbeg.push_back((int32_t)P.npos);
+    // a slot of every observed variable (its datum)
+    F.dslot.assign((size_t)nv, 0);
+    std::vector<int32_t> &dslot = F.dslot;
+    for (int64_t v = 0; v < nv; v++) if (h->var_off[v + 1] > h->var_off[v]) dslot[v] = slot_of_edge(h, h->var_off[v]);
+    return CX_OK;
+}
+
+// the forest's device side (the status bytes and flags with it)
+inline int32_t upload_forest(cx_handle *h, ForestDev &P, const ForestDims &D, const Forest &F) {
+    using namespace cxh;
+    int32_t rc;
+    if ((rc = dev_upload(h, &P.d_pos_var, F.pos_var)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_var_pos, F.var_pos)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_comp, F.pcomp)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_cpos, F.cpos)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_cbeg, F.cbeg)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_ccb, F.ccb)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &P.d_cpart, D.n_chunk)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_dslot, F.dslot)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_roots, F.roots)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_top, F.top)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_rng, F.rngs)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &P.d_st, D.npos)) != CX_OK) return rc;
+    return dev_alloc(h, &P.d_cflag, D.n_comp);
+}
+
+inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::string &who) {
+    using namespace cxh;
+    const int64_t nv = h->nv, nf = h->nf;
+    Forest F;
+    int32_t rc = build_forest(h, P, F, who);
+    if (rc != CX_OK) return rc;
+    const std::vector<int32_t> &order = F.order, &vpar = F.vpar, &vfac = F.vfac, &pos_var = F.pos_var, &var_pos = F.var_pos;
+    const std::vector<int4> &top = F.top;
+    const std::vector<int2> &rngs = F.rngs;
+    auto is_free = [&](int32_t v) { return !(h->vinfo[v] & (kClamped | kGhost)); };
     // links: two-variable factors and factors of 3 .. 7 variables (their children's extra noise blocks)
+    // (E.pair, E.krec: the pair rows (out slot, in slot, out var, in var) and k-ary rows (slots | vars) of cx_evidence.hip, on the host)
     std::vector<int4> plink;
     std::vector<int32_t> klink, xcnt((size_t)P.npos, 0);
     std::vector<std::pair<int32_t, int32_t>> kfac;       // (factor, parent variable) of every k-ary link factor
@@ -644,39 +717,11 @@ inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::
         for (int64_t q = 0; q < P.npos; q++)
             for (int32_t x = xoff[q]; x < xoff[q + 1]; x++) xt_ent[(size_t)xt[var_pos[xvar[x]]]++] = make_int2((int32_t)q, x);
     }
-    // components: their positions, contiguous, in chunks of at most kFlagChunk
-    std::vector<int32_t> coff((size_t)P.n_comp + 1, 0), cpos((size_t)P.npos), pcomp((size_t)P.npos), cbeg, ccb;
-    for (int64_t q = 0; q < P.npos; q++) { pcomp[q] = vcomp[pos_var[q]]; coff[pcomp[q] + 1]++; }
-    for (int64_t c = 0; c < P.n_comp; c++) coff[c + 1] += coff[c];
-    {
-        std::vector<int32_t> at(coff.begin(), coff.end() - 1);
-        for (int64_t q = 0; q < P.npos; q++) cpos[at[pcomp[q]]++] = (int32_t)q;
-    }
-    for (int64_t c = 0; c < P.n_comp; c++) {
-        ccb.push_back((int32_t)cbeg.size());
-        for (int32_t a = coff[c]; a < coff[c + 1]; a += kFlagChunk) cbeg.push_back(a);
-    }
-    ccb.push_back((int32_t)cbeg.size());
-    P.n_chunk = (int64_t)cbeg.size();
-    cbeg.push_back((int32_t)P.npos);
-    // a slot of every observed variable (its datum)
-    std::vector<int32_t> dslot((size_t)nv, 0);
-    for (int64_t v = 0; v < nv; v++) if (h->var_off[v + 1] > h->var_off[v]) dslot[v] = slot_of_edge(h, h->var_off[v]);
     static_cast<PlanDev &>(P) = PlanDev();
     P.valid = false;
     const int d = h->cfg.dim, ln = 2 * d * d + d;
-    if ((rc = dev_upload(h, &P.d_pos_var, pos_var)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_var_pos, var_pos)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_comp, pcomp)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_cpos, cpos)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_cbeg, cbeg)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_ccb, ccb)) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &P.d_cpart, P.n_chunk)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_dslot, dslot)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_roots, roots)) != CX_OK) return rc;
+    if ((rc = upload_forest(h, P, P, F)) != CX_OK) return rc;
     if ((rc = dev_upload(h, &P.d_plink, plink)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_top, top)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &P.d_rng, rngs)) != CX_OK) return rc;
     if ((rc = dev_upload(h, &P.d_att_off, att_off)) != CX_OK) return rc;
     if (!att_head.empty() && (rc = dev_upload(h, &P.d_att_head, att_head)) != CX_OK) return rc;
     if (P.n_klink) {
@@ -688,8 +733,6 @@ inline int32_t build_plan(cx_handle *h, const ev::Cache &E, Plan &P, const std::
         if ((rc = dev_alloc(h, &P.d_xblk, std::max<int64_t>(P.n_xent, 1) * d * d)) != CX_OK) return rc;
     }
     if ((rc = dev_alloc(h, &P.d_link, std::max<int64_t>(P.npos, 1) * ln)) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &P.d_st, P.npos)) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &P.d_cflag, P.n_comp)) != CX_OK) return rc;
     const int levels = (int)P.level_cap.size() - 1;
     P.d_Gc.resize((size_t)levels + 1); P.d_oc.resize((size_t)levels + 1); P.d_carry.resize((size_t)levels + 1);
     for (int l = 1; l <= levels; l++)

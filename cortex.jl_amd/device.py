@@ -506,6 +506,18 @@ class DeviceGraph:
         Returns (samples [n_samples, n, d] for variable_ids — None: every variable in ascending id —, counts) with counts "free",
         "components", "undefined", "not_positive_definite".  noise: the standard normals [n_samples, n_variables, d] in ascending
         variable-id order (observed rows ignored) in place of the device's Philox4x32-10 draws; the result is then affine in noise."""
+        return self._sample_posterior(self.lib.cx_sample_posterior, n_samples, seed, variable_ids, noise)
+
+    def sample_posterior_mfma(self, n_samples, seed=0, variable_ids=None, noise=None):
+        """cx_sample_posterior_mfma: sample_posterior at the matrix-core dims (a handle created with dim 5 .. 64) — the same arguments,
+        shapes, counts and NaN rule; d is the dim the handle was created with, whatever tile size it runs in (the padding of an
+        embedded dim gets no noise and never shows).  The links of the forest are computed once per call, one wave each on the f64
+        matrix cores (cortex_hip.h states the size of their workspace); the samples run in panels of 16 through a blocked scan.  A
+        component with no information at all (no observed neighbour, no opaque message) is NaN and counted "not_positive_definite".
+        sample_posterior itself keeps refusing these dims."""
+        return self._sample_posterior(self.lib.cx_sample_posterior_mfma, n_samples, seed, variable_ids, noise)
+
+    def _sample_posterior(self, call, n_samples, seed, variable_ids, noise):
         d = self.dim
         S = int(n_samples)
         if variable_ids is None:
@@ -521,9 +533,8 @@ class DeviceGraph:
                 raise ValueError(f"noise must be [{S}, {nv}, {d}]")
         out = np.zeros((max(S, 0), n, d), dtype=np.float64)
         cnt = (C.c_int64 * 4)()
-        self._check(self.lib.cx_sample_posterior(self.h, S, C.c_uint64(int(seed) & (2 ** 64 - 1)), None if eps is None else _p(eps, C.c_double),
-                                                 n if ids is not None else 0, None if ids is None else _p(ids, C.c_int64),
-                                                 _p(out, C.c_double) if S >= 1 else None, cnt))
+        self._check(call(self.h, S, C.c_uint64(int(seed) & (2 ** 64 - 1)), None if eps is None else _p(eps, C.c_double),
+                         n if ids is not None else 0, None if ids is None else _p(ids, C.c_int64), _p(out, C.c_double) if S >= 1 else None, cnt))
         return out, dict(zip(("free", "components", "undefined", "not_positive_definite"), [int(x) for x in cnt]))
 
     def linear_moments(self, functionals, cov=True):

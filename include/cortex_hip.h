@@ -950,6 +950,45 @@ int32_t cx_predictive_rows_mfma(cx_handle *h, int64_t cap, int64_t *factor_ids, 
  * CX_ERR_INVALID_ARGUMENT; an unknown id CX_ERR_NOT_FOUND.  Synchronous; moves no message, marginal, readiness bit or counter. */
 int32_t cx_causal_marginals_mfma(cx_handle *h, int32_t mode, int32_t lag, int64_t n, const int64_t *variable_ids, double *out, int64_t *counts4);
 
+/* ---- joint posterior samples at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
+ * cx_sample_posterior_mfma: cx_sample_posterior for a handle created with dim 5 .. 64 — the same arguments, output layout, counts4 and
+ * NaN rule (see "joint posterior samples" above), with d the CALLER's dim: out is a host array [n_samples][n][d] for variable_ids in the
+ * caller's order (NULL: every variable in ascending id; n ignored), an observed variable's rows hold its datum (one on no connection has
+ * no stored datum: NaN), counts4 = {free variables sampled, components, components with an undefined input, components not positive
+ * definite}; every row of a failed component is NaN and the other components are unaffected.
+ * noise != NULL: the caller's ε, a host array [n_samples][n_variables][d] in ascending variable-id order (rows of observed variables are
+ * ignored); the call is then a fixed affine map of ε.  noise == NULL: Philox4x32-10 with the counter and key of cx_sample_posterior:
+ * counter (j, v, s mod 2^32, s / 2^32), key (seed mod 2^32, seed / 2^32) yields components 2j and 2j + 1 of the variable of index v in
+ * sample s; for an odd d the second normal of the last pair is dropped.  A dim embedded in the next tile size (5 .. 15 in 16, 17 .. 31 in
+ * 32, 33 .. 63 in 64, or one forced by CX_MFMA_DIM) draws ε for the d real components only: the padding components get exactly zero
+ * noise, stay exactly zero and are not returned.  A draw depends only on (seed, sample index, variable, component) and on the handle's
+ * state: not on n_samples, on variable_ids or on how the call is chunked.  No atomics: two calls on one state are bit-identical.
+ * The draw is §4g's q(x) = b_r(x_r) Π_a b_a(x_C | x_p) on the forest of non-observed variables, rooted where the tree
+ * schedule's plan roots it.  Only two-variable CX_FACTOR_GAUSS_LINEAR factors and opaque messages exist at these dims.  For a link
+ * factor with child end C and parent end p, (P, B') the rule table towards p:  M = P + Σ (C's other stored messages) = U'U,
+ * x_C = M^-1 (B' x_p + Σ their η) + U^-1 ε_C;  the root: Λ_r = Σ all its stored messages = U'U, x_r = Λ_r^-1 η_r + U^-1 ε_r.  The
+ * recursion is uncentred.  It reads the stored factor→variable messages and the data, never the marginals; at a fixed point on a
+ * forest q is exactly p(x | data).  One wave per root and link computes the links on the f64 matrix cores, once per call; the samples
+ * run in panels of 16 through a blocked scan of the affine maps (tiles of 64 items; CX_SAMPLE_MFMA_TILE = 2 .. 64, read when the plan is
+ * built, sets another tile), in chunks of whole panels that keep the per-call scratch under 2^27 doubles (CX_SAMPLE_MFMA_CHUNK, a
+ * multiple of 16 read per call, sets the samples per chunk); the least chunk is one panel.
+ * A component is "not positive definite" when a pivot below d of a root's or a link's M is not positive and finite — and, decided on the
+ * host, when the component touches no observed variable and carries no opaque message: it has no information at all, its stored messages
+ * are roundings of differences, and it is not sampled (its rows are NaN, it counts under counts4[3]).  A component whose only
+ * information is an opaque message that is itself flat is outside this contract: what it returns is not defined.
+ * Device workspace: 2 KD² + KD doubles per non-observed variable for the links (G' | U^-T | off), KD the internal dim — 65,664 B at
+ * KD = 64: 6.6 GB at 1e5 states, 1.6 GB at KD = 32, 0.41 GB at KD = 16; allocated with the plan and kept, growing only, until the
+ * handle's graph goes, also across a change of the observed flags, which rebuilds the plan alone (a failed allocation is
+ * CX_ERR_OUT_OF_MEMORY).  The plan is cached and rebuilt when the graph or the observed flags change; rule tables, messages and data are
+ * read by every call.  cx_sample_posterior keeps returning CX_ERR_UNSUPPORTED at these dims exactly as before.
+ * Refused as cx_causal_marginals_mfma refuses, each text naming the function: other families, a handle created with dim 1 - 4 (use
+ * cx_sample_posterior), partitioned handles, a factor of another kind, a cycle among the non-observed variables (naming a variable of
+ * the component) CX_ERR_UNSUPPORTED; no graph, a captured stream, parameter sets never set CX_ERR_STATE; n_samples < 1, a NULL out or
+ * counts4, or n < 0 with ids CX_ERR_INVALID_ARGUMENT; an unknown id CX_ERR_NOT_FOUND.  Synchronous; moves no message, marginal,
+ * readiness bit or counter. */
+int32_t cx_sample_posterior_mfma(cx_handle *h, int64_t n_samples, uint64_t seed, const double *noise, int64_t n, const int64_t *variable_ids,
+                                 double *out, int64_t *counts4);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

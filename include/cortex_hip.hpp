@@ -278,6 +278,19 @@ class Handle {
                                   out.data(), o.data()));
         return {out, o};
     }
+    // the same at the matrix-core dims, 5 .. 64 (cx_sample_posterior_mfma): the links of the forest on the f64 matrix cores, the samples in
+    // panels of 16 through a blocked scan; dim is the caller's, the padding of an embedded dim never shows
+    std::pair<std::vector<double>, std::array<int64_t, 4>> sample_posterior_mfma(int64_t n_samples, uint64_t seed, const std::vector<int64_t> &variable_ids,
+                                                                                 const std::vector<double> *noise = nullptr) {
+        const int64_t nv = stats().n_variables, n = variable_ids.empty() ? nv : (int64_t)variable_ids.size();
+        if (noise) need(noise->size(), (size_t)(n_samples * nv * dim_), "sample_posterior_mfma noise");
+        std::vector<double> out((size_t)((n_samples > 0 ? n_samples : 0) * n * dim_) + 1);      // (+ 1: never a NULL out)
+        std::array<int64_t, 4> o{};
+        check(cx_sample_posterior_mfma(h_, n_samples, seed, noise ? noise->data() : nullptr, n, variable_ids.empty() ? nullptr : variable_ids.data(),
+                                       out.data(), o.data()));
+        out.resize(out.size() - 1);
+        return {out, o};
+    }
     // exact mean (K) and covariance (K x K, row-major; want_cov == false: empty) of K linear functionals of the joint posterior of a forest
     // (cx_linear_moments), in CSR form: functional k has the entries offsets[k] .. offsets[k + 1] - 1 of variable_ids and weights (dim per
     // entry).  counts: components, failed components, functionals made NaN, non-observed variables

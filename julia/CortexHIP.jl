@@ -488,6 +488,27 @@ function sample_posterior(p, n_samples::Integer; seed::Integer = 0, variable_ids
     return out, counts
 end
 
+# the same at the matrix-core dims (cx_create dim 5 - 64; cx_sample_posterior_mfma): the links of the forest on the f64 matrix cores, the
+# samples in panels of 16 through a blocked scan; d is the dim the handle was created with
+function sample_posterior_mfma(p, n_samples::Integer; seed::Integer = 0, variable_ids::Union{Nothing, Vector{Int64}} = nothing,
+                               noise::Union{Nothing, Array{Float64, 3}} = nothing)
+    d = p.dim
+    st = zeros(Int64, 9)                                                  # cx_stats: n_variables first
+    check(p.handle, ccall((:cx_graph_stats, lib), Int32, (Ptr{Cvoid}, Ptr{Int64}), p.handle, st))
+    n = variable_ids === nothing ? Int(st[1]) : length(variable_ids)
+    noise === nothing || size(noise) == (d, Int(st[1]), n_samples) ||
+        throw(ArgumentError("noise must be $d x $(st[1]) x $n_samples, got $(size(noise))"))
+    out = zeros(Float64, d, n, n_samples)
+    counts = zeros(Int64, 4)
+    ip = variable_ids === nothing ? Ptr{Int64}(C_NULL) : pointer(variable_ids)
+    np_ = noise === nothing ? Ptr{Float64}(C_NULL) : pointer(noise)
+    GC.@preserve variable_ids noise begin
+        check(p.handle, ccall((:cx_sample_posterior_mfma, lib), Int32, (Ptr{Cvoid}, Int64, UInt64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                              p.handle, n_samples, UInt64(seed), np_, variable_ids === nothing ? 0 : n, ip, out, counts))
+    end
+    return out, counts
+end
+
 # exact mean and covariance of K linear functionals of the joint posterior of a forest (ABI 9; dim 1 - 4), in CSR form with 0-based
 # offsets (length K + 1), variable ids (nnz) and a d x nnz weight matrix: (mean [K], cov [K x K] or nothing,
 # [components, failed, functionals made NaN, free])
