@@ -133,6 +133,7 @@ SIGNATURES = {
     "cx_chain_scan_stats": (_i32, [_vp, _pi64]),
     "cx_sweep_stats": (_i32, [_vp, _pi64]),
     "cx_sweep_deep_stats": (_i32, [_vp, _pi64]),
+    "cx_sweep_deep_launches": (_i32, [_vp, _pi64]),
     "cx_tree_plan_stats": (_i32, [_vp, _pi64]),
     "cx_tree_heavy_path_stats": (_i32, [_vp, _pi64]),
     "cx_set_marginals": (_i32, [_vp, _i64, _pi64, _i32, _pd]),

@@ -355,10 +355,12 @@ int32_t tree_sweep(cx_handle *h) {
     return CX_OK;
 }
 
-// ---- two sweeps per launch (cx_sweep_pair.hip), three or four in long calls (cx_sweep_deep.hip) ------------------------------------------
-// A call of at least kDeepMinSweeps sweeps runs its sweeps before the last at depth kDeepDefault (CX_SWEEP_DEPTH=2|3|4, read per call: a
+// ---- two sweeps per launch (cx_sweep_pair.hip), three to six in long calls (cx_sweep_deep.hip) ------------------------------------------
+// A call of at least kDeepMinSweeps sweeps runs its sweeps before the last at depth kDeepDefault (CX_SWEEP_DEPTH=2 .. 6, read per call: a
 // test runs every depth in one process).  Shorter calls decompose into pairs exactly as they did before there were deeper launches.
-constexpr int kDeepMax = 4, kDeepDefault = 4, kDeepMinSweeps = 16;
+constexpr int kDeepMax = 6, kDeepDefault = 5, kDeepMinSweeps = 16;
+static_assert(kDeepMax == cx::lattice::deep::kMaxDepth && sizeof(cx_handle::deep_rows) / sizeof(int32_t) == kDeepMax + 1 &&
+              sizeof(cx_handle::deep_launches) / sizeof(int64_t) == kDeepMax + 1, "deep_rows and deep_launches are indexed by depth");
 static int deep_depth_of_call(int32_t n_sweeps) {
     if (n_sweeps < kDeepMinSweeps) return 2;
     const char *e = std::getenv("CX_SWEEP_DEPTH");
@@ -571,6 +573,13 @@ int32_t cx_sweep_deep_stats(const cx_handle *h, int64_t *out4) {
     const int d = h->pair_H ? h->deep_depth : 0;
     out4[0] = h->deep_launches[3]; out4[1] = h->deep_launches[4]; out4[2] = d;
     out4[3] = d == 0 ? 0 : d == 2 ? h->pair_rows : h->deep_rows[d];
+    return CX_OK;
+}
+
+int32_t cx_sweep_deep_launches(const cx_handle *h, int64_t *out7) {
+    if (!h || !out7) return CX_ERR_INVALID_ARGUMENT;
+    out7[0] = 0; out7[1] = 0; out7[2] = h->pair_launches;
+    for (int d = 3; d <= kDeepMax; d++) out7[d] = h->deep_launches[d];
     return CX_OK;
 }
 

@@ -395,7 +395,7 @@ int32_t cxh_flat_lattice(const void *p, int32_t rows, int64_t *hw4, int32_t *des
 }
 
 // the deep sweep's geometry on the grid plan of the flattened graph (cx_lattice_deep.h) at depth K and `rows` rows per segment.  Returns the
-// number of (strip, segment) waves, 0 without a plan, -1 for a depth outside 2 .. 4 or rows < 1.  geom6 (may be NULL) = {owned columns per
+// number of (strip, segment) waves, 0 without a plan, -1 for a depth outside 2 .. 6 or rows < 1.  geom6 (may be NULL) = {owned columns per
 // wave, strips, workgroup columns, segments, the floor of choose_rows, kMaxRows}; count (may be NULL) = [nv] how many waves store for the
 // variable; rows_for_capacity as in cxh_flat_lattice, at depth K.  wave3 / level / owned (all three or none): per wave {strip, r0, r1} and, for
 // the window of rows r0 - K - 1 .. r0 + rows + K (rows + 2 K + 2 of them) by lanes -1 .. 64 (66), the highest level at which the cell is valid

@@ -164,10 +164,11 @@ struct DevState {
     // checked when due (raised by: cx_derived.h) and, while it does not hold, again once pair_check_at sweeps are done
     bool pair_check_due = true, pair_inputs_ok = false;
     int64_t pair_check_at = 0, pair_launches = 0;
-    // three or four sweeps per launch (cx_lattice_deep.h, cx_sweep_deep.hip), in calls of at least 16 sweeps: the rows per segment of each
-    // depth (chosen with pair_rows; 0: not yet), the launches that ran at each depth, the depth of the last call that could run them
-    int32_t deep_rows[5] = {0, 0, 0, 0, 0}, deep_depth = 0;
-    int64_t deep_launches[5] = {0, 0, 0, 0, 0};
+    // three to six sweeps per launch (cx_lattice_deep.h, cx_sweep_deep.hip), in calls of at least 16 sweeps: the rows per segment of each
+    // depth (indexed by depth, 3 .. 6; chosen with pair_rows; 0: not yet), the launches that ran at each depth, the depth of the last
+    // call that could run them
+    int32_t deep_rows[7] = {}, deep_depth = 0;      // (7 = kMaxDepth + 1: cx_api_sweep.hip asserts it)
+    int64_t deep_launches[7] = {};
 
     // factors with more than two edges (cx_kary.hip, CX_FACTOR_GAUSS_LINEAR_N): entry = 8 * row + edge position (OUT first, then IN by
     // ascending variable id); coefficient c_e = +1 (OUT) / -a_i (IN); their slots have partner -1 (no pairwise rule touches them)
@@ -500,7 +501,7 @@ void launch_residual(cx_handle *h, const double2 *cur, const double2 *prev, int6
 int64_t pair_capacity_blocks(const cx_handle *h);
 void launch_sweep_pair(cx_handle *h, const double2 *f2v_in, double2 *f2v_out);
 void launch_pair_check(cx_handle *h, const double2 *f2v, const double2 *alt, unsigned *d_flag);
-int64_t deep_capacity_blocks(const cx_handle *h, int depth);      // cx_sweep_deep.hip: depth 3 or 4
+int64_t deep_capacity_blocks(const cx_handle *h, int depth);      // cx_sweep_deep.hip: depth 3 .. 6 (cx_lattice_deep.h: kMaxDepth)
 void launch_sweep_deep(cx_handle *h, int depth, const double2 *f2v_in, double2 *f2v_out);
 void launch_chain_scan(cx_handle *h, double2 *f2v, bool fused_leaves, int marg_form, bool chain_v2f);
 void launch_chain_totals(cx_handle *h, double2 *f2v, bool fused_leaves, int64_t *ntiles_out);

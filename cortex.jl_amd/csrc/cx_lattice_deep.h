@@ -21,7 +21,7 @@ namespace cx {
 namespace lattice {
 namespace deep {
 
-constexpr int kMinDepth = 2, kMaxDepth = 4;
+constexpr int kMinDepth = 2, kMaxDepth = 6;
 
 CX_LAT_HD int strip_cols(int K) { return 64 - 2 * (K - 1); }
 CX_LAT_HD int lane_col(int strip, int lane, int K) { return strip * strip_cols(K) - (K - 1) + lane; }                             // (< 0 and >= W: outside)

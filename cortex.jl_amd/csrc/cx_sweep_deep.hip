@@ -1,4 +1,4 @@
-// cx_sweep_deep.hip — K = 3 or 4 fused sweeps per launch on a 4-neighbour grid: the pipeline of cx_sweep_pair.hip with K levels instead of two
+// cx_sweep_deep.hip — K = 3 .. 6 fused sweeps per launch on a 4-neighbour grid: the pipeline of cx_sweep_pair.hip with K levels instead of two
 // (the geometry: cx_lattice_deep.h).
 //
 // A wave owns 64 - 2 (K - 1) columns, with K - 1 halo lanes on each side, and streams down rows r0 - (K - 1) .. r1 + (K - 1) - 1 of its segment.
@@ -7,7 +7,7 @@
 // lane sideways (a whole-wave shift; kept for one iteration), the up input that level j - 1 of the row above sent down (kept for two) and the
 // down input that level j - 1 of the row below sends up in this very iteration.  What a row needs at every level — the unary message, the q
 // of its right and its lower factor, its first slot — is carried in registers from the one time it is loaded (K + 1 rows of them; loading
-// them again at level K was not tried: with them K = 4 still fits three waves per SIMD).  No LDS, no barrier, no atomics, no wait on another
+// them again at level K was not tried: with them K = 4 still fits three waves per SIMD, K = 5 and 6 two: profiles/deep_sweep_56.md).  No LDS, no barrier, no atomics, no wait on another
 // workgroup; every global access is a unit-stride run of 16 B per lane.
 //
 // The loop and its loads (profiles/deep_sweep_issue.md).  The loads of row i + 1 are issued at the top of the iteration of row i and are first
@@ -20,13 +20,18 @@
 // make that wait a vmcnt(4) and stay in flight over it; on the card that was not faster, three waves per SIMD cover the wait already:
 // profiles/deep_sweep_stores.md.)
 //
+// Depth and waves per SIMD (profiles/deep_sweep_56.md).  K = 3 and 4 fit three waves per SIMD, K = 5 and 6 two; the rows per segment are
+// chosen so that the launch is resident at once (choose_rows_packed), 12 at K = 4 and 19 at K = 5 on the flagship grid.  A deeper launch
+// moves fewer bytes per sweep for the same arithmetic per stored cell; the vector unit is busy 0.66 - 0.69 of the launch at every depth.
+//
 // Three instances per depth, chosen per wave (wave-uniformly; cx_lattice_deep.h: wave_class).  INTERIOR: a wave all of whose columns and rows
 // have four neighbours in the grid (strip_interior, segment_interior) runs the loop with every edge test folded to true.  COLUMN-EDGE: a
 // wave of an interior segment whose strip holds the grid's first or last column (both, on a grid narrower than a strip): every row it
 // touches at any level lies in 1 .. H - 2, so every row test is folded to true, and what depends on the lane — whether its column lies in
 // the grid and has a left and a right neighbour, the ranks of its loads, of qR / qD and of the four stores — is the same for every row and
 // is formed once in front of the loop; its loads are issued without a branch like the interior loop's, each direction from its own rank.
-// GENERAL: every other wave, the top and bottom segments.  921 / 891 / 1,144 instructions per row at K = 4 (profiles/deep_sweep_edges.md).
+// GENERAL: every other wave, the top and bottom segments.  950 / 914 / 1,164 instructions per row at K = 4, 1,170 / 1,120 / 1,404 at K = 5
+// (profiles/deep_sweep_edges.md, profiles/deep_sweep_56.md).
 // The arithmetic, its order, the point-mass branch of the rule and the test for an undefined message are the same in all three.
 //
 // Waves to workgroups (cx_lattice_deep.h: packed_wave).  Four adjacent strips of one segment make a workgroup.  Where the last workgroup
@@ -193,7 +198,16 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
     DeepRow nxt = zero_row(0);
     int raw_next = load_raw(i0);
     asm volatile("" : "+v"(raw_next));
+    // Priority that falls with progress: a wave starts at priority 3 and steps down one level at a quarter, a half and three quarters of
+    // its row loop.  A SIMD serves its oldest wave first, so its waves end one after the other and the youngest runs on alone; with the
+    // wave that is behind served first they end closer together (profiles/deep_sweep_56.md: 1 - 2 % at K = 4, nothing at K = 5 and 6)
+    const int quarter = (i1 - i0 + 2) >> 2;
+    const int p1 = i0 - 1 + quarter, p2 = p1 + quarter, p3 = p2 + quarter;
+    __builtin_amdgcn_s_setprio(3);
     for (int i = i0 - 1; i <= i1; i++) {
+        if (i == p1) __builtin_amdgcn_s_setprio(2);          // (uniform)
+        else if (i == p2) __builtin_amdgcn_s_setprio(1);
+        else if (i == p3) __builtin_amdgcn_s_setprio(0);
         const DeepRow cur = nxt;                             // the one wait for loads of the iteration: in front of the next row's loads
         const int base_next = finish_base(i + 1, raw_next);  // (the word came in behind row i's loads, one iteration ago)
         if (i < i1) nxt = load_row(i + 1, base_next);        // (uniform) in flight until the top of the next iteration: nothing below waits for a load
@@ -322,16 +336,30 @@ static int64_t deep_capacity(const cx_handle *h) {
     return (int64_t)per_cu * prop.multiProcessorCount;
 }
 
-// workgroups of k_sweep_deep<depth> the device holds at once
-int64_t deep_capacity_blocks(const cx_handle *h, int depth) { return depth == 3 ? deep_capacity<3>(h) : deep_capacity<4>(h); }
+// workgroups of k_sweep_deep<depth> the device holds at once, depth 3 .. 6: three waves per SIMD at depths 3 and 4, two at 5 and 6
+int64_t deep_capacity_blocks(const cx_handle *h, int depth) {
+    switch (depth) {
+    case 3: return deep_capacity<3>(h);
+    case 4: return deep_capacity<4>(h);
+    case 5: return deep_capacity<5>(h);
+    default: return deep_capacity<6>(h);
+    }
+}
+
+template <int K>
+static void deep_launch(cx_handle *h, dim3 grid, int R, int nseg, const double2 *f2v_in, double2 *f2v_out) {
+    hipLaunchKernelGGL(k_sweep_deep<K>, grid, dim3(kBlock), 0, h->stream, h->pair_H, h->pair_W, R, nseg, h->d_slice_off, h->d_q, f2v_in, f2v_out, h->pair_abort.dev);
+}
 
 void launch_sweep_deep(cx_handle *h, int depth, const double2 *f2v_in, double2 *f2v_out) {
     const int R = h->deep_rows[depth], nseg = (h->pair_H + R - 1) / R;
     const dim3 grid((unsigned)lattice::deep::packed_blocks(h->pair_W, nseg, depth));
-    if (depth == 3)
-        hipLaunchKernelGGL(k_sweep_deep<3>, grid, dim3(kBlock), 0, h->stream, h->pair_H, h->pair_W, R, nseg, h->d_slice_off, h->d_q, f2v_in, f2v_out, h->pair_abort.dev);
-    else
-        hipLaunchKernelGGL(k_sweep_deep<4>, grid, dim3(kBlock), 0, h->stream, h->pair_H, h->pair_W, R, nseg, h->d_slice_off, h->d_q, f2v_in, f2v_out, h->pair_abort.dev);
+    switch (depth) {
+    case 3: deep_launch<3>(h, grid, R, nseg, f2v_in, f2v_out); break;
+    case 4: deep_launch<4>(h, grid, R, nseg, f2v_in, f2v_out); break;
+    case 5: deep_launch<5>(h, grid, R, nseg, f2v_in, f2v_out); break;
+    default: deep_launch<6>(h, grid, R, nseg, f2v_in, f2v_out); break;
+    }
 }
 
 }  // namespace cx

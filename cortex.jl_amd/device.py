@@ -146,11 +146,17 @@ class DeviceGraph:
                 "paired_launches": int(out[3])}
 
     def sweep_deep_stats(self):
-        """cx_sweep_deep_stats: launches that ran three / four sweeps at once (cx_sweep_deep.hip), the depth of the last call that ran multi-sweep
+        """cx_sweep_deep_stats: launches that ran three / four sweeps at once (cx_sweep_deep.hip; every depth: sweep_deep_launches), the depth of the last call that ran multi-sweep
         launches and the rows per segment at that depth"""
         out = (C.c_int64 * 4)()
         self._check(self.lib.cx_sweep_deep_stats(self.h, out))
         return {"depth3_launches": int(out[0]), "depth4_launches": int(out[1]), "depth": int(out[2]), "rows": int(out[3])}
+
+    def sweep_deep_launches(self):
+        """cx_sweep_deep_launches: [d] = launches that ran d sweeps at once, d = 2 .. 6; [0] = [1] = 0"""
+        out = (C.c_int64 * 7)()
+        self._check(self.lib.cx_sweep_deep_launches(self.h, out))
+        return tuple(int(x) for x in out)
 
     def edge_index(self, variable_ids, factor_ids):
         v, f = _i64(np.atleast_1d(variable_ids)), _i64(np.atleast_1d(factor_ids))

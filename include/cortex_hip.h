@@ -373,11 +373,14 @@ int32_t cx_chain_scan_stats(const cx_handle *h, int64_t *out4);
  * calls so far that stored no marginals (every sweep of a call but the last), [3] launches so far that ran two sweeps at once (grids:
  * floor((n - 1) / 2) per cx_sweep(h, n) call; CX_SWEEP_PAIRS=0 in the environment turns them off) */
 int32_t cx_sweep_stats(const cx_handle *h, int64_t *out4);
-/* ... and of its deep launches (additive; tests): in a cx_sweep call of at least 16 sweeps the sweeps before the last run three or four to
- * a launch (CX_SWEEP_DEPTH=2|3|4 forces the depth, CX_DEEP_ROWS the rows per segment; CX_SWEEP_PAIRS=0 turns every multi-sweep launch
+/* ... and of its deep launches (additive; tests): in a cx_sweep call of at least 16 sweeps the sweeps before the last run three to six to
+ * a launch (CX_SWEEP_DEPTH=2 .. 6 forces the depth, CX_DEEP_ROWS the rows per segment; CX_SWEEP_PAIRS=0 turns every multi-sweep launch
  * off).  out4 = { launches so far at depth 3, at depth 4, the depth of the last call that ran multi-sweep launches (2 in a call of fewer
  * than 16 sweeps; 0: none yet, or no grid plan), the rows per segment at that depth }.  cx_sweep_stats' [3] keeps counting depth 2 only. */
 int32_t cx_sweep_deep_stats(const cx_handle *h, int64_t *out4);
+/* ... by depth (additive; tests): out7[d] = launches so far that ran d sweeps at once, d = 2 .. 6 (CX_SWEEP_DEPTH=2 .. 6; [2] is
+ * cx_sweep_stats' [3]); out7[0] = out7[1] = 0 */
+int32_t cx_sweep_deep_launches(const cx_handle *h, int64_t *out7);
 /* the XCD-resident cluster (reference-order plans of many dependent stages of 1 - 16 k items — calls on loopy graphs — run as ONE launch
  * of the workgroups of one XCD behind barriers that stay in that XCD's L2): out4 = { 1 ready / 0 not prepared / -1 off
  * (CX_REF_CLUSTER=0, a device that is neither gfx942 nor gfx950, or a barrier once timed out), workgroups per launch (compute units),

@@ -1,4 +1,4 @@
-"""lab: two, three and four sweeps per launch (cx_sweep_pair.hip, cx_sweep_deep.hip) on one grid, regions of every form alternating in one
+"""lab: two to six sweeps per launch (cx_sweep_pair.hip, cx_sweep_deep.hip) on one grid, regions of every form alternating in one
 process, and every form's results compared bit for bit with a handle that swept the same number of sweeps under CX_SWEEP_PAIRS=0.
 The levers are environment variables: CX_SWEEP_DEPTH (read per call), CX_DEEP_ROWS / CX_PAIR_ROWS (rows per segment, read when the handle's
 geometry is chosen: one handle per setting).
@@ -61,5 +61,5 @@ for (depth, rows), dev, t in zip(FORMS, devs, times):
     same_msg = np.array_equal(dev.get_messages(model.edge_var[sample], model.edge_fac[sample], L.TO_VARIABLE, L.FORM_NATURAL), want_msg, equal_nan=True)
     st = dev.sweep_deep_stats()
     print(f"depth {depth}, rows per segment {st['rows']}{'' if rows else ' (by occupancy)'}: {sorted(t)[len(t) // 2]:.2f} us per sweep ({min(t):.2f} - {max(t):.2f}); "
-          f"launches of 2 / 3 / 4 sweeps {dev.sweep_stats()['paired_launches']} / {st['depth3_launches']} / {st['depth4_launches']}; "
+          f"launches of 2 / 3 / 4 / 5 / 6 sweeps {' / '.join(str(x) for x in dev.sweep_deep_launches()[2:])}; "
           f"marginals identical: {same}, sampled messages identical: {same_msg}", flush=True)
