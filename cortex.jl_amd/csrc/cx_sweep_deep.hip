@@ -22,7 +22,8 @@
 //
 // Depth and waves per SIMD (profiles/deep_sweep_56.md).  K = 3 and 4 fit three waves per SIMD, K = 5 and 6 two; the rows per segment are
 // chosen so that the launch is resident at once (choose_rows_packed), 12 at K = 4 and 19 at K = 5 on the flagship grid.  A deeper launch
-// moves fewer bytes per sweep for the same arithmetic per stored cell; the vector unit is busy 0.66 - 0.69 of the launch at every depth.
+// moves fewer bytes per sweep for the same arithmetic per stored cell; the vector unit is busy 0.74 - 0.80 of the launch (0.66 - 0.71 while
+// every rule held a branch: profiles/deep_sweep_div.md).
 //
 // Three instances per depth, chosen per wave (wave-uniformly; cx_lattice_deep.h: wave_class).  INTERIOR: a wave all of whose columns and rows
 // have four neighbours in the grid (strip_interior, segment_interior) runs the loop with every edge test folded to true.  COLUMN-EDGE: a
@@ -30,9 +31,10 @@
 // touches at any level lies in 1 .. H - 2, so every row test is folded to true, and what depends on the lane — whether its column lies in
 // the grid and has a left and a right neighbour, the ranks of its loads, of qR / qD and of the four stores — is the same for every row and
 // is formed once in front of the loop; its loads are issued without a branch like the interior loop's, each direction from its own rank.
-// GENERAL: every other wave, the top and bottom segments.  950 / 914 / 1,164 instructions per row at K = 4, 1,170 / 1,120 / 1,404 at K = 5
-// (profiles/deep_sweep_edges.md, profiles/deep_sweep_56.md).
-// The arithmetic, its order, the point-mass branch of the rule and the test for an undefined message are the same in all three.
+// GENERAL: every other wave, the top and bottom segments.  757 / 721 / 929 instructions per row at K = 4, 921 / 874 / 1,114 at K = 5, with
+// 16 and 20 v_rcp_f64 (profiles/deep_sweep_div.md; with a division in each branch of the rule 950 / 914 / 1,164 and 1,170 / 1,120 / 1,404
+// stood in the listing, of which a wave without point masses skipped some 50 per level: profiles/deep_sweep_edges.md, deep_sweep_56.md).
+// The arithmetic, its order, the rule at a point mass and the test for an undefined message are the same in all three.
 //
 // Waves to workgroups (cx_lattice_deep.h: packed_wave).  Four adjacent strips of one segment make a workgroup.  Where the last workgroup
 // column has s < 4 strips, a workgroup takes floor(4 / s) consecutive segments of it instead, so that no wave slot of a resident workgroup
@@ -40,9 +42,21 @@
 // segment instead of 13 (choose_rows_packed; profiles/deep_sweep_stores.md).  Which wave runs which (strip, segment) changes no stored bit.
 //
 // Bit-identity with K plain sweeps.  Every level is the pair kernel's: the same leave_one_out over the fixed order unary, left, right, up,
-// down with +0 for an absent direction, the same factor_rule<kRuleAdditive>(., q, 1.0, 0.0), q of a factor read at one of its two slots.
+// down with +0 for an absent direction, the bits of factor_rule<kRuleAdditive>(., q, 1.0, 0.0), q of a factor read at one of its two slots.
 // The argument in the header of cx_sweep_pair.hip therefore holds level by level, at the cells valid at that level (cx_lattice_deep.h);
 // the others hold garbage, which reaches no valid cell, is not tested for an undefined message and is not stored.
+// The rule is written here with ONE division (deep_rule).  factor_rule has two branches, 1 / q at a point mass (m.y == +inf) and
+// 1 / (1 + q m.y) otherwise, an IEEE division in each (v_rcp_f64 and about ten f64 instructions).  The compiler kept the point-mass branch
+// as a block behind s_and_saveexec / s_cbranch_execz: a wave without point masses skipped its body but paid 40 mask-and-branch pairs per
+// row at K = 5, and the block boundaries kept the four division chains of a level from being interleaved; without them the launch takes
+// 0.895 of its busy cycles at K = 5 for as many executed instructions (profiles/deep_sweep_div.md).  With s = 1 / den the branches differ only in den and in one factor of o.y: at a point mass
+// den = q, o.y = s, o.x = m.x s, which is factor_rule's 1 / q and m.x (1 / q); otherwise den, o.y = m.y s and o.x = m.x s are factor_rule's
+// own expressions, and 1 + q m.y is contracted into one fused multiply-add or not as it is there (the same source expression, the same
+// compiler; the bit-for-bit tests against plain sweeps would show a difference).  NaN and -inf compare unequal to +inf and take the
+// ordinary branch, as they do there.  deep_rule selects the operands instead of the results (den = a + q t with (a, t) = (-0, 1) at a point
+// mass, (1, m.y) otherwise; q 1 + -0 is q for every q, -0 included), which costs three instructions per rule where selecting den and o.y
+// costs four.  tests/test_deep_rule_host.py holds both forms for the host: the same bits on 1e6 random and special inputs;
+// tests/test_gpu_sweep_deep_rule.py reaches the point-mass branch on the card.  profiles/deep_sweep_div.md.
 //
 // Undefined messages: as in the pair kernel.  Every level tests the variable→factor messages of its valid cells and raises the same word.
 
@@ -85,6 +99,18 @@ __device__ __forceinline__ void deep_leave_one_out(const double2 (&in)[5], doubl
     for (int k = 4; k >= 0; k--) { out[k] = add2(out[k], acc); acc = add2(acc, in[k]); }
 }
 
+// factor_rule<kRuleAdditive>(m, q, 1.0, 0.0) with one division and no branch, the same bits (the header: bit-identity).  The rule has two
+// branches, 1 / q at a point mass (m.y == +inf) and 1 / (1 + q m.y) otherwise, which the compiler kept as branches on the exec mask.  Here
+// the branches differ in t, which is 1 at a point mass and m.y otherwise, and in the addend a, -0 or 1: the denominator a + q t is q
+// exactly at a point mass (q 1 is q, and q + -0 is q, a q of -0 included) and the rule's own expression otherwise, contracted or not as
+// the rule's is; o.y = t s is s exactly resp. m.y s.  +inf and 1.0 have the same low word, so t is m.y with one select on its high word
+__device__ __forceinline__ double2 deep_rule(double2 m, double q) {
+    const bool pm = m.y == __builtin_inf();
+    const double t = __hiloint2double(pm ? 0x3ff00000 : __double2hiint(m.y), __double2loint(m.y));
+    const double s = 1.0 / ((pm ? -0.0 : 1.0) + q * t);
+    return make_double2(m.x * s, t * s);
+}
+
 struct DeepRow {          // one grid row as loaded: the five ranks (a column-edge wave: by direction), the q of the right and the lower factor, the lane's first slot
     double2 x[5];
     double qR, qD;
@@ -101,13 +127,13 @@ struct DeepPending {      // the inputs of a level that wait for their row's tur
 // receiver's own (one q per factor), up through the factor above (q came with the row above), down through the row's lower factor
 __device__ __forceinline__ DeepOut deep_emit(const double2 (&o)[5], bool hasL, bool hasR, double qR, double qU, double qD) {
     DeepOut e;
-    const double2 to_right = factor_rule<kRuleAdditive>(o[2], qR, 1.0, 0.0);
+    const double2 to_right = deep_rule(o[2], qR);
     const double2 from_left = dshfl_up2(to_right);
-    const double2 from_right = factor_rule<kRuleAdditive>(dshfl_down2(o[1]), qR, 1.0, 0.0);
+    const double2 from_right = deep_rule(dshfl_down2(o[1]), qR);
     e.L = dsel2(hasL, from_left, zero2());
     e.R = dsel2(hasR, from_right, zero2());
-    e.up = factor_rule<kRuleAdditive>(o[3], qU, 1.0, 0.0);
-    e.down = factor_rule<kRuleAdditive>(o[4], qD, 1.0, 0.0);
+    e.up = deep_rule(o[3], qU);
+    e.down = deep_rule(o[4], qD);
     return e;
 }
 
@@ -121,8 +147,8 @@ __device__ __forceinline__ bool deep_undefined(const double2 (&o)[5], bool hasL,
 // row touched, resp. every lane's column, lies inside the grid with both neighbours in that direction, so the edge tests of that direction
 // below are the constant true and the selects on them compile to nothing.  With both every cell has degree 5 and the ranks are constants.
 // With ROWS alone (a column-edge wave) nothing that is tested depends on the row: colv, hasL, hasR and the rank offsets of the loads and
-// the stores are per-lane constants of the whole loop, formed once in front of it.  The point-mass branch of factor_rule and
-// the test for an undefined message stay in every instance.
+// the stores are per-lane constants of the whole loop, formed once in front of it.  The rule's point mass (deep_rule: selected
+// operands, no branch) and the test for an undefined message stay in every instance.
 template <int K, bool ROWS, bool COLS>
 __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int W, const int32_t *__restrict__ slice_off, const double *__restrict__ q,
                                           const double2 *__restrict__ f2v_in, double2 *__restrict__ f2v_out, unsigned *__restrict__ abort_word) {
@@ -251,10 +277,10 @@ __device__ __forceinline__ void deep_wave(int strip, int r0, int r1, int H, int 
                 if (dp::lane_valid_at_level(lane, COLS ? 0 : c, COLS ? 1 : W, j)) bad = bad || deep_undefined(o, hasL, hasR, mU, mD);
                 if (j < K) f = deep_emit(o, hasL, hasR, qR[j - 1], qD[j], qD[j - 1]);
                 else if (own) {                              // level K of an owned row (row_valid_at_level at j = K: r0 <= m < r1): stored
-                    if (hasL) f2v_out[baseL + offRofL] = factor_rule<kRuleAdditive>(o[1], qL, 1.0, 0.0);
-                    if (hasR) f2v_out[baseR + lattice::rank_left() * kBlock] = factor_rule<kRuleAdditive>(o[2], qR[K - 1], 1.0, 0.0);
-                    if (mU) f2v_out[base[K] + (ROWS ? offU + kBlock : lattice::rank_down(m - 1, c, W) * kBlock)] = factor_rule<kRuleAdditive>(o[3], qD[K], 1.0, 0.0);
-                    if (mD) f2v_out[base[K - 2] + offU] = factor_rule<kRuleAdditive>(o[4], qD[K - 1], 1.0, 0.0);
+                    if (hasL) f2v_out[baseL + offRofL] = deep_rule(o[1], qL);
+                    if (hasR) f2v_out[baseR + lattice::rank_left() * kBlock] = deep_rule(o[2], qR[K - 1]);
+                    if (mU) f2v_out[base[K] + (ROWS ? offU + kBlock : lattice::rank_down(m - 1, c, W) * kBlock)] = deep_rule(o[3], qD[K]);
+                    if (mD) f2v_out[base[K - 2] + offU] = deep_rule(o[4], qD[K - 1]);
                 }
             }
             // what level j - 1 produced in this iteration waits for its row's turn at level j
