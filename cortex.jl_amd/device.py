@@ -549,6 +549,18 @@ class DeviceGraph:
         triple (offsets [K + 1], variable_ids [nnz], weights [nnz, d]).  Returns (mean [K], cov [K, K] or None, counts) with counts
         "components", "failed", "nan_functionals", "free"; a functional that touches a failed component is NaN (its row and column of
         cov too).  cov=False: the means only."""
+        return self._linear_moments(self.lib.cx_linear_moments, functionals, cov)
+
+    def linear_moments_mfma(self, functionals, cov=True):
+        """cx_linear_moments_mfma: linear_moments at the matrix-core dims (a handle created with dim 5 .. 64) — the same arguments,
+        shapes, counts and NaN rule; d is the dim the handle was created with, whatever tile size it runs in.  The distribution is the
+        one sample_posterior_mfma draws from: mean = W x⁰ and cov = W B Bᵀ Wᵀ of its affine map x = x⁰ + B ε, exact, with no
+        Monte-Carlo error and K² + K doubles to the host.  The call shares the sampler's plan and link workspace; functionals run in
+        panels of 16 on the f64 matrix cores.  A component with no information at all is failed.  linear_moments itself keeps refusing
+        these dims."""
+        return self._linear_moments(self.lib.cx_linear_moments_mfma, functionals, cov)
+
+    def _linear_moments(self, call, functionals, cov):
         d = self.dim
         if isinstance(functionals, tuple) and len(functionals) == 3 and not isinstance(functionals[0], tuple):
             off, ids, w = _i64(np.atleast_1d(functionals[0])), _i64(np.atleast_1d(functionals[1])), _f64(functionals[2])
@@ -568,9 +580,8 @@ class DeviceGraph:
         mean = np.zeros(K, dtype=np.float64)
         cv = np.zeros((K, K), dtype=np.float64) if cov else None
         cnt = (C.c_int64 * 4)()
-        self._check(self.lib.cx_linear_moments(self.h, K, _p(off, C.c_int64), _p(ids, C.c_int64) if len(ids) else None,
-                                               _p(w, C.c_double) if w.size else None, _p(mean, C.c_double) if K else None,
-                                               _p(cv, C.c_double) if cov and K else None, cnt))
+        self._check(call(self.h, K, _p(off, C.c_int64), _p(ids, C.c_int64) if len(ids) else None, _p(w, C.c_double) if w.size else None,
+                         _p(mean, C.c_double) if K else None, _p(cv, C.c_double) if cov and K else None, cnt))
         return mean, cv, dict(zip(("components", "failed", "nan_functionals", "free"), [int(x) for x in cnt]))
 
     def posterior_covariance(self, var_a, var_b):
@@ -586,6 +597,20 @@ class DeviceGraph:
         """Var(1'(x_a - x_b)) under the joint posterior of a forest (dim 1: the variance of x_a - x_b): one functional of linear_moments"""
         one = np.ones((1, self.dim))
         _, cv, _ = self.linear_moments([([var_a, var_b], np.concatenate([one, -one]))])
+        return float(cv[0, 0])
+
+    def posterior_covariance_mfma(self, var_a, var_b):
+        """posterior_covariance at the matrix-core dims: 2d unit functionals of linear_moments_mfma"""
+        d = self.dim
+        eye = np.eye(d)
+        fs = [([var_a], eye[i:i + 1]) for i in range(d)] + [([var_b], eye[i:i + 1]) for i in range(d)]
+        _, cv, _ = self.linear_moments_mfma(fs)
+        return cv[:d, d:].copy()
+
+    def contrast_variance_mfma(self, var_a, var_b):
+        """contrast_variance at the matrix-core dims: one functional of linear_moments_mfma"""
+        one = np.ones((1, self.dim))
+        _, cv, _ = self.linear_moments_mfma([([var_a, var_b], np.concatenate([one, -one]))])
         return float(cv[0, 0])
 
     # -- halo -----------------------------------------------------------------------------------

@@ -992,6 +992,36 @@ int32_t cx_causal_marginals_mfma(cx_handle *h, int32_t mode, int32_t lag, int64_
 int32_t cx_sample_posterior_mfma(cx_handle *h, int64_t n_samples, uint64_t seed, const double *noise, int64_t n, const int64_t *variable_ids,
                                  double *out, int64_t *counts4);
 
+/* ---- exact moments of linear functionals at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
+ * cx_linear_moments_mfma: cx_linear_moments for a handle created with dim 5 .. 64 — the same arguments (see "linear functionals"
+ * above), with d the CALLER's dim: the functionals in CSR form, weights [nnz][d]; a variable named twice in a functional counts with
+ * the sum of its weights (merged on the host, in the order given); an observed variable adds w'·datum to the mean and nothing to cov.
+ * mean is a host array [K]; cov is NULL (means only: the leaf-to-root scan is skipped) or a host array [K][K], one triangle computed
+ * and mirrored; counts4 = {components, failed components, functionals made NaN, non-observed variables}.
+ * The distribution is cx_sample_posterior_mfma's q(x) (above) on the forest of non-observed variables, rooted where that
+ * call roots it, read from the stored factor→variable messages and the data, never from the marginals.  With x = x⁰ + B ε the sampler's
+ * affine map: mean[k] = φ_k(x⁰) and cov = W B B' W'  — exact at a fixed point on a forest, elsewhere the moments of the q
+ * the sampler draws from.  The recursion is uncentred, like the sampler's: §4r's note on data far from the origin applies unchanged.
+ * A functional has a NaN mean and a NaN row and column of cov when it touches a failed component: one with a NaN input record, with a
+ * pivot below d of a root's or a link's M that is not positive and finite, or with no information at all (decided on the host, as for
+ * the sampler).  The other functionals are unaffected.
+ * No atomics; every sum runs in a fixed order that does not depend on K: two calls on one state are bit-identical, a functional alone
+ * gives the bits it gives among the others, and a call cut into chunks gives the bits of one chunk.
+ * The call shares the sampler's plan and link workspace (whichever runs first builds them; the size is stated above) and computes the
+ * links once per call.  Functionals run in panels of 16, in chunks of whole panels that keep the per-chunk scratch under 2^27 doubles
+ * (CX_FN_MFMA_CHUNK, a multiple of 16 read per call, sets the functionals per chunk); the least chunk is one panel.  With cov, the noise
+ * coordinates of all K functionals are kept ([non-observed variables][K in whole panels][KD] doubles): past 2^30 doubles, or block
+ * partials of the covariance past 2^28 pairs, the call returns CX_ERR_OUT_OF_MEMORY; cov == NULL has no such bound.
+ * CX_SAMPLE_MFMA_TILE and CX_MFMA_DIM act as for cx_sample_posterior_mfma.  cx_linear_moments keeps returning CX_ERR_UNSUPPORTED at
+ * these dims exactly as before.
+ * Refused as cx_sample_posterior_mfma refuses, each text starting with this function's name: other families, a handle created with dim
+ * 1 - 4 (use cx_linear_moments), partitioned handles, a factor of another kind, a cycle among the non-observed variables
+ * CX_ERR_UNSUPPORTED; no graph, a captured stream, parameter sets never set CX_ERR_STATE; n_functionals < 0 or above 32768, NULL offsets,
+ * mean or counts4, NULL ids or weights with entries, offsets that do not start at 0 or that decrease CX_ERR_INVALID_ARGUMENT; an unknown
+ * id CX_ERR_NOT_FOUND.  A refused call writes nothing.  Synchronous; moves no message, marginal, readiness bit or counter. */
+int32_t cx_linear_moments_mfma(cx_handle *h, int64_t n_functionals, const int64_t *offsets, const int64_t *variable_ids, const double *weights,
+                               double *mean, double *cov, int64_t *counts4);
+
 /* ---- checkpoint (the reference keeps no persistent state — src/ has no serialisation at all) ----
  * The mutable state of a handle (every message buffer, the marginals, the observed-variable flags, the sweep counter)
  * as one relocatable host blob.  A blob restores only into a handle created with the same dim / family / schedule and

@@ -307,6 +307,20 @@ class Handle {
                                 r.counts.data()));
         return r;
     }
+    // the same at the matrix-core dims (cx_linear_moments_mfma; a handle created with dim 5 .. 64): the moments of the distribution
+    // sample_posterior_mfma draws from, exact
+    LinearMoments linear_moments_mfma(const std::vector<int64_t> &offsets, const std::vector<int64_t> &variable_ids, const std::vector<double> &weights,
+                                      bool want_cov = true) {
+        need(offsets.empty() ? 0 : 1, 1, "linear_moments_mfma offsets");
+        const int64_t K = (int64_t)offsets.size() - 1;
+        need(weights.size(), variable_ids.size() * (size_t)dim_, "linear_moments_mfma weights");
+        LinearMoments r;
+        r.mean.resize((size_t)K);
+        if (want_cov) r.cov.resize((size_t)(K * K));
+        check(cx_linear_moments_mfma(h_, K, offsets.data(), variable_ids.data(), weights.data(), r.mean.data(), want_cov && K ? r.cov.data() : nullptr,
+                                     r.counts.data()));
+        return r;
+    }
     std::pair<int32_t, double> sweep_until(double tol, int32_t max_sweeps, int32_t check_every = 10) {
         int32_t n = 0; double r = 0;
         check(cx_sweep_until(h_, tol, max_sweeps, check_every, &n, &r));
