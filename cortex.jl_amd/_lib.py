@@ -86,6 +86,7 @@ SIGNATURES = {
     "cx_log_evidence": (_i32, [_vp, _pd, _pi64]),
     "cx_graph_components": (_i32, [_vp, _i64, _pi64, _pi64, _pi64]),
     "cx_log_evidence_components": (_i32, [_vp, _i64, _pd, _pi64, _pi64, _pi64]),
+    "cx_log_evidence_components_mfma": (_i32, [_vp, _i64, _pd, _pi64, _pi64, _pi64]),
     "cx_log_evidence_mfma": (_i32, [_vp, _pd, _pi64]),
     "cx_factor_beliefs": (_i32, [_vp, _i64, _pi64, _pd]),
     "cx_factor_statistics": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pd, _pi64]),

@@ -573,41 +573,89 @@ void launch(cx_handle *h, Cache &C) {
     final_sum(h, C.nb, part, C.d_out);
 }
 
+// ---- the per-component sum of a term array: shared with cx_log_evidence_components_mfma (cx_evidence_mfma.hip) ----------
+int32_t plan_components(cx_handle *h, CompPlan &P, int64_t n_comp, const std::vector<int32_t> &term_label, const std::string &who) {
+    using namespace cxh;
+    CX_REQUIRE(h, (int64_t)term_label.size() < (int64_t)0x3fffffff, CX_ERR_UNSUPPORTED, who + ": more than 2^30 terms");
+    std::vector<int32_t> perm, key, span;
+    std::vector<int64_t> beg, end;
+    P.n_comp = n_comp;
+    P.n_pos = comp::sort_terms(n_comp, term_label, kTile, kSI, perm, key, beg, end);
+    for (int64_t k = 0; k < n_comp; k++)
+        if (end[(size_t)k] - beg[(size_t)k] > kTile) span.push_back((int32_t)k);
+    P.n_tile = (P.n_pos + kTile - 1) / kTile; P.n_span = (int64_t)span.size();
+    P.h_cout.assign((size_t)(n_comp * (1 + kNCnt)), 0.0);
+    int32_t rc;
+    if ((rc = dev_upload(h, &P.d_perm, perm)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_key, key)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_sbeg, beg)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_send, end)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_span, span)) != CX_OK) return rc;
+    if ((rc = dev_alloc(h, &P.d_tpart, P.n_tile)) != CX_OK) return rc;
+    if ((rc = dev_upload(h, &P.d_cout, P.h_cout)) != CX_OK) return rc;      // (zeros: a component without a term is never written)
+    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
+    return CX_OK;
+}
+
+void reduce_components(cx_handle *h, const CompPlan &P, const double *tval, const uint8_t *tflag) {
+    double *cval = P.d_cout;
+    unsigned long long *ccnt = reinterpret_cast<unsigned long long *>(cval + P.n_comp);
+    if (P.n_tile)
+        k_ev_seg<<<dim3((unsigned)P.n_tile), dim3(kSB), 0, h->stream>>>(P.n_pos, P.d_perm, P.d_key, P.d_sbeg, P.d_send, tval, tflag, P.d_tpart, cval, ccnt);
+    if (P.n_span)
+        k_ev_span<<<dim3((unsigned)((P.n_span + kSB / 64 - 1) / (kSB / 64))), dim3(kSB), 0, h->stream>>>(P.n_span, P.d_span, P.d_sbeg, P.d_send, P.d_tpart, cval, ccnt);
+}
+
+int32_t read_components(cx_handle *h, CompPlan &P, const std::string &who, int64_t n_fac_terms, const std::vector<int64_t> &comp_fac_terms, int64_t cap,
+                        double *values, int64_t *comp_counts4, int64_t *n_components, int64_t *counts4) {
+    using namespace cxh;
+    CX_HIP(h, hipGetLastError());
+    const int64_t nc = P.n_comp;
+    if (nc) CX_HIP(h, hipMemcpyAsync(P.h_cout.data(), P.d_cout, (size_t)(nc * (1 + kNCnt)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    CX_HIP(h, hipStreamSynchronize(h->stream));
+    // the whole graph's counters are the sums of the components'
+    const double *val = P.h_cout.data();
+    const uint64_t *cnt = reinterpret_cast<const uint64_t *>(val + nc);
+    uint64_t tot[kNCnt] = {0, 0, 0, 0};
+    for (int64_t k = 0; k < nc; k++)
+        for (int q = 0; q < kNCnt; q++) tot[q] += cnt[k * kNCnt + q];
+    CX_REQUIRE(h, tot[3] == 0, CX_ERR_UNSUPPORTED, who + ": the graph holds stand-in variables of a partition");
+    counts4[0] = n_fac_terms;
+    for (int q = 1; q < 4; q++) counts4[q] = (int64_t)tot[q - 1];
+    *n_components = nc;
+    for (int64_t k = 0; k < std::min(cap, nc); k++) {
+        const uint64_t *c = cnt + k * kNCnt;
+        values[k] = c[1] + c[2] > 0 ? kNaN : val[k];
+        if (comp_counts4) {
+            comp_counts4[4 * k] = comp_fac_terms[(size_t)k];
+            for (int q = 1; q < 4; q++) comp_counts4[4 * k + q] = (int64_t)c[q - 1];
+        }
+    }
+    return CX_OK;
+}
+
 // the plan of cx_log_evidence_components: the labels, the terms sorted by (component, term index) into aligned positions, every
-// component's first and last position, the components of more than a tile, and the call's scratch
+// component's first and last position, the components of more than a tile (plan_components), and the call's scratch
 int32_t build_components(cx_handle *h, Cache &C, const std::string &who) {
     using namespace cxh;
     const int64_t nv = h->nv, nf = h->nf, ne = h->ne, nt = nv + C.n_pair + C.n_kary;
-    CX_REQUIRE(h, nt < (int64_t)0x3fffffff, CX_ERR_UNSUPPORTED, who + ": more than 2^30 terms");
     std::vector<int32_t> efac((size_t)ne);
     for (int64_t e = 0; e < ne; e++) efac[(size_t)e] = (int32_t)find_factor(h, h->edge_fac_id[(size_t)e]);
-    C.n_comp = comp::label(nv, nf, ne, h->edge_var.data(), efac.data(), C.var_label, C.fac_label);
-    std::vector<int32_t> term_label((size_t)nt), perm, key, span;
-    std::vector<int64_t> beg, end;
+    const int64_t n_comp = comp::label(nv, nf, ne, h->edge_var.data(), efac.data(), C.var_label, C.fac_label);
+    std::vector<int32_t> term_label((size_t)nt);
     std::copy(C.var_label.begin(), C.var_label.end(), term_label.begin());
-    C.comp_fac_terms.assign((size_t)C.n_comp, 0);
+    C.comp_fac_terms.assign((size_t)n_comp, 0);
     for (int64_t f = 0; f < nf; f++) {
         const int32_t rp = C.row_of_fac[(size_t)f], rk = C.kary_row_of_fac[(size_t)f];
         if (rp < 0 && rk < 0) continue;
         term_label[(size_t)(rp >= 0 ? nv + rp : nv + C.n_pair + rk)] = C.fac_label[(size_t)f];
         C.comp_fac_terms[(size_t)C.fac_label[(size_t)f]]++;
     }
-    C.n_pos = comp::sort_terms(C.n_comp, term_label, kTile, kSI, perm, key, beg, end);
-    for (int64_t k = 0; k < C.n_comp; k++)
-        if (end[(size_t)k] - beg[(size_t)k] > kTile) span.push_back((int32_t)k);
-    C.n_term = nt; C.n_tile = (C.n_pos + kTile - 1) / kTile; C.n_span = (int64_t)span.size();
     int32_t rc;
-    if ((rc = dev_upload(h, &C.d_perm, perm)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &C.d_key, key)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &C.d_sbeg, beg)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &C.d_send, end)) != CX_OK) return rc;
-    if ((rc = dev_upload(h, &C.d_span, span)) != CX_OK) return rc;
+    if ((rc = plan_components(h, C.comp, n_comp, term_label, who)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &C.d_tval, nt)) != CX_OK) return rc;
     if ((rc = dev_alloc(h, &C.d_tflag, nt)) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &C.d_tpart, C.n_tile)) != CX_OK) return rc;
-    if ((rc = dev_alloc(h, &C.d_cout, C.n_comp * (1 + kNCnt))) != CX_OK) return rc;
-    C.h_cout.assign((size_t)(C.n_comp * (1 + kNCnt)), 0.0);
-    CX_HIP(h, hipStreamSynchronize(h->stream));      // (the local host vectors die here)
+    C.n_term = nt;
     C.comp_built = true;
     return CX_OK;
 }
@@ -624,12 +672,7 @@ void launch_components(cx_handle *h, Cache &C) {
     if (nb_p) k_ev_pair<D, true><<<dim3((unsigned)nb_p), dim3(kB), 0, h->stream>>>(C.n_pair, C.pair_tab(), msg, TermOut{tv + nv, tf + nv});
     if (nb_k)
         k_ev_kary<D, true><<<dim3((unsigned)nb_k), dim3(kKB), 0, h->stream>>>(C.n_kary, C.kary_tab(), msg, TermOut{tv + nv + C.n_pair, tf + nv + C.n_pair});
-    double *cval = C.d_cout;
-    unsigned long long *ccnt = reinterpret_cast<unsigned long long *>(cval + C.n_comp);
-    if (C.n_tile)
-        k_ev_seg<<<dim3((unsigned)C.n_tile), dim3(kSB), 0, h->stream>>>(C.n_pos, C.d_perm, C.d_key, C.d_sbeg, C.d_send, C.d_tval, C.d_tflag, C.d_tpart, cval, ccnt);
-    if (C.n_span)
-        k_ev_span<<<dim3((unsigned)((C.n_span + kSB / 64 - 1) / (kSB / 64))), dim3(kSB), 0, h->stream>>>(C.n_span, C.d_span, C.d_sbeg, C.d_send, C.d_tpart, cval, ccnt);
+    reduce_components(h, C.comp, C.d_tval, C.d_tflag);
 }
 
 }  // namespace ev
@@ -705,7 +748,7 @@ extern "C" int32_t cx_graph_components(cx_handle *h, int64_t n, const int64_t *v
         // the labels of the evidence plan when a component call has built it (a handle has one graph for life), else a union-find now
         std::vector<int32_t> mine, fl;
         const bool planned = h->evidence && h->evidence->comp_built;
-        if (planned) *n_components = h->evidence->n_comp;
+        if (planned) *n_components = h->evidence->comp.n_comp;
         else {
             std::vector<int32_t> efac((size_t)h->ne);
             for (int64_t e = 0; e < h->ne; e++) efac[(size_t)e] = (int32_t)find_factor(h, h->edge_fac_id[(size_t)e]);
@@ -728,28 +771,6 @@ extern "C" int32_t cx_log_evidence_components(cx_handle *h, int64_t cap, double 
         ev::Cache &C = *Cp;
         if (!C.comp_built && (rc = ev::build_components(h, C, "cx_log_evidence_components")) != CX_OK) return rc;
         ev::with_dim(h->cfg.dim, [&](auto D) { ev::launch_components<D()>(h, C); });
-        CX_HIP(h, hipGetLastError());
-        const int64_t nc = C.n_comp;
-        if (nc) CX_HIP(h, hipMemcpyAsync(C.h_cout.data(), C.d_cout, (size_t)(nc * (1 + ev::kNCnt)) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        CX_HIP(h, hipStreamSynchronize(h->stream));
-        // the whole graph's counters are the sums of the components'
-        const double *val = C.h_cout.data();
-        const uint64_t *cnt = reinterpret_cast<const uint64_t *>(val + nc);
-        uint64_t tot[ev::kNCnt] = {0, 0, 0, 0};
-        for (int64_t k = 0; k < nc; k++)
-            for (int q = 0; q < ev::kNCnt; q++) tot[q] += cnt[k * ev::kNCnt + q];
-        CX_REQUIRE(h, tot[3] == 0, CX_ERR_UNSUPPORTED, "cx_log_evidence_components: the graph holds stand-in variables of a partition");
-        counts4[0] = C.n_pair + C.n_kary;
-        for (int q = 1; q < 4; q++) counts4[q] = (int64_t)tot[q - 1];
-        *n_components = nc;
-        for (int64_t k = 0; k < std::min(cap, nc); k++) {
-            const uint64_t *c = cnt + k * ev::kNCnt;
-            values[k] = c[1] + c[2] > 0 ? kNaN : val[k];
-            if (comp_counts4) {
-                comp_counts4[4 * k] = C.comp_fac_terms[(size_t)k];
-                for (int q = 1; q < 4; q++) comp_counts4[4 * k + q] = (int64_t)c[q - 1];
-            }
-        }
-        return CX_OK;
+        return ev::read_components(h, C.comp, "cx_log_evidence_components", C.n_pair + C.n_kary, C.comp_fac_terms, cap, values, comp_counts4, n_components, counts4);
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence_components: host allocation failed"); }
 }

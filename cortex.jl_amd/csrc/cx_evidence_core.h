@@ -538,6 +538,29 @@ __device__ __forceinline__ void kary_joint(int64_t f, const KaryTab &T, const Ms
     }
 }
 
+// ---- host: the per-component sum of a term array (cx_log_evidence_components, cx_log_evidence_components_mfma) ----------------------
+// The terms sorted by (component, term index) into the aligned positions of comp::sort_terms, and the scratch and output of the
+// segmented sum over them (k_ev_seg, k_ev_span: cx_evidence.hip).  Whose terms they are is the owner's business
+struct CompPlan {
+    int64_t n_comp = 0, n_pos = 0, n_tile = 0, n_span = 0;
+    DevBuf<int32_t> d_perm, d_key;        // [n_pos] the term at every position and its component (-1: none; comp::sort_terms)
+    DevBuf<int64_t> d_sbeg, d_send;       // [C] first position of every component and the one past its last
+    DevBuf<int32_t> d_span;               // [n_span] the components of more than a tile of terms
+    DevBuf<TilePart> d_tpart;             // [n_tile] the piece of the long component that reaches the tile
+    DevBuf<double> d_cout;                // [C] values | [C][kNCnt] counters (u64)
+    std::vector<double> h_cout;
+};
+// the plan of n_comp components from the component of every term (the terms keep their indices); `who` prefixes the error texts
+int32_t plan_components(cx_handle *h, CompPlan &P, int64_t n_comp, const std::vector<int32_t> &term_label, const std::string &who);
+// k_ev_seg, then k_ev_span for the components longer than a tile, on the handle's stream: tval / tflag [terms] -> P.d_cout.  The one
+// launch site of the two kernels
+void reduce_components(cx_handle *h, const CompPlan &P, const double *tval, const uint8_t *tflag);
+// The tail of a component call: P.d_cout to the host in one copy, the stream waited for; counts4 = {n_fac_terms, the column sums of the
+// components' counters}, *n_components, and for k < min(cap, C): values[k] (NaN when the component has an undefined or not positive
+// definite term) and comp_counts4[4 k ..] = {comp_fac_terms[k], its three counters}
+int32_t read_components(cx_handle *h, CompPlan &P, const std::string &who, int64_t n_fac_terms, const std::vector<int64_t> &comp_fac_terms, int64_t cap,
+                        double *values, int64_t *comp_counts4, int64_t *n_components, int64_t *counts4);
+
 // ---- host: the work lists -------------------------------------------------------------------------------------------------------
 struct Cache {
     bool built = false;
@@ -562,17 +585,12 @@ struct Cache {
     // cx_log_evidence_components: the plan of the first component call, dropped with the cache.  Terms: index v for
     // variable v, nv + pair row, nv + n_pair + k-ary row; sorted by (component, term index) into aligned positions
     bool comp_built = false;
-    int64_t n_comp = 0, n_term = 0, n_pos = 0, n_tile = 0, n_span = 0;
+    int64_t n_term = 0;
     std::vector<int32_t> var_label, fac_label;      // component of every variable / factor index
     std::vector<int64_t> comp_fac_terms;            // [C] the factor terms of every component
-    DevBuf<int32_t> d_perm, d_key;        // [n_pos] the term at every position and its component (-1: none; comp::sort_terms)
-    DevBuf<int64_t> d_sbeg, d_send;       // [C] first position of every component and the one past its last
-    DevBuf<int32_t> d_span;               // [n_span] the components of more than a tile of terms
+    CompPlan comp;
     DevBuf<double> d_tval;                // [n_term] the terms
     DevBuf<uint8_t> d_tflag;              // [n_term] their flag bits (kTermVar ..)
-    DevBuf<TilePart> d_tpart;             // [n_tile] the piece of the long component that reaches the tile
-    DevBuf<double> d_cout;                // [C] values | [C][kNCnt] counters (u64)
-    std::vector<double> h_cout;
     Cache() = default;
     Cache(const Cache &) = delete;
     ~Cache() { if (h_out) (void)hipHostFree(h_out); }

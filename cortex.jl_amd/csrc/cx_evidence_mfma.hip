@@ -30,6 +30,12 @@
 // (k_ev_final, cx_evidence.hip) adds the parts in index order: no atomics, two calls on one state are bit-identical.
 // cx_log_evidence and cx_log_evidence_components keep refusing these dims (their tests pin that); routing them here is a later,
 // separate decision.
+//
+// cx_log_evidence_components_mfma: the same k_evm_terms launch, then the terms summed per connected component of the
+// graph by the segmented sum of cx_log_evidence_components (ev::reduce_components: k_ev_seg / k_ev_span of cx_evidence.hip, §4l) over
+// d_tval / d_tflag in place of k_evm_part and k_ev_final.  The term list keeps its order; the plan (evm::build_components) only
+// says which component every term belongs to.
+#include "cx_components.h"
 #include "cx_evidence_mfma_core.h"
 #include "cx_mfma_reader.h"
 
@@ -161,6 +167,13 @@ struct Cache {
     DevBuf<uint8_t> d_tflag;
     DevBuf<ev::Part> d_part;
     mfr::Totals totals;
+    // cx_log_evidence_components_mfma: the plan of the first component call, dropped with the cache.  term_var / term_fac: the variable
+    // every term of d_rec is filed under and whether it is a factor's (kept from build() until the plan is made)
+    bool comp_built = false;
+    std::vector<int32_t> term_var;
+    std::vector<uint8_t> term_fac;
+    std::vector<int64_t> comp_fac_terms;      // [C] the factor terms of every component
+    ev::CompPlan comp;
 };
 
 static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
@@ -207,7 +220,12 @@ static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[(size_t)a] < key[(size_t)b]; });
     rec.reserve(made.size());
-    for (int32_t i : order) rec.insert(rec.end(), made.begin() + 8 * (size_t)i, made.begin() + 8 * (size_t)i + 8);
+    C.term_var.clear(); C.term_fac.clear();
+    for (int32_t i : order) {
+        rec.insert(rec.end(), made.begin() + 8 * (size_t)i, made.begin() + 8 * (size_t)i + 8);
+        C.term_var.push_back(key[(size_t)i]);
+        C.term_fac.push_back(made[8 * (size_t)i] >= kFacFree);
+    }
     CX_REQUIRE(h, C.n_term < (int64_t)0x7fffffff && (int64_t)srcs.size() < (int64_t)0x7fffffff, CX_ERR_UNSUPPORTED, who + ": more than 2^31 terms");
     C.nb = (C.n_term + kTB - 1) / kTB;
     int32_t rc;
@@ -245,7 +263,44 @@ static void fill_ldq(const cx_handle *h, std::vector<double> &ldq) {
     }
 }
 
-static void launch(cx_handle *h, Cache &C) {
+// The plan of cx_log_evidence_components_mfma: the labels of the graph as cx_graph_create received it (comp::label), every term under
+// the label of the variable it is filed under — an opaque term's variable, one end of a factor: the same component as the factor —
+// and ev::plan_components' positions.  The term list itself stays as build() left it
+static int32_t build_components(cx_handle *h, Cache &C, const std::string &who) {
+    using namespace cxh;
+    std::vector<int32_t> efac((size_t)h->ne), var_label, fac_label, term_label((size_t)C.n_term);
+    for (int64_t e = 0; e < h->ne; e++) efac[(size_t)e] = (int32_t)find_factor(h, h->edge_fac_id[(size_t)e]);
+    const int64_t n_comp = comp::label(h->nv, h->nf, h->ne, h->edge_var.data(), efac.data(), var_label, fac_label);
+    C.comp_fac_terms.assign((size_t)n_comp, 0);
+    for (int64_t t = 0; t < C.n_term; t++) {
+        term_label[(size_t)t] = var_label[(size_t)C.term_var[(size_t)t]];
+        C.comp_fac_terms[(size_t)term_label[(size_t)t]] += C.term_fac[(size_t)t];
+    }
+    int32_t rc;
+    if ((rc = ev::plan_components(h, C.comp, n_comp, term_label, who)) != CX_OK) return rc;
+    std::vector<int32_t>().swap(C.term_var);
+    std::vector<uint8_t>().swap(C.term_fac);
+    C.comp_built = true;
+    return CX_OK;
+}
+
+// the handle's cache with its term lists and its log-det table, the messages in their slots: what both entries do after mfr::prepare
+static int32_t ready(cx_handle *h, const std::string &who, Cache *&Cp) {
+    using namespace cxh;
+    int32_t rc;
+    if (h->evidence_mfma && h->evidence_mfma->vinfo_epoch != h->vinfo_epoch) h->evidence_mfma.reset();      // other variables are observed
+    if (!h->evidence_mfma) h->evidence_mfma.reset(new Cache());
+    Cache &C = *h->evidence_mfma;
+    if (!C.built && (rc = build(h, C, who)) != CX_OK) { h->evidence_mfma.reset(); return rc; }
+    if (C.unsupported_fac >= 0) return mfr::refuse_factor(h, who, C.unsupported_fac);
+    if ((rc = C.ldq.refresh(h, [&](std::vector<double> &t) { fill_ldq(h, t); })) != CX_OK) return rc;
+    if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
+    Cp = &C;
+    return CX_OK;
+}
+
+// k_evm_terms: one (value, flags) per term into d_tval / d_tflag
+static void launch_terms(cx_handle *h, Cache &C) {
     const int n = (int)C.n_term, u = mfr::user_dim(h);
     if (!n) return;
     const unsigned grid = 8u * (unsigned)((n + 7) / 8);      // (k_evm_terms: an eighth of the terms per XCD)
@@ -256,7 +311,11 @@ static void launch(cx_handle *h, Cache &C) {
         hipLaunchKernelGGL((k_evm_terms<NT, W>), dim3(grid), dim3(64), 0, h->stream, n, C.d_rec, C.d_srcs, h->d_ptab, h->d_ptab_bt, C.ldq.d, h->d_mv_f2v,
                            h->d_mv_v2f, u, C.d_tval, C.d_tflag);
     });
-    hipLaunchKernelGGL(k_evm_part, dim3((unsigned)C.nb), dim3(kTB), 0, h->stream, n, C.d_tval, C.d_tflag, C.d_part);
+}
+
+static void launch(cx_handle *h, Cache &C) {
+    launch_terms(h, C);
+    if (C.n_term) hipLaunchKernelGGL(k_evm_part, dim3((unsigned)C.nb), dim3(kTB), 0, h->stream, (int)C.n_term, C.d_tval, C.d_tflag, C.d_part);
 }
 
 }  // namespace evm
@@ -275,16 +334,30 @@ extern "C" int32_t cx_log_evidence_mfma(cx_handle *h, double *value, int64_t *co
         int32_t rc;
         if ((rc = mfr::prepare(h, who, value && counts4 ? nullptr : "null argument", {"cx_log_evidence", "no variational free energy, no Beta-Bernoulli evidence", "terms"})) != CX_OK)
             return rc;
-        if (h->evidence_mfma && h->evidence_mfma->vinfo_epoch != h->vinfo_epoch) h->evidence_mfma.reset();      // other variables are observed
-        if (!h->evidence_mfma) h->evidence_mfma.reset(new evm::Cache());
-        evm::Cache &C = *h->evidence_mfma;
-        if (!C.built && (rc = evm::build(h, C, who)) != CX_OK) { h->evidence_mfma.reset(); return rc; }
-        if (C.unsupported_fac >= 0) return mfr::refuse_factor(h, who, C.unsupported_fac);
-        if ((rc = C.ldq.refresh(h, [&](std::vector<double> &t) { evm::fill_ldq(h, t); })) != CX_OK) return rc;
-        if ((rc = mv_ensure_chain_msgs(h)) != CX_OK) return rc;      // (every reader of d_mv_f2v calls this first)
+        evm::Cache *Cp = nullptr;
+        if ((rc = evm::ready(h, who, Cp)) != CX_OK) return rc;
+        evm::Cache &C = *Cp;
         evm::launch(h, C);
         if ((rc = C.totals.read(h, C.nb, C.d_part, C.n_fac, counts4, value)) != CX_OK) return rc;
         if (counts4[2] + counts4[3] > 0) *value = kNaN;
         return CX_OK;
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence_mfma: host allocation failed"); }
+}
+
+extern "C" int32_t cx_log_evidence_components_mfma(cx_handle *h, int64_t cap, double *values, int64_t *comp_counts4, int64_t *n_components, int64_t *counts4) {
+    try {
+        namespace evm = cx::evm;
+        namespace mfr = cx::mfr;
+        const std::string who = "cx_log_evidence_components_mfma";
+        const char *bad = !n_components || !counts4 ? "null n_components or counts4" : cap < 0 ? "cap < 0" : cap > 0 && !values ? "cap > 0 with null values" : nullptr;
+        int32_t rc;
+        if ((rc = mfr::prepare(h, who, bad, {"cx_log_evidence_components", "no variational free energy, no Beta-Bernoulli evidence", "terms"})) != CX_OK) return rc;
+        evm::Cache *Cp = nullptr;
+        if ((rc = evm::ready(h, who, Cp)) != CX_OK) return rc;
+        evm::Cache &C = *Cp;
+        if (!C.comp_built && (rc = evm::build_components(h, C, who)) != CX_OK) return rc;
+        evm::launch_terms(h, C);
+        cx::ev::reduce_components(h, C.comp, C.d_tval, C.d_tflag);
+        return cx::ev::read_components(h, C.comp, who, C.n_fac, C.comp_fac_terms, cap, values, comp_counts4, n_components, counts4);
+    } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_log_evidence_components_mfma: host allocation failed"); }
 }

@@ -44,6 +44,10 @@ class DeviceGraph:
         if rc != L.OK:
             raise L.CortexHipError(rc, self.lib.cx_last_error(self.h).decode())
 
+    def last_error(self) -> str:
+        """cx_last_error: the text of the handle's last refused call (what CortexHipError carries; here for a raw self.lib call)"""
+        return self.lib.cx_last_error(self.h).decode()
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.cx_destroy(self.h)
@@ -349,6 +353,16 @@ class DeviceGraph:
         read an undefined message or a belief that is not positive definite (the other components keep their values); comp_counts[k]
         = (factor terms, variable terms, undefined, not positive definite) of component k; counts is log_evidence's dict for the
         whole graph.  cap: return the first min(cap, C) components only."""
+        return self._log_evidence_components(self.lib.cx_log_evidence_components, cap)
+
+    def log_evidence_components_mfma(self, cap=None):
+        """cx_log_evidence_components_mfma: log_evidence_components at the matrix-core dims (a handle created with dim 5 .. 64) — the
+        same return value, with the terms, counts and NaN rule of log_evidence_mfma: the independent models of one handle told apart
+        (K candidates of a likelihood profile, K starts of EM, a panel of series).  log_evidence_components itself keeps refusing
+        these dims."""
+        return self._log_evidence_components(self.lib.cx_log_evidence_components_mfma, cap)
+
+    def _log_evidence_components(self, call, cap):
         nc = C.c_int64()
         if getattr(self, "_n_components", None) is None:      # (a handle has one graph for life: counted once, host work)
             self._check(self.lib.cx_graph_components(self.h, 0, None, None, C.byref(nc)))
@@ -357,8 +371,7 @@ class DeviceGraph:
         val = np.zeros(n, dtype=np.float64)
         cc = np.zeros((n, 4), dtype=np.int64)
         out = (C.c_int64 * 4)()
-        self._check(self.lib.cx_log_evidence_components(self.h, n, _p(val, C.c_double) if n else None, _p(cc, C.c_int64) if n else None,
-                                                        C.byref(nc), out))
+        self._check(call(self.h, n, _p(val, C.c_double) if n else None, _p(cc, C.c_int64) if n else None, C.byref(nc), out))
         return val, cc, dict(zip(("factor_terms", "variable_terms", "undefined", "not_positive_definite"), [int(x) for x in out]))
 
     def factor_beliefs(self, factor_ids):

@@ -76,7 +76,8 @@ def group(stats, g):
 def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_component=False):
     """EM on the parameter sets of a dim 2..4 DeviceGraph: per iteration sweep(sweeps_per_iter) → log_evidence → factor_statistics
     (one group per parameter set) → m_step → set_factor_matrices.  On a handle of dim 5..64 the same loop runs on log_evidence_mfma and
-    factor_statistics_mfma; offsets= and by_component=True raise ValueError there (neither exists at these dims).
+    factor_statistics_mfma; offsets= and by_component=True raise ValueError there (multi_start_em is the way to run several starts in
+    one handle at these dims: it uses log_evidence_components_mfma).
 
     sets: {set: (A, Q)}, the starting parameters (set on the handle here).  learn: a tuple for every set, or {set: tuple}.
     Returns (trace, params): trace[i] = log p(data) under the parameters of iteration i (n_iter + 1 values, the last under the final
@@ -100,11 +101,7 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_
         raise ValueError("em: offsets= at dim 5..64: these dims have no per-factor offsets (set_factor_offsets is dim 2..4)")
     if mfma and by_component:
         raise ValueError("em: by_component=True at dim 5..64: log_evidence_components does not exist at these dims (log_evidence_mfma gives the total)")
-    if dev.schedule not in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE):
-        warnings.warn("em: the log-evidence is guaranteed non-decreasing only under an exact E-step (chain scan, tree, reference order on "
-                      "a forest)", RuntimeWarning, stacklevel=2)
     params = {int(s): (np.array(A, float), np.array(Q, float)) for s, (A, Q) in sets.items()}
-    n_groups = max(params) + 1
     for s, (A, Q) in params.items():
         dev.set_factor_matrices(s, A, Q)
     offs, facs = None, {}
@@ -119,17 +116,34 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_
         ls = learn.get(s, ("A", "Q")) if isinstance(learn, dict) else learn
         if "b" in ls and offs is not None and s not in offs:
             raise ValueError(f'em: "b" is learned for the sets that offsets names (set {s} is not one)')
+    if by_component:
+        evidence = lambda: dev.log_evidence_components()[0]      # noqa: E731
+    else:
+        evidence = lambda: (dev.log_evidence_mfma() if mfma else dev.log_evidence())[0]      # noqa: E731
+    trace = _em_loop(dev, params, offs, facs, n_iter, sweeps_per_iter, learn, evidence)
+    if by_component:
+        trace = np.array(trace, dtype=np.float64).reshape(n_iter + 1, -1)
+    if offs is not None:
+        return trace, params, offs
+    return trace, params
+
+
+def _em_loop(dev, params, offs, facs, n_iter, sweeps_per_iter, learn, evidence):
+    """The iterations of em and multi_start_em on a handle that holds the starting parameters: sweep → evidence() (the trace's row) →
+    factor_statistics (factor_statistics_mfma at dim 5..64), one group per parameter set → m_step → set_factor_matrices (and the
+    offsets of the sets in offs).  params and offs are updated in place; returns the n_iter + 1 rows."""
+    if dev.schedule not in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE):
+        warnings.warn("em: the log-evidence is guaranteed non-decreasing only under an exact E-step (chain scan, tree, reference order on "
+                      "a forest)", RuntimeWarning, stacklevel=3)
+    statistics = dev.factor_statistics_mfma if dev.dim >= 5 else dev.factor_statistics
+    n_groups = max(params) + 1
     trace = []
     for it in range(n_iter + 1):
         dev.sweep(sweeps_per_iter)
-        if by_component:
-            trace.append(dev.log_evidence_components()[0])
-        else:
-            value, cnt = dev.log_evidence_mfma() if mfma else dev.log_evidence()
-            trace.append(value)
+        trace.append(evidence())
         if it == n_iter:
             break
-        stats, _ = (dev.factor_statistics_mfma if mfma else dev.factor_statistics)(n_groups=n_groups)
+        stats, _ = statistics(n_groups=n_groups)
         for s, (A, Q) in params.items():
             ls = learn.get(s, ("A", "Q")) if isinstance(learn, dict) else learn
             if not ls:
@@ -140,19 +154,52 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_
             if offs is not None and s in offs:
                 offs[s] = new["b"]
                 dev.set_factor_offsets(facs[s], np.tile(offs[s], (len(facs[s]), 1)))
-    if by_component:
-        trace = np.array(trace, dtype=np.float64).reshape(n_iter + 1, -1)
-    if offs is not None:
-        return trace, params, offs
-    return trace, params
+    return trace
+
+
+def multi_start_em(model, starts, n_iter, learn=("A", "Q"), schedule=L.SCHED_CHAIN_SCAN, sweeps_per_iter=1):
+    """EM on one dim 2..64 model from K starting points at once: K replicas of the model as one graph (synth.replicas) in a handle of
+    its own, replica k under starts[k] = {set: (A, Q)} (a set a start does not name begins at model.psets), em's iterations with the
+    log-evidence per connected component (log_evidence_components, log_evidence_components_mfma at dim 5..64) as the trace.  The
+    statistics are grouped by parameter set and replica k's sets are k * S + s, so every start is updated from its own statistics:
+    the K runs do not interact and each column is the trace that em gives from that start alone.
+    learn: a tuple for every set, or {set: tuple} in the MODEL's set numbers (the same for every start).  schedule: an exact one for
+    the model (SCHED_CHAIN_SCAN on chains, SCHED_TREE on forests).
+    Returns (trace [n_iter + 1, K], params, best): params[k] = {set: (A, Q)} of start k in the model's set numbers, best = the argmax
+    of the last row of the trace (a start whose component read an undefined input or a belief that is not positive definite has NaN
+    there and is never the best)."""
+    from . import synth
+    from .device import DeviceGraph
+
+    starts = [{int(s): AQ for s, AQ in st.items()} for st in starts]
+    rep = synth.replicas(model, starts)
+    S, K = rep.meta["S"], len(starts)
+    if isinstance(learn, dict):
+        learn = {k * S + int(s): tuple(learn.get(int(s), ("A", "Q"))) for k in range(K) for s in model.psets}
+    dev = DeviceGraph(dim=model.dim, schedule=schedule)
+    try:
+        synth.load_into_device(rep, dev)
+        components = dev.log_evidence_components_mfma if dev.dim >= 5 else dev.log_evidence_components
+        if dev.components()[1] != K:
+            raise ValueError("multi_start_em: the model is not one connected component (its replicas are not the components of the graph)")
+        params = {int(s): (np.array(A, float), np.array(Q, float)) for s, (A, Q) in rep.psets.items()}
+        for s, (A, Q) in params.items():
+            dev.set_factor_matrices(s, A, Q)
+        trace = _em_loop(dev, params, None, {}, n_iter, sweeps_per_iter, learn, lambda: components()[0])
+    finally:
+        dev.close()
+    trace = np.array(trace, dtype=np.float64).reshape(n_iter + 1, K)
+    last = np.where(np.isnan(trace[-1]), -np.inf, trace[-1])
+    return trace, [{int(s): params[k * S + int(s)] for s in model.psets} for k in range(K)], int(np.argmax(last))
 
 
 def profile(model, candidates, schedule=L.SCHED_TREE):
-    """The log-likelihood of one dim 2..4 model under K candidate parameter sets from ONE handle and one exact sweep: K replicas of the
+    """The log-likelihood of one dim 2..64 model under K candidate parameter sets from ONE handle and one exact sweep: K replicas of the
     model as one graph (synth.replicas), one component each.  candidates: a list of {set: (A, Q)}; a set a candidate does not name
     falls back to model.psets.  schedule: an exact one for the model (SCHED_TREE, or SCHED_CHAIN_SCAN on chains).
     Returns (loglik [K], comp_counts [K, 4]) of DeviceGraph.log_evidence_components: loglik[k] = log p(data | candidate k), NaN when
-    that replica read an undefined message or a belief that is not positive definite (comp_counts[k, 2:])."""
+    that replica read an undefined message or a belief that is not positive definite (comp_counts[k, 2:]).  A model of dim 5..64 goes
+    through log_evidence_components_mfma."""
     from . import synth
     from .device import DeviceGraph
 
@@ -161,7 +208,7 @@ def profile(model, candidates, schedule=L.SCHED_TREE):
     try:
         synth.load_into_device(rep, dev)
         dev.sweep(1)
-        values, comp_counts, _ = dev.log_evidence_components()
+        values, comp_counts, _ = dev.log_evidence_components_mfma() if model.dim >= 5 else dev.log_evidence_components()
     finally:
         dev.close()
     if len(values) != len(rep.meta["replica_offset"]):

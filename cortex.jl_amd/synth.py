@@ -242,11 +242,12 @@ def concat_models(models) -> Model:
 
 
 def replicas(model: Model, psets_list) -> Model:
-    """K copies of one dim 2..4 model as ONE graph of disjoint components (ids shifted past each other, as concat_models does), replica k
+    """K copies of one dim >= 2 model as ONE graph of disjoint components (ids shifted past each other, as concat_models does), replica k
     under its own parameter sets: psets_list[k] = {set: (A, Q)}, a set it does not name falls back to model.psets.  Set s of replica k
     is renumbered k * S + s with S = 1 + the model's largest set; psets holds the K * S entries (of the sets the model has);
-    meta["replica_offset"] lists the id shifts, meta["S"] = S.  One exact sweep and DeviceGraph.log_evidence_components then give the K
-    log-likelihoods of the one series (a likelihood profile); with learn.em(by_component=True), multi-start EM in one handle."""
+    meta["replica_offset"] lists the id shifts, meta["S"] = S.  One exact sweep and DeviceGraph.log_evidence_components
+    (log_evidence_components_mfma at dim 5..64) then give the K log-likelihoods of the one series (a likelihood profile: learn.profile);
+    with learn.multi_start_em (or learn.em(by_component=True) at dim 2..4), multi-start EM in one handle."""
     if model.dim < 2:
         raise ValueError("replicas: dim 2..4 (dim 1 factors carry their own parameters)")
     K = len(psets_list)

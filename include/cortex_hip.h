@@ -834,12 +834,35 @@ int32_t cx_log_evidence_components(cx_handle *h, int64_t cap, double *values, in
  * one chain-scan sweep, median of 30 calls: 4.68 ms at d = 64 (config C5), 1.51 ms at d = 32, 0.73 ms at d = 16 — 1.16, 1.36 and 1.65
  * times one fused sweep of the same model (4.05, 1.11, 0.44 ms): the call factors 4 T matrices where that sweep factors 2 T.
  * cx_log_evidence and cx_log_evidence_components keep returning CX_ERR_UNSUPPORTED at these dims exactly as before; routing them here
- * is a later, separate decision.
+ * is a later, separate decision (the per-component call at these dims is cx_log_evidence_components_mfma, below).
  * Refused: NULL value or counts4 CX_ERR_INVALID_ARGUMENT; no graph or a captured stream CX_ERR_STATE; a handle created with dim 1 - 4
  * (use cx_log_evidence), other families, a factor of another kind, partitioned handles (halo lists, state halos, a chain's time
  * block) CX_ERR_UNSUPPORTED; wired handles (cx_graph_wire) cannot exist at these dims.  Synchronous; moves no message, marginal,
  * readiness bit or counter. */
 int32_t cx_log_evidence_mfma(cx_handle *h, double *value, int64_t *counts4);
+
+/* ---- log-evidence per connected component at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
+ * cx_log_evidence_components_mfma: cx_log_evidence_components for a handle created with dim 5 .. 64 — the same arguments, outputs,
+ * counts and NaN rule (see "cx_log_evidence_components" above and DESIGN.md §4t).  values[k] = the sum of exactly the terms of
+ * cx_log_evidence_mfma that belong to component k (an opaque term belongs to its variable's component, a factor term to its
+ * factor's); NaN iff one of those terms has an undefined input or is not positive definite, the other components keep their values
+ * (cx_log_evidence_mfma's one total would be NaN).  comp_counts4 (NULL, or [cap][4]) = {factor terms, variable terms, undefined, not
+ * positive definite} of every component; counts4 is cx_log_evidence_mfma's for the whole graph, the column sums of the components'.
+ * Components are numbered as cx_graph_components numbers them.  It writes the first min(cap, C) entries and *n_components = C; cap == 0
+ * with NULL arrays is the sizing call; values and counts4 do not depend on cap.
+ * The device work is cx_log_evidence_mfma's term kernel (one wave per term, the same launch), then the segmented sum of
+ * cx_log_evidence_components over the term array: compensated, in an order that a component's own terms fix, no atomics — two calls on
+ * one state are bit-identical, a component's value does not depend on which others share the graph, and the sum of the values agrees
+ * with cx_log_evidence_mfma to the rounding of two orders of summation, not bit for bit.  The labels and the sorted positions are
+ * built on the first call (O(connections) on the host) and kept with cx_log_evidence_mfma's term lists, until other variables are
+ * observed.  MI355X (profiles/evidence_components_mfma.md, session of 2026-10-21), medians of 30 calls interleaved with
+ * cx_log_evidence_mfma on the same handle: 1.001, 1.007 and 1.001 times that call on a T = 1e5 chain at d = 16, 32 and 64 (0.69, 1.49,
+ * 4.65 ms), 0.995 times on 1000 chains of T = 100 at d = 16.
+ * Refused as cx_log_evidence_mfma refuses, with the same codes (a handle created with dim 1 - 4: use cx_log_evidence_components; other
+ * families, a factor of another kind, partitioned handles CX_ERR_UNSUPPORTED; no graph or a captured stream CX_ERR_STATE); a NULL
+ * n_components or counts4, cap < 0, or cap > 0 with a NULL values are CX_ERR_INVALID_ARGUMENT.  A refused call writes nothing.
+ * Synchronous; moves no message, marginal, readiness bit or counter. */
+int32_t cx_log_evidence_components_mfma(cx_handle *h, int64_t cap, double *values, int64_t *comp_counts4, int64_t *n_components, int64_t *counts4);
 
 /* ---- factor beliefs and EM statistics at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
  * cx_factor_beliefs_mfma / cx_factor_statistics_mfma: cx_factor_beliefs and cx_factor_statistics for a handle created with dim 5 .. 64 —

@@ -156,17 +156,20 @@ class Handle {
     // undefined input or a belief that is not positive definite, the others keep theirs), comp_counts [C][4] and counts (the whole graph's)
     // as log_evidence's counts
     struct EvidenceComponents { std::vector<double> values; std::vector<std::array<int64_t, 4>> comp_counts; std::array<int64_t, 4> counts{}; };
-    EvidenceComponents log_evidence_components() {
+    EvidenceComponents evidence_components(int32_t (*call)(cx_handle *, int64_t, double *, int64_t *, int64_t *, int64_t *)) {
         EvidenceComponents r;
         int64_t c = 0;
         check(cx_graph_components(h_, 0, nullptr, nullptr, &c));
         r.values.resize((size_t)c + 1);
         r.comp_counts.resize((size_t)c + 1);
-        check(cx_log_evidence_components(h_, c, r.values.data(), r.comp_counts[0].data(), &c, r.counts.data()));
+        check(call(h_, c, r.values.data(), r.comp_counts[0].data(), &c, r.counts.data()));
         r.values.resize((size_t)c);
         r.comp_counts.resize((size_t)c);
         return r;
     }
+    EvidenceComponents log_evidence_components() { return evidence_components(cx_log_evidence_components); }
+    // the same at the matrix-core dims, 5 .. 64 (cx_log_evidence_components_mfma): the terms, counts and NaN rule of log_evidence_mfma
+    EvidenceComponents log_evidence_components_mfma() { return evidence_components(cx_log_evidence_components_mfma); }
     // the joint posterior of two-variable Gaussian factors from the stored messages: per factor 2d means then the 2d x 2d covariance
     // (row-major), (out, in) (NaN rows: an undefined input or a belief that is not positive definite)
     std::vector<double> factor_beliefs(const std::vector<int64_t> &factor_ids) {

@@ -318,15 +318,23 @@ end
 
 # log p(data) of every connected component from the stored messages (dim 1 - 4): (values [C], counts 4 x C, whole-graph counts [4]);
 # values[k] is NaN when component k read an undefined input or a belief that is not positive definite — the others keep their values
-function log_evidence_components(p)
+log_evidence_components(p) = evidence_components(p, (c, values, comp_counts, nc, out) ->
+    ccall((:cx_log_evidence_components, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), p.handle, c, values, comp_counts, nc, out))
+
+# the same at the matrix-core dims (cx_create dim 5 - 64; cx_log_evidence_components_mfma): the terms, counts and NaN rule of
+# log_evidence_mfma, one value per connected component
+log_evidence_components_mfma(p) = evidence_components(p, (c, values, comp_counts, nc, out) ->
+    ccall((:cx_log_evidence_components_mfma, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), p.handle, c, values, comp_counts, nc, out))
+
+# sizes the arrays by cx_graph_components, then call(c, values, comp_counts, nc, out): one of the two entries above
+function evidence_components(p, call)
     nc = Ref{Int64}(0)
     check(p.handle, ccall((:cx_graph_components, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), p.handle, 0, C_NULL, C_NULL, nc))
     c = nc[]
     values = zeros(Float64, max(c, 1))
     comp_counts = zeros(Int64, 4, max(c, 1))
     out = zeros(Int64, 4)
-    check(p.handle, ccall((:cx_log_evidence_components, lib), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
-                          p.handle, c, values, comp_counts, nc, out))
+    check(p.handle, call(c, values, comp_counts, nc, out))
     return values[1:c], comp_counts[:, 1:c], out
 end
 
