@@ -103,6 +103,7 @@ SIGNATURES = {
     "cx_causal_marginals_mfma": (_i32, [_vp, _i32, _i32, _i64, _pi64, _pd, _pi64]),
     "cx_sample_posterior_mfma": (_i32, [_vp, _i64, C.c_uint64, _pd, _i64, _pi64, _pd, _pi64]),
     "cx_set_factor_offsets": (_i32, [_vp, _i64, _pi64, _pd]),
+    "cx_set_factor_offsets_mfma": (_i32, [_vp, _i64, _pi64, _pd]),
     "cx_halo_configure": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pi64, _pi64]),
     "cx_halo_buffers": (_i32, [_vp, C.POINTER(_vp), _pi64, C.POINTER(_vp), _pi64]),
     "cx_halo_set_buffers": (_i32, [_vp, _vp, _vp]),

@@ -216,16 +216,19 @@ int32_t cx_set_factor_matrices(cx_handle *h, int64_t parameter_set, const double
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "cx_set_factor_matrices: host allocation failed"); }
 }
 
-// h->offsets (by factor) -> d_off_b (by slot, every slot: the arrays are small next to the messages) -> d_off_g (k_mv_offset_terms)
+// h->offsets (by factor) -> d_off_b (by slot, every slot: the arrays are small next to the messages) -> d_off_g (k_mv_offset_terms).
+// dim 2 - 4: [d][nslots], component-major (a thread reads one component of many slots); the matrix-core dims: [nslots][d], one contiguous
+// vector per slot (a wave reads one slot's), h->offsets in the user's dim and zeros in the padding of an embedded one (k_offset_terms64)
 static int32_t upload_offsets(cx_handle *h) {
-    const int d = h->cfg.dim;
+    const int d = h->cfg.dim, ud = h->user_dim ? h->user_dim : d;
+    const bool mfma = cx::is_mfma_dim(d);
     const int64_t ns = h->nslots;
     std::vector<double> bs((size_t)d * ns, 0.0);
     for (int64_t f = 0; f < h->nf; f++)
         for (int k = 0; k < 2; k++) {
             const int32_t sl = h->off_fac_slots[2 * (size_t)f + k];
             if (sl < 0) continue;
-            for (int i = 0; i < d; i++) bs[(size_t)i * ns + sl] = h->offsets[(size_t)f * d + i];
+            for (int i = 0; i < ud; i++) bs[mfma ? (size_t)sl * d + i : (size_t)i * ns + sl] = h->offsets[(size_t)f * ud + i];
         }
     CX_HIP(h, hipMemcpyAsync(h->d_off_b, bs.data(), bs.size() * 8, hipMemcpyHostToDevice, h->stream));
     cx::mv_launch_offset_terms(h);
@@ -234,12 +237,9 @@ static int32_t upload_offsets(cx_handle *h) {
     return CX_OK;
 }
 
-int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets) {
-    const std::string who = "cx_set_factor_offsets";
-    CX_REQUIRE(h, h, CX_ERR_INVALID_ARGUMENT, "null handle");
-    CX_REQUIRE(h, h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only");
-    CX_REQUIRE(h, h->cfg.dim != 1, CX_ERR_STATE, who + ": dim 1 factors carry b in their parameters (CX_FACTOR_GAUSS_LINEAR: params[2])");
-    CX_REQUIRE(h, h->cfg.dim <= 4 && !h->user_dim, CX_ERR_UNSUPPORTED, who + ": dim 2, 3 and 4 (the matrix-core dims, 5 - 64, have no offsets)");
+// what cx_set_factor_offsets (dim 2 - 4) and cx_set_factor_offsets_mfma (dim 5 - 64) share, after each has checked the handle's dim:
+// offsets is [n][the user's dim]
+static int32_t set_factor_offsets(cx_handle *h, const std::string &who, int64_t n, const int64_t *factor_ids, const double *offsets) {
     CX_REQUIRE(h, h->has_graph, CX_ERR_STATE, who + ": no graph");
     CX_REQUIRE(h, h->cfg.schedule != CX_SCHED_REFERENCE, CX_ERR_UNSUPPORTED,
                who + ": not for CX_SCHED_REFERENCE handles or wirings (cx_graph_wire): the reference order has no d-dimensional offset to be pinned against");
@@ -253,7 +253,7 @@ int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids
         CX_REQUIRE(h, st == hipStreamCaptureStatusNone, CX_ERR_STATE, who + ": the handle's stream is being captured (the call is synchronous)");
     }
     try {
-        const int d = h->cfg.dim;
+        const int d = h->user_dim ? h->user_dim : h->cfg.dim;      // (the caller's rows; the device arrays are cfg.dim wide)
         // everything is checked before anything changes
         std::vector<int64_t> fac((size_t)n);
         for (int64_t i = 0; i < n; i++) {
@@ -287,17 +287,37 @@ int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids
             CX_HIP(h, hipStreamSynchronize(h->stream));
             captured_graphs_drop(h);      // a captured sweep names the kernels' instances without offsets
             if ((rc = dev_upload(h, &h->d_off_rt, rt)) != CX_OK) return rc;
-            if ((rc = dev_alloc(h, &h->d_off_b, (int64_t)d * h->nslots)) != CX_OK) return rc;
-            if ((rc = dev_alloc(h, &h->d_off_g, (int64_t)d * h->nslots)) != CX_OK) return rc;
+            if ((rc = dev_alloc(h, &h->d_off_b, (int64_t)h->cfg.dim * h->nslots)) != CX_OK) return rc;
+            if ((rc = dev_alloc(h, &h->d_off_g, (int64_t)h->cfg.dim * h->nslots)) != CX_OK) return rc;
+            if (cx::is_mfma_dim(h->cfg.dim) && (rc = dev_alloc(h, &h->d_off_kappa, h->nslots)) != CX_OK) return rc;
             CX_HIP(h, hipStreamSynchronize(h->stream));      // (rt dies here)
             h->offsets.assign((size_t)h->nf * d, 0.0);
             h->has_offsets = true;
+            // the matrix-core dims' chain plans (chain scan, heavy paths of the tree schedule) name the links' linear terms: built again, once
+            if (cx::is_mfma_dim(h->cfg.dim)) { h->chains_dirty = true; h->tree_dirty = true; }      // (work site: the plans were built without the kOff space)
         }
         changed(*h, Change::RuleOffsets);
         for (int64_t i = 0; i < n; i++) std::copy(offsets + i * d, offsets + (i + 1) * d, h->offsets.begin() + fac[(size_t)i] * d);
         h->offsets_nonzero = std::any_of(h->offsets.begin(), h->offsets.end(), [](double v) { return v != 0.0; });
         return upload_offsets(h);
     } catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
+}
+
+int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets) {
+    const std::string who = "cx_set_factor_offsets";
+    CX_REQUIRE(h, h, CX_ERR_INVALID_ARGUMENT, "null handle");
+    CX_REQUIRE(h, h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only");
+    CX_REQUIRE(h, h->cfg.dim != 1, CX_ERR_STATE, who + ": dim 1 factors carry b in their parameters (CX_FACTOR_GAUSS_LINEAR: params[2])");
+    CX_REQUIRE(h, h->cfg.dim <= 4 && !h->user_dim, CX_ERR_UNSUPPORTED, who + ": dim 2, 3 and 4 (the matrix-core dims, 5 - 64: cx_set_factor_offsets_mfma)");
+    return set_factor_offsets(h, who, n, factor_ids, offsets);
+}
+
+int32_t cx_set_factor_offsets_mfma(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets) {
+    const std::string who = "cx_set_factor_offsets_mfma";
+    CX_REQUIRE(h, h, CX_ERR_INVALID_ARGUMENT, "null handle");
+    CX_REQUIRE(h, h->cfg.family == CX_FAMILY_GAUSSIAN, CX_ERR_UNSUPPORTED, who + ": the Gaussian family only");
+    CX_REQUIRE(h, cx::is_mfma_dim(h->cfg.dim), CX_ERR_UNSUPPORTED, who + ": dim 5 - 64 (dim 2, 3 and 4: cx_set_factor_offsets; dim 1 factors carry b in their parameters)");
+    return set_factor_offsets(h, who, n, factor_ids, offsets);
 }
 
 

@@ -9,7 +9,8 @@
 //   A segment [a, b] of a path (positions a..b, links a..b-1) has the pairwise potential of its two end variables with
 //   everything in between summed out — interior side information (likelihoods, priors) included, the ends' excluded:
 //       psi(x_a, x_b) = exp( -1/2 x_a' P x_a - 1/2 x_b' C x_b + x_b' B x_a + h' x_a + c' x_b ).
-//   A single link is the factor's rule table (P, B, C) with h = c = 0.  Two adjacent segments compose over their joint m
+//   A single link is the factor's rule table (P, B, C) with h = c = 0 — or, with factor offsets x_b = A x_a + b + w (Input.offsets), with
+//   the offset's linear terms at its two ends, h = g[the link's slot at a], c = g[the link's slot at b].  Two adjacent segments compose over their joint m
 //   (side information (eta_m, Lambda_m)):  M = C1 + Lambda_m + P2,  g = c1 + eta_m + h2,
 //       P = P1 - B1' M^-1 B1,  B = B2 M^-1 B1,  C = C2 - B2 M^-1 B2',  h = h1 + B1' M^-1 g,  c = c2 + B2 M^-1 g.
 //   The SAME potential serves both directions: forwards it is the rule (P, B, C, h, c) on the message entering a, backwards
@@ -34,7 +35,9 @@
 namespace cx {
 namespace plan64 {
 
-enum Space : int64_t { kZero = 0, kF2V = 1, kPtab = 2, kBtab = 3, kPot = 4, kEnt = 5, kAux = 6, kSpaces = 7 };
+// kOff: the linear terms of the factors' offsets, one d-vector per message slot (cx_set_factor_offsets_mfma); named only by a plan built
+// with Input.offsets
+enum Space : int64_t { kZero = 0, kF2V = 1, kPtab = 2, kBtab = 3, kPot = 4, kEnt = 5, kAux = 6, kOff = 7, kSpaces = 8 };
 constexpr int64_t kOffMask = ((int64_t)1 << 56) - 1;
 inline int64_t H(Space s, int64_t off) { return ((int64_t)s << 56) | off; }
 
@@ -65,6 +68,7 @@ struct Input {
     int K0 = 0;                         // links per level-0 block (0: chosen from the chain length and `lanes`)
     int fan = 2;                        // potentials per group of the upper levels
     int64_t lanes = 1024;               // waves the composition launch should fill (SIMDs of the device)
+    bool offsets = false;               // the factors carry offsets: a link's potential has h = g[from slot], c = g[to slot] (kOff) instead of the zero page
     bool root = false;                  // every path also gets the ONE potential of its two end variables (a time block of a partitioned
                                         // chain hands it to the other blocks: cx_chain_block_maps); the tree then has a single top segment
 };
@@ -108,6 +112,7 @@ inline Plan build(const Input &in) {
     auto pot_part = [&](int64_t id, int part) { return H(kPot, id * p.pot + (part < 4 ? part * dd : 4 * dd + (part - 4) * in.d)); };   // 0 P, 1 B, 2 Bt, 3 C, 4 h, 5 c
     auto ent = [&](int64_t id) { return H(kEnt, id * p.msg); };
     auto slot = [&](int32_t s) { return H(kF2V, (int64_t)s * p.msg); };
+    auto goff = [&](int32_t s) { return in.offsets ? H(kOff, (int64_t)s * in.d) : zero; };      // the offset's linear term at the slot's end
     auto sides_of = [&](int64_t pos, int64_t out[3]) {
         int n = 0;
         if (in.side_aux && in.side_aux[pos] >= 0) out[n++] = H(kAux, (int64_t)in.side_aux[pos] * p.msg);
@@ -163,7 +168,7 @@ inline Plan build(const Input &in) {
                 Job j{pot_part(s.pot, 0), (int32_t)p.children.size(), (int32_t)s.nchild};
                 for (int64_t l = s.child0; l < s.child0 + s.nchild; l++) {
                     const int64_t t = in.tab_fwd[l];
-                    Child c{H(kPtab, t * 3 * dd), H(kPtab, t * 3 * dd + dd), H(kBtab, t * dd), H(kPtab, t * 3 * dd + 2 * dd), zero, zero, {zero, zero, zero}, 0};
+                    Child c{H(kPtab, t * 3 * dd), H(kPtab, t * 3 * dd + dd), H(kBtab, t * dd), H(kPtab, t * 3 * dd + 2 * dd), goff(in.from[l]), goff(in.to[l]), {zero, zero, zero}, 0};
                     if (l > s.child0) sides_of(in.link_pos[l], c.side);
                     p.children.push_back(c);
                 }
@@ -219,7 +224,7 @@ inline Plan build(const Input &in) {
             Job jf{0, (int32_t)p.steps.size(), (int32_t)s.nchild};
             for (int64_t l = la; l <= lb; l++) {
                 const int64_t t = in.tab_fwd[l];
-                Step st{{zero, zero, zero}, H(kPtab, t * 3 * dd), H(kBtab, t * dd), H(kPtab, t * 3 * dd + 2 * dd), zero, zero, slot(in.to[l]), 0};
+                Step st{{zero, zero, zero}, H(kPtab, t * 3 * dd), H(kBtab, t * dd), H(kPtab, t * 3 * dd + 2 * dd), goff(in.from[l]), goff(in.to[l]), slot(in.to[l]), 0};
                 sources(l == la ? s.in_f : slot(in.to[l - 1]), in.link_pos[l], st.src);
                 p.steps.push_back(st);
             }
@@ -227,7 +232,7 @@ inline Plan build(const Input &in) {
             Job jb{0, (int32_t)p.steps.size(), (int32_t)s.nchild};
             for (int64_t l = lb; l >= la; l--) {
                 const int64_t t = in.tab_bwd[l];
-                Step st{{zero, zero, zero}, H(kPtab, t * 3 * dd), H(kBtab, t * dd), H(kPtab, t * 3 * dd + 2 * dd), zero, zero, slot(in.from[l]), 0};
+                Step st{{zero, zero, zero}, H(kPtab, t * 3 * dd), H(kBtab, t * dd), H(kPtab, t * 3 * dd + 2 * dd), goff(in.to[l]), goff(in.from[l]), slot(in.from[l]), 0};
                 sources(l == lb ? s.in_b : slot(in.from[l + 1]), (int64_t)in.link_pos[l] + 1, st.src);
                 p.steps.push_back(st);
             }

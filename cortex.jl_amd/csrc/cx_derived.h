@@ -23,7 +23,7 @@ enum class Change : int32_t {
     ForeignSweepRan,        // a reference-order call ran: messages changed behind the back of the other schedules' constants
     StateImported,          // cx_state_import: messages, marginals and the observed flags are another handle's
     GraphCreated,           // cx_graph_create flattened a graph into the handle
-    RuleOffsets,            // cx_set_factor_offsets (dim 2..4)
+    RuleOffsets,            // cx_set_factor_offsets (dim 2..4), cx_set_factor_offsets_mfma (dim 5..64)
     kCount
 };
 
@@ -125,8 +125,10 @@ void changed(H &h, Change c) {
         // what RuleMatrices voids and that reads eta: the messages out of observed variables, N(A y + b, Q), cached in both Jacobi buffers;
         // the chains' leaf messages and side sums.  Precisions, k-ary tables, the tree plan and the matrix cores' state do not see b.  (The
         // linear terms themselves are rewritten by the entry, and again by cx_set_factor_matrices: they follow (A, Q) too.)
+        // The matrix-core dims cache the same messages by k_point64, and a time block's potentials would hold the links' terms.
         h.param_epoch++;
         h.observed_passes_due = 2; h.chain_side_dirty = true;
+        if (mfma) { h.point64_dirty = true; h.pot64_fresh = false; }
         break;
     case Change::kCount: break;
     }

@@ -36,114 +36,24 @@
 // d_tval / d_tflag in place of k_evm_part and k_ev_final.  The term list keeps its order; the plan (evm::build_components) only
 // says which component every term belongs to.
 #include "cx_components.h"
-#include "cx_evidence_mfma_core.h"
-#include "cx_mfma_reader.h"
+#include "cx_evidence_mfma_terms.h"
 
 namespace cx {
 namespace evm {
 
 using namespace w64;
 
-// term record (8 int32): {kind, rule-table index, A offset, A count, B offset, B count, y0, y1}; A and B are runs of message slots in `srcs`
-//   kVar      B = every slot of the variable, y0 = d_i            kOpaque  B = the slot of the opaque message
-//   kFacFree  table 2 set + 1 (towards IN), A = the OUT variable's other slots, B = the IN variable's other slots
-//   kFacObs   table towards the free end, B = the free variable's other slots, y0 = the observed end's slot (its datum: v2f)
-//   kFacBoth  table 2 set + 1, y0 = the OUT end's slot, y1 = the IN end's slot
-constexpr int kVar = 0, kOpaque = 1, kFacFree = 2, kFacObs = 3, kFacBoth = 4;
-constexpr int kTB = 256;      // terms per block of k_evm_part
-
-// one wave per term.  ptab: [table][P | B | C], btab: [table] B' (upload_ptab); ldq[set] = log det 2πQ of the real block; u: the user's dim
+// one wave per term (evm_term, cx_evidence_mfma_terms.h: the records, the kinds and the arithmetic).  This is the entry point of a handle
+// without factor offsets; k_evm_terms_off (cx_evidence_mfma_off.hip) is the one of a handle with them
 template <int NT, int WAVES_PER_SIMD>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
 void k_evm_terms(int nterm, const int32_t *__restrict__ rec, const int32_t *__restrict__ srcs, const double *__restrict__ ptab,
                  const double *__restrict__ btab, const double *__restrict__ ldq, const double *__restrict__ f2v,
                  const double *__restrict__ v2f, const int u, double *__restrict__ tval, uint8_t *__restrict__ tflag) {
-    constexpr int KD = 16 * NT, KM = KD + KD * KD, NU = NT * (NT + 1) / 2;
     __shared__ double S[16 * kLdT];
     __shared__ double Vs[NT][16 * kLdT];
-    // Workgroups go to the eight XCDs in turn, each with an L2 of its own: XCD x takes the x-th eighth of the terms in index order, so
-    // that terms next to each other in the list — the host sorts them by variable: they share most of their message records — run at
-    // about the same time behind ONE L2
-    const int per = (nterm + 7) >> 3, w = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (w >= nterm) return;
-    const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, mo = g * KD + c;
-    const int32_t *t = rec + 8 * (int64_t)w;
-    const int kind = t[0], tab_i = t[1], a_off = t[2], a_n = t[3], b_off = t[4], b_n = t[5], y0 = t[6], y1 = t[7];
-    const double *tab = ptab + (int64_t)(tab_i < 0 ? 0 : tab_i) * 3 * KD * KD;
-    const double *bt = btab + (int64_t)(tab_i < 0 ? 0 : tab_i) * KD * KD;
-    const double hl2pi = 0.5 * u * ev::kLog2Pi;
-
-    if (kind == kFacBoth) {      // log N(y_o; A y_i, Q): r'Q⁻¹r = y_o'Q⁻¹y_o - 2 y_o'(Q⁻¹A y_i) + y_i'(A'Q⁻¹A) y_i from the table towards IN
-        double orv[NT][4], ocv[NT], irv[NT][4], icv[NT], po[NT], bi[NT], ci[NT];
-        load_y<NT>(v2f + (int64_t)y0 * KM, orv, ocv, g, c);
-        load_y<NT>(v2f + (int64_t)y1 * KM, irv, icv, g, c);
-        xty<NT>(tab, orv, po, mo);                       // Q⁻¹ y_o (P is symmetric)
-        xty<NT>(tab + KD * KD, irv, bi, mo);             // B' y_i = Q⁻¹A y_i
-        xty<NT>(tab + 2 * KD * KD, irv, ci, mo);         // C y_i
-        const double q = dot_cv<NT>(ocv, po, g, c, u) - 2.0 * dot_cv<NT>(ocv, bi, g, c, u) + dot_cv<NT>(icv, ci, g, c, u);
-        const bool undef = __builtin_isnan(q);
-        if (lane == 0) { tval[w] = undef ? 0.0 : -0.5 * ldq[tab_i >> 1] - 0.5 * q; tflag[w] = undef ? ev::kTermUndef : 0; }
-        return;
-    }
-
-    d4 Sm[NU];
-    double hcv[NT], zrv[NT][4];
-#pragma unroll
-    for (int i = 0; i < NU; i++) Sm[i] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < NT; j++) hcv[j] = 0.0;
-    double cst = 0.0;      // what the term holds besides ½ h'S⁻¹h - ½ log det S of the last factorisation
-    bool pd_a = true, undef_a = false;      // the first factorisation of a factor with two free ends: positive definite; its inputs undefined
-    if (kind == kFacFree) {
-        // the rule towards IN on m_{out→a} (rule64_body's passes), its message left in Sm / hcv
-        d4 M[NU];
-        double wcv[NT];
-#pragma unroll
-        for (int j = 0; j < NT; j++) wcv[j] = 0.0;
-        load_upper<NT>(M, [&](int k) { return ((gcdp)tab)[mo + k]; });
-        add_sources<NT>(M, wcv, f2v, srcs + a_off, a_n, mo, c);
-        undef_a = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
-        double ld1, q1;
-        factor_solve<NT>(M, wcv, zrv, S, Vs, g, c, u, ld1, q1, pd_a);
-        cst = -0.5 * ldq[tab_i >> 1] + 0.5 * q1 - 0.5 * ld1 + 2.0 * hl2pi;
-        __shared__ double ZS[KD];
-        park_z<NT>(ZS, zrv, g);
-        // Yt = U^-T B', then Λ' = C - Yt'Yt (upper tiles), η' = Yt' z
-        d4 Y[NT][NT];
-        solve_block_cols<NT, false>(Y, M, Vs, [&](int k) { return ((gcdp)bt)[mo + k]; }, g, c);
-        gram_pass<NT, -1>(Sm, Y, ZS, [&](int k) { return ((gcdp)tab)[2 * KD * KD + mo + k]; }, [&](int a, double v) { hcv[a] = v; }, g);
-    } else if (kind == kFacObs) {      // (kVar, kOpaque: S and h start at zero)
-        double yrv[NT][4], ycv[NT], py[NT];
-        load_y<NT>(v2f + (int64_t)y0 * KM, yrv, ycv, g, c);
-        xty<NT>(tab, yrv, py, mo);                       // P y
-        xty<NT>(bt, yrv, hcv, mo);                       // B y
-        cst = -0.5 * ldq[tab_i >> 1] - 0.5 * dot_cv<NT>(ycv, py, g, c, u) + hl2pi;
-        load_upper<NT>(Sm, [&](int k) { return ((gcdp)tab)[2 * KD * KD + mo + k]; });
-    }
-    add_sources<NT>(Sm, hcv, f2v, srcs + b_off, b_n, mo, c);
-    // Undefined: an INPUT is NaN (whole messages are NaN together; a NaN datum reaches hcv and cst).  A first factorisation that is not
-    // positive definite also leaves NaN in Λ', η' and cst: that term is "not positive definite", so with two free ends the inputs of the
-    // second stage are looked at themselves (Λ[0][0] and η[0] of every source record), not through Sm
-    bool undef = undef_a;
-    if (kind == kFacFree) undef = any_nan_record<NT>(undef, f2v, srcs + b_off, b_n);
-    else undef = __builtin_isnan(bcast(Sm[0][0], 0)) || __builtin_isnan(bcast(hcv[0], 0)) || __builtin_isnan(cst);
-    double ld, q;
-    bool pd;
-    factor_solve<NT>(Sm, hcv, zrv, S, Vs, g, c, u, ld, q, pd);
-    if (lane != 0) return;
-    double val;
-    unsigned fl = 0;
-    if (kind == kOpaque) {
-        val = (!undef && pd) ? 0.5 * ld - 0.5 * q - hl2pi : 0.0;      // improper (a flat forecast end) or undefined: no constant
-    } else {
-        const bool npd = !undef && !(pd && pd_a);
-        if (kind == kVar) { val = (double)(1 - y0) * (0.5 * q - 0.5 * ld + hl2pi); fl = ev::kTermVar; }
-        else val = cst + 0.5 * q - 0.5 * ld;
-        fl |= (undef ? ev::kTermUndef : 0u) | (npd ? ev::kTermNpd : 0u);
-        if (undef || npd) val = 0.0;
-    }
-    tval[w] = val;
-    tflag[w] = (uint8_t)fl;
+    __shared__ double ZS[16 * NT];
+    evm_term<NT, false>(nterm, rec, srcs, ptab, btab, ldq, f2v, v2f, nullptr, nullptr, u, tval, tflag, S, Vs, ZS);
 }
 
 // 256 terms -> one ev::Part (fixed-order tree); ev::final_sum adds the parts in index order
@@ -207,11 +117,11 @@ static int32_t build(cx_handle *h, Cache &C, const std::string &who) {
         const int32_t so = P.so[f], si = P.si[f], vo = P.vo[f], vi = P.vi[f], set = P.set[f];
         const bool oo = (h->vinfo[vo] & kClamped) != 0, oi = (h->vinfo[vi] & kClamped) != 0;
         if (oo && oi) term(std::min(vo, vi), kFacBoth, 2 * set + 1, {}, {}, so, si);
-        else if (oo) term(vi, kFacObs, 2 * set + 1, {}, mfr::other_slots(h, vi, si, srcs), so, 0);      // towards IN
-        else if (oi) term(vo, kFacObs, 2 * set, {}, mfr::other_slots(h, vo, so, srcs), si, 0);          // towards OUT
+        else if (oo) term(vi, kFacObs, 2 * set + 1, {}, mfr::other_slots(h, vi, si, srcs), so, si);      // towards IN
+        else if (oi) term(vo, kFacObs, 2 * set, {}, mfr::other_slots(h, vo, so, srcs), si, so);          // towards OUT
         else {
             const Run a = mfr::other_slots(h, vo, so, srcs);
-            term(std::min(vo, vi), kFacFree, 2 * set + 1, a, mfr::other_slots(h, vi, si, srcs), 0, 0);
+            term(std::min(vo, vi), kFacFree, 2 * set + 1, a, mfr::other_slots(h, vi, si, srcs), so, si);
         }
         C.n_fac++;
     }
@@ -303,6 +213,7 @@ static int32_t ready(cx_handle *h, const std::string &who, Cache *&Cp) {
 static void launch_terms(cx_handle *h, Cache &C) {
     const int n = (int)C.n_term, u = mfr::user_dim(h);
     if (!n) return;
+    if (h->has_offsets) { launch_terms_off(h, n, C.d_rec, C.d_srcs, C.ldq.d, C.d_tval, C.d_tflag); return; }      // cx_set_factor_offsets_mfma: the instances that read g and κ
     const unsigned grid = 8u * (unsigned)((n + 7) / 8);      // (k_evm_terms: an eighth of the terms per XCD)
     mfr::for_tiles(h->cfg.dim, [&](auto nt) {
         // waves per SIMD as the register counts allow; the launch bound makes hipcc keep to them without scratch.
@@ -332,7 +243,7 @@ extern "C" int32_t cx_log_evidence_mfma(cx_handle *h, double *value, int64_t *co
         namespace mfr = cx::mfr;
         const std::string who = "cx_log_evidence_mfma";
         int32_t rc;
-        if ((rc = mfr::prepare(h, who, value && counts4 ? nullptr : "null argument", {"cx_log_evidence", "no variational free energy, no Beta-Bernoulli evidence", "terms"})) != CX_OK)
+        if ((rc = mfr::prepare(h, who, value && counts4 ? nullptr : "null argument", {"cx_log_evidence", "no variational free energy, no Beta-Bernoulli evidence", "terms", true})) != CX_OK)
             return rc;
         evm::Cache *Cp = nullptr;
         if ((rc = evm::ready(h, who, Cp)) != CX_OK) return rc;
@@ -351,7 +262,7 @@ extern "C" int32_t cx_log_evidence_components_mfma(cx_handle *h, int64_t cap, do
         const std::string who = "cx_log_evidence_components_mfma";
         const char *bad = !n_components || !counts4 ? "null n_components or counts4" : cap < 0 ? "cap < 0" : cap > 0 && !values ? "cap > 0 with null values" : nullptr;
         int32_t rc;
-        if ((rc = mfr::prepare(h, who, bad, {"cx_log_evidence_components", "no variational free energy, no Beta-Bernoulli evidence", "terms"})) != CX_OK) return rc;
+        if ((rc = mfr::prepare(h, who, bad, {"cx_log_evidence_components", "no variational free energy, no Beta-Bernoulli evidence", "terms", true})) != CX_OK) return rc;
         evm::Cache *Cp = nullptr;
         if ((rc = evm::ready(h, who, Cp)) != CX_OK) return rc;
         evm::Cache &C = *Cp;

@@ -34,19 +34,31 @@ using cx::plan64::Plan;
 
 extern "C" {
 
-void *cxh_plan64_create(int32_t d, int64_t npos, int64_t nlinks, const int32_t *link_pos, const int32_t *from, const int32_t *to,
-                        const int32_t *tab_fwd, const int32_t *tab_bwd, const uint8_t *head_fwd, const uint8_t *head_bwd,
-                        const int32_t *side, int32_t K0, int32_t fan, int64_t lanes, int32_t root, char *err, int32_t errlen) {
+static void *plan64_create(bool offsets, int32_t d, int64_t npos, int64_t nlinks, const int32_t *link_pos, const int32_t *from, const int32_t *to,
+                           const int32_t *tab_fwd, const int32_t *tab_bwd, const uint8_t *head_fwd, const uint8_t *head_bwd, const int32_t *side,
+                           int32_t K0, int32_t fan, int64_t lanes, int32_t root, char *err, int32_t errlen) {
     try {
         cx::plan64::Input in;
         in.d = d; in.npos = npos; in.nlinks = nlinks; in.link_pos = link_pos; in.from = from; in.to = to;
         in.tab_fwd = tab_fwd; in.tab_bwd = tab_bwd; in.head_fwd = head_fwd; in.head_bwd = head_bwd; in.side = side;
-        in.K0 = K0; in.fan = fan; in.lanes = lanes; in.root = root != 0;
+        in.K0 = K0; in.fan = fan; in.lanes = lanes; in.root = root != 0; in.offsets = offsets;
         return new Plan(cx::plan64::build(in));
     } catch (const std::exception &e) {
         if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", e.what());
         return nullptr;
     }
+}
+
+void *cxh_plan64_create(int32_t d, int64_t npos, int64_t nlinks, const int32_t *link_pos, const int32_t *from, const int32_t *to,
+                        const int32_t *tab_fwd, const int32_t *tab_bwd, const uint8_t *head_fwd, const uint8_t *head_bwd,
+                        const int32_t *side, int32_t K0, int32_t fan, int64_t lanes, int32_t root, char *err, int32_t errlen) {
+    return plan64_create(false, d, npos, nlinks, link_pos, from, to, tab_fwd, tab_bwd, head_fwd, head_bwd, side, K0, fan, lanes, root, err, errlen);
+}
+// the same plan for a handle with factor offsets (Input.offsets: the links' h and c name rows of the kOff space)
+void *cxh_plan64_create_offsets(int32_t d, int64_t npos, int64_t nlinks, const int32_t *link_pos, const int32_t *from, const int32_t *to,
+                                const int32_t *tab_fwd, const int32_t *tab_bwd, const uint8_t *head_fwd, const uint8_t *head_bwd,
+                                const int32_t *side, int32_t K0, int32_t fan, int64_t lanes, int32_t root, char *err, int32_t errlen) {
+    return plan64_create(true, d, npos, nlinks, link_pos, from, to, tab_fwd, tab_bwd, head_fwd, head_bwd, side, K0, fan, lanes, root, err, errlen);
 }
 
 void cxh_plan64_destroy(void *p) { delete (Plan *)p; }

@@ -191,10 +191,12 @@ struct DevState {
     int64_t ptab_sets = 0, ptab_bt_sets = 0;      // parameter sets the device tables have room for (rewritten in place while that holds)
     DevBuf<double> d_mv_f2v, d_mv_f2v_alt, d_mv_v2f, d_mv_marg, d_mv_prev;
     int mv_max_deg = 0;             // dim 2..4: widest slice of the graph (0: not computed yet)
-    // cx_set_factor_offsets (dim 2..4): x_out = A x_in + b + N(0, Q).  Allocated by the first call, for every slot, and rewritten in place
+    // cx_set_factor_offsets (dim 2..4; cx_set_factor_offsets_mfma at the matrix-core dims: the same arrays as [nslots][d], a vector per slot,
+    // h->offsets in the user's dim): x_out = A x_in + b + N(0, Q).  Allocated by the first call, for every slot, and rewritten in place
     // from then on (a captured sweep holds d_off_g by value): the offset of each slot's factor, [d][nslots]; the linear term it puts at
     // the slot's end, [d][nslots] (k_mv_offset_terms, again after cx_set_factor_matrices); the rule table of the messages INTO each slot
     DevBuf<double> d_off_b, d_off_g;
+    DevBuf<double> d_off_kappa;     // the matrix-core dims: b'Q⁻¹b of each slot's factor, [nslots] (k_offset_terms64; the evidence reads it)
     DevBuf<int32_t> d_off_rt;
     // d = 64 work lists (built lazily: they depend on which variables are observed)
     bool work64_dirty = true, point64_dirty = true;
@@ -526,6 +528,7 @@ void mv64w_launch_rule(cx_handle *h, int nwork, const int32_t *d_rec, const doub
 void mv64_launch_marginals(cx_handle *h, int n, const int32_t *d_vars, const double *f2v, double *out);
 void mv64w_launch_marginal_rule(cx_handle *h, int n, const int32_t *d_rec, const double *ident_tab, const double *ident_bt, const double *sums, double *out);
 void mv64_launch_point(cx_handle *h, int nwork, const int32_t *d_slots, double *out_a, double *out_b);
+void mv64_launch_offset_terms(cx_handle *h);      // cx_set_factor_offsets_mfma: d_off_b and the rule tables -> d_off_g, [nslots][d]
 void mv64_launch_v2f(cx_handle *h, int n, const int32_t *d_slots, const int32_t *d_vars, const double *f2v);
 void mv64_launch_damp(cx_handle *h, int n, const int32_t *d_rec, const double *old, double *out, double lam);
 void mv64_launch_range_sums(cx_handle *h, int n, const int32_t *d_rec4, const double *f2v, double *out);      // rec: destination row, n sources, first slot, slot stride

@@ -22,6 +22,10 @@
 //   an observed IN end (datum y):   μ_i = y, Σ_ii = 0; stage 1 as it is (E[x_out] = M⁻¹(η_o + bt y))
 // Embedded dims: every matrix is block-diagonal (real block, identity block) and so is every product; rows and sums hold the real
 // block only, d below is the user's.
+// Factor offsets (cx_set_factor_offsets_mfma; OFF, entry points of their own): x_out = A x_in + b + N(0, Q) puts the linear terms g_out, g_in
+//   (goff: by slot, [nslots][KD]) into the factor's potential — η_o + g_out enters stage 1, η_i + η' + g_in stage 2 (an observed OUT end:
+//   η' = B y as before) — and the statistics' residual is r = x_out - A x_in - b: E[r] = m0 + J μ_i - b with the factor's own b (boff: by
+//   slot, the same layout; it may differ within a group), Cov as it was.
 // Undefined / not positive definite: cx_log_evidence_mfma's rules.  An input record (or datum) that is NaN: undefined; a failed pivot of
 // either factorisation: not positive definite; with two free ends the inputs of the second stage are looked at themselves.
 //
@@ -157,12 +161,12 @@ __device__ __forceinline__ void xty_ws(const Mat X, const double (&yrv)[NT][4], 
 // A count, B offset, B count, OUT slot, IN slot}; A / B: the OUT / IN variable's other message slots in `srcs` (a free end only)
 // wbeg (null: wave w takes partial w): the partials of wave w; pbeg (null: partial p is item p): the items of partial p; items: factor indices
 // ptab: [table][P | B | C], btab: [table] B' (upload_ptab); atab: [set][A | A']; u: the user's dim
-template <int NT, bool STATS, int WAVES_PER_SIMD>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
-void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32_t *__restrict__ pbeg, const int32_t *__restrict__ items,
-                  const int32_t *__restrict__ rec, const int32_t *__restrict__ srcs, const double *__restrict__ ptab, const double *__restrict__ btab,
-                  const double *__restrict__ atab, const double *__restrict__ f2v, const double *__restrict__ v2f, const int u, double *ws_all,
-                  double *acc_all, int32_t *__restrict__ meta, double *__restrict__ out) {
+template <int NT, bool STATS, bool OFF>
+__device__ __forceinline__ void lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32_t *__restrict__ pbeg, const int32_t *__restrict__ items,
+                                           const int32_t *__restrict__ rec, const int32_t *__restrict__ srcs, const double *__restrict__ ptab,
+                                           const double *__restrict__ btab, const double *__restrict__ atab, const double *__restrict__ f2v,
+                                           const double *__restrict__ v2f, const double *__restrict__ goff, const double *__restrict__ boff, const int u,
+                                           double *ws_all, double *acc_all, int32_t *__restrict__ meta, double *__restrict__ out) {
     constexpr int KD = 16 * NT, KM = KD + KD * KD, NU = NT * (NT + 1) / 2, DD = KD * KD;
     __shared__ double S[16 * kLdT];
     __shared__ double Vs[NT][16 * kLdT];
@@ -184,6 +188,8 @@ void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32
             const double *ptab_ = ptab, *btab_ = btab, *atab_ = atab, *f2v_ = f2v, *v2f_ = v2f;
             double *ws_ = ws_all + (int64_t)w * ws_doubles(KD);
             asm volatile("" : "+s"(ptab_), "+s"(btab_), "+s"(atab_), "+s"(f2v_), "+s"(v2f_), "+s"(ws_));
+            const double *goff_ = goff, *boff_ = boff;
+            if constexpr (OFF) asm volatile("" : "+s"(goff_), "+s"(boff_));
             const gdp ws = (gdp)ws_;
             const gdp P0 = ws, P2 = ws + 2 * DD, P4 = ws + 4 * DD, vf = ws + kNMat * DD, vx = vf + KD;      // (the element-wise passes at the end)
             const BufAcc wsb = buf_of((gcdp)ws);
@@ -206,6 +212,11 @@ void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32
                 for (int j = 0; j < NT; j++) wcv[j] = 0.0;
                 evm::load_upper<NT>(M, [&](int k) { return tabP.ld(mo, k); });
                 evm::add_sources<NT>(M, wcv, f2v_, srcs + a_off, a_n, mo, c);
+                if constexpr (OFF) {      // η_o + g_out
+                    const gcdp go = (gcdp)(goff_ + (int64_t)so * KD);
+#pragma unroll
+                    for (int j = 0; j < NT; j++) wcv[j] += go[16 * j + c];
+                }
                 undef = __builtin_isnan(bcast(M[0][0], 0)) || __builtin_isnan(bcast(wcv[0], 0));      // (whole messages are NaN together)
                 if (STATS) {      // Λ_o whole, for K = M⁻¹ Λ_o A
 #pragma unroll 1
@@ -262,6 +273,11 @@ void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32
                     }
                 if (!oo) undef = evm::any_nan_record<NT>(undef, f2v_, srcs + b_off, b_n);      // (a first factorisation that failed left NaN in Λ', η')
                 evm::add_sources<NT>(Sm, hcv, f2v_, srcs + b_off, b_n, mo, c);
+                if constexpr (OFF) {      // η_i + η' + g_in
+                    const gcdp gi = (gcdp)(goff_ + (int64_t)si * KD);
+#pragma unroll
+                    for (int j = 0; j < NT; j++) hcv[j] += gi[16 * j + c];
+                }
                 if (oo) undef = undef || __builtin_isnan(bcast(Sm[0][0], 0)) || __builtin_isnan(bcast(hcv[0], 0));
                 evm::factor_solve<NT>(Sm, hcv, zrv, S, Vs, g, c, u, ld, q, pd);
                 solve_cols<NT, true>(Sm, Vs, W1, W1, g, c, mo);
@@ -287,7 +303,11 @@ void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32
             mm_tn<NT>(W4, W5, W0, true, W3, 1.0, mo);
             if (g == 0) {
 #pragma unroll
-                for (int j = 0; j < NT; j++) { vf[16 * j + c] = m0cv[j] + fcv[j]; vx[16 * j + c] = mucv[j]; }
+                for (int j = 0; j < NT; j++) {
+                    double f = m0cv[j] + fcv[j];
+                    if constexpr (OFF && STATS) f -= ((gcdp)(boff_ + (int64_t)so * KD))[16 * j + c];      // r = x_out - A x_in - b
+                    vf[16 * j + c] = f; vx[16 * j + c] = mucv[j];
+                }
             }
             ws_sync();
             const bool npd = !undef && !(pd_a && pd);
@@ -326,6 +346,24 @@ void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32
         }
         if (STATS && lane == 0) { meta[2 * p] = n_undef; meta[2 * p + 1] = n_npd; }
     }
+}
+
+template <int NT, bool STATS, int WAVES_PER_SIMD>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
+void k_lm_factors(const int nwave, const int32_t *__restrict__ wbeg, const int32_t *__restrict__ pbeg, const int32_t *__restrict__ items,
+                  const int32_t *__restrict__ rec, const int32_t *__restrict__ srcs, const double *__restrict__ ptab, const double *__restrict__ btab,
+                  const double *__restrict__ atab, const double *__restrict__ f2v, const double *__restrict__ v2f, const int u, double *ws_all,
+                  double *acc_all, int32_t *__restrict__ meta, double *__restrict__ out) {
+    lm_factors<NT, STATS, false>(nwave, wbeg, pbeg, items, rec, srcs, ptab, btab, atab, f2v, v2f, nullptr, nullptr, u, ws_all, acc_all, meta, out);
+}
+// the factors of a handle with factor offsets
+template <int NT, bool STATS, int WAVES_PER_SIMD>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
+void k_lm_factors_off(const int nwave, const int32_t *__restrict__ wbeg, const int32_t *__restrict__ pbeg, const int32_t *__restrict__ items,
+                      const int32_t *__restrict__ rec, const int32_t *__restrict__ srcs, const double *__restrict__ ptab, const double *__restrict__ btab,
+                      const double *__restrict__ atab, const double *__restrict__ f2v, const double *__restrict__ v2f, const double *__restrict__ goff,
+                      const double *__restrict__ boff, const int u, double *ws_all, double *acc_all, int32_t *__restrict__ meta, double *__restrict__ out) {
+    lm_factors<NT, STATS, true>(nwave, wbeg, pbeg, items, rec, srcs, ptab, btab, atab, f2v, v2f, goff, boff, u, ws_all, acc_all, meta, out);
 }
 
 // row g of out = the rows gbeg[g] .. gbeg[g + 1] - 1 of acc, added in index order
@@ -407,7 +445,7 @@ static void fill_atab(const cx_handle *h, std::vector<double> &at) {
 static int32_t prepare(cx_handle *h, const std::string &who, const char *small_dims, const char *bad_args, Cache *&out) {
     using namespace cxh;
     int32_t rc;
-    if ((rc = mfr::prepare(h, who, bad_args, {small_dims, "the variational and Beta-Bernoulli families have no Gaussian factor beliefs", "factors"})) != CX_OK) return rc;
+    if ((rc = mfr::prepare(h, who, bad_args, {small_dims, "the variational and Beta-Bernoulli families have no Gaussian factor beliefs", "factors", true})) != CX_OK) return rc;
     if (h->learn_mfma && h->learn_mfma->vinfo_epoch != h->vinfo_epoch) h->learn_mfma.reset();      // other variables are observed
     if (!h->learn_mfma) h->learn_mfma.reset(new Cache());
     Cache &C = *h->learn_mfma;
@@ -497,6 +535,10 @@ static void launch(cx_handle *h, Cache &C, int nwave, const int32_t *wbeg, const
     const int u = mfr::user_dim(h);
     mfr::for_tiles(h->cfg.dim, [&](auto nt) {
         constexpr int NT = decltype(nt)::value, W = NT == 4 ? 1 : 2;      // (4 x 4 tiles at two waves per SIMD: 7 to 11 registers spilled, so one)
+        if (h->has_offsets)      // cx_set_factor_offsets_mfma: the instances that read g and b
+            hipLaunchKernelGGL((k_lm_factors_off<NT, STATS, W>), dim3((unsigned)nwave), dim3(64), 0, h->stream, nwave, wbeg, pbeg, items, C.d_rec, C.d_srcs, h->d_ptab,
+                               h->d_ptab_bt, C.atab.d, h->d_mv_f2v, h->d_mv_v2f, (const double *)h->d_off_g, (const double *)h->d_off_b, u, C.d_ws, C.d_acc, C.d_meta, out);
+        else
         hipLaunchKernelGGL((k_lm_factors<NT, STATS, W>), dim3((unsigned)nwave), dim3(64), 0, h->stream, nwave, wbeg, pbeg, items, C.d_rec, C.d_srcs, h->d_ptab,
                            h->d_ptab_bt, C.atab.d, h->d_mv_f2v, h->d_mv_v2f, u, C.d_ws, C.d_acc, C.d_meta, out);
     });

@@ -92,7 +92,8 @@ inline Run other_slots(const cx_handle *h, int32_t v, int32_t skip, std::vector<
 
 // ---- the refusals of a call ---------------------------------------------------------------------------------------------------------------
 // the words of a caller: the call for dims 1 .. 4, what the other families lack, what a partitioned handle would need owners for
-struct Words { const char *small, *lack, *owners; };
+// takes_offsets: the call reads the factor offsets of cx_set_factor_offsets_mfma; the others refuse while one is non-zero
+struct Words { const char *small, *lack, *owners; bool takes_offsets = false; };
 
 inline int32_t prepare(cx_handle *h, const std::string &who, const char *bad_args, const Words &w) {
     using namespace cxh;
@@ -103,6 +104,9 @@ inline int32_t prepare(cx_handle *h, const std::string &who, const char *bad_arg
     // (a user wiring, cx_graph_wire, cannot exist here: it is refused at these dims)
     CX_REQUIRE(h, !h->chain_partition && !h->halo_state && h->send_slots.empty() && h->recv_slots.empty(), CX_ERR_UNSUPPORTED,
                who + ": not for a partitioned handle (halo lists, state halos or a chain's time block: its " + w.owners + " would need owners)");
+    // factor offsets at these dims: a reader that does not take them refuses while one is non-zero (dim 2 - 4's rule for its uncovered
+    // readers) — none computes as if b were 0
+    CX_REQUIRE(h, w.takes_offsets || !h->offsets_nonzero, CX_ERR_UNSUPPORTED, who + ": the handle has non-zero factor offsets (cx_set_factor_offsets_mfma), which this call does not implement");
     CX_HIP(h, hipSetDevice(h->cfg.device));
     if (h->stream) {
         hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

@@ -416,6 +416,7 @@ void mv_launch_residual(cx_handle *h, const double *cur, const double *prev, int
 }
 // d_off_b (the offsets by slot) and the rule tables -> d_off_g (the slots' linear terms)
 void mv_launch_offset_terms(cx_handle *h) {
+    if (cx::is_mfma_dim(h->cfg.dim)) { mv64_launch_offset_terms(h); return; }      // [nslots][d] there (cx_mv64.hip)
     const dim3 g((unsigned)((h->nslots + kBlock - 1) / kBlock)), b(kBlock);
 #define CX_MV(DD) hipLaunchKernelGGL((k_mv_offset_terms<DD>), g, b, 0, h->stream, h->nslots, h->d_off_rt, h->d_ptab, h->d_off_b, h->d_off_g)
     if (h->cfg.dim == 2) CX_MV(2);

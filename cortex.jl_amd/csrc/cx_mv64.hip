@@ -513,12 +513,13 @@ __global__ __launch_bounds__(kBlock, 3) void k_rule64s(int nwork, const int32_t 
     if (tid < kD) out[dst + tid] = eo[tid];
 }
 
-// observed senders: Lambda_out = C, eta_out = B y  (one workgroup per message; pure streaming)
-__global__ __launch_bounds__(kBlock) void k_point64(const int kd, int nwork, const int32_t *__restrict__ work_slots, const int32_t *__restrict__ partner,
-                                                    const int32_t *__restrict__ spdir, const double *__restrict__ ptab,
-                                                    const double *__restrict__ v2f, double *__restrict__ out_a, double *__restrict__ out_b) {
+// observed senders: Lambda_out = C, eta_out = B y  (one workgroup per message; pure streaming).  GOFF (a handle with factor offsets,
+// cx_set_factor_offsets_mfma): eta_out = g[destination slot] + B y — the datum itself takes no term
+template <bool GOFF>
+__device__ __forceinline__ void point64_body(const int kd, int nwork, const int32_t *__restrict__ work_slots, const int32_t *__restrict__ partner,
+                                             const int32_t *__restrict__ spdir, const double *__restrict__ ptab, const double *__restrict__ v2f,
+                                             const double *__restrict__ goff, double *__restrict__ out_a, double *__restrict__ out_b, double *y) {
     const int km = kd + kd * kd;      // doubles per message record: eta[kd] | Lambda[kd][kd]
-    __shared__ double y[64];
     const int w = blockIdx.x;
     if (w >= nwork) return;
     const int slot = work_slots[w], tid = threadIdx.x;
@@ -535,9 +536,55 @@ __global__ __launch_bounds__(kBlock) void k_point64(const int kd, int nwork, con
     if (tid < kd) {
         double s = 0.0;
         for (int k = 0; k < kd; k++) s += tab[kd * kd + tid * kd + k] * y[k];
+        if (GOFF) s += goff[(int64_t)partner[slot] * kd + tid];
         out_a[dst + tid] = s;
         out_b[dst + tid] = s;
     }
+}
+__global__ __launch_bounds__(kBlock) void k_point64(const int kd, int nwork, const int32_t *__restrict__ work_slots, const int32_t *__restrict__ partner,
+                                                    const int32_t *__restrict__ spdir, const double *__restrict__ ptab,
+                                                    const double *__restrict__ v2f, double *__restrict__ out_a, double *__restrict__ out_b) {
+    __shared__ double y[64];
+    point64_body<false>(kd, nwork, work_slots, partner, spdir, ptab, v2f, nullptr, out_a, out_b, y);
+}
+__global__ __launch_bounds__(kBlock) void k_point64_off(const int kd, int nwork, const int32_t *__restrict__ work_slots, const int32_t *__restrict__ partner,
+                                                        const int32_t *__restrict__ spdir, const double *__restrict__ ptab, const double *__restrict__ v2f,
+                                                        const double *__restrict__ goff, double *__restrict__ out_a, double *__restrict__ out_b) {
+    __shared__ double y[64];
+    point64_body<true>(kd, nwork, work_slots, partner, spdir, ptab, v2f, goff, out_a, out_b, y);
+}
+
+// The linear terms of the factors' offsets at the matrix-core dims (cx_set_factor_offsets_mfma), one workgroup per slot: g = Q^-1 b at the
+// OUT end of the slot's factor, -A' Q^-1 b at its IN end — C b and -B b of the (P | B | C) triple of the messages INTO the slot (rt[slot]:
+// its index, odd = the slot is the IN end; -1: no pairwise rule factor, g = 0).  b and g: [nslots][kd], one contiguous vector per slot (a
+// wave of the rule kernel reads one slot's).  An embedded dim: b is zero above the user's dim and the tables are blockdiag(., I) there, so
+// g is zero there too.  kap[slot] = κ = b'Q⁻¹b of the slot's factor, the constant the offset leaves in the factor's potential (the evidence
+// reads it; both slots of a factor hold it): Q⁻¹ is the C of a triple towards OUT and the P of one towards IN.  Runs when offsets or rule
+// matrices change, never in a sweep.
+__global__ __launch_bounds__(64) void k_offset_terms64(const int kd, int64_t nslots, const int32_t *__restrict__ rt, const double *__restrict__ ptab,
+                                                       const double *__restrict__ b, double *__restrict__ g, double *__restrict__ kap) {
+    __shared__ double bv[64];
+    const int64_t s = blockIdx.x;
+    const int i = threadIdx.x;
+    if (s >= nslots) return;
+    const int t = rt[s];
+    bv[i] = i < kd ? b[s * kd + i] : 0.0;
+    __syncthreads();
+    if (t < 0) {
+        if (i < kd) g[s * kd + i] = 0.0;
+        if (i == 0) kap[s] = 0.0;
+        return;
+    }
+    const double *tab = ptab + (int64_t)t * 3 * kd * kd;
+    const double *M = tab + ((t & 1) ? kd * kd : 2 * kd * kd), *Qi = tab + ((t & 1) ? 0 : 2 * kd * kd);
+    double a = 0.0, q = 0.0;
+    if (i < kd) {
+        for (int k = 0; k < kd; k++) { a += M[i * kd + k] * bv[k]; q += Qi[i * kd + k] * bv[k]; }
+        g[s * kd + i] = (t & 1) ? -a : a;
+    }
+    q *= bv[i];
+    for (int m = 1; m < 64; m <<= 1) q += __shfl_xor(q, m, 64);      // (the workgroup is one wave)
+    if (i == 0) kap[s] = q;
 }
 
 // variable→factor message of a listed slot, on demand: the sum of the variable's other incoming messages
@@ -677,7 +724,8 @@ void mv64_launch_rule(cx_handle *h, int nwork, const int32_t *d_rec, const doubl
     // form below (8.8 ms).  Read per launch so that a test can switch forms inside one process.
     const char *form_env = getenv("CX_RULE64");
     const int wave_form = (form_env && form_env[0] == 'g' && h->cfg.dim == kD) ? 0 : 1;      // (the workgroup forms are written for 64)
-    if (wave_form && (!classic || h->cfg.dim != kD))
+    // (a handle with offsets, cx_set_factor_offsets_mfma: the wave form whatever the switches say — the workgroup forms do not read them)
+    if (h->has_offsets || (wave_form && (!classic || h->cfg.dim != kD)))
         mv64w_launch_rule(h, nwork, d_rec, f2v_in, f2v_out);
     else if (classic)
         hipLaunchKernelGGL((k_rule64<0>), dim3(nwork), dim3(kBlock), 0, h->stream, nwork, d_rec, (const int32_t *)nullptr, h->d_vbase, h->d_var_deg, h->d_vinfo,
@@ -720,8 +768,18 @@ void mv64_launch_marginals(cx_handle *h, int n, const int32_t *d_vars, const dou
 
 void mv64_launch_point(cx_handle *h, int nwork, const int32_t *d_slots, double *out_a, double *out_b) {
     if (nwork == 0) return;
+    if (h->has_offsets)
+        hipLaunchKernelGGL(k_point64_off, dim3(nwork), dim3(kBlock), 0, h->stream, h->cfg.dim, nwork, d_slots, h->d_partner, h->d_spdir, h->d_ptab,
+                           h->d_mv_v2f, (const double *)h->d_off_g, out_a, out_b);
+    else
     hipLaunchKernelGGL(k_point64, dim3(nwork), dim3(kBlock), 0, h->stream, h->cfg.dim, nwork, d_slots, h->d_partner, h->d_spdir, h->d_ptab,
                        h->d_mv_v2f, out_a, out_b);
+}
+
+// d_off_b (the offsets by slot) and the rule tables -> d_off_g (the slots' linear terms), dim 16 / 32 / 64
+void mv64_launch_offset_terms(cx_handle *h) {
+    if (h->nslots == 0) return;
+    hipLaunchKernelGGL(k_offset_terms64, dim3((unsigned)h->nslots), dim3(64), 0, h->stream, h->cfg.dim, h->nslots, h->d_off_rt, h->d_ptab, h->d_off_b, h->d_off_g, h->d_off_kappa);
 }
 
 void mv64_launch_v2f(cx_handle *h, int n, const int32_t *d_slots, const int32_t *d_vars, const double *f2v) {

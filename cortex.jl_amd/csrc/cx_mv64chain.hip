@@ -84,6 +84,12 @@ void k_walk64b(int njobs, const DJob *__restrict__ jobs, const DStep *__restrict
         asm volatile("" : "+v"(lane));
         lane &= 63;
         const int g = lane >> 4, c = lane & 15;
+        // the affine rule at two waves per SIMD (the link walks of a handle with factor offsets): h and c take the registers that
+        // were left, so z waits in LDS (rule64_body: Z_IN_LDS) — in registers this instance spilled five of them
+        if constexpr (AFFINE && WAVES_PER_SIMD == 2) {
+            __shared__ double ZS[kD];
+            if (!rule64b_apply<true, true>(st->P, st->Bt, st->C, st->h, st->c, st->src[0], st->src[1], st->src[2], st->has2 != 0, st->dst, S, Vs, lane, g, c, ZS)) break;
+        } else
         if (!rule64b_apply<AFFINE>(st->P, st->Bt, st->C, st->h, st->c, st->src[0], st->src[1], st->src[2], st->has2 != 0, st->dst, S, Vs, lane, g, c)) break;
         // the next step reads what this one stored (its entering message): the stores have to have left the wave
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -507,13 +513,14 @@ struct Chain64 {
     std::vector<p64::Job> jobs;            // the plan's records (handles), kept to be resolved again when a base pointer moves
     std::vector<p64::Child> children;
     std::vector<p64::Step> steps;
-    double *bases[p64::kSpaces] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // what the device records were resolved against
+    double *bases[p64::kSpaces] = {};     // what the device records were resolved against
     double *d_pot = nullptr, *d_ent = nullptr, *d_ring = nullptr;      // d_ring: the Y2 hand-off of k_compose64p, 32 KB per job of the widest launch
     // positions with three or more side slots (a path variable of degree 5 .. 8): their side information is summed into one message of
     // this arena at the head of every sweep (k_side64), and the plan reads that one
     double *d_aux = nullptr;
     int32_t *d_aux_src = nullptr;          // 8 slots per arena message, -1 = none
     int64_t n_aux = 0;
+    bool offsets = false;                  // built for a handle with factor offsets: the links' h and c name rows of d_off_g (kOff)
     struct Launch { int kind; int64_t first; int n; int steps; };      // kind 0: compose, 1: walk over potentials, 2: walk along links; steps: longest job
     std::vector<Launch> launches;
     int64_t n_pot = 0, n_ent = 0, n_compositions = 0, n_rules = 0;
@@ -824,6 +831,7 @@ static int32_t chain64_make(cx_handle *h, Chain64 **out, bool root, const std::v
     // the walks) or two (2 x 2) waves per SIMD, and their time is a wave's chain of dependent pivots: more, shorter blocks
     in.lanes = 4 * (int64_t)ncu * (h->cfg.dim == 16 ? env_int("CX_MVC_NT_WAVES", 3) : h->cfg.dim == 32 ? env_int("CX_MVC_NT_WAVES", 2) : 1);
     in.root = root;                              // a time block hands its whole potential to the other blocks
+    in.offsets = h->has_offsets;                 // cx_set_factor_offsets_mfma: the links carry the offsets' linear terms
     p64::Plan plan;
     try { plan = p64::build(in); }
     catch (const std::bad_alloc &) { return fail(h, CX_ERR_OUT_OF_MEMORY, "chain-scan schedule, dim 64: host allocation failed"); }
@@ -831,6 +839,7 @@ static int32_t chain64_make(cx_handle *h, Chain64 **out, bool root, const std::v
     Chain64 *c = new (std::nothrow) Chain64();
     if (!c) return fail(h, CX_ERR_OUT_OF_MEMORY, "chain-scan schedule, dim 64: host allocation failed");
     *out = c;
+    c->offsets = in.offsets;
     c->n_pot = plan.n_pot; c->n_ent = plan.n_ent; c->K0 = plan.K0; c->fan = plan.fan; c->levels = plan.levels;
     c->n_compositions = plan.n_compositions; c->n_rules = plan.n_rules;
     c->n_roots = (int)plan.root_pot.size();
@@ -875,7 +884,7 @@ static int32_t chain64_make(cx_handle *h, Chain64 **out, bool root, const std::v
 // The device records hold POINTERS: the plan's handles resolved against the six base pointers of the moment.  Redone (host loop +
 // one upload per array) only when a base has moved: new rule tables (cx_set_factor_matrices) or a new plan.
 static int32_t chain64_resolve(cx_handle *h, Chain64 *c) {
-    double *bases[p64::kSpaces] = {h->d_zero_msg, h->d_mv_f2v, h->d_ptab, h->d_ptab_bt, c->d_pot, c->d_ent, c->d_aux};
+    double *bases[p64::kSpaces] = {h->d_zero_msg, h->d_mv_f2v, h->d_ptab, h->d_ptab_bt, c->d_pot, c->d_ent, c->d_aux, c->offsets ? (double *)h->d_off_g : nullptr};
     if (std::memcmp(bases, c->bases, sizeof bases) == 0) return CX_OK;
     try {
         auto ptr = [&](int64_t hd) { return (uint64_t)(uintptr_t)(bases[hd >> 56] + (hd & p64::kOffMask)); };
@@ -955,11 +964,15 @@ static int32_t chain64_run(cx_handle *h, Chain64 *c, bool skip_compose) {
             const bool two = dim == 32;
             if (L.kind == 0) { if (two) hipLaunchKernelGGL(k_compose_nt<2>, dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_children); else hipLaunchKernelGGL(k_compose_nt<1>, dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_children); }
             else if (L.kind == 1) { if (two) hipLaunchKernelGGL((k_walk_nt<2, true>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps); else hipLaunchKernelGGL((k_walk_nt<1, true>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps); }
+            else if (c->offsets) { if (two) hipLaunchKernelGGL((k_walk_nt<2, true>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps); else hipLaunchKernelGGL((k_walk_nt<1, true>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps); }      // the links carry offsets: h, c = rows of g
             else { if (two) hipLaunchKernelGGL((k_walk_nt<2, false>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps); else hipLaunchKernelGGL((k_walk_nt<1, false>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps); }
         } else if (L.kind == 0) {
             hipLaunchKernelGGL(k_compose64p, dim3(L.n), dim3(128), 0, h->stream, L.n, c->d_jobs + L.first, c->d_children, c->d_ring);
         } else if (L.kind == 1) {          // few jobs: a wave alone on its SIMD
             hipLaunchKernelGGL((k_walk64b<1, true>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps);
+        } else if (c->offsets) {           // the links carry offsets (h, c = rows of g): the affine instances
+            if (walk_waves == 1) hipLaunchKernelGGL((k_walk64b<1, true>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps);
+            else hipLaunchKernelGGL((k_walk64b<2, true>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps);
         } else if (walk_waves == 1) {
             hipLaunchKernelGGL((k_walk64b<1, false>), dim3(L.n), dim3(64), 0, h->stream, L.n, c->d_jobs + L.first, c->d_steps);
         } else {

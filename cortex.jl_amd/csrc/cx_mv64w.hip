@@ -43,14 +43,14 @@ using namespace w64;
 //   factorisation   M upper tiles (80) + the column-layout temporaries of diag_factor (~100); V_k go to LDS (2 KB each)
 //   solve           U off-diagonal (48) + Yt column blocks as they are finished (<= 160) + one V tile / negated U tile (16)
 //   Gram + store    Yt (160) + one G tile, one C tile; every G tile leaves for HBM as soon as its 16 instructions are done
-template <int WAVES_PER_SIMD, int NT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
-void k_rule64w(int nwork, const int32_t *__restrict__ work_rec, const double *__restrict__ ptab, const double *__restrict__ btab,
-               const double *__restrict__ zero_msg, const double *__restrict__ f2v_in, const double *__restrict__ v2f,
-               double *__restrict__ out) {
+// one work record, by one wave: where the sources are, then the rule.  GOFF (cx_set_factor_offsets_mfma, entry points of their own below):
+// the linear terms of the factor's offset, one KD-vector per slot — hv = g[sender slot] joins the sender's eta (also the sum k_v2f64
+// stored for a "fixed" sender), cv = g[destination slot] the outgoing one; without GOFF nothing of it is compiled
+template <bool GOFF, int NT>
+__device__ __forceinline__ void rule64w_record(int nwork, const int32_t *__restrict__ work_rec, const double *__restrict__ ptab, const double *__restrict__ btab,
+                                               const double *__restrict__ zero_msg, const double *__restrict__ f2v_in, const double *__restrict__ v2f,
+                                               const double *__restrict__ goff, double *__restrict__ out, double *S, double (*Vs)[16 * kLdT]) {
     constexpr int KD = 16 * NT, KM = KD + KD * KD;      // (round 6) NT x NT tiles of 16: d = 16, 32, 64; a record is eta[KD] | Lambda[KD][KD]
-    __shared__ double S[16 * kLdT];
-    __shared__ double Vs[NT][16 * kLdT];
     const int w = blockIdx.x;
     if (w >= nwork) return;
     const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
@@ -65,28 +65,59 @@ void k_rule64w(int nwork, const int32_t *__restrict__ work_rec, const double *__
     const double *src1 = (!fixed && s1 >= 0) ? f2v_in + (int64_t)s1 * KM : zero_msg;
     const bool has2 = !fixed && s2 >= 0;
     const double *src2 = has2 ? f2v_in + (int64_t)s2 * KM : zero_msg;
+    const double *hv = GOFF ? goff + (int64_t)slot * KD : nullptr, *cv = GOFF ? goff + (int64_t)dst_slot * KD : nullptr;
 
-    (void)rule64w_apply<false, false, NT>((gcdp)tab, (gcdp)bt, (gcdp)(tab + 2 * KD * KD), nullptr, nullptr, (gcdp)src0, (gcdp)src1, (gcdp)src2, has2,
-                                          (gdp)(out + (int64_t)dst_slot * KM), S, Vs, lane, g, c);
+    (void)rule64w_apply<GOFF, false, NT>((gcdp)tab, (gcdp)bt, (gcdp)(tab + 2 * KD * KD), (gcdp)hv, (gcdp)cv, (gcdp)src0, (gcdp)src1, (gcdp)src2, has2,
+                                         (gdp)(out + (int64_t)dst_slot * KM), S, Vs, lane, g, c);
+}
+
+template <int WAVES_PER_SIMD, int NT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
+void k_rule64w(int nwork, const int32_t *__restrict__ work_rec, const double *__restrict__ ptab, const double *__restrict__ btab,
+               const double *__restrict__ zero_msg, const double *__restrict__ f2v_in, const double *__restrict__ v2f,
+               double *__restrict__ out) {
+    __shared__ double S[16 * kLdT];
+    __shared__ double Vs[NT][16 * kLdT];
+    rule64w_record<false, NT>(nwork, work_rec, ptab, btab, zero_msg, f2v_in, v2f, nullptr, out, S, Vs);
+}
+
+// the same rule for a handle with factor offsets: goff = [nslots][KD] (k_offset_terms64, cx_mv64.hip)
+template <int WAVES_PER_SIMD, int NT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES_PER_SIMD, WAVES_PER_SIMD)))
+void k_rule64w_off(int nwork, const int32_t *__restrict__ work_rec, const double *__restrict__ ptab, const double *__restrict__ btab,
+                   const double *__restrict__ zero_msg, const double *__restrict__ f2v_in, const double *__restrict__ v2f,
+                   const double *__restrict__ goff, double *__restrict__ out) {
+    __shared__ double S[16 * kLdT];
+    __shared__ double Vs[NT][16 * kLdT];
+    rule64w_record<true, NT>(nwork, work_rec, ptab, btab, zero_msg, f2v_in, v2f, goff, out, S, Vs);
 }
 
 // the launch for the handle's tile count; the tables and the stored variable→factor messages may be given (the marginal read-out of
 // dim 16 / 32 runs the rule on a table of its own: P = 0, B = I, C = 0 gives (M^-1 eta, -M^-1))
-static void launch_rule_tiles(cx_handle *h, int nwork, const int32_t *d_rec, const double *ptab, const double *btab, const double *f2v_in, const double *v2f, double *out) {
+static void launch_rule_tiles(cx_handle *h, int nwork, const int32_t *d_rec, const double *ptab, const double *btab, const double *f2v_in, const double *v2f, double *out,
+                              const double *goff = nullptr) {
     static const int one = [] { const char *e = getenv("CX_RULE64_WAVES"); return (e && e[0] == '1') ? 1 : 0; }();
     // (holding back the odd wave slot of every SIMD's first pair by half a message, so that the two waves would not run their
     // vector and matrix phases in lockstep, was measured in tools/ab_c5.py: no difference at 2, 3, 4 or 6 x 8k cycles)
     // 1 x 1 and 2 x 2 tiles hold their matrices in a few registers: four waves per SIMD (128 registers: the diagonal tile's column arrays)
 #define CX_R(W, N) hipLaunchKernelGGL((k_rule64w<W, N>), dim3(nwork), dim3(64), 0, h->stream, nwork, d_rec, ptab, btab, h->d_zero_msg, f2v_in, v2f, out)
-    if (h->cfg.dim == 16) CX_R(4, 1);
+#define CX_RO(W, N) hipLaunchKernelGGL((k_rule64w_off<W, N>), dim3(nwork), dim3(64), 0, h->stream, nwork, d_rec, ptab, btab, h->d_zero_msg, f2v_in, v2f, goff, out)
+    if (goff) {      // a handle with offsets: the instances that read them
+        if (h->cfg.dim == 16) CX_RO(4, 1);
+        else if (h->cfg.dim == 32) CX_RO(4, 2);
+        else if (one) CX_RO(1, 4);
+        else CX_RO(2, 4);
+    }
+    else if (h->cfg.dim == 16) CX_R(4, 1);
     else if (h->cfg.dim == 32) CX_R(4, 2);
     else if (one) CX_R(1, 4);
     else CX_R(2, 4);
 #undef CX_R
+#undef CX_RO
 }
 
 void mv64w_launch_rule(cx_handle *h, int nwork, const int32_t *d_rec, const double *f2v_in, double *f2v_out) {
-    launch_rule_tiles(h, nwork, d_rec, h->d_ptab, h->d_ptab_bt, f2v_in, h->d_mv_v2f, f2v_out);
+    launch_rule_tiles(h, nwork, d_rec, h->d_ptab, h->d_ptab_bt, f2v_in, h->d_mv_v2f, f2v_out, h->has_offsets ? (const double *)h->d_off_g : nullptr);
 }
 
 // marginals of dim 16 / 32 (dim 64: k_rule64<1>, cx_mv64.hip): `sums` holds the sum of every incoming message of the w-th listed

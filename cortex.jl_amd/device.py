@@ -100,6 +100,16 @@ class DeviceGraph:
             raise ValueError(f"b must be [{len(f)}, {self.dim}]")
         self._check(self.lib.cx_set_factor_offsets(self.h, len(f), _p(f, C.c_int64) if len(f) else None, _p(b, C.c_double) if len(f) else None))
 
+    def set_factor_offsets_mfma(self, factor_ids, b):
+        """cx_set_factor_offsets_mfma (dim 5..64): set_factor_offsets for a handle on the matrix-core kernels; b: [n, dim] in the handle's own
+        (user's) dim.  log_evidence_mfma, log_evidence_components_mfma, factor_beliefs_mfma and factor_statistics_mfma take the offsets; the
+        other derived calls of these dims refuse while an offset is non-zero."""
+        f = _i64(np.atleast_1d(factor_ids))
+        b = _f64(b).reshape(-1, self.dim) if len(f) else _f64(np.zeros((0, self.dim)))
+        if len(b) != len(f):
+            raise ValueError(f"b must be [{len(f)}, {self.dim}]")
+        self._check(self.lib.cx_set_factor_offsets_mfma(self.h, len(f), _p(f, C.c_int64) if len(f) else None, _p(b, C.c_double) if len(f) else None))
+
     def linear_factors_of_set(self, parameter_set: int):
         """the ids of the two-variable CX_FACTOR_GAUSS_LINEAR factors that name `parameter_set` (dim > 1), from what graph_create was given"""
         lin = self._factor_kind == L.FACTOR_GAUSS_LINEAR
@@ -402,7 +412,7 @@ class DeviceGraph:
 
     def factor_statistics_mfma(self, factor_ids=None, groups=None, n_groups=None):
         """cx_factor_statistics_mfma: factor_statistics at the matrix-core dims (a handle created with dim 5 .. 64) — the same
-        arguments, dict keys, shapes, counts and NaN rule, r = x_out - A x_in (no offsets exist there).  One wave per factor on the f64
+        arguments, dict keys, shapes, counts and NaN rule, r = x_out - A x_in - b (b: set_factor_offsets_mfma, 0 unless set).  One wave per factor on the f64
         matrix cores; sums in a fixed order, bit-identical across calls.  factor_statistics itself keeps refusing these dims."""
         return self._factor_statistics(self.lib.cx_factor_statistics_mfma, factor_ids, groups, n_groups)
 

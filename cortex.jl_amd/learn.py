@@ -98,7 +98,7 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_
         raise ValueError("em: dim 2..4 (dim 1 has per-factor parameters: call factor_statistics with explicit groups and m_step)")
     mfma = dev.dim >= 5      # the matrix-core dims: log_evidence_mfma and factor_statistics_mfma
     if mfma and offsets is not None:
-        raise ValueError("em: offsets= at dim 5..64: these dims have no per-factor offsets (set_factor_offsets is dim 2..4)")
+        raise ValueError("em: offsets= at dim 5..64: em_mfma takes them (set_factor_offsets is dim 2..4, set_factor_offsets_mfma dim 5..64)")
     if mfma and by_component:
         raise ValueError("em: by_component=True at dim 5..64: log_evidence_components does not exist at these dims (log_evidence_mfma gives the total)")
     params = {int(s): (np.array(A, float), np.array(Q, float)) for s, (A, Q) in sets.items()}
@@ -128,14 +128,42 @@ def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_
     return trace, params
 
 
+def em_mfma(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None):
+    """em for a DeviceGraph of dim 5..64: the same iterations (_em_loop) on log_evidence_mfma and factor_statistics_mfma, with per-factor
+    offsets through set_factor_offsets_mfma.  sets, learn, the trace and what makes it non-decreasing: as em.
+
+    offsets: None, or {set: b} with em's meaning — every two-variable CX_FACTOR_GAUSS_LINEAR factor of that set starts at
+    x_out = A x_in + b + N(0, Q), and "b" may be learned for it, one b per set.  Always returns (trace, params, offsets); offsets is
+    {set: b}, empty when none was given."""
+    if dev.dim < 5:
+        raise ValueError("em_mfma: dim 5..64 (dim 2..4: em)")
+    params = {int(s): (np.array(A, float), np.array(Q, float)) for s, (A, Q) in sets.items()}
+    for s, (A, Q) in params.items():
+        dev.set_factor_matrices(s, A, Q)
+    offs = {int(s): np.array(b, float).reshape(-1) * np.ones(dev.dim) for s, b in (offsets or {}).items()}
+    if not set(offs) <= set(params):
+        raise ValueError("em_mfma: offsets names a set that sets does not")
+    facs = {}
+    for s, b in offs.items():
+        facs[s] = dev.linear_factors_of_set(s)
+        dev.set_factor_offsets_mfma(facs[s], np.tile(b, (len(facs[s]), 1)))
+    for s in params:
+        ls = learn.get(s, ("A", "Q")) if isinstance(learn, dict) else learn
+        if "b" in ls and s not in offs:
+            raise ValueError(f'em_mfma: "b" is learned for the sets that offsets names (set {s} is not one)')
+    trace = _em_loop(dev, params, offs, facs, n_iter, sweeps_per_iter, learn, lambda: dev.log_evidence_mfma()[0])
+    return trace, params, offs
+
+
 def _em_loop(dev, params, offs, facs, n_iter, sweeps_per_iter, learn, evidence):
-    """The iterations of em and multi_start_em on a handle that holds the starting parameters: sweep → evidence() (the trace's row) →
-    factor_statistics (factor_statistics_mfma at dim 5..64), one group per parameter set → m_step → set_factor_matrices (and the
-    offsets of the sets in offs).  params and offs are updated in place; returns the n_iter + 1 rows."""
+    """The iterations of em, em_mfma and multi_start_em on a handle that holds the starting parameters: sweep → evidence() (the trace's
+    row) → factor_statistics (factor_statistics_mfma at dim 5..64), one group per parameter set → m_step → set_factor_matrices (and the
+    offsets of the sets in offs, by the setter of the handle's dim).  params and offs are updated in place; returns the n_iter + 1 rows."""
     if dev.schedule not in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE):
         warnings.warn("em: the log-evidence is guaranteed non-decreasing only under an exact E-step (chain scan, tree, reference order on "
                       "a forest)", RuntimeWarning, stacklevel=3)
     statistics = dev.factor_statistics_mfma if dev.dim >= 5 else dev.factor_statistics
+    set_offsets = dev.set_factor_offsets_mfma if dev.dim >= 5 else dev.set_factor_offsets
     n_groups = max(params) + 1
     trace = []
     for it in range(n_iter + 1):
@@ -153,7 +181,7 @@ def _em_loop(dev, params, offs, facs, n_iter, sweeps_per_iter, learn, evidence):
             dev.set_factor_matrices(s, *params[s])
             if offs is not None and s in offs:
                 offs[s] = new["b"]
-                dev.set_factor_offsets(facs[s], np.tile(offs[s], (len(facs[s]), 1)))
+                set_offsets(facs[s], np.tile(offs[s], (len(facs[s]), 1)))
     return trace
 
 

@@ -770,13 +770,35 @@ int32_t cx_causal_marginals(cx_handle *h, int32_t mode, int32_t lag, int64_t n, 
  * exchange blobs as before).
  * A handle on which the function was never called launches the kernels it always launched; a handle whose offsets are all 0 computes the
  * same numbers (==) through the offset instances of the kernels.
- * Refused: dim 1 CX_ERR_STATE (dim 1 factors carry b in their parameters); dim 5 - 64, other families, CX_SCHED_REFERENCE handles (wired
+ * Refused: dim 1 CX_ERR_STATE (dim 1 factors carry b in their parameters); dim 5 - 64 (cx_set_factor_offsets_mfma is theirs), other families, CX_SCHED_REFERENCE handles (wired
  * or not: the reference order has nothing to pin a d-dimensional offset against), a partitioned handle (halo lists, state halos, a
  * chain's time block — and configuring a halo or asking for block maps on a handle that has offsets) CX_ERR_UNSUPPORTED; a factor of
  * another kind (CX_FACTOR_GAUSS_LINEAR_N included) CX_ERR_UNSUPPORTED, naming it; an unknown id CX_ERR_NOT_FOUND; a non-finite entry,
  * n < 0 or NULL arrays with n > 0 CX_ERR_INVALID_ARGUMENT; no graph or a captured stream CX_ERR_STATE.  A refused call changes nothing.
  * Synchronous. */
 int32_t cx_set_factor_offsets(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets);
+
+/* ---- per-factor offsets, dim 5 - 64 (added after ABI 9: a new function breaks no caller, CX_ABI_VERSION stays) ----
+ * cx_set_factor_offsets_mfma: cx_set_factor_offsets for a handle of dim 5 - 64 — a state-space model with a control input B u_t, a drift
+ * or an observation mean y = H x + c + v at d = 16.  offsets: [n][the user's dim], row-major (an embedded dim, 5 - 15, 17 - 31, 33 - 63:
+ * the caller's rows; nothing of b reaches the identity block of the padding).  The contract is cx_set_factor_offsets' own: offsets of
+ * factors not named, the initial value 0, n == 0, finite values only, unknown id, factor of another kind, captured stream, no graph, the
+ * checkpoint fingerprint, and what cx_set_factor_matrices afterwards does.
+ * What it does: the linear terms g_out = Q^-1 b, g_in = -A' Q^-1 b are kept per message slot as one contiguous vector
+ * each; the wave-per-message rule takes g of the sender's slot into its input eta and g of the destination slot into its output (its
+ * offset instances; an observed sender: eta_p = g_p + B y), the chain plans name the same vectors as the h and c of a link's potential.
+ * Covered: CX_SCHED_FUSED (senders of degree 5 - 8 and damping included), CX_SCHED_CHAIN_SCAN, CX_SCHED_TREE (level plans, heavy paths,
+ * the captured sweep), cx_update_batch message items, cx_get_marginals / cx_get_messages / cx_get_products / cx_residual (they read
+ * messages), and of the derived calls cx_log_evidence_mfma, cx_log_evidence_components_mfma, cx_factor_beliefs_mfma and
+ * cx_factor_statistics_mfma (r = x_out - A x_in - b with the factor's own b).  cx_predictive_mfma, cx_predictive_rows_mfma,
+ * cx_causal_marginals_mfma, cx_sample_posterior_mfma and cx_linear_moments_mfma return CX_ERR_UNSUPPORTED, naming this function, while any
+ * offset is non-zero, and work as before once all are 0 again: no call computes as if b were 0.
+ * A handle on which the function was never called launches the kernels it always launched; a handle whose offsets are all 0 computes the
+ * same numbers (==) through the offset instances.
+ * Refused: dim 1 - 4 CX_ERR_UNSUPPORTED (naming cx_set_factor_offsets); other families, CX_SCHED_REFERENCE handles, a partitioned handle
+ * (and configuring a halo or asking for block maps afterwards) CX_ERR_UNSUPPORTED; the argument errors of cx_set_factor_offsets.  A
+ * refused call changes nothing.  Synchronous. */
+int32_t cx_set_factor_offsets_mfma(cx_handle *h, int64_t n, const int64_t *factor_ids, const double *offsets);
 
 /* ---- connected components and the log-evidence of each (added after ABI 9: a new function breaks no caller, CX_ABI_VERSION stays; no
  * counterpart in the reference) ----
@@ -870,7 +892,7 @@ int32_t cx_log_evidence_components_mfma(cx_handle *h, int64_t cap, double *value
  * CALLER's dim: a belief row is 2d + (2d)^2 doubles, a statistics row 1 + 2d + 3d^2.  A dim embedded in the next tile size (5 .. 15 in
  * 16, 17 .. 31 in 32, 33 .. 63 in 64, or one forced by CX_MFMA_DIM) returns the real block only, with the real model's values at any
  * internal tile size.  Covered: the two-variable CX_FACTOR_GAUSS_LINEAR factor with either, both or none of its ends observed; opaque
- * messages are part of each variable's sum.  There are no offsets at these dims: r = x_out - A x_in.  They read what
+ * messages are part of each variable's sum.  r = x_out - A x_in - b with the factor's own b (cx_set_factor_offsets_mfma; 0 unless set).  They read what
  * cx_log_evidence_mfma reads (the STORED factor→variable messages and the data; a leave-one-out message is the sum of the variable's
  * other messages, never a difference), work after every schedule, are exact on forests at a fixed point and give the Bethe factor
  * beliefs elsewhere.  One wave per factor on the f64 matrix cores: OUT is eliminated first, IN's marginal follows, and

@@ -82,6 +82,11 @@ class Handle {
         need(offsets.size(), factor_ids.size() * (size_t)dim_, "set_factor_offsets offsets");
         check(cx_set_factor_offsets(h_, (int64_t)factor_ids.size(), factor_ids.empty() ? nullptr : factor_ids.data(), offsets.empty() ? nullptr : offsets.data()));
     }
+    // dim 5 - 64: the same through the matrix-core kernels (cx_set_factor_offsets_mfma); offsets: the user's dim doubles per factor
+    void set_factor_offsets_mfma(const std::vector<int64_t> &factor_ids, const std::vector<double> &offsets) {
+        need(offsets.size(), factor_ids.size() * (size_t)dim_, "set_factor_offsets_mfma offsets");
+        check(cx_set_factor_offsets_mfma(h_, (int64_t)factor_ids.size(), factor_ids.empty() ? nullptr : factor_ids.data(), offsets.empty() ? nullptr : offsets.data()));
+    }
     cx_stats stats() const { cx_stats s{}; check(cx_graph_stats(h_, &s)); return s; }
     // CX_SCHED_TREE: { depth, stages, items, k-ary entries, components, messages up, messages down, marginals } of the last sweep's plan
     std::array<int64_t, 8> tree_plan_stats() const { std::array<int64_t, 8> o{}; check(cx_tree_plan_stats(h_, o.data())); return o; }
