@@ -92,6 +92,8 @@ SIGNATURES = {
     "cx_factor_statistics": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pd, _pi64]),
     "cx_factor_beliefs_mfma": (_i32, [_vp, _i64, _pi64, _pd]),
     "cx_factor_statistics_mfma": (_i32, [_vp, _i64, _pi64, _pi64, _i64, _pd, _pi64]),
+    "cx_factor_disturbances_mfma": (_i32, [_vp, _i64, _pi64, _pd, _pd, _pd, _pi64]),
+    "cx_factor_disturbance_rows_mfma": (_i32, [_vp, _i64, _pi64, _pi64]),
     "cx_sample_posterior": (_i32, [_vp, _i64, C.c_uint64, _pd, _i64, _pi64, _pd, _pi64]),
     "cx_linear_moments": (_i32, [_vp, _i64, _pi64, _pi64, _pd, _pd, _pd, _pi64]),
     "cx_linear_moments_mfma": (_i32, [_vp, _i64, _pi64, _pi64, _pd, _pd, _pd, _pi64]),

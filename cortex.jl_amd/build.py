@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcortex_hip.so")
-SOURCES = ["cx_api.hip", "cx_api_mv.hip", "cx_api_msg.hip", "cx_api_sweep.hip", "cx_api_halo.hip", "cx_api_ipc.hip", "cx_api_state.hip", "cx_api_ref.hip", "cx_health.hip", "cx_evidence.hip", "cx_evidence_mfma.hip", "cx_evidence_mfma_off.hip", "cx_learn.hip", "cx_learn_mfma.hip", "cx_sample.hip", "cx_sample_mfma.hip", "cx_functional.hip", "cx_functional_mfma.hip", "cx_predict.hip", "cx_predict_mfma.hip", "cx_causal.hip", "cx_causal_mfma.hip", "cx_kernels.hip", "cx_sweep_pair.hip", "cx_sweep_deep.hip", "cx_batch.hip", "cx_kary.hip", "cx_kary_mv.hip", "cx_chain.hip", "cx_planscan.hip", "cx_mv.hip", "cx_mvchain.hip", "cx_mv64chain.hip", "cx_mvbatch.hip", "cx_mv64.hip", "cx_mv64w.hip", "cx_comm.hip", "cx_vmp.hip"]
+SOURCES = ["cx_api.hip", "cx_api_mv.hip", "cx_api_msg.hip", "cx_api_sweep.hip", "cx_api_halo.hip", "cx_api_ipc.hip", "cx_api_state.hip", "cx_api_ref.hip", "cx_health.hip", "cx_evidence.hip", "cx_evidence_mfma.hip", "cx_evidence_mfma_off.hip", "cx_learn.hip", "cx_learn_mfma.hip", "cx_disturb_mfma.hip", "cx_sample.hip", "cx_sample_mfma.hip", "cx_functional.hip", "cx_functional_mfma.hip", "cx_predict.hip", "cx_predict_mfma.hip", "cx_causal.hip", "cx_causal_mfma.hip", "cx_kernels.hip", "cx_sweep_pair.hip", "cx_sweep_deep.hip", "cx_batch.hip", "cx_kary.hip", "cx_kary_mv.hip", "cx_chain.hip", "cx_planscan.hip", "cx_mv.hip", "cx_mvchain.hip", "cx_mv64chain.hip", "cx_mvbatch.hip", "cx_mv64.hip", "cx_mv64w.hip", "cx_comm.hip", "cx_vmp.hip"]
 # every header a source may include: a change in any of them rebuilds everything
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "cortex_hip.h")]
 

@@ -262,7 +262,8 @@ struct DevState {
     std::unique_ptr<ev::Cache, Deleter<ev::Cache>> evidence;
     // cx_log_evidence_mfma (cx_evidence_mfma.hip): the term lists of the matrix-core dims, the log-det table and the call's scratch
     std::unique_ptr<evm::Cache, Deleter<evm::Cache>> evidence_mfma;
-    // cx_factor_beliefs_mfma / cx_factor_statistics_mfma (cx_learn_mfma.hip): the factor records, the grouping's partials and the workspace
+    // cx_factor_beliefs_mfma / cx_factor_statistics_mfma (cx_learn_mfma.hip) and cx_factor_disturbances_mfma (cx_disturb_mfma.hip): the factor
+    // records, the grouping's partials, the disturbances' rows and the workspace
     std::unique_ptr<lm::Cache, Deleter<lm::Cache>> learn_mfma;
     std::unique_ptr<fs::Cache, Deleter<fs::Cache>> learn;
     std::unique_ptr<sp::Plan, Deleter<sp::Plan>> sample;

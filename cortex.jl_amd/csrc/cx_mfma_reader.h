@@ -1,5 +1,5 @@
 // cx_mfma_reader.h — the host kit of the readers of the stored messages at the matrix-core dims: cx_evidence_mfma.hip, cx_learn_mfma.hip,
-// cx_predict_mfma.hip, cx_causal_mfma.hip and cx_sample_mfma.hip.  What the graph says about its two-variable rule factors, the refusals of a call, the key
+// cx_disturb_mfma.hip, cx_predict_mfma.hip, cx_causal_mfma.hip and cx_sample_mfma.hip.  What the graph says about its two-variable rule factors, the refusals of a call, the key
 // of the last request, a parameter table that follows param_epoch, the payload through a bounded device buffer, the totals of a call and
 // the choice of the tile count.  The wave side: cx_evidence_mfma_core.h.
 #pragma once

@@ -102,7 +102,7 @@ class DeviceGraph:
 
     def set_factor_offsets_mfma(self, factor_ids, b):
         """cx_set_factor_offsets_mfma (dim 5..64): set_factor_offsets for a handle on the matrix-core kernels; b: [n, dim] in the handle's own
-        (user's) dim.  log_evidence_mfma, log_evidence_components_mfma, factor_beliefs_mfma and factor_statistics_mfma take the offsets; the
+        (user's) dim.  log_evidence_mfma, log_evidence_components_mfma, factor_beliefs_mfma, factor_statistics_mfma and factor_disturbances_mfma take the offsets; the
         other derived calls of these dims refuse while an offset is non-zero."""
         f = _i64(np.atleast_1d(factor_ids))
         b = _f64(b).reshape(-1, self.dim) if len(f) else _f64(np.zeros((0, self.dim)))
@@ -443,6 +443,37 @@ class DeviceGraph:
                  "S_rr": out[:, o:o + d * d].reshape(G, d, d).copy(), "S_rx": out[:, o + d * d:o + 2 * d * d].reshape(G, d, d).copy(),
                  "S_xx": out[:, o + 2 * d * d:].reshape(G, d, d).copy()}
         return stats, dict(zip(("factors", "groups", "undefined", "not_positive_definite"), [int(x) for x in cnt]))
+
+    def factor_disturbance_rows_mfma(self):
+        """cx_factor_disturbance_rows_mfma: the factor ids of the rows factor_disturbances_mfma(factor_ids=None) returns, ascending"""
+        return self._predictive_rows(self.lib.cx_factor_disturbance_rows_mfma)
+
+    def factor_disturbances_mfma(self, factor_ids=None, rows=True):
+        """cx_factor_disturbances_mfma: the smoothed disturbance of every two-variable x_out = A x_in + b + w, w ~ N(0, Q), factor of a
+        handle created with dim 5 .. 64 — PER FACTOR what factor_statistics_mfma sums per group (r = x_out - A x_in - b is w).
+        factor_ids=None: every such factor in ascending id; otherwise the named ones in the caller's order.  Returns {"factor_ids",
+        "mean" [n, d] = E[r | data], "cov" [n, d, d] = Cov(r | data), "expected_mahalanobis" [n] = E[r'Q⁻¹r | data], "mahalanobis" [n]
+        = E[r]'Q⁻¹E[r], "total" (the sum of expected_mahalanobis over the finite rows: minus twice the quadratic part of the EM
+        Q-function), "counts"}; a row with an undefined input or a failed factorisation is NaN (counts "undefined" /
+        "not_positive_definite").  rows=False: no "mean" and "cov" (the scores, the total and the counts alone come to the host, and
+        they are the bits of the call with rows).  learn.auxiliary_residuals standardises the means."""
+        d = self.dim
+        f = None if factor_ids is None else _i64(np.atleast_1d(factor_ids))
+        pf = None if f is None else _p(f, C.c_int64)
+        n = 0 if f is None else len(f)
+        ids = self.factor_disturbance_rows_mfma() if f is None else f
+        tot, cnt = C.c_double(), (C.c_int64 * 4)()
+        sc = np.zeros((len(ids), 2), dtype=np.float64)
+        out = np.zeros((len(ids), d + d * d), dtype=np.float64) if rows else None
+        self._check(self.lib.cx_factor_disturbances_mfma(self.h, n, pf, _p(out, C.c_double) if rows and out.size else None,
+                                                         _p(sc, C.c_double) if sc.size else None, C.byref(tot), cnt))
+        assert cnt[0] == len(ids)
+        res = {"factor_ids": ids, "expected_mahalanobis": sc[:, 0].copy(), "mahalanobis": sc[:, 1].copy(), "total": float(tot.value),
+               "counts": dict(zip(("rows", "finite", "undefined", "not_positive_definite"), [int(x) for x in cnt]))}
+        if rows:
+            res["mean"] = out[:, :d].copy()
+            res["cov"] = out[:, d:].reshape(len(ids), d, d).copy()
+        return res
 
     def predictive_rows(self):
         """cx_predictive_rows: the factor ids of the rows predictive(factor_ids=None) scores, ascending"""

@@ -73,6 +73,21 @@ def group(stats, g):
     return {k: np.asarray(v)[g] for k, v in stats.items()}
 
 
+def auxiliary_residuals(dist, Q):
+    """The auxiliary residuals of the disturbance smoother (Durbin and Koopman) from DeviceGraph.factor_disturbances_mfma's rows:
+    z = E[w | data] / sqrt(diag(Var(E[w | data]))), and Var(E[w | data]) = Q - Cov(w | data), so z = mean / sqrt(diag(Q - cov)), [n, d].
+    Under the model every entry is standard normal: a large one on a likelihood factor marks an outlier, on a transition a structural
+    break.  dist: the dict (with "mean" and "cov"); Q: [d, d], or [n, d, d] with the Q of every row.  z is NaN where
+    diag(Q - cov) <= 64 d ε diag(Q): such a factor tells nothing about its disturbance (Cov(w | data) = Q: a forecast's transitions, the
+    factor behind missing data) and the quotient would be rounding over rounding — the flat-pivot factor of the readers at these dims."""
+    mean, cov = np.asarray(dist["mean"], float), np.asarray(dist["cov"], float)
+    n, d = mean.shape
+    Qd = np.broadcast_to(np.diagonal(np.asarray(Q, float), axis1=-2, axis2=-1), (n, d))
+    v = Qd - np.diagonal(cov, axis1=1, axis2=2)
+    ok = v > 64.0 * d * np.finfo(np.float64).eps * Qd
+    return np.where(ok, mean / np.sqrt(np.where(ok, v, 1.0)), np.nan)
+
+
 def em(dev, sets, n_iter, sweeps_per_iter=1, learn=("A", "Q"), offsets=None, by_component=False):
     """EM on the parameter sets of a dim 2..4 DeviceGraph: per iteration sweep(sweeps_per_iter) → log_evidence → factor_statistics
     (one group per parameter set) → m_step → set_factor_matrices.  On a handle of dim 5..64 the same loop runs on log_evidence_mfma and

@@ -922,6 +922,43 @@ int32_t cx_factor_beliefs_mfma(cx_handle *h, int64_t n, const int64_t *factor_id
 int32_t cx_factor_statistics_mfma(cx_handle *h, int64_t n, const int64_t *factor_ids, const int64_t *groups, int64_t n_groups, double *out,
                                   int64_t *counts4);
 
+/* ---- smoothed disturbances at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
+ * cx_factor_disturbances_mfma / cx_factor_disturbance_rows_mfma: for a handle created with dim 5 .. 64, the posterior of every factor's own
+ * noise.  Every two-variable CX_FACTOR_GAUSS_LINEAR factor is x_out = A x_in + b + w, w ~ N(0, Q) (b: cx_set_factor_offsets_mfma, 0 unless
+ * set), and r = x_out - A x_in - b IS w: the call returns, PER FACTOR, what cx_factor_statistics_mfma adds up per group — the disturbance
+ * smoother of a state-space model (auxiliary residuals: outliers on the likelihood factors, structural breaks on the transitions).
+ * A ROW is such a factor with either, both or none of its ends observed (what cx_factor_beliefs_mfma covers); opaque messages are part
+ * of each variable's sum.  factor_ids == NULL returns every row in ascending factor id (cx_factor_disturbance_rows_mfma names them;
+ * n is ignored; a factor of any other kind but an opaque message is CX_ERR_UNSUPPORTED, naming it), otherwise the n named factors in
+ * the caller's order (an id may repeat): an unknown id is CX_ERR_NOT_FOUND, an opaque factor or one of another kind CX_ERR_UNSUPPORTED
+ * (naming it).
+ * out (may be NULL): n rows of d + d^2 doubles, d the CALLER's dim (an embedded dim returns the real block only),
+ *     E[r | data][d] | Cov(r | data)[d][d] (row-major, full; symmetric to the rounding of its last product).
+ * scores (may be NULL): n rows of two doubles,  t = E[r'Q^-1 r | data]  and  q = E[r]'Q^-1 E[r].  The kernel forms
+ * s = sum_ab (Q^-1)_ab Cov(r)_ab and q separately over the real block and stores t = s + q, so t >= q whenever Cov(r) is positive
+ * semi-definite to rounding; Q^-1 is the rule table's own.  t is the factor's share of -2 x the quadratic part of the EM Q-function and
+ * what a reweighting scheme reads.
+ * *total (may be NULL): the sum of t over the finite rows, folded 256 rows at a time in index order (no atomics).
+ * counts4 = {rows, finite, undefined, not positive definite} with cx_factor_statistics_mfma's two rules: a NaN input record or datum
+ * makes a row undefined, a failed pivot of either factorisation not positive definite; such a row is all NaN in out and in scores.
+ * With both ends observed r is a number: the mean is y_out - A y_in - b, the covariance exact zeros and t = q.  Behind a flat OUT leaf
+ * Cov(r) = Q to the rounding of one inverse, the mean is 0 and t = d: the factor says nothing about its disturbance.
+ * The arithmetic is cx_factor_statistics_mfma's, on the f64 matrix cores; at most W waves per launch (W = 1024 at an
+ * internal dim of 64, 2048 below), each with a workspace of its own and a contiguous run of rows.  A row's bits depend on neither the
+ * wave that took it nor the other rows of the list: two calls on one state are bit-identical, rows, scores and total; the scores and
+ * the total with out == NULL are the ones with rows; one factor alone gives the bits it gives in any list.  The payload passes through a
+ * device buffer of at most 32 MiB, a launch and a copy per chunk with nothing waiting in between; scores and statuses are whole-call
+ * arrays (25 bytes per row).  The row list of the last request is cached (an O(n) comparison on the host) and rebuilt when other
+ * variables are observed.  It shares the factor records, the A table and the wave workspaces with the two calls above; calling it
+ * between two cx_factor_statistics_mfma calls leaves the second one's output bit-identical to the first.
+ * Refused as cx_factor_statistics_mfma refuses, each text naming the function: other families, a handle created with dim 1 - 4 (there
+ * cx_factor_statistics sums the same moments per group), partitioned handles CX_ERR_UNSUPPORTED; no graph, a captured stream, a
+ * parameter set never set CX_ERR_STATE; a NULL counts4 or n < 0 with ids CX_ERR_INVALID_ARGUMENT.  Synchronous; moves no message,
+ * marginal, readiness bit or counter.  MI355X: profiles/factor_disturbances_mfma.md. */
+int32_t cx_factor_disturbances_mfma(cx_handle *h, int64_t n, const int64_t *factor_ids, double *out, double *scores, double *total,
+                                    int64_t *counts4);
+int32_t cx_factor_disturbance_rows_mfma(cx_handle *h, int64_t cap, int64_t *factor_ids, int64_t *n_rows);
+
 /* ---- predictive scores of the data at the matrix-core dims (added after ABI 9; no counterpart in the reference) ----
  * cx_predictive_mfma / cx_predictive_rows_mfma: cx_predictive and cx_predictive_rows for a handle created with dim 5 .. 64 — the same
  * contract, modes (CX_PREDICT_LOO, CX_PREDICT_CAUSAL), row order, row layout, counts4 = {rows, scored, undefined, improper}, NaN rule and

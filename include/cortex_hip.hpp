@@ -212,6 +212,27 @@ class Handle {
                                         out.data(), o.data()));
         return {out, o};
     }
+    // the smoothed disturbance of every two-variable x_out = A x_in + b + w factor at the matrix-core dims (cx_factor_disturbances_mfma): per
+    // row E[w | data] (d) then Cov(w | data) (d x d, row-major), per score row t = E[w'Q⁻¹w | data] and q = E[w]'Q⁻¹E[w]; factor_ids empty:
+    // every such factor in ascending id (`ids` names them).  counts: rows, finite, with an undefined input, not positive definite (NaN rows);
+    // total: Σ t of the finite rows.  rows == false: scores, total and counts only
+    struct Disturbances { std::vector<int64_t> ids; std::vector<double> rows, scores; double total = 0; std::array<int64_t, 4> counts{}; };
+    Disturbances factor_disturbances_mfma(const std::vector<int64_t> &factor_ids = {}, bool rows = true) {
+        Disturbances r;
+        r.ids = factor_ids;
+        if (factor_ids.empty()) {
+            int64_t n = 0;
+            check(cx_factor_disturbance_rows_mfma(h_, 0, nullptr, &n));
+            r.ids.resize((size_t)n);
+            if (n) check(cx_factor_disturbance_rows_mfma(h_, n, r.ids.data(), &n));
+        }
+        if (rows) r.rows.resize(r.ids.size() * (size_t)(dim_ + dim_ * dim_));
+        r.scores.resize(r.ids.size() * 2);
+        check(cx_factor_disturbances_mfma(h_, (int64_t)factor_ids.size(), factor_ids.empty() ? nullptr : factor_ids.data(),
+                                          rows && !r.rows.empty() ? r.rows.data() : nullptr, r.scores.empty() ? nullptr : r.scores.data(), &r.total,
+                                          r.counts.data()));
+        return r;
+    }
     // the predictive score of every datum that a Gaussian rule factor generates, from the stored messages (cx_predictive): per row ŷ (d), S
     // (d x d, row-major), log density, squared standardised residual; factor_ids empty: every row in ascending factor id (`ids` names them).
     // mode CX_PREDICT_LOO: given all other data; CX_PREDICT_CAUSAL: given the data of the inputs' ancestors (a chain: the Kalman innovations,
