@@ -23,6 +23,7 @@ import numpy as np
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
 from oracle import exact
+from tests.helpers import assert_close_by_max
 
 
 def _orth(rng, d):
@@ -254,3 +255,14 @@ def latent_edges(g, model):
     """edges of a FloodGraph whose message towards the variable has a reader: pairwise, into a latent variable"""
     xs = set(np.searchsorted(g.var_ids, model.x_ids).tolist())
     return np.array([e for e in np.flatnonzero(g.partner >= 0) if int(np.searchsorted(g.var_ids, g.edge_var[e])) in xs])
+
+
+def check_marginals(dev, model, ref, tol, what, close=assert_close_by_max):
+    """the marginals of the latent states against ref = (means, covariances); close: the caller's assert_close where it prints"""
+    d, n = model.dim, len(model.x_ids)
+    em, ecov = ref
+    marg = dev.get_marginals(model.x_ids)
+    assert not np.any(np.isnan(marg)), f"{what}: undefined marginals"
+    close(marg[:, :d], em, tol, f"{what}: marginal means")
+    close(marg[:, d:].reshape(n, d, d), ecov, tol, f"{what}: marginal covariances")
+    return marg

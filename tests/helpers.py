@@ -68,6 +68,11 @@ def assert_close(actual, expected, rtol, what="", scale_by="median"):
     return worst
 
 
+def assert_close_by_max(a, b, rtol, what=""):
+    """assert_close for matrices: they carry numerically-zero entries, so errors are measured against the largest entry"""
+    return assert_close(a, b, rtol, what, scale_by="max")
+
+
 def random_loopy_model(seed, world, nv=60, extra=25):
     """A connected random model with unary priors and `nv - 1 + extra` pairwise factors, plus a random variable→rank map."""
     import cortex.jl_amd as cx

@@ -19,6 +19,20 @@ from tests import learning_support as S
 OK, UNDEFINED, NOT_PD = 0, 1, 2
 
 
+def assert_within(got, want, tol, what):
+    """every entry finite and within the absolute bound tol of want's; prints the largest error"""
+    got, want = np.asarray(got, float), np.asarray(want, float)
+    err = float(np.max(np.abs(got - want))) if want.size else 0.0
+    print(f"{what}: max abs error {err:.3e} (bound {tol:.3e})")
+    assert np.all(np.isfinite(got)), what
+    assert err <= tol, (what, err, tol)
+
+
+def bound_of(want):
+    """the bound of covariances and statistics: 1e-9 max(1, max|want|)"""
+    return 1e-9 * max(1.0, float(np.max(np.abs(want)))) if np.size(want) else 1e-9
+
+
 def _winv(M):
     """W = U^-T for M = U'U (numpy's lower Cholesky factor is U'); raises LinAlgError when M is not positive definite"""
     return np.linalg.inv(np.linalg.cholesky(M))

@@ -20,6 +20,13 @@ LOG2PI = math.log(2.0 * math.pi)
 KEYS = ("n", "sum_r", "sum_x", "S_rr", "S_rx", "S_xx")
 
 
+def assert_rel_close(got, want, rtol, what=""):
+    """every entry within rtol of want's, relative to max(|want|, 1)"""
+    got, want = np.asarray(got, float), np.asarray(want, float)
+    err = float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0))) if got.size else 0.0
+    assert err <= rtol, (what, err)
+
+
 # ---- dense ----------------------------------------------------------------------------------------------------------------------
 def dense_posterior(gm: E.GModel):
     """(mean [nv, d] — the datum on observed variables —, covariance [nv, nv, d, d] — zero on observed ones —) of the whole model"""

@@ -16,6 +16,7 @@ import dataclasses
 
 import numpy as np
 
+import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
 from tests import anisotropic as AN
 from tests import evidence_support as E
@@ -121,3 +122,44 @@ def shifted_twin(model, b, s):
         return nat
     return twin, to_twin
 
+
+
+# ---- shared by tests/test_gpu_factor_offsets.py (dim 2 .. 4) and tests/test_gpu_factor_offsets_mfma.py (dim 5 .. 64) ------------------------
+def latent_edges(model):
+    keep = np.isin(model.edge_var, model.x_ids)
+    return model.edge_var[keep], model.edge_fac[keep]
+
+
+def messages(dev, model):
+    ev, ef = latent_edges(model)
+    return dev.get_messages(ev, ef, L.TO_VARIABLE, L.FORM_NATURAL)
+
+
+_REF = {}
+
+
+def ref(key, make):
+    """a reference computed once per key and left unchanged (one cache for both files: their keys carry the dim or differ in form)"""
+    if key not in _REF:
+        _REF[key] = make()
+    return _REF[key]
+
+
+def tree_case(name, make):
+    def build():
+        model = make()
+        b1, b2 = with_offsets(model, 5), with_offsets(model, 6, scale=2.0)
+        return model, b1, dense_posterior_offsets(model, b1), b2, dense_posterior_offsets(model, b2)
+    return ref(("tree", name), build)
+
+
+def hub_model(d, seed=9):
+    """u (observed) -> x -> y (observed), x -> z (a free leaf): every direction of a message through a factor, from either kind of sender"""
+    A, Q, R, H = AN.general_sets(d, seed)
+    rng = np.random.default_rng([seed, d, 93])
+    IN, OUT = L.ROLE_IN, L.ROLE_OUT
+    return cx.synth.Model(edge_var=np.array([1, 2, 2, 3, 2, 4], np.int64), edge_fac=np.array([10, 10, 11, 11, 12, 12], np.int64),
+                          edge_role=np.array([IN, OUT, IN, OUT, IN, OUT], np.int32), factor_ids=np.array([10, 11, 12], np.int64),
+                          factor_kind=np.full(3, L.FACTOR_GAUSS_LINEAR, np.int32), factor_var=np.array([0.0, 1.0, 0.0]), x_ids=np.array([2, 4], np.int64),
+                          data_var=np.array([1, 3], np.int64), data_fac=np.array([10, 11], np.int64), data_y=rng.standard_normal((2, d)), dim=d,
+                          psets={0: (A, Q), 1: (H, R)}, meta={"kind": "hub"})

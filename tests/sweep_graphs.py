@@ -3,6 +3,7 @@ test_gpu_sweep_pairs.py, test_gpu_grid_between_calls.py and test_lattice_plan.py
 import dataclasses
 
 import numpy as np
+import pytest
 
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
@@ -178,3 +179,61 @@ def natural_form_sweeps(model, seed_variance, set_vars, set_facs, payload, n):
             msg = new
             out.append((int(np.sum(msg[:, 1] == -np.inf)), int(np.sum(np.isnan(msg[:, 1]))), undefined_read))
     return out
+
+
+# ---- what the grid-sweep tests (test_gpu_sweep_deep*.py, test_gpu_sweep_pairs.py, test_gpu_grid_between_calls.py) do to a handle ---------
+_grids = {}
+
+
+def model_of(shape, seed=7):
+    """cx.synth.gaussian_grid(*shape, seed), made once"""
+    if (shape, seed) not in _grids:
+        _grids[(shape, seed)] = cx.synth.gaussian_grid(*shape, seed=seed)
+    return _grids[(shape, seed)]
+
+
+def fused_device(model, seed_variance=1e6):
+    dev = cx.DeviceGraph(schedule=L.SCHED_FUSED)
+    cx.synth.load_into_device(model, dev, seed_variance)
+    return dev
+
+
+def everything(dev, model):
+    """factor→variable messages, marginals, and the variable→factor messages (formed on demand from the last sweep's input)"""
+    f2v, marg = read_back(dev, model)
+    return f2v, marg, dev.get_messages(model.edge_var, model.edge_fac, L.TO_FACTOR, L.FORM_NATURAL)
+
+
+def assert_same(a, b, what):
+    """two read_back or everything tuples, bit for bit"""
+    for x, y, name in zip(a, b, ("messages to variables", "marginals", "messages to factors")):
+        assert np.array_equal(x, y, equal_nan=True), f"{what}: {name} differ"
+
+
+def paired_launches(dev):
+    return dev.sweep_stats()["paired_launches"]
+
+
+def launches(dev):
+    """(launches of two sweeps, of three, of four)"""
+    d = dev.sweep_deep_stats()
+    return dev.sweep_stats()["paired_launches"], d["depth3_launches"], d["depth4_launches"]
+
+
+def rows_cases(K):
+    return (1, 3, 4 * (K - 1))
+
+
+def load_undefined_midcall():
+    model, sv, sf, payload = undefined_midcall_grid()
+    dev = fused_device(model)
+    dev.set_messages(sv, sf, L.TO_VARIABLE, L.FORM_NATURAL, payload)
+    return model, dev
+
+
+@pytest.fixture
+def clean_env(monkeypatch):
+    """(a fixture: a test file imports it by name)"""
+    for name in ("CX_SWEEP_PAIRS", "CX_SWEEP_DEPTH", "CX_PAIR_ROWS", "CX_DEEP_ROWS", "CX_MARG_EVERY_SWEEP"):
+        monkeypatch.delenv(name, raising=False)
+    return monkeypatch

@@ -99,11 +99,9 @@ def test_cpp_host_classes_compile_against_the_abi(tmp_path):
     builds with g++ -Wall -Wextra -Werror against the C ABI alone and fails loudly without a GPU."""
     import subprocess
 
-    exe = str(tmp_path / "host_class_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "host_class_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
+    from tests.gpu_support import build_demo
+
+    exe = build_demo("host_class_demo", tmp_path)
     import torch
     if not torch.cuda.is_available():
         out = subprocess.run([exe], capture_output=True, text=True, timeout=120)

@@ -17,13 +17,10 @@ from tests import functional_support as F
 from tests import learning_support as LS
 from tests import predictive_support as P
 from tests import sampling_support as SS
-from tests.helpers import assert_close as _assert_close
+from tests.helpers import assert_close_by_max as assert_close
+from tests.learning_support import assert_rel_close as _close
 
 pytestmark = pytest.mark.gpu
-
-
-def assert_close(a, b, rtol, what=""):
-    return _assert_close(a, b, rtol, what, scale_by="max")
 
 
 def _tols(d):
@@ -57,16 +54,6 @@ def _per_sweep(dev, o, model, sweeps, tol, what):
             assert_close(row[d:].reshape(d, d), S, tol, f"{what} sweep {sweep} f2v covariance edge {e}")
 
 
-def _check_marginals(dev, model, ref, tol, what):
-    d, n = model.dim, len(model.x_ids)
-    em, ecov = ref
-    marg = dev.get_marginals(model.x_ids)
-    assert not np.any(np.isnan(marg)), f"{what}: undefined marginals"
-    assert_close(marg[:, :d], em, tol, f"{what}: marginal means")
-    assert_close(marg[:, d:].reshape(n, d, d), ecov, tol, f"{what}: marginal covariances")
-    return marg
-
-
 # ---- flooding-order sweeps, d = 2, 3, 4 (dim > 1 has one iterative schedule, CX_SCHED_FUSED; cx_create refuses CX_SCHED_FLOODING) ----------
 @pytest.mark.parametrize("d", [2, 3, 4])
 def test_sweeps_on_a_general_chain(hip_lib, d):
@@ -75,7 +62,7 @@ def test_sweeps_on_a_general_chain(hip_lib, d):
     dev = _dev(model)
     _per_sweep(dev, MvFloodC(model), model, 8, 1e-8, f"d={d}")
     dev.sweep(T + 3 - 8)
-    _check_marginals(dev, model, AN.dense_posterior(model), 1e-9, f"d={d} fixed point vs the joint solve")
+    AN.check_marginals(dev, model, AN.dense_posterior(model), 1e-9, f"d={d} fixed point vs the joint solve")
     dev.residual()
     dev.sweep(2)
     assert dev.residual() < 1e-10
@@ -91,7 +78,7 @@ def test_sweeps_with_variables_of_high_degree(hip_lib, name, make, total):
     assert np.diff(o.g.var_off).max() == (11 if "branching" in name else 5)
     _per_sweep(dev, o, model, 6, 1e-8, name)
     dev.sweep(total - 6)
-    _check_marginals(dev, model, AN.dense_posterior(model), 1e-9, name + " fixed point vs the joint solve")
+    AN.check_marginals(dev, model, AN.dense_posterior(model), 1e-9, name + " fixed point vs the joint solve")
 
 
 # ---- chain scan, d = 2, 3, 4 -------------------------------------------------------------------------------------------------------------
@@ -104,7 +91,7 @@ def test_chain_scan_one_sweep(hip_lib, monkeypatch, d, T, K, general_h):
     model = AN.chain(T, d, general_h=general_h)
     dev = _dev(model, L.SCHED_CHAIN_SCAN)
     dev.sweep(1)
-    marg = _check_marginals(dev, model, AN.chain_posterior(model), 1e-9, f"d={d} T={T} K={K}")
+    marg = AN.check_marginals(dev, model, AN.chain_posterior(model), 1e-9, f"d={d} T={T} K={K}")
     lazy = _dev(model, L.SCHED_CHAIN_SCAN, marginals_in_sweep=2)
     lazy.sweep(1)
     assert np.array_equal(marg, lazy.get_marginals(model.x_ids)), "marginals on demand: the same bits"
@@ -122,7 +109,7 @@ def test_matrix_core_sweeps_on_a_general_chain(hip_lib, monkeypatch, d, form):
     o.sweep(1)            # the matrix-core path evaluates the messages out of observed variables at data injection
     _per_sweep(dev, o, model, T + 1, 1e-7, f"d={d}")
     dev.sweep(2)
-    _check_marginals(dev, model, AN.chain_posterior(model), 1e-8, f"d={d} fixed point")
+    AN.check_marginals(dev, model, AN.chain_posterior(model), 1e-8, f"d={d} fixed point")
 
 
 @pytest.mark.parametrize("d", [16, 24])
@@ -143,7 +130,7 @@ def test_native_tiles_equal_the_embedding_in_64_on_a_general_chain(hip_lib, monk
         ok = ~np.isnan(ma)
         assert_close(ma[ok], mb[ok], 1e-9, f"d={d} sweep {sweep}: messages, native tiles vs embedded")
     assert_close(a.get_marginals(model.x_ids), b.get_marginals(model.x_ids), 1e-9, f"d={d}: marginals, native tiles vs embedded")
-    _check_marginals(a, model, AN.chain_posterior(model), 1e-8, f"d={d} native tiles")
+    AN.check_marginals(a, model, AN.chain_posterior(model), 1e-8, f"d={d} native tiles")
 
 
 # ---- matrix cores: chain scan ------------------------------------------------------------------------------------------------------------
@@ -155,7 +142,7 @@ def test_matrix_core_chain_scan_one_sweep(hip_lib, monkeypatch, d, T, K, fan):
     model = AN.chain(T, d)
     dev = _dev(model, L.SCHED_CHAIN_SCAN)
     dev.sweep(1)
-    _check_marginals(dev, model, AN.chain_posterior(model), 1e-8, f"d={d} T={T}")
+    AN.check_marginals(dev, model, AN.chain_posterior(model), 1e-8, f"d={d} T={T}")
     if K:
         assert dev.chain_plan_stats()["levels"] >= 2
 
@@ -174,7 +161,7 @@ def test_tree_schedule_one_sweep(hip_lib, monkeypatch, name, make, heavy_paths):
     dev.sweep(1)
     launches = dev.tree_heavy_path_stats()["launches"]
     assert launches == 0 if heavy_paths == "0" else (launches > 0 or "comb" not in name)
-    _check_marginals(dev, model, AN.dense_posterior(model), _tols(model.dim)[1], f"{name} heavy paths {heavy_paths}")
+    AN.check_marginals(dev, model, AN.dense_posterior(model), _tols(model.dim)[1], f"{name} heavy paths {heavy_paths}")
 
 
 # ---- reference order ---------------------------------------------------------------------------------------------------------------------
@@ -186,7 +173,7 @@ def test_reference_order_one_call_on_a_general_chain(hip_lib, d):
     dev.sweep(1)
     st = dev.ref_plan_stats()
     assert st["messages"] == 5 * T - 4 and st["executions"] == 6 * T - 4
-    _check_marginals(dev, model, AN.chain_posterior(model), _tols(d)[1], f"d={d} reference order")
+    AN.check_marginals(dev, model, AN.chain_posterior(model), _tols(d)[1], f"d={d} reference order")
 
 
 @pytest.mark.parametrize("d,T,skips", AN.REF_LOOPY)
@@ -221,12 +208,6 @@ def test_fused_sweeps_on_a_general_loopy_graph(hip_lib, d):
 
 
 # ---- readers -----------------------------------------------------------------------------------------------------------------------------
-def _close(got, want, rtol, what=""):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    err = float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0))) if got.size else 0.0
-    assert err <= rtol, (what, err)
-
-
 @pytest.fixture(scope="module")
 def reader_case():
     """per (d, shape): the model, its GModel and every reference number, computed once and left unchanged"""
@@ -316,4 +297,4 @@ def test_rank_deficient_observation_matrix(hip_lib, d, schedule):
     model = AN.velocity_chain(T, d)
     dev = _dev(model, schedule)
     dev.sweep(T + 3 if schedule == L.SCHED_FUSED else 1)
-    _check_marginals(dev, model, AN.chain_posterior(model), 1e-9, f"d={d} schedule {schedule}")
+    AN.check_marginals(dev, model, AN.chain_posterior(model), 1e-9, f"d={d} schedule {schedule}")

@@ -10,8 +10,6 @@ no case needs more.
 At d = 1 the models are the scalar counterparts of the anisotropic builders, which name parameter sets and have no dim-1 form
 (test_causal_checker.chain_of / tree_of): synth.ssm_chain_linear (CX_FACTOR_GAUSS_LINEAR with b != 0) and causal_support.scalar_tree."""
 import copy
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,9 +23,9 @@ from tests import missing_data as MD
 from tests import predictive_support as P
 from tests.test_causal_checker import chain_of, tree_of
 from tests.test_gpu_kary_mv import _kary_tree, _load as _load_kary
+from tests.gpu_support import code_of
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXACT, PARITY = 1e-9, 1e-10
 T = 12
 MODES = (("predicted", 0, CS.PREDICTED), ("filtered", 0, CS.FILTERED), ("filtered", 1, CS.FILTERED), ("filtered", 3, CS.FILTERED), ("filtered", T, CS.FILTERED))
@@ -246,24 +244,18 @@ def test_cache_rules(hip_lib):
     dev.close()
 
 
-def _code(fn):
-    with pytest.raises(L.CortexHipError) as e:
-        fn()
-    return e.value.code, e.value.message
-
-
 def test_refusals(hip_lib):
     dev = cx.DeviceGraph()
-    assert _code(dev.causal_marginals)[0] == L.ERR_STATE                      # no graph
+    assert code_of(dev.causal_marginals)[0] == L.ERR_STATE                      # no graph
     dev.close()
     dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    assert _code(dev.causal_marginals)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.causal_marginals)[0] == L.ERR_UNSUPPORTED
     dev.close()
     m16 = cx.synth.lgssm_chain(4, d=16, seed=91)
     dev = cx.DeviceGraph(dim=16, schedule=L.SCHED_FUSED)
     cx.synth.load_into_device(m16, dev, seed_variance=1e6)
     dev.sweep(2)
-    assert _code(dev.causal_marginals)[0] == L.ERR_UNSUPPORTED                # dim >= 5
+    assert code_of(dev.causal_marginals)[0] == L.ERR_UNSUPPORTED                # dim >= 5
     dev.close()
     n = 20
     model = cx.synth.ssm_chain(n, seed=92)
@@ -280,16 +272,16 @@ def test_refusals(hip_lib):
     assert call(dev.h, L.CAUSAL_FILTERED, 0, 0, None, po, None) == L.ERR_INVALID_ARGUMENT     # NULL counts4
     ids = np.array([1, 2], np.int64)
     assert call(dev.h, L.CAUSAL_FILTERED, 0, -1, ids.ctypes.data_as(L.C.POINTER(L.C.c_int64)), po, cnt) == L.ERR_INVALID_ARGUMENT
-    code, msg = _code(lambda: dev.causal_marginals("filtered", 0, [1, 999]))
+    code, msg = code_of(lambda: dev.causal_marginals("filtered", 0, [1, 999]))
     assert code == L.ERR_NOT_FOUND and "999" in msg
     assert dev.causal_marginals("filtered", 2, [3, 1])["counts"]["finite"] == 2               # and the handle works on
     dev.halo_configure([1], [2 * n + 1], [], [])                                              # a halo list: a partitioned handle
-    assert _code(dev.causal_marginals)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.causal_marginals)[0] == L.ERR_UNSUPPORTED
     dev.close()
     model = cx.synth.ssm_chain(10, seed=93, q=0.0)
     dev = cx.DeviceGraph(schedule=L.SCHED_TREE)
     cx.synth.load_into_device(model, dev)
-    code, msg = _code(dev.causal_marginals)
+    code, msg = code_of(dev.causal_marginals)
     assert code == L.ERR_UNSUPPORTED and "factor 31" in msg                   # zero noise: the first transition (ids 3T + 1 ..)
     dev.close()
 
@@ -302,7 +294,7 @@ def test_transitions_of_three_or_more_variables(hip_lib):
     gm = E.gmodel(model, edge_sets=edge_sets, opaque=(model.x_ids, model.x_ids + n, prior[0], prior[1]))
     dev = _load_kary(model, prior, facs, fid, sets, L.SCHED_TREE)
     dev.sweep(1)
-    code, msg = _code(lambda: dev.causal_marginals("filtered", 1))
+    code, msg = code_of(lambda: dev.causal_marginals("filtered", 1))
     assert code == L.ERR_UNSUPPORTED and f"factor {int(fid[0])}" in msg, msg
     f2v, opq = E.device_messages(gm, dev)
     for mode, m in (("predicted", CS.PREDICTED), ("filtered", CS.FILTERED)):                  # lag 0: such factors are simply classified

@@ -10,8 +10,6 @@ predictive_support.assert_rows_close (vectors and matrices scaled by their large
 import ctypes as C
 import dataclasses
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,25 +23,12 @@ from tests import evidence_support as E
 from tests import missing_data as MD
 from tests import predictive_mfma_support as PM
 from tests import predictive_support as P
+from tests.gpu_support import (HANDLE_CASES, STREAM_CASES, assert_reader_refusals, code_of, demo_chain, missing_data_device, run_demo,
+                               swept_device, under_capture, with_sets)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-9
 WHO = "cx_causal_marginals_mfma"
-
-
-def _dev(model, schedule, fused_sweeps=60):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule == L.SCHED_FUSED else None)
-    dev.sweep(fused_sweeps if schedule == L.SCHED_FUSED else 1)      # (reference order: cx_sweep requests every variable)
-    return dev
-
-
-def _md_dev(model):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=L.SCHED_TREE)
-    MD.load(model, dev)                    # the flat message on the one edge of every latent leaf
-    dev.sweep(1)
-    return dev
 
 
 def _all(dev, gm, mode, lag):
@@ -98,7 +83,7 @@ def test_chains_and_combs_after_every_schedule(hip_lib, d, shape):
     x = _x(gm, model)
     for s in [L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED] + ([L.SCHED_CHAIN_SCAN] if shape == "chain" else []):
         what = f"d {d} {shape} schedule {s}"
-        dev = _dev(model, s)      # (fused: seed variance 1e6 and 60 sweeps, the diameter is under 20)
+        dev = swept_device(model, s)      # (fused: seed variance 1e6 and 60 sweeps, the diameter is under 20)
         for mode, lag, _m in CM.MODES:
             got, want = _all(dev, gm, mode, lag), dense[(mode, lag)]
             assert got["counts"] == want["counts"], (what, mode, lag, got["counts"], want["counts"])
@@ -116,7 +101,7 @@ def test_chains_and_combs_after_every_schedule(hip_lib, d, shape):
 def test_gaps_and_a_forecast_tail(hip_lib, d):
     model = PM.gen(d)
     gm = E.gmodel(model)
-    dev = _md_dev(model)
+    dev = missing_data_device(model)
     for mode, lag, m in CM.MODES:
         got, want = _all(dev, gm, mode, lag), CS.dense_causal_all(gm, m, lag)
         assert got["counts"] == want["counts"], (mode, lag, got["counts"], want["counts"])
@@ -135,7 +120,7 @@ def test_a_leading_gap(hip_lib, d):
     model = PM.leading_gap(d)
     gm = E.gmodel(model)
     x = _x(gm, model)
-    dev = _md_dev(model)
+    dev = missing_data_device(model)
     pattern = {("predicted", 0): [2, 2, 0, 0, 0], ("filtered", 0): [2, 0, 0, 0, 0]}      # lag >= 1: none
     for mode, lag, m in CM.MODES:
         got = _all(dev, gm, mode, lag)
@@ -171,7 +156,7 @@ def test_a_clamped_state_in_the_middle(hip_lib, d):
     gm = E.gmodel(model)
     x = _x(gm, model)
     c = x[model.meta["clamped_state"]]
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     for mode, lag, m in CM.MODES:
         got, want = _all(dev, gm, mode, lag), _definition(gm, dev, m, lag)
         assert got["counts"] == want["counts"], (mode, lag, got["counts"], want["counts"])
@@ -185,7 +170,7 @@ def test_a_clamped_state_in_the_middle(hip_lib, d):
 def test_a_loop_matches_the_definition_on_the_device_messages(hip_lib, d):
     model = S.ring(d)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_FUSED, S.RING_SWEEPS)
+    dev = swept_device(model, L.SCHED_FUSED, S.RING_SWEEPS)
     for mode, lag, m in (("predicted", 0, CS.PREDICTED), ("filtered", 0, CS.FILTERED), ("filtered", 1, CS.FILTERED), ("filtered", 3, CS.FILTERED)):
         got, again = _all(dev, gm, mode, lag), _all(dev, gm, mode, lag)
         want = _definition(gm, dev, m, lag)
@@ -199,11 +184,11 @@ def test_a_loop_matches_the_definition_on_the_device_messages(hip_lib, d):
 @pytest.mark.parametrize("d", [8, 20])
 def test_embedded_dims_give_the_real_models_rows_at_any_tile_size(hip_lib, d, monkeypatch):
     model = cx.synth.lgssm_chain(5, d=d, seed=90 + d)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     native = {lag: dev.causal_marginals_mfma("filtered", lag) for lag in (0, 2)}
     dev.close()
     monkeypatch.setenv("CX_MFMA_DIM", "64")
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     monkeypatch.delenv("CX_MFMA_DIM")
     for lag in (0, 2):
         forced = dev.causal_marginals_mfma("filtered", lag)
@@ -213,12 +198,6 @@ def test_embedded_dims_give_the_real_models_rows_at_any_tile_size(hip_lib, d, mo
 
 
 # ---- 8. undefined inputs; new parameters -----------------------------------------------------------------------------------------------
-def _with_sets(model, psets):
-    A, Q = psets[0]
-    _, R = psets[1]
-    return dataclasses.replace(model, meta={**model.meta, "A": np.asarray(A), "Q": np.asarray(Q), "R": np.asarray(R)})
-
-
 @pytest.mark.parametrize("d", [8, 32])
 def test_undefined_then_exact_then_new_parameters(hip_lib, d):
     T = 7
@@ -241,7 +220,7 @@ def test_undefined_then_exact_then_new_parameters(hip_lib, d):
             psets[1] = (psets[1][0], 2.0 * np.asarray(psets[1][1]))
             dev.set_factor_matrices(1, *psets[1])
         dev.sweep(1)
-        _against_kalman(dev, _with_sets(model, psets), f"d {d} {step}")      # the rule tables are read by every call
+        _against_kalman(dev, with_sets(model, psets), f"d {d} {step}")      # the rule tables are read by every call
         lag2 = dev.causal_marginals_mfma("filtered", 2, model.x_ids)
         if first is not None:
             assert np.abs(lag2["cov"][1] - first["cov"][1]).max() > 1e-3
@@ -254,7 +233,7 @@ def test_named_rows_in_the_callers_order(hip_lib):
     d, T = 16, 9
     model = cx.synth.lgssm_chain(T, d=d, seed=83)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     for mode, lag, m in (("predicted", 0, CS.PREDICTED), ("filtered", 0, CS.FILTERED), ("filtered", 2, CS.FILTERED)):
         full = _all(dev, gm, mode, lag)
         want = CS.dense_causal_all(gm, m, lag)
@@ -288,7 +267,7 @@ def test_named_rows_in_the_callers_order(hip_lib):
 def test_long_chains_against_the_kalman_filter(hip_lib, T, d):
     model = cx.synth.lgssm_chain(T, d=d, seed=33)
     assert T * (d + d * d) * 8 > 32 << 20      # more than one chunk of the payload
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = swept_device(model, L.SCHED_CHAIN_SCAN)
     _against_kalman(dev, model, f"d = {d}, T = {T}, chain scan")
     dev.close()
 
@@ -297,7 +276,7 @@ def test_long_chains_against_the_kalman_filter(hip_lib, T, d):
 def test_agreement_with_predictive_mfma(hip_lib):
     """the PREDICTED row of x_t pushed through its observation factor, ŷ = H μ, S = H Σ H' + R, is the CX_PREDICT_CAUSAL row of that factor"""
     model = PM.gen(16)
-    dev = _md_dev(model)
+    dev = missing_data_device(model)
     s = MD.chain_spec(model)
     steps = np.flatnonzero(s["keep"])
     pre = dev.causal_marginals_mfma("predicted", 0, np.asarray(model.x_ids)[steps])
@@ -316,7 +295,7 @@ def test_agreement_with_predictive_mfma(hip_lib):
 def test_moves_nothing(hip_lib):
     model = cx.synth.lgssm_chain(8, d=16, seed=72)
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_REFERENCE, L.SCHED_TREE):
-        dev = _dev(model, s)
+        dev = swept_device(model, s)
         if s == L.SCHED_CHAIN_SCAN:      # (another reader first: every reader of the messages brings them to their slots)
             dev.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE)
         blob, marg = dev.export_state(), dev.get_marginals(model.x_ids)
@@ -327,7 +306,7 @@ def test_moves_nothing(hip_lib):
         assert np.array_equal(blob, dev.export_state())
         dev.close()
     # fused: the next sweeps are those of a twin handle that never called it, bit for bit
-    a, b = _dev(model, L.SCHED_FUSED, 5), _dev(model, L.SCHED_FUSED, 5)
+    a, b = swept_device(model, L.SCHED_FUSED, 5), swept_device(model, L.SCHED_FUSED, 5)
     assert a.residual() == b.residual()      # (the first call takes the snapshot the next one measures against)
     a.causal_marginals_mfma("predicted"); a.causal_marginals_mfma("filtered", 2)
     a.sweep(3); b.sweep(3)
@@ -340,36 +319,21 @@ def test_moves_nothing(hip_lib):
 
 
 # ---- 13. refusals ------------------------------------------------------------------------------------------------------------------------
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
+def _raw(dev, out):
+    """the filtered states at lag 1 of every variable through the C ABI, into out [n_variables, d + d d]; the status"""
+    return dev.lib.cx_causal_marginals_mfma(dev.h, L.CAUSAL_FILTERED, 1, 0, None, out.ctypes.data_as(C.POINTER(C.c_double)), (C.c_int64 * 4)())
+
+
+_COMMON = dict(who=WHO, small="cx_causal_marginals", call=lambda dev: dev.causal_marginals_mfma(), small_call=lambda dev: dev.causal_marginals(),
+               raw=lambda dev: _raw(dev, np.zeros((8, 16 + 256))))      # what assert_reader_refusals asks of this reader
 
 
 def test_refusals(hip_lib):
-    m4 = cx.synth.lgssm_chain(5, d=4, seed=91)
+    assert_reader_refusals(**_COMMON, cases=HANDLE_CASES)
     m16 = cx.synth.lgssm_chain(4, d=16, seed=92)
-    dev = _dev(m4, L.SCHED_TREE)
-    code, msg = _code(dev.causal_marginals_mfma)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "cx_causal_marginals" in msg.replace(WHO, "")      # names the call for dims 1 .. 4
-    dev.close()
-    dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    code, msg = _code(dev.causal_marginals_mfma)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "Gaussian family" in msg
-    dev.close()
-    vm = cx.synth.vmp_ssm(8)
-    dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
-    cx.synth.load_vmp_into_device(vm, dev)
-    code, msg = _code(dev.causal_marginals_mfma)
-    assert code == L.ERR_UNSUPPORTED and "Gaussian family" in msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16)
-    code, msg = _code(dev.causal_marginals_mfma)
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "no graph" in msg
-    dev.close()
-    dev = _dev(m16, L.SCHED_FUSED, 2)
-    code, msg = _code(dev.causal_marginals)
-    assert code == L.ERR_UNSUPPORTED and "cx_causal_marginals" in msg and WHO not in msg      # the old call keeps refusing these dims
+    dev = swept_device(m16, L.SCHED_FUSED, 2)
+    code, msg = code_of(dev.causal_marginals)
+    assert code == L.ERR_UNSUPPORTED and "cx_causal_marginals" in msg and WHO not in msg      # the old call refuses under its own name
     n = 8
     out, c4 = np.zeros((n, 16 + 256)), (C.c_int64 * 4)()
     po = out.ctypes.data_as(C.POINTER(C.c_double))
@@ -381,18 +345,9 @@ def test_refusals(hip_lib):
                        ((L.CAUSAL_FILTERED, 0, 0, None, po, None), "null argument"), ((L.CAUSAL_FILTERED, 0, -1, ids, po, c4), "negative count")):
         assert call(dev.h, *args) == L.ERR_INVALID_ARGUMENT, args
         assert dev.lib.cx_last_error(dev.h).decode().startswith(WHO) and text in dev.lib.cx_last_error(dev.h).decode()
-    code, msg = _code(dev.causal_marginals_mfma, "filtered", 0, [int(m16.x_ids[0]), 10 ** 9])
+    code, msg = code_of(dev.causal_marginals_mfma, "filtered", 0, [int(m16.x_ids[0]), 10 ** 9])
     assert code == L.ERR_NOT_FOUND and msg.startswith(WHO) and str(10 ** 9) in msg
     assert dev.causal_marginals_mfma("filtered", 2, [int(m16.x_ids[2]), int(m16.x_ids[0])])["counts"]["finite"] == 2      # and the handle works on
-    dev.halo_configure_state([m16.x_ids[0]], [3 * 4 + 1], [], [])      # a halo list: a partitioned handle
-    code, msg = _code(dev.causal_marginals_mfma)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "partitioned handle" in msg
-    dev.close()
-    dev = _dev(m16, L.SCHED_CHAIN_SCAN)
-    dev.causal_marginals_mfma()
-    dev.halo_configure([m16.x_ids[0]], [3 * 4 + 1], [], [])            # a chain's time block
-    code, msg = _code(dev.causal_marginals_mfma)
-    assert code == L.ERR_UNSUPPORTED and "partitioned handle" in msg and "time block" in msg
     dev.close()
 
 
@@ -406,67 +361,37 @@ def test_no_factor_of_another_kind_enters_a_handle_of_these_dims(hip_lib):
         dev = cx.DeviceGraph(dim=16, schedule=L.SCHED_TREE)
         for k, (A, Q) in m.psets.items():
             dev.set_factor_matrices(k, A, Q)
-        code, msg = _code(dev.graph_create, np.concatenate([m.edge_var, ev]), np.concatenate([m.edge_fac, ef]), np.concatenate([m.factor_ids, [99]]),
+        code, msg = code_of(dev.graph_create, np.concatenate([m.edge_var, ev]), np.concatenate([m.edge_fac, ef]), np.concatenate([m.factor_ids, [99]]),
                           np.concatenate([m.factor_kind, [kind]]).astype(np.int32), np.concatenate([m.factor_var, [0.0]]),
                           edge_role=np.concatenate([m.edge_role, er]).astype(np.int32))
         assert code == L.ERR_UNSUPPORTED and msg.startswith("cx_graph_create"), (kind, code, msg)
         dev.close()
 
 
-def _under_capture(dev, call):
-    """the status of `call` while the handle's stream is being captured (relaxed mode: the refusal's own runtime queries do not void
-    the capture); the handle is back on its own stream afterwards"""
-    hip = C.CDLL([ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0])
-    stream, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    dev.set_stream(stream.value)
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
-    rc = call()
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    dev.set_stream(None)
-    assert hip.hipStreamDestroy(stream) == 0
-    return rc, dev.lib.cx_last_error(dev.h).decode()
-
-
 def test_refusals_of_a_captured_stream_and_of_parameter_sets_never_set(hip_lib):
+    assert_reader_refusals(**_COMMON, cases=STREAM_CASES)
     d = 16
     model = cx.synth.lgssm_chain(5, d=d, seed=93)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     want = dev.causal_marginals_mfma("filtered", 1)
-    out, c4 = np.zeros((10, d + d * d)), (C.c_int64 * 4)()
-    rc, msg = _under_capture(dev, lambda: dev.lib.cx_causal_marginals_mfma(dev.h, L.CAUSAL_FILTERED, 1, 0, None, out.ctypes.data_as(C.POINTER(C.c_double)), c4))
+    out = np.zeros((10, d + d * d))
+    rc, msg = under_capture(dev, lambda: _raw(dev, out))
     assert rc == L.ERR_STATE and msg.startswith(WHO) and "captured" in msg, (rc, msg)
     assert not out.any()                                       # nothing was written
     got = dev.causal_marginals_mfma("filtered", 1)             # and the handle works on, bit for bit
     assert _bits(got) == _bits(want) and got["counts"] == want["counts"]
     dev.close()
-    dev = cx.DeviceGraph(dim=d, schedule=L.SCHED_TREE)
-    dev.set_factor_matrices(0, *model.psets[0])                # set 1, the likelihoods', is never set
-    dev.graph_create(model.edge_var, model.edge_fac, model.factor_ids, model.factor_kind, model.factor_var, edge_role=model.edge_role)
-    code, msg = _code(dev.causal_marginals_mfma)
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "never set" in msg and "cx_set_factor_matrices" in msg, (code, msg)
-    dev.close()
 
 
 # ---- 14. the C++ host class --------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_causal_marginals_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "causal_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "causal_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    lines = [line.split() for line in out.stdout.splitlines()]
+    lines = [line.split() for line in run_demo("causal_mfma_demo", tmp_path)]
     head = {ln[0]: ln[1:] for ln in lines if ln[0] != "row"}
     rows = [[float(v) for v in ln[2:]] for ln in lines if ln[0] == "row"]
     T, d = 12, 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
-    y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
-    s = dict(A=np.broadcast_to(A, (T - 1, d, d)), b=np.zeros((T - 1, d)), Q=np.broadcast_to(0.5 * np.eye(d), (T - 1, d, d)), H=np.eye(d),
-             R=np.broadcast_to(np.eye(d), (T, d, d)), y=y, keep=np.ones(T, bool))
+    A, Q, R, y = demo_chain(T, d)
+    s = dict(A=np.broadcast_to(A, (T - 1, d, d)), b=np.zeros((T - 1, d)), Q=np.broadcast_to(Q, (T - 1, d, d)), H=np.eye(d),
+             R=np.broadcast_to(R, (T, d, d)), y=y, keep=np.ones(T, bool))
     f = MD.kalman_filter(s["A"], s["b"], s["Q"], s["H"], s["R"], s["y"], s["keep"])
     ms, Ps = CM.rts_lag(s, f, 2)
     assert head["before"] == [str(T), "0", str(T), "0"] and head["all"] == [str(2 * T)] * 2 + ["0", "0"]
@@ -485,7 +410,7 @@ def test_a_state_with_four_sources_goes_through_the_summed_record(hip_lib, d):
     scratch record (k_cmm_presum); from lag 2 on that sum reads the β of the other buffer"""
     model = CM.branching(d)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     for mode, lag, m in CM.BRANCH_MODES:
         got, want = _all(dev, gm, mode, lag), CS.dense_causal_all(gm, m, lag)
         assert got["counts"] == want["counts"] and got["counts"]["finite"] == len(gm.var_ids), (d, mode, lag, got["counts"], want["counts"])
@@ -501,7 +426,7 @@ def test_two_transitions_out_of_one_state_share_its_summed_record(hip_lib, d):
     the device's own messages (causal_mfma_support.two_parents says why the dense solve is none)"""
     model = CM.two_parents(d)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     for mode, lag, m in CM.BRANCH_MODES:
         got, want = _all(dev, gm, mode, lag), _definition(gm, dev, m, lag)
         assert got["counts"] == want["counts"] and got["counts"]["finite"] == len(gm.var_ids), (d, mode, lag, got["counts"], want["counts"])

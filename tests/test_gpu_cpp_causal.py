@@ -1,7 +1,5 @@
 """-m gpu: cortex::Handle::causal_marginals of include/cortex_hip.hpp (g++ + the C ABI, nothing else) on a scalar SSM chain, against
 DeviceGraph.causal_marginals on the same model and the reverse-time Kalman filter (tests/cpp/causal_demo.cpp)."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,20 +8,14 @@ import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
 from tests import missing_data as MD
 from tests import predictive_support as P
+from tests.gpu_support import run_demo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_host_class_causal_marginals(hip_lib, tmp_path):
-    exe = str(tmp_path / "causal_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "causal_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    lines = [line.split() for line in out.stdout.splitlines()]
+    out_lines = run_demo("causal_demo", tmp_path)
+    lines = [line.split() for line in out_lines]
     T = 50
     model = cx.synth.ssm_chain(T, seed=1)
     model.data_y = np.array([0.5 * t + (7 * t) % 5 for t in range(1, T + 1)], dtype=np.float64)

@@ -1,28 +1,20 @@
 """-m gpu: the C++ host classes of include/cortex_hip.hpp (g++ + the C ABI, nothing else) on the reference's SSM test graphs:
 sum-product through cortex::HipProcessor against the exact smoother, structured VMP through cortex::VmpProcessor against
 the array form of the reference's update_marginals! (oracle/vmp.py)."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import exact, vmp
+from tests.gpu_support import run_demo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_host_classes_drive_the_device(hip_lib, tmp_path):
-    exe = str(tmp_path / "host_class_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "host_class_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
+    out_lines = run_demo("host_class_demo", tmp_path)
     rows = {}
-    for line in out.stdout.splitlines():
+    for line in out_lines:
         p = line.split()
         rows.setdefault(p[0], []).append(p[1:])
     y = [2.1, 3.9, 6.2, 8.0, 9.7, 12.3]

@@ -1,8 +1,6 @@
 """-m gpu: cx_log_evidence — log p(data) of Gaussian models from the stored messages — against the dense joint, the
 Kalman filter and the numpy restatement of the formula (tests/evidence_support.py, pinned by tests/test_evidence_checker.py)."""
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,17 +11,9 @@ from cortex.jl_amd import get_value, get_variable_marginal, update_marginals
 from tests import evidence_support as E
 from tests.test_gpu_kary_mv import _kary_tree, _load as _load_kary
 from tests.test_host_mirror import make_ssm
+from tests.gpu_support import code_of, iterative_device, run_demo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ITER = (L.SCHED_FUSED, L.SCHED_FLOODING)
-
-
-def _dev(model, schedule, iterative_sweeps=0):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule in ITER else None)
-    dev.sweep(iterative_sweeps if schedule in ITER else 1)      # (reference order: cx_sweep requests every variable)
-    return dev
 
 
 def _exact(dev, want, rtol=1e-9, what=""):
@@ -46,7 +36,7 @@ def test_dim1_exact_after_every_schedule(hip_lib, name, make, n_iter, chain):
     want = E.dense_log_z(gm)
     schedules = [L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED, L.SCHED_FLOODING] + ([L.SCHED_CHAIN_SCAN] if chain else [])
     for s in schedules:
-        dev = _dev(model, s, n_iter)
+        dev = iterative_device(model, s, n_iter)
         _, cnt = _exact(dev, want, what=f"{name} schedule {s}")
         assert cnt["factor_terms"] == sum(len(g["fid"]) for g in gm.groups.values())
         dev.close()
@@ -61,7 +51,7 @@ def test_dims_2_to_4_exact_after_every_schedule(hip_lib, d):
     for name, model, chain in _dim_models(d):
         want = E.dense_log_z(E.gmodel(model))
         for s in [L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED] + ([L.SCHED_CHAIN_SCAN] if chain else []):
-            dev = _dev(model, s, 200)
+            dev = iterative_device(model, s, 200)
             _exact(dev, want, what=f"d {d} {name} schedule {s}")
             dev.close()
     # a k-ary tree (factors of 3 .. 6 variables, a parameter set per input)
@@ -79,20 +69,20 @@ def test_dims_2_to_4_exact_after_every_schedule(hip_lib, d):
 
 def test_size_scalar_chain_of_a_million_states(hip_lib):
     model = cx.synth.ssm_chain(10**6, seed=31)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     _exact(dev, E.kalman_of_chain(model), what="T = 1e6, chain scan")
     dev.close()
 
 
 def test_size_d4_chain_of_1e5_states(hip_lib):
     model = cx.synth.lgssm_chain(10**5, d=4, seed=32)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     _exact(dev, E.kalman_of_chain(model), what="d = 4, T = 1e5, chain scan")
     dev.close()
 
 
 def _loopy_check(model, n_sweeps):
-    dev = _dev(model, L.SCHED_FUSED, n_sweeps)
+    dev = iterative_device(model, L.SCHED_FUSED, n_sweeps)
     gm = E.gmodel(model)
     got, cnt = dev.log_evidence()
     again, _ = dev.log_evidence()
@@ -117,7 +107,7 @@ def test_loopy_c4_after_200_fused_sweeps_matches_the_restatement(hip_lib):
 def test_new_parameters_are_read(hip_lib):
     # dim 2, chain scan: new (A, Q) of the transition set
     model = cx.synth.lgssm_chain(40, d=2, seed=61)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     first, _ = _exact(dev, E.dense_log_z(E.gmodel(model)), what="old (A, Q)")
     A2, Q2 = 0.7 * np.array([[0.9, -0.3], [0.2, 0.8]]), np.array([[0.3, 0.05], [0.05, 0.2]])
     dev.set_factor_matrices(0, A2, Q2)
@@ -129,7 +119,7 @@ def test_new_parameters_are_read(hip_lib):
     dev.close()
     # dim 1, tree: new coefficients of the factors of more than two variables
     model = cx.synth.tree_model(30, seed=62, k_choices=(2, 3), observe=0.2)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = iterative_device(model, L.SCHED_TREE)
     _exact(dev, E.dense_log_z(E.gmodel(model)), what="old coefficients")
     meta = model.meta
     new = np.asarray(meta["coef"]) * 1.3 + 0.1
@@ -156,7 +146,7 @@ def test_new_parameters_are_read(hip_lib):
 def test_no_side_effects(hip_lib):
     # reference order: the state blob and the trace are unchanged by the call
     model = cx.synth.tree_model(40, seed=71, k_choices=(1, 2, 3), observe=0.2)
-    dev = _dev(model, L.SCHED_REFERENCE)
+    dev = iterative_device(model, L.SCHED_REFERENCE)
     blob, trace = dev.export_state(), dev.ref_trace()
     dev.log_evidence()
     assert np.array_equal(blob, dev.export_state())
@@ -164,7 +154,7 @@ def test_no_side_effects(hip_lib):
     dev.close()
     # dim 4 chain scan: the blob too
     model = cx.synth.lgssm_chain(50, d=4, seed=72)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     dev.log_evidence()
     blob = dev.export_state()
     dev.log_evidence()
@@ -172,7 +162,7 @@ def test_no_side_effects(hip_lib):
     dev.close()
     # fused: the next sweeps are those of a twin handle that never called it, bit for bit
     model = cx.synth.gaussian_grid(12, 10, seed=73)
-    a, b = _dev(model, L.SCHED_FUSED, 5), _dev(model, L.SCHED_FUSED, 5)
+    a, b = iterative_device(model, L.SCHED_FUSED, 5), iterative_device(model, L.SCHED_FUSED, 5)
     a.log_evidence()
     a.sweep(3); b.sweep(3)
     assert np.array_equal(a.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE), b.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE))
@@ -199,38 +189,32 @@ def test_undefined_states_are_nan(hip_lib):
     dev.close()
 
 
-def _code(fn):
-    with pytest.raises(L.CortexHipError) as e:
-        fn()
-    return e.value.code, e.value.message
-
-
 def test_refusals(hip_lib):
     dev = cx.DeviceGraph()
-    assert _code(dev.log_evidence)[0] == L.ERR_STATE                          # no graph
+    assert code_of(dev.log_evidence)[0] == L.ERR_STATE                          # no graph
     dev.close()
     dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    assert _code(dev.log_evidence)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.log_evidence)[0] == L.ERR_UNSUPPORTED
     dev.close()
     vm = cx.synth.vmp_ssm(8)
     dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
     cx.synth.load_vmp_into_device(vm, dev)
-    assert _code(dev.log_evidence)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.log_evidence)[0] == L.ERR_UNSUPPORTED
     dev.close()
     m16 = cx.synth.lgssm_chain(4, d=16, seed=91)
-    dev = _dev(m16, L.SCHED_FUSED, 2)
-    assert _code(dev.log_evidence)[0] == L.ERR_UNSUPPORTED                    # dim >= 5
+    dev = iterative_device(m16, L.SCHED_FUSED, 2)
+    assert code_of(dev.log_evidence)[0] == L.ERR_UNSUPPORTED                    # dim >= 5
     dev.close()
     model = cx.synth.ssm_chain(20, seed=92)
-    dev = _dev(model, L.SCHED_FUSED, 5)
+    dev = iterative_device(model, L.SCHED_FUSED, 5)
     assert dev.lib.cx_log_evidence(dev.h, None, None) == L.ERR_INVALID_ARGUMENT
     dev.halo_configure([1], [2 * 20 + 1], [], [])                             # a halo list: a partitioned handle
-    assert _code(dev.log_evidence)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.log_evidence)[0] == L.ERR_UNSUPPORTED
     dev.close()
     model = cx.synth.ssm_chain(10, seed=93, q=0.0)
     dev = cx.DeviceGraph(schedule=L.SCHED_TREE)
     cx.synth.load_into_device(model, dev)
-    code, msg = _code(dev.log_evidence)
+    code, msg = code_of(dev.log_evidence)
     assert code == L.ERR_UNSUPPORTED and "factor 31" in msg                   # the first transition (ids 3T + 1 ..)
     dev.close()
 
@@ -251,14 +235,8 @@ def test_hip_processor_log_evidence(hip_lib):
 
 
 def test_cpp_host_class_log_evidence(hip_lib, tmp_path):
-    exe = str(tmp_path / "evidence_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "evidence_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: line.split()[1:] for line in out.stdout.splitlines()}
+    out_lines = run_demo("evidence_demo", tmp_path)
+    rows = {line.split()[0]: line.split()[1:] for line in out_lines}
     T = 50
     y = np.array([0.5 * t + (7 * t) % 5 for t in range(1, T + 1)], dtype=np.float64)
     want = E.kalman_log_lik(np.ones(T - 1), np.zeros(T - 1), np.ones(T - 1), np.ones(T), y.reshape(T, 1))

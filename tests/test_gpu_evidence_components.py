@@ -4,8 +4,6 @@
 import ctypes as C
 import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,9 +14,9 @@ from cortex.jl_amd import learn
 from tests import components_support as CS
 from tests import evidence_support as E
 from tests import missing_data as MD
+from tests.gpu_support import code_of, run_demo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LENGTHS = (2, 3, 65, 300)
 
 
@@ -181,12 +179,6 @@ def test_an_undefined_component_leaves_the_others_alone(hip_lib):
 
 
 # ---- 7: refusals and arguments -------------------------------------------------------------------------------------------------------
-def _code(fn, *args):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*args)
-    return e.value.code, e.value.message
-
-
 def test_refusals_and_arguments(hip_lib):
     # dim 16: the components, no evidence
     m16 = cx.synth.lgssm_chain(4, d=16)
@@ -194,7 +186,7 @@ def test_refusals_and_arguments(hip_lib):
     cx.synth.load_into_device(m16, dev)                   # (cx_graph_create and the data; no sweep)
     lab, n = dev.components()
     assert n == 1 and len(lab) == 8 and not lab.any()
-    assert _code(dev.log_evidence_components)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.log_evidence_components)[0] == L.ERR_UNSUPPORTED
     assert dev.components()[1] == 1
     dev.close()
     # a variational family
@@ -222,7 +214,7 @@ def test_refusals_and_arguments(hip_lib):
         assert _bits(dev.log_evidence_components()[0]) == _bits(good)
     assert dev.lib.cx_log_evidence_components(dev.h, 0, None, None, C.byref(nc), out) == L.OK and nc.value == 2      # the sizing call
     assert dev.lib.cx_log_evidence_components(dev.h, 2, pv, None, C.byref(nc), out) == L.OK and _bits(val) == _bits(good)
-    code, msg = _code(dev.components, [1, 987654321])
+    code, msg = code_of(dev.components, [1, 987654321])
     assert code == L.ERR_NOT_FOUND and "987654321" in msg
     assert dev.lib.cx_graph_components(dev.h, 0, None, None, None) == L.ERR_INVALID_ARGUMENT
     assert dev.components()[1] == 2
@@ -230,7 +222,7 @@ def test_refusals_and_arguments(hip_lib):
     # a partitioned handle
     dev = _dev(model, L.SCHED_FUSED, 2)
     dev.halo_configure_state([], [], [], [])
-    assert _code(dev.log_evidence_components)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.log_evidence_components)[0] == L.ERR_UNSUPPORTED
     assert dev.components()[1] == 2
     dev.close()
 
@@ -285,14 +277,8 @@ def test_multi_start_em_by_component(hip_lib):
 
 # ---- 9: the C++ client ---------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_components(hip_lib, tmp_path):
-    exe = str(tmp_path / "components_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "components_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    lines = [line.split() for line in out.stdout.splitlines()]
+    out_lines = run_demo("components_demo", tmp_path)
+    lines = [line.split() for line in out_lines]
     # the same graph here: two scalar chains of 5 and 9 states with the demo's data
     parts = []
     for T in (5, 9):

@@ -3,8 +3,6 @@
 tests/components_mfma_support.py (pinned by tests/test_components_mfma_checker.py); learn.profile and learn.multi_start_em at d = 16."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,9 +15,9 @@ from tests import components_support as CS
 from tests import evidence_mfma_support as S
 from tests import evidence_support as E
 from tests import missing_data as MD
+from tests.gpu_support import assert_reader_refusals, demo_chain, run_demo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bits(a):
@@ -149,12 +147,6 @@ def test_an_undefined_component_leaves_the_others_alone(hip_lib):
 
 
 # ---- 6: refusals and arguments -----------------------------------------------------------------------------------------------------------
-def _code(fn, *args):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*args)
-    return e.value.code, e.value.message
-
-
 class _Out:
     """output arrays of the raw call, filled with marks: a refused call leaves them as they are"""
 
@@ -167,11 +159,17 @@ class _Out:
         return (self.val == 7.25).all() and (self.cc == -5).all() and self.nc.value == -9 and list(self.out) == [-1, -2, -3, -4]
 
 
+def _raw(dev, o, cap=2):
+    return dev.lib.cx_log_evidence_components_mfma(dev.h, cap, o.pv, o.pc, C.byref(o.nc), o.out)
+
+
 def test_refusals_and_arguments(hip_lib):
-    # a dim 2 handle: the call for dims 1 .. 4 is named
+    # (call: the C entry itself, raised by the binding's own check — DeviceGraph.log_evidence_components_mfma counts the components
+    # first, and a handle without a graph is refused by that count under another name)
+    assert_reader_refusals("cx_log_evidence_components_mfma", "cx_log_evidence_components", lambda dev: dev._check(_raw(dev, _Out())),
+                           lambda dev: dev.log_evidence_components(), lambda dev: _raw(dev, _Out()))
+    # a dim 2 handle: a refused call leaves its outputs as they are
     dev = _dev(cx.synth.concat_models(CS.chain_parts(2, (2, 3))), L.SCHED_TREE)
-    code, msg = _code(dev.log_evidence_components_mfma)
-    assert code == L.ERR_UNSUPPORTED and "cx_log_evidence_components" in msg.replace("cx_log_evidence_components_mfma", ""), msg
     o = _Out()
     assert dev.lib.cx_log_evidence_components_mfma(dev.h, 2, o.pv, o.pc, C.byref(o.nc), o.out) == L.ERR_UNSUPPORTED and o.untouched()
     assert "cx_log_evidence_components" in dev.last_error().replace("cx_log_evidence_components_mfma", "")
@@ -202,8 +200,7 @@ def test_refusals_and_arguments(hip_lib):
     val = np.zeros(3)
     assert call(dev.h, 3, val.ctypes.data_as(C.POINTER(C.c_double)), None, C.byref(nc), out) == L.OK and _bits(val) == _bits(good)
     assert list(out) == list(good_counts.values())
-    # the dim 1 - 4 call keeps refusing these dims
-    assert _code(dev.log_evidence_components)[0] == L.ERR_UNSUPPORTED
+    # the dim 1 - 4 call keeps refusing these dims, and writes nothing
     assert dev.lib.cx_log_evidence_components(dev.h, 3, o.pv, o.pc, C.byref(o.nc), o.out) == L.ERR_UNSUPPORTED and o.untouched()
     dev.close()
     # a partitioned handle (a halo list: x_1 and the first transition of a T = 4 chain)
@@ -267,23 +264,15 @@ def test_multi_start_em(hip_lib):
 
 # ---- 9: the C++ client -------------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_components_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "components_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "components_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    lines = [line.split() for line in out.stdout.splitlines()]
+    lines = [line.split() for line in run_demo("components_mfma_demo", tmp_path)]
     assert [l for l in lines if l[0] == "components"][0][1:] == ["2"]
     d = 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
     rows = [l for l in lines if l[0] == "value"]
     assert len(rows) == 2
     for row, T in zip(rows, (5, 9)):
-        y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
-        want = E.kalman_log_lik(np.broadcast_to(A, (T - 1, d, d)), np.zeros((T - 1, d)), np.broadcast_to(0.5 * np.eye(d), (T - 1, d, d)),
-                                np.broadcast_to(np.eye(d), (T, d, d)), y)
+        A, Q, R, y = demo_chain(T, d)
+        want = E.kalman_log_lik(np.broadcast_to(A, (T - 1, d, d)), np.zeros((T - 1, d)), np.broadcast_to(Q, (T - 1, d, d)),
+                                np.broadcast_to(R, (T, d, d)), y)
         got = float(row[2])
         assert abs(got - want) <= 1e-9 * abs(want), (T, got, want)
         assert row[3:] == [str(2 * T - 1), str(T), "0", "0"]

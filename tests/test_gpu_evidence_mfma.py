@@ -1,9 +1,8 @@
 """-m gpu: cx_log_evidence_mfma — log p(data) at the matrix-core dims (cx_create dim 5 .. 64) — against the dense
 joint, the Kalman filter and the numpy restatement of the formula on the device's own messages (tests/evidence_support.py; the inputs of
 the loop and forecast cases are pinned on the CPU by tests/test_evidence_mfma_checker.py)."""
+import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,17 +12,10 @@ from cortex.jl_amd import _lib as L
 from tests import evidence_mfma_support as S
 from tests import evidence_support as E
 from tests import missing_data as MD
+from tests.gpu_support import assert_reader_refusals, code_of, demo_chain, run_demo, swept_device
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIMS = (5, 8, 16, 17, 32, 33, 64)      # 5: the least; 17, 33: the first of the next tile size; 16, 32, 64: native
-
-
-def _dev(model, schedule, fused_sweeps=60):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule == L.SCHED_FUSED else None)
-    dev.sweep(fused_sweeps if schedule == L.SCHED_FUSED else 1)      # (reference order: cx_sweep requests every variable)
-    return dev
 
 
 def _exact(dev, want, rtol=1e-9, what=""):
@@ -46,7 +38,7 @@ def test_exact_after_every_schedule(hip_lib, d, shape):
     gm = E.gmodel(model)
     want = E.dense_log_z(gm)
     for s in [L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED] + ([L.SCHED_CHAIN_SCAN] if shape == "chain" else []):
-        dev = _dev(model, s)      # (fused: seed variance 1e6 and 60 sweeps, the diameter is under 20)
+        dev = swept_device(model, s)      # (fused: seed variance 1e6 and 60 sweeps, the diameter is under 20)
         _, cnt = _exact(dev, want, what=f"d {d} {shape} schedule {s}")
         assert cnt["factor_terms"] == _n_rule_factors(gm)
         assert cnt["variable_terms"] == len(model.x_ids)      # every state has two or three factors
@@ -58,7 +50,7 @@ def test_exact_after_every_schedule(hip_lib, d, shape):
 def test_loop_matches_the_restatement_on_the_device_messages(hip_lib, d):
     model = S.ring(d)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_FUSED, S.RING_SWEEPS)
+    dev = swept_device(model, L.SCHED_FUSED, S.RING_SWEEPS)
     got, cnt = dev.log_evidence_mfma()
     again, _ = dev.log_evidence_mfma()
     assert np.float64(got).tobytes() == np.float64(again).tobytes()         # two calls on one state: bit-identical
@@ -137,7 +129,7 @@ def test_an_observed_state_in_the_middle(hip_lib, d):
     gm = E.gmodel(model)
     want = E.dense_log_z(gm)
     for s in (L.SCHED_TREE, L.SCHED_FUSED):
-        dev = _dev(model, s)
+        dev = swept_device(model, s)
         _, cnt = _exact(dev, want, what=f"clamped middle d {d} schedule {s}")
         assert cnt["factor_terms"] == _n_rule_factors(gm) and cnt["variable_terms"] == len(model.x_ids) - 1      # every free state has two or three factors
         dev.close()
@@ -168,11 +160,11 @@ def test_undefined_then_exact_then_new_parameters(hip_lib, d):
 def test_embedded_dims_give_the_real_models_value_at_any_tile_size(hip_lib, d, monkeypatch):
     model = cx.synth.lgssm_chain(5, d=d, seed=90 + d)
     want = E.dense_log_z(E.gmodel(model))
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     native, _ = _exact(dev, want, what=f"d {d}, native tile")
     dev.close()
     monkeypatch.setenv("CX_MFMA_DIM", "64")
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     monkeypatch.delenv("CX_MFMA_DIM")
     forced, _ = _exact(dev, want, what=f"d {d}, 4 x 4 tiles")
     dev.close()
@@ -183,7 +175,7 @@ def test_embedded_dims_give_the_real_models_value_at_any_tile_size(hip_lib, d, m
 def test_moves_nothing(hip_lib):
     model = cx.synth.lgssm_chain(8, d=16, seed=72)
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_REFERENCE, L.SCHED_TREE):
-        dev = _dev(model, s)
+        dev = swept_device(model, s)
         if s == L.SCHED_CHAIN_SCAN:      # (another reader first: every reader of the messages brings them to their slots)
             dev.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE)
         blob, marg = dev.export_state(), dev.get_marginals(model.x_ids)
@@ -194,7 +186,7 @@ def test_moves_nothing(hip_lib):
         assert np.array_equal(blob, dev.export_state())
         dev.close()
     # fused: the next sweeps are those of a twin handle that never called it, bit for bit
-    a, b = _dev(model, L.SCHED_FUSED, 5), _dev(model, L.SCHED_FUSED, 5)
+    a, b = swept_device(model, L.SCHED_FUSED, 5), swept_device(model, L.SCHED_FUSED, 5)
     assert a.residual() == b.residual()      # (the first call takes the snapshot the next one measures against)
     a.log_evidence_mfma()
     a.sweep(3); b.sweep(3)
@@ -210,77 +202,33 @@ def test_moves_nothing(hip_lib):
 @pytest.mark.parametrize("T,d", [(2000, 64), (20000, 16)])
 def test_long_chains_against_the_kalman_filter(hip_lib, T, d):
     model = cx.synth.lgssm_chain(T, d=d, seed=33)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = swept_device(model, L.SCHED_CHAIN_SCAN)
     _, cnt = _exact(dev, E.kalman_of_chain(model), what=f"d = {d}, T = {T}, chain scan")
     assert cnt["factor_terms"] == 2 * T - 1 and cnt["variable_terms"] == T
     dev.close()
 
 
 # ---- 8. refusals ---------------------------------------------------------------------------------------------------------------------
-def _code(fn):
-    with pytest.raises(L.CortexHipError) as e:
-        fn()
-    return e.value.code, e.value.message
-
-
 def test_refusals(hip_lib):
-    m4 = cx.synth.lgssm_chain(5, d=4, seed=91)
-    dev = _dev(m4, L.SCHED_TREE)
-    code, msg = _code(dev.log_evidence_mfma)
-    assert code == L.ERR_UNSUPPORTED and "cx_log_evidence" in msg.replace("cx_log_evidence_mfma", "")      # names the call for dims 1 .. 4
-    dev.close()
-    dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    code, msg = _code(dev.log_evidence_mfma)
-    assert code == L.ERR_UNSUPPORTED and "Gaussian family" in msg
-    dev.close()
-    vm = cx.synth.vmp_ssm(8)
-    dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
-    cx.synth.load_vmp_into_device(vm, dev)
-    code, msg = _code(dev.log_evidence_mfma)
-    assert code == L.ERR_UNSUPPORTED and "Gaussian family" in msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16)
-    code, msg = _code(dev.log_evidence_mfma)
-    assert code == L.ERR_STATE and "no graph" in msg
-    dev.close()
+    val, c4 = C.c_double(), (C.c_int64 * 4)()
+    assert_reader_refusals("cx_log_evidence_mfma", "cx_log_evidence", lambda dev: dev.log_evidence_mfma(), lambda dev: dev.log_evidence(),
+                           lambda dev: dev.lib.cx_log_evidence_mfma(dev.h, C.byref(val), c4))
     m16 = cx.synth.lgssm_chain(4, d=16, seed=92)
-    dev = _dev(m16, L.SCHED_FUSED, 2)
+    dev = swept_device(m16, L.SCHED_FUSED, 2)
     assert dev.lib.cx_log_evidence_mfma(dev.h, None, None) == L.ERR_INVALID_ARGUMENT
     assert b"null argument" in dev.lib.cx_last_error(dev.h)
-    assert _code(dev.log_evidence)[0] == L.ERR_UNSUPPORTED                    # the old call keeps refusing these dims
-    dev.halo_configure_state([m16.x_ids[0]], [3 * 4 + 1], [], [])      # a halo list (x_1, the first transition): a partitioned handle
-    code, msg = _code(dev.log_evidence_mfma)
-    assert code == L.ERR_UNSUPPORTED and "partitioned handle" in msg
-    dev.close()
-    # a halo list through cx_halo_configure: at these dims it is accepted under the chain scan alone, where it makes the handle a chain's
-    # time block (a plain per-sweep message halo is refused by cx_halo_configure itself at dim > 1)
-    dev = _dev(m16, L.SCHED_CHAIN_SCAN)
-    dev.log_evidence_mfma()
-    dev.halo_configure([m16.x_ids[0]], [3 * 4 + 1], [], [])
-    code, msg = _code(dev.log_evidence_mfma)
-    assert code == L.ERR_UNSUPPORTED and "partitioned handle" in msg and "time block" in msg
-    dev.close()
-    dev = _dev(m16, L.SCHED_FUSED, 2)
-    code, msg = _code(lambda: dev.halo_configure([m16.x_ids[0]], [3 * 4 + 1], [], []))
+    code, msg = code_of(dev.halo_configure, [m16.x_ids[0]], [3 * 4 + 1], [], [])
     assert code == L.ERR_UNSUPPORTED and "dim == 1" in msg      # (no plain halo list exists at these dims)
     dev.close()
 
 
 # ---- the C++ host class ---------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_log_evidence_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "evidence_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "evidence_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: line.split()[1:] for line in out.stdout.splitlines()}
+    rows = {line.split()[0]: line.split()[1:] for line in run_demo("evidence_mfma_demo", tmp_path)}
     T, d = 12, 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
-    y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
-    want = E.kalman_log_lik(np.broadcast_to(A, (T - 1, d, d)), np.zeros((T - 1, d)), np.broadcast_to(0.5 * np.eye(d), (T - 1, d, d)),
-                            np.broadcast_to(np.eye(d), (T, d, d)), y)
+    A, Q, R, y = demo_chain(T, d)
+    want = E.kalman_log_lik(np.broadcast_to(A, (T - 1, d, d)), np.zeros((T - 1, d)), np.broadcast_to(Q, (T - 1, d, d)),
+                            np.broadcast_to(R, (T, d, d)), y)
     assert math.isnan(float(rows["before"][0])) and int(rows["before"][3]) > 0
     got = float(rows["evidence"][0])
     assert abs(got - want) <= 1e-9 * abs(want), (got, want)

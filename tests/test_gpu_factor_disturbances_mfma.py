@@ -7,8 +7,6 @@ behind a flat leaf 1e-12 max|Q|, a forced tile size against the native one 1e-12
 formed in numpy from the device's OWN rows and the model's Q: the rounding of a d²-term sum, 4 d² ε Σ|term|."""
 import ctypes as C
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,9 +22,11 @@ from tests import learn_mfma_support as M
 from tests import learning_support as S
 from tests import missing_data as MD
 from tests import offsets_support as O
+from tests.gpu_support import HANDLE_CASES, STREAM_CASES, assert_reader_refusals, code_of, demo_chain, run_demo, under_capture
+from tests.learn_mfma_support import assert_within as _close
+from tests.learn_mfma_support import bound_of as _scale
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = float(np.finfo(np.float64).eps)
 WHO = "cx_factor_disturbances_mfma"
 KEYS = ("mean", "cov", "expected_mahalanobis", "mahalanobis")
@@ -42,18 +42,6 @@ def _dev(model, schedule, sweeps=1, b=None, loader=None):
         dev.set_factor_offsets_mfma(*O.arrays(b))
     dev.sweep(sweeps)
     return dev
-
-
-def _close(got, want, tol, what):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    err = float(np.max(np.abs(got - want))) if want.size else 0.0
-    print(f"{what}: max abs error {err:.3e} (bound {tol:.3e})")
-    assert np.all(np.isfinite(got)), what
-    assert err <= tol, (what, err, tol)
-
-
-def _scale(want):
-    return 1e-9 * max(1.0, float(np.max(np.abs(want)))) if np.size(want) else 1e-9
 
 
 def _check_scores(res, Q, what):
@@ -93,12 +81,6 @@ def _check_trace(res, model, want_cov, what):
 
 def _bits(a, b, keys=KEYS):
     return all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in keys)
-
-
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
 
 
 # ---- 1, 2. the dense posterior on forests; the rows add up to the statistics -------------------------------------------------------------
@@ -415,33 +397,33 @@ def test_moves_nothing(hip_lib):
 
 
 # ---- 12. refusals -----------------------------------------------------------------------------------------------------------------------
+P64, PD = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+
+
+def _raw(dev, out, sc, tot, c4):
+    """every row through the C ABI; the status"""
+    return dev.lib.cx_factor_disturbances_mfma(dev.h, 0, None, out.ctypes.data_as(PD), sc.ctypes.data_as(PD), C.byref(tot), c4.ctypes.data_as(P64))
+
+
+# what assert_reader_refusals asks of this reader.  call: without ids the binding asks cx_factor_disturbance_rows_mfma first; factor 13 is a
+# likelihood of its dim 4 chain and the first transition of its dim 16 one.  raw: that chain has 7 rows.  "small call" is skipped: the
+# disturbances have no dim 1 .. 4 call (the refusal names cx_factor_statistics, whose sums they are), so none can keep refusing dim 16
+_COMMON = dict(who=WHO, small="cx_factor_statistics", call=lambda dev: dev.factor_disturbances_mfma([13]), small_call=None,
+               raw=lambda dev: _raw(dev, np.zeros((7, 16 + 256)), np.zeros((7, 2)), C.c_double(), np.zeros(4, np.int64)), skip=("small call",))
+
+
 def test_refusals(hip_lib):
-    call = lambda dev: dev.factor_disturbances_mfma([1])      # (without ids the binding asks cx_factor_disturbance_rows_mfma first)
+    assert_reader_refusals(**_COMMON, cases=HANDLE_CASES)
     m2 = cx.synth.lgssm_chain(5, d=2, seed=91)
     m16 = cx.synth.lgssm_chain(4, d=16, seed=92)
-    dev = _dev(m2, L.SCHED_TREE)
-    code, msg = _code(call, dev)
+    dev = _dev(m2, L.SCHED_TREE)      # dim 2 as well as the helper's dim 4; the row list refuses under its own name
+    code, msg = code_of(dev.factor_disturbances_mfma, [1])
     assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "cx_factor_statistics" in msg.replace(WHO, "") and "5 .. 64" in msg, msg
-    code, msg = _code(dev.factor_disturbance_rows_mfma)
+    code, msg = code_of(dev.factor_disturbance_rows_mfma)
     assert code == L.ERR_UNSUPPORTED and msg.startswith("cx_factor_disturbance_rows_mfma"), msg
     dev.close()
-    vm = cx.synth.vmp_ssm(8)
-    dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
-    cx.synth.load_vmp_into_device(vm, dev)
-    code, msg = _code(call, dev)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "Gaussian family" in msg, msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16)
-    code, msg = _code(call, dev)
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "no graph" in msg, msg
-    dev.close()
-    dev = _dev(m16, L.SCHED_FUSED, 2)
-    dev.halo_configure_state([m16.x_ids[0]], [3 * 4 + 1], [], [])      # a halo list: a partitioned handle
-    code, msg = _code(call, dev)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "partitioned handle" in msg, msg
-    dev.close()
     dev = _dev(m16, L.SCHED_TREE)
-    code, msg = _code(dev.factor_disturbances_mfma, [10 ** 6])
+    code, msg = code_of(dev.factor_disturbances_mfma, [10 ** 6])
     assert code == L.ERR_NOT_FOUND and msg.startswith(WHO) and str(10 ** 6) in msg, msg
     tot, sc = C.c_double(), np.zeros((7, 2))
     assert dev.lib.cx_factor_disturbances_mfma(dev.h, 0, None, None, sc.ctypes.data_as(C.POINTER(C.c_double)), C.byref(tot), None) == L.ERR_INVALID_ARGUMENT
@@ -456,64 +438,32 @@ def test_refusals(hip_lib):
     cx.synth.load_into_device(model, dev)
     EM.set_opaque(dev, opq)
     dev.sweep(1)
-    code, msg = _code(dev.factor_disturbances_mfma, opq[1])
+    code, msg = code_of(dev.factor_disturbances_mfma, opq[1])
     assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and str(int(opq[1][0])) in msg and "CX_FACTOR_GAUSS_LINEAR" in msg, msg
     dev.close()
 
 
-def _under_capture(dev, call):
-    """the status of `call` while the handle's stream is being captured (relaxed mode: the refusal's own runtime queries do not void
-    the capture); the handle is back on its own stream afterwards"""
-    hip = C.CDLL([ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0])
-    stream, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    dev.set_stream(stream.value)
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
-    rc = call()
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    dev.set_stream(None)
-    assert hip.hipStreamDestroy(stream) == 0
-    return rc, dev.lib.cx_last_error(dev.h).decode()
-
-
 def test_refusals_of_a_captured_stream_and_of_parameter_sets_never_set(hip_lib):
+    assert_reader_refusals(**_COMMON, cases=STREAM_CASES)
     d = 16
     model = cx.synth.lgssm_chain(5, d=d, seed=93)
     dev = _dev(model, L.SCHED_TREE)
     want = dev.factor_disturbances_mfma()
     n = len(want["factor_ids"])
     out, sc, tot, c4 = np.zeros((n, d + d * d)), np.zeros((n, 2)), C.c_double(), np.zeros(4, np.int64)
-    p64, pd = C.POINTER(C.c_int64), C.POINTER(C.c_double)
-    rc, msg = _under_capture(dev, lambda: dev.lib.cx_factor_disturbances_mfma(dev.h, 0, None, out.ctypes.data_as(pd), sc.ctypes.data_as(pd), C.byref(tot), c4.ctypes.data_as(p64)))
+    rc, msg = under_capture(dev, lambda: _raw(dev, out, sc, tot, c4))
     assert rc == L.ERR_STATE and msg.startswith(WHO) and "captured" in msg, (rc, msg)
     assert not out.any() and not sc.any() and not c4.any()      # nothing was written
     got = dev.factor_disturbances_mfma()                        # and the handle works on, bit for bit
     assert _bits(want, got) and want["total"] == got["total"]
     dev.close()
-    dev = cx.DeviceGraph(dim=d, schedule=L.SCHED_TREE)
-    dev.set_factor_matrices(0, *model.psets[0])                # set 1, the likelihoods', is never set
-    dev.graph_create(model.edge_var, model.edge_fac, model.factor_ids, model.factor_kind, model.factor_var, edge_role=model.edge_role)
-    code, msg = _code(lambda: dev.factor_disturbances_mfma(S.pset_groups(model)[0]))
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "never set" in msg and "cx_set_factor_matrices" in msg, (code, msg)
-    dev.close()
 
 
 # ---- 13. the C++ host class -------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_factor_disturbances_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "disturbances_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "disturbances_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: line.split()[1:] for line in out.stdout.splitlines()}
+    rows = {line.split()[0]: line.split()[1:] for line in run_demo("disturbances_mfma_demo", tmp_path)}
     T, d = 12, 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
-    Q, R = 0.5 * np.eye(d), np.eye(d)
-    y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
+    A, Q, R, y = demo_chain(T, d)
 
     class _Chain:      # what rts_factor_moments reads of a model
         dim, data_y, meta = d, y, {"T": T, "A": A, "Q": Q, "R": R}

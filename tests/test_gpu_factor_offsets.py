@@ -10,8 +10,6 @@ support modules' constants; the batch items against the closed formulas at 1e-10
 The dim > 1 chain scan refuses a chain with a forecast tail (tests/test_gpu_missing_data.py pins that): the tail with offsets runs under
 the tree schedule here, the chain with unobserved states under the chain scan."""
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,14 +23,11 @@ from tests import learning_support as LS
 from tests import missing_data as MD
 from tests import offsets_support as O
 from tests import predictive_support as P
-from tests.helpers import assert_close as _assert_close
+from tests.helpers import assert_close_by_max as assert_close
+from tests.gpu_support import code_of, run_demo
+from tests.learning_support import assert_rel_close as _close
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def assert_close(a, b, rtol, what=""):
-    return _assert_close(a, b, rtol, what, scale_by="max")
 
 
 def _dev(model, schedule=L.SCHED_FUSED, b=None, seed_variance=None, loader=None, **kw):
@@ -46,48 +41,12 @@ def _dev(model, schedule=L.SCHED_FUSED, b=None, seed_variance=None, loader=None,
     return dev
 
 
-def _check_marginals(dev, model, ref, tol, what):
-    d, n = model.dim, len(model.x_ids)
-    em, ecov = ref
-    marg = dev.get_marginals(model.x_ids)
-    assert not np.any(np.isnan(marg)), f"{what}: undefined marginals"
-    assert_close(marg[:, :d], em, tol, f"{what}: marginal means")
-    assert_close(marg[:, d:].reshape(n, d, d), ecov, tol, f"{what}: marginal covariances")
-    return marg
-
-
-def _latent_edges(model):
-    keep = np.isin(model.edge_var, model.x_ids)
-    return model.edge_var[keep], model.edge_fac[keep]
-
-
-def _messages(dev, model):
-    ev, ef = _latent_edges(model)
-    return dev.get_messages(ev, ef, L.TO_VARIABLE, L.FORM_NATURAL)
-
-
-def _code(call):
-    with pytest.raises(cx.CortexHipError) as ei:
-        call()
-    return ei.value.code, ei.value.message
-
-
-_REF = {}
-
-
-def _ref(key, make):
-    """a reference computed once per key and left unchanged"""
-    if key not in _REF:
-        _REF[key] = make()
-    return _REF[key]
-
-
 def _chain_case(d, T, general_h=True):
     def make():
         model = AN.chain(T, d, general_h=general_h)
         b = O.with_offsets(model, 1)
         return model, b, O.dense_posterior_offsets(model, b)
-    return _ref(("chain", d, T, general_h), make)
+    return O.ref(("chain", d, T, general_h), make)
 
 
 # ---- 1. fused sweeps on a chain -------------------------------------------------------------------------------------------------------
@@ -98,9 +57,9 @@ def test_fused_sweeps_on_a_chain_with_offsets(hip_lib, d):
     dev, plain = _dev(model, b=b), _dev(model)
     dev.sweep(T + 3)
     plain.sweep(T + 3)
-    marg = _check_marginals(dev, model, ref, 1e-9, f"d={d} fixed point vs the joint solve with offsets")
+    marg = AN.check_marginals(dev, model, ref, 1e-9, f"d={d} fixed point vs the joint solve with offsets")
     # the offsets move no precision: the precision part of every message into a latent variable is the no-offset handle's, bit for bit
-    ma, mp = _messages(dev, model), _messages(plain, model)
+    ma, mp = O.messages(dev, model), O.messages(plain, model)
     assert np.array_equal(np.isnan(ma), np.isnan(mp))
     assert np.array_equal(ma[:, d:], mp[:, d:], equal_nan=True), "precisions differ from the handle without offsets"
     assert np.nanmax(np.abs(ma[:, :d] - mp[:, :d])) > 0.1, "the offsets did not reach the messages"
@@ -120,11 +79,11 @@ def test_every_sweep_is_the_shifted_twins(hip_lib, d):
     b, s = O.consistent_offsets(model, 2)
     twin, to_twin = O.shifted_twin(model, b, s)
     dev, tw = _dev(model, b=b), _dev(twin)
-    ev, _ = _latent_edges(model)
+    ev, _ = O.latent_edges(model)
     for sweep in range(8):
         dev.sweep(1)
         tw.sweep(1)
-        ma, mt = _messages(dev, model), _messages(tw, twin)
+        ma, mt = O.messages(dev, model), O.messages(tw, twin)
         assert np.array_equal(np.isnan(ma), np.isnan(mt)), f"sweep {sweep}: not the same messages undefined"
         ok = ~np.isnan(mt[:, d])
         assert ok.any()
@@ -141,7 +100,7 @@ def test_fused_sweeps_with_variables_of_high_degree(hip_lib, name, make, total):
     b = O.with_offsets(model, 3)
     dev = _dev(model, b=b)
     dev.sweep(total)
-    _check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, name + " fixed point vs the joint solve with offsets")
+    AN.check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, name + " fixed point vs the joint solve with offsets")
 
 
 # ---- 4. chain scan ----------------------------------------------------------------------------------------------------------------------
@@ -153,7 +112,7 @@ def test_chain_scan_one_sweep(hip_lib, monkeypatch, d, T, K):
     model, b, ref = _chain_case(d, T)
     dev = _dev(model, L.SCHED_CHAIN_SCAN, b=b)
     dev.sweep(1)
-    marg = _check_marginals(dev, model, ref, 1e-9, f"d={d} T={T} K={K}")
+    marg = AN.check_marginals(dev, model, ref, 1e-9, f"d={d} T={T} K={K}")
     lazy = _dev(model, L.SCHED_CHAIN_SCAN, b=b, marginals_in_sweep=2)
     lazy.sweep(1)
     assert np.array_equal(marg, lazy.get_marginals(model.x_ids)), "marginals on demand: the same bits"
@@ -161,7 +120,7 @@ def test_chain_scan_one_sweep(hip_lib, monkeypatch, d, T, K):
     if T == 9:
         fused = _dev(model, b=b)
         fused.sweep(T + 3)
-        ma, mf = _messages(dev, model), _messages(fused, model)
+        ma, mf = O.messages(dev, model), O.messages(fused, model)
         assert_close(ma, mf, 1e-9, f"d={d} K={K}: chain messages on demand vs the fused fixed point")
 
 
@@ -172,7 +131,7 @@ def test_chain_scan_with_unobserved_states(hip_lib, d):
     b = O.with_offsets(model, 4)
     dev = _dev(model, L.SCHED_CHAIN_SCAN, b=b, loader=MD.load)
     dev.sweep(1)
-    _check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, f"d={d} chain scan, every second state unobserved")
+    AN.check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, f"d={d} chain scan, every second state unobserved")
 
 
 # ---- 5. tree schedule ---------------------------------------------------------------------------------------------------------------------
@@ -180,29 +139,21 @@ TREES = [(f"comb {n} x {t} d={d}", (lambda d=d, n=n, t=t: AN.comb(n, d, teeth=t)
         [(f"branching {n} b={b} d={d}", (lambda d=d, b=b, n=n: AN.branching(n, d, b=b))) for d, b, n in AN.TREE_BRANCHING if d <= 4]
 
 
-def _tree_case(name, make):
-    def build():
-        model = make()
-        b1, b2 = O.with_offsets(model, 5), O.with_offsets(model, 6, scale=2.0)
-        return model, b1, O.dense_posterior_offsets(model, b1), b2, O.dense_posterior_offsets(model, b2)
-    return _ref(("tree", name), build)
-
-
 @pytest.mark.parametrize("heavy_paths", ["0", "1"])
 @pytest.mark.parametrize("name,make", TREES, ids=[t[0] for t in TREES])
 def test_tree_schedule_sweeps_follow_the_offsets(hip_lib, monkeypatch, name, make, heavy_paths):
     monkeypatch.setenv("CX_TREE_HP", heavy_paths)
-    model, b1, ref1, b2, ref2 = _tree_case(name, make)
+    model, b1, ref1, b2, ref2 = O.tree_case(name, make)
     dev = _dev(model, L.SCHED_TREE, b=b1)
     dev.sweep(1)
     launches = dev.tree_heavy_path_stats()["launches"]
     assert launches == 0 if heavy_paths == "0" else (launches > 0 or "comb" not in name)
-    _check_marginals(dev, model, ref1, 1e-9, f"{name} heavy paths {heavy_paths}")
+    AN.check_marginals(dev, model, ref1, 1e-9, f"{name} heavy paths {heavy_paths}")
     dev.sweep(1)                # the captured sweep, replayed
-    _check_marginals(dev, model, ref1, 1e-9, f"{name} heavy paths {heavy_paths}, second sweep")
+    AN.check_marginals(dev, model, ref1, 1e-9, f"{name} heavy paths {heavy_paths}, second sweep")
     dev.set_factor_offsets(*O.arrays(b2))
     dev.sweep(1)
-    _check_marginals(dev, model, ref2, 1e-9, f"{name} heavy paths {heavy_paths}, new offsets")
+    AN.check_marginals(dev, model, ref2, 1e-9, f"{name} heavy paths {heavy_paths}, new offsets")
 
 
 @pytest.mark.parametrize("heavy_paths", ["0", "1"])
@@ -213,7 +164,7 @@ def test_a_forecast_tail_accumulates_the_offsets(hip_lib, monkeypatch, heavy_pat
     b = O.with_offsets(model, 7)
     dev = _dev(model, L.SCHED_TREE, b=b, loader=MD.load)
     dev.sweep(1)
-    marg = _check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, f"tail, heavy paths {heavy_paths}")
+    marg = AN.check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, f"tail, heavy paths {heavy_paths}")
     A = model.psets[0][0]
     for k, f in enumerate(model.factor_ids[-h:].tolist()):      # the tail's transitions, in time order
         want = A @ marg[T - 1 + k, :d] + b[f]
@@ -252,21 +203,9 @@ def test_fused_sweeps_on_a_loopy_graph(hip_lib, d, T):
 
 
 # ---- 7. batch items ---------------------------------------------------------------------------------------------------------------------
-def _hub_model(d, seed=9):
-    """u (observed) -> x -> y (observed), x -> z (a free leaf): every direction of a message through a factor, from either kind of sender"""
-    A, Q, R, H = AN.general_sets(d, seed)
-    rng = np.random.default_rng([seed, d, 93])
-    IN, OUT = L.ROLE_IN, L.ROLE_OUT
-    return cx.synth.Model(edge_var=np.array([1, 2, 2, 3, 2, 4], np.int64), edge_fac=np.array([10, 10, 11, 11, 12, 12], np.int64),
-                          edge_role=np.array([IN, OUT, IN, OUT, IN, OUT], np.int32), factor_ids=np.array([10, 11, 12], np.int64),
-                          factor_kind=np.full(3, L.FACTOR_GAUSS_LINEAR, np.int32), factor_var=np.array([0.0, 1.0, 0.0]), x_ids=np.array([2, 4], np.int64),
-                          data_var=np.array([1, 3], np.int64), data_fac=np.array([10, 11], np.int64), data_y=rng.standard_normal((2, d)), dim=d,
-                          psets={0: (A, Q), 1: (H, R)}, meta={"kind": "hub"})
-
-
 @pytest.mark.parametrize("d", [2, 3, 4])
 def test_batch_message_items_through_factors_with_offsets(hip_lib, d):
-    model = _hub_model(d)
+    model = O.hub_model(d)
     (A, Q), (H, R) = model.psets[0], model.psets[1]
     Qi, Ri = np.linalg.inv(Q), np.linalg.inv(R)
     b = O.with_offsets(model, 10)
@@ -311,12 +250,6 @@ def test_batch_message_items_through_factors_with_offsets(hip_lib, d):
 
 
 # ---- 8. the readers on forests ----------------------------------------------------------------------------------------------------------
-def _close(got, want, rtol, what=""):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    err = float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0))) if got.size else 0.0
-    assert err <= rtol, (what, err)
-
-
 def _reader_case(d, shape):
     def build():
         model = AN.chain(60, d) if shape == "chain" else AN.comb(15, d, teeth=1)
@@ -325,7 +258,7 @@ def _reader_case(d, shape):
         fids, sets = LS.pset_groups(model)
         return dict(model=model, b=b, gm=gm, log_z=O.joint_solve_offsets(model, b)[3], beliefs=LS.dense_factor_beliefs(gm),
                     stats=LS.grouped_statistics(gm, fids, sets, 2), n_factors=len(fids), loo=P.dense_loo_all(gm))
-    return _ref(("readers", d, shape), build)
+    return O.ref(("readers", d, shape), build)
 
 
 @pytest.mark.parametrize("d,shape,sched", [(d, shape, s) for d in (2, 4) for shape, s in (("chain", "chain-scan"), ("chain", "tree"), ("comb", "tree"))])
@@ -373,7 +306,7 @@ def test_readers_that_do_not_take_offsets_say_so(hip_lib):
     calls = {"sample_posterior": lambda h: h.sample_posterior(2, noise=noise)[0], "linear_moments": lambda h: np.concatenate([x.reshape(-1) for x in h.linear_moments(fs)[:2]]),
              "causal_marginals": lambda h: h.causal_marginals("filtered", 2)["mean"]}
     for name, call in calls.items():
-        code, msg = _code(lambda: call(dev))
+        code, msg = code_of(lambda: call(dev))
         assert code == L.ERR_UNSUPPORTED and "cx_set_factor_offsets" in msg, (name, code, msg)
     ids, bb = O.arrays(b)
     dev.set_factor_offsets(ids, np.zeros_like(bb))
@@ -389,13 +322,13 @@ def test_changes_after_the_offsets(hip_lib, schedule, sweeps):
     model, b, ref = _chain_case(d, T)
     dev = _dev(model, schedule, b=b)
     dev.sweep(sweeps)
-    _check_marginals(dev, model, ref, 1e-9, "offsets")
+    AN.check_marginals(dev, model, ref, 1e-9, "offsets")
     # new matrices under the same offsets: the linear terms follow (A, Q)
     A, Q = model.psets[0]
     dev.set_factor_matrices(0, 0.5 * A, 2.0 * Q)
     changed = dataclasses.replace(model, psets={**model.psets, 0: (0.5 * A, 2.0 * Q)})
     dev.sweep(sweeps)
-    _check_marginals(dev, changed, O.dense_posterior_offsets(changed, b), 1e-9, "offsets, then new matrices")
+    AN.check_marginals(dev, changed, O.dense_posterior_offsets(changed, b), 1e-9, "offsets, then new matrices")
     # all offsets back to zero: a fresh handle without offsets, bit for bit
     ids, bb = O.arrays(b)
     dev.set_factor_offsets(ids, np.zeros_like(bb))
@@ -403,7 +336,7 @@ def test_changes_after_the_offsets(hip_lib, schedule, sweeps):
     fresh = _dev(changed, schedule)
     fresh.sweep(sweeps)
     assert np.array_equal(dev.get_marginals(model.x_ids), fresh.get_marginals(model.x_ids))
-    assert np.array_equal(_messages(dev, model), _messages(fresh, model), equal_nan=True)
+    assert np.array_equal(O.messages(dev, model), O.messages(fresh, model), equal_nan=True)
 
 
 @pytest.mark.parametrize("schedule,sweeps", [(L.SCHED_FUSED, 5), (L.SCHED_CHAIN_SCAN, 1), (L.SCHED_TREE, 1)], ids=["fused", "chain-scan", "tree"])
@@ -415,7 +348,7 @@ def test_zero_offsets_equal_a_handle_that_never_called(hip_lib, schedule, sweeps
     for h in (zero, never):
         h.sweep(sweeps)
     assert np.array_equal(zero.get_marginals(model.x_ids), never.get_marginals(model.x_ids), equal_nan=True)
-    assert np.array_equal(_messages(zero, model), _messages(never, model), equal_nan=True)
+    assert np.array_equal(O.messages(zero, model), O.messages(never, model), equal_nan=True)
 
 
 # ---- 11. checkpoint ---------------------------------------------------------------------------------------------------------------------
@@ -430,10 +363,10 @@ def test_checkpoint_carries_the_offsets_in_its_fingerprint(hip_lib):
     twin.import_state(blob)
     a.sweep(1)
     twin.sweep(1)
-    assert np.array_equal(_messages(a, model), _messages(twin, model), equal_nan=True)
+    assert np.array_equal(O.messages(a, model), O.messages(twin, model), equal_nan=True)
     assert np.array_equal(a.get_marginals(model.x_ids), twin.get_marginals(model.x_ids), equal_nan=True)
     for wrong in (_dev(model, b=other), _dev(model)):
-        code, msg = _code(lambda: wrong.import_state(blob))
+        code, msg = code_of(lambda: wrong.import_state(blob))
         assert code == L.ERR_INVALID_ARGUMENT and "different graph" in msg
     # without offsets the fingerprint is what it was: such blobs go round as before, and not into a handle that has offsets
     p, q = _dev(model, seed_variance=AN.LOOPY_SEED_VARIANCE), _dev(model)
@@ -442,8 +375,8 @@ def test_checkpoint_carries_the_offsets_in_its_fingerprint(hip_lib):
     q.import_state(plain_blob)
     p.sweep(1)
     q.sweep(1)
-    assert np.array_equal(_messages(p, model), _messages(q, model), equal_nan=True)
-    assert _code(lambda: twin.import_state(plain_blob))[0] == L.ERR_INVALID_ARGUMENT
+    assert np.array_equal(O.messages(p, model), O.messages(q, model), equal_nan=True)
+    assert code_of(lambda: twin.import_state(plain_blob))[0] == L.ERR_INVALID_ARGUMENT
 
 
 # ---- 12. EM -----------------------------------------------------------------------------------------------------------------------------
@@ -493,7 +426,7 @@ def test_refusals(hip_lib):
     assert rc == L.ERR_UNSUPPORTED and who in nat2.lib.cx_last_error(nat2.h).decode()
     # no graph
     empty = cx.DeviceGraph(dim=d)
-    code, msg = _code(lambda: empty.set_factor_offsets([f0], one))
+    code, msg = code_of(lambda: empty.set_factor_offsets([f0], one))
     assert code == L.ERR_STATE and who in msg and "no graph" in msg
     # a factor of another kind, an unknown id, bad arguments
     top = int(max(model.edge_var.max(), model.edge_fac.max())) + 1
@@ -501,12 +434,12 @@ def test_refusals(hip_lib):
                                      edge_role=np.append(model.edge_role, L.ROLE_OUT).astype(np.int32), factor_ids=np.append(model.factor_ids, top),
                                      factor_kind=np.append(model.factor_kind, L.FACTOR_OPAQUE).astype(np.int32), factor_var=np.append(model.factor_var, 0.0))
     dev = _dev(with_prior)
-    code, msg = _code(lambda: dev.set_factor_offsets([top], one))
+    code, msg = code_of(lambda: dev.set_factor_offsets([top], one))
     assert code == L.ERR_UNSUPPORTED and who in msg and f"factor {top}" in msg
-    code, msg = _code(lambda: dev.set_factor_offsets([f0, 10 ** 9], np.ones((2, d))))
+    code, msg = code_of(lambda: dev.set_factor_offsets([f0, 10 ** 9], np.ones((2, d))))
     assert code == L.ERR_NOT_FOUND and who in msg and str(10 ** 9) in msg
     for bad in (np.nan, np.inf):
-        code, msg = _code(lambda: dev.set_factor_offsets([f0], np.array([[0.0, bad]])))
+        code, msg = code_of(lambda: dev.set_factor_offsets([f0], np.array([[0.0, bad]])))
         assert code == L.ERR_INVALID_ARGUMENT and who in msg
     ids = np.array([f0], np.int64)
     p64, pd = L.C.POINTER(L.C.c_int64), L.C.POINTER(L.C.c_double)
@@ -531,27 +464,27 @@ def test_refusals(hip_lib):
     dev.set_factor_offsets([f0], one)           # and the handle works on
     # the reference order, wired or not
     ref = _dev(model, L.SCHED_REFERENCE)
-    code, msg = _code(lambda: ref.set_factor_offsets([f0], one))
+    code, msg = code_of(lambda: ref.set_factor_offsets([f0], one))
     assert code == L.ERR_UNSUPPORTED and who in msg and "CX_SCHED_REFERENCE" in msg
     wired = cx.DeviceGraph(dim=d, schedule=L.SCHED_REFERENCE)
     for k, (A, Q) in model.psets.items():
         wired.set_factor_matrices(k, A, Q)
     wired.graph_create(model.edge_var, model.edge_fac, model.factor_ids, model.factor_kind, model.factor_var, edge_role=model.edge_role)
     wired.graph_wire(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0, np.int32))      # (wired right after graph_create, as the reference wires)
-    code, msg = _code(lambda: wired.set_factor_offsets([f0], one))
+    code, msg = code_of(lambda: wired.set_factor_offsets([f0], one))
     assert code == L.ERR_UNSUPPORTED and "cx_graph_wire" in msg
     # partitions, in either order
     halo = _dev(model)
     halo.halo_configure_state([], [], [], [])
-    code, msg = _code(lambda: halo.set_factor_offsets([f0], one))
+    code, msg = code_of(lambda: halo.set_factor_offsets([f0], one))
     assert code == L.ERR_UNSUPPORTED and who in msg and "partitioned" in msg
     block = _dev(model, L.SCHED_CHAIN_SCAN)
     block.halo_configure([], [], [], [])        # a chain's time block
-    assert _code(lambda: block.set_factor_offsets([f0], one))[0] == L.ERR_UNSUPPORTED
+    assert code_of(lambda: block.set_factor_offsets([f0], one))[0] == L.ERR_UNSUPPORTED
     for schedule, call in ((L.SCHED_FUSED, lambda h: h.halo_configure_state([], [], [], [])), (L.SCHED_CHAIN_SCAN, lambda h: h.halo_configure([], [], [], [])),
                            (L.SCHED_CHAIN_SCAN, lambda h: h.chain_block_maps())):
         h = _dev(model, schedule, b={f0: np.ones(d)})
-        code, msg = _code(lambda: call(h))
+        code, msg = code_of(lambda: call(h))
         assert code == L.ERR_UNSUPPORTED and who in msg
 
 
@@ -559,14 +492,8 @@ def test_refusals(hip_lib):
 def test_cpp_host_class_factor_offsets(hip_lib, tmp_path):
     """tests/cpp/offsets_demo.cpp: a d = 2 chain with a control input on every transition and an observation mean, through
     cortex::Handle::set_factor_offsets; its marginals against DeviceGraph's on the same model and the joint solve with offsets"""
-    exe = str(tmp_path / "offsets_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "offsets_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = np.array([[float(x) for x in line.split()[1:]] for line in out.stdout.splitlines() if line.startswith("marginal")])
+    out_lines = run_demo("offsets_demo", tmp_path)
+    rows = np.array([[float(x) for x in line.split()[1:]] for line in out_lines if line.startswith("marginal")])
     T, d = 12, 2
     A, Q = np.array([[0.9, 0.2], [-0.1, 0.8]]), np.array([[0.3, 0.05], [0.05, 0.2]])
     H, R = np.array([[1.0, 0.5], [0.0, 1.0]]), np.array([[0.5, 0.1], [0.1, 0.4]])

@@ -30,6 +30,9 @@ from tests import learning_support as LS
 from tests import missing_data as MD
 from tests import offsets_support as O
 from tests.helpers import assert_close as _assert_close
+from tests.gpu_support import code_of
+from tests.learn_mfma_support import assert_within as _close
+from tests.learn_mfma_support import bound_of as _scale
 
 pytestmark = pytest.mark.gpu
 
@@ -55,60 +58,12 @@ def _dev(model, schedule=L.SCHED_FUSED, b=None, seed_variance=None, loader=None,
     return dev
 
 
-def _check_marginals(dev, model, ref, tol, what):
-    d, n = model.dim, len(model.x_ids)
-    em, ecov = ref
-    marg = dev.get_marginals(model.x_ids)
-    assert not np.any(np.isnan(marg)), f"{what}: undefined marginals"
-    assert_close(marg[:, :d], em, tol, f"{what}: marginal means")
-    assert_close(marg[:, d:].reshape(n, d, d), ecov, tol, f"{what}: marginal covariances")
-    return marg
-
-
-def _latent_edges(model):
-    keep = np.isin(model.edge_var, model.x_ids)
-    return model.edge_var[keep], model.edge_fac[keep]
-
-
-def _messages(dev, model):
-    ev, ef = _latent_edges(model)
-    return dev.get_messages(ev, ef, L.TO_VARIABLE, L.FORM_NATURAL)
-
-
-def _code(call):
-    with pytest.raises(cx.CortexHipError) as ei:
-        call()
-    return ei.value.code, ei.value.message
-
-
-def _close(got, want, tol, what):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    err = float(np.max(np.abs(got - want))) if want.size else 0.0
-    print(f"{what}: max abs error {err:.3e} (bound {tol:.3e})")
-    assert np.all(np.isfinite(got)), what
-    assert err <= tol, (what, err, tol)
-
-
-def _scale(want):
-    return 1e-9 * max(1.0, float(np.max(np.abs(want)))) if np.size(want) else 1e-9
-
-
-_REF = {}
-
-
-def _ref(key, make):
-    """a reference computed once per key and left unchanged"""
-    if key not in _REF:
-        _REF[key] = make()
-    return _REF[key]
-
-
 def _chain_case(d, T):
     def make():
         model = AN.chain(T, d)
         b = O.with_offsets(model, 1)      # scale 1: the means stay at the data's scale
         return model, b, O.dense_posterior_offsets(model, b)
-    return _ref(("chain", d, T), make)
+    return O.ref(("chain", d, T), make)
 
 
 def _set_plan(monkeypatch, K, fan):
@@ -125,9 +80,9 @@ def test_fused_sweeps_on_a_chain_with_offsets(hip_lib, d):
     dev, plain = _dev(model, b=b), _dev(model)
     dev.sweep(T + 3)
     plain.sweep(T + 3)
-    marg = _check_marginals(dev, model, ref, 1e-8, f"d={d} fixed point vs the joint solve with offsets")
+    marg = AN.check_marginals(dev, model, ref, 1e-8, f"d={d} fixed point vs the joint solve with offsets", close=assert_close)
     # the offsets move no precision: the precision part of every message into a latent variable is the no-offset handle's, bit for bit
-    ma, mp = _messages(dev, model), _messages(plain, model)
+    ma, mp = O.messages(dev, model), O.messages(plain, model)
     assert np.array_equal(np.isnan(ma), np.isnan(mp))
     assert np.array_equal(ma[:, d:], mp[:, d:], equal_nan=True), "precisions differ from the handle without offsets"
     assert np.nanmax(np.abs(ma[:, :d] - mp[:, :d])) > 0.1, "the offsets did not reach the messages"
@@ -150,7 +105,7 @@ def test_every_sweep_is_the_shifted_twins(hip_lib, shape, d):
     twin, to_twin = O.shifted_twin(model, b, s)
     seed = None if shape == "chain" else G.RING_SEED_VARIANCE
     dev, tw = _dev(model, b=b, seed_variance=seed), _dev(twin, seed_variance=seed)
-    ev, ef = _latent_edges(model)
+    ev, ef = O.latent_edges(model)
     if seed is not None:
         lam = np.eye(d) / seed
         dev.set_messages(ev, ef, L.TO_VARIABLE, L.FORM_NATURAL, np.stack([np.concatenate([lam @ s[int(x)], lam.reshape(-1)]) for x in ev]))
@@ -159,7 +114,7 @@ def test_every_sweep_is_the_shifted_twins(hip_lib, shape, d):
         dev.sweep(upto - done)
         tw.sweep(upto - done)
         done = upto
-        ma, mt = _messages(dev, model), _messages(tw, twin)
+        ma, mt = O.messages(dev, model), O.messages(tw, twin)
         assert np.array_equal(np.isnan(ma), np.isnan(mt)), f"sweep {upto}: not the same messages undefined"
         ok = ~np.isnan(mt[:, d])
         assert ok.any()
@@ -178,7 +133,7 @@ def test_chain_scan_one_sweep(hip_lib, monkeypatch, d, T, K, fan):
     dev.sweep(1)
     if (T, K) == (9, 2):
         assert dev.chain_plan_stats()["levels"] >= 2
-    _check_marginals(dev, model, ref, 1e-9, f"d={d} T={T} K={K} fan={fan}")
+    AN.check_marginals(dev, model, ref, 1e-9, f"d={d} T={T} K={K} fan={fan}", close=assert_close)
 
 
 @pytest.mark.parametrize("d", [7, 16, 64])
@@ -189,36 +144,28 @@ def test_chain_scan_with_unobserved_states(hip_lib, monkeypatch, d):
     b = O.with_offsets(model, 4)
     dev = _dev(model, L.SCHED_CHAIN_SCAN, b=b, loader=MD.load)
     dev.sweep(1)
-    _check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, f"d={d} chain scan, every second state unobserved")
+    AN.check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-9, f"d={d} chain scan, every second state unobserved", close=assert_close)
 
 
 # ---- 4. tree schedule ---------------------------------------------------------------------------------------------------------------------
 TREES = [(f"comb d={d}", (lambda d=d: G.comb(d))) for d in (5, 16, 64)] + [(f"forest d={d}", (lambda d=d: G.forest(d))) for d in (5, 17)]
 
 
-def _tree_case(name, make):
-    def build():
-        model = make()
-        b1, b2 = O.with_offsets(model, 5), O.with_offsets(model, 6, scale=2.0)
-        return model, b1, O.dense_posterior_offsets(model, b1), b2, O.dense_posterior_offsets(model, b2)
-    return _ref(("tree", name), build)
-
-
 @pytest.mark.parametrize("heavy_paths", ["0", "1"])
 @pytest.mark.parametrize("name,make", TREES, ids=[t[0] for t in TREES])
 def test_tree_schedule_sweeps_follow_the_offsets(hip_lib, monkeypatch, name, make, heavy_paths):
     monkeypatch.setenv("CX_TREE_HP", heavy_paths)
-    model, b1, ref1, b2, ref2 = _tree_case(name, make)
+    model, b1, ref1, b2, ref2 = O.tree_case(name, make)
     dev = _dev(model, L.SCHED_TREE, b=b1)
     dev.sweep(1)
     launches = dev.tree_heavy_path_stats()["launches"]
     assert launches == 0 if heavy_paths == "0" else launches > 0, launches
-    _check_marginals(dev, model, ref1, 1e-8, f"{name} heavy paths {heavy_paths}")
+    AN.check_marginals(dev, model, ref1, 1e-8, f"{name} heavy paths {heavy_paths}", close=assert_close)
     dev.sweep(1)                # the captured sweep, replayed
-    _check_marginals(dev, model, ref1, 1e-8, f"{name} heavy paths {heavy_paths}, second sweep")
+    AN.check_marginals(dev, model, ref1, 1e-8, f"{name} heavy paths {heavy_paths}, second sweep", close=assert_close)
     dev.set_factor_offsets_mfma(*O.arrays(b2))
     dev.sweep(1)
-    _check_marginals(dev, model, ref2, 1e-8, f"{name} heavy paths {heavy_paths}, new offsets")
+    AN.check_marginals(dev, model, ref2, 1e-8, f"{name} heavy paths {heavy_paths}, new offsets", close=assert_close)
 
 
 @pytest.mark.parametrize("heavy_paths", ["0", "1"])
@@ -229,7 +176,7 @@ def test_a_forecast_tail_accumulates_the_offsets(hip_lib, monkeypatch, heavy_pat
     b = O.with_offsets(model, 7)
     dev = _dev(model, L.SCHED_TREE, b=b, loader=MD.load)
     dev.sweep(1)
-    marg = _check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-8, f"tail, heavy paths {heavy_paths}")
+    marg = AN.check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-8, f"tail, heavy paths {heavy_paths}", close=assert_close)
     A = model.psets[0][0]
     for k, f in enumerate(model.factor_ids[-h:].tolist()):      # the tail's transitions, in time order
         want = A @ marg[T - 1 + k, :d] + b[f]
@@ -245,26 +192,14 @@ def test_fused_sweeps_with_a_sender_of_degree_five(hip_lib):
     b = O.with_offsets(model, 3)
     dev = _dev(model, b=b)
     dev.sweep(8)
-    _check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-8, "multi-sensor d=16 fixed point vs the joint solve with offsets")
-
-
-def _hub_model(d, seed=9):
-    """u (observed) -> x -> y (observed), x -> z (a free leaf): every direction of a message through a factor, from either kind of sender"""
-    A, Q, R, H = AN.general_sets(d, seed)
-    rng = np.random.default_rng([seed, d, 93])
-    IN, OUT = L.ROLE_IN, L.ROLE_OUT
-    return cx.synth.Model(edge_var=np.array([1, 2, 2, 3, 2, 4], np.int64), edge_fac=np.array([10, 10, 11, 11, 12, 12], np.int64),
-                          edge_role=np.array([IN, OUT, IN, OUT, IN, OUT], np.int32), factor_ids=np.array([10, 11, 12], np.int64),
-                          factor_kind=np.full(3, L.FACTOR_GAUSS_LINEAR, np.int32), factor_var=np.array([0.0, 1.0, 0.0]), x_ids=np.array([2, 4], np.int64),
-                          data_var=np.array([1, 3], np.int64), data_fac=np.array([10, 11], np.int64), data_y=rng.standard_normal((2, d)), dim=d,
-                          psets={0: (A, Q), 1: (H, R)}, meta={"kind": "hub"})
+    AN.check_marginals(dev, model, O.dense_posterior_offsets(model, b), 1e-8, "multi-sensor d=16 fixed point vs the joint solve with offsets", close=assert_close)
 
 
 @pytest.mark.parametrize("d", [5, 16])
 def test_batch_message_items_through_factors_with_offsets(hip_lib, d):
     """cx_update_batch's message items against the closed formulas, one application of the rule each (1e-7: the per-sweep bound on the
     matrix cores)"""
-    model = _hub_model(d)
+    model = O.hub_model(d)
     (A, Q), (H, R) = model.psets[0], model.psets[1]
     Qi, Ri = np.linalg.inv(Q), np.linalg.inv(R)
     b = O.with_offsets(model, 10)
@@ -314,7 +249,7 @@ def _reader_case(shape, d):
         beliefs = LS.dense_factor_beliefs(gm, fids)
         return dict(model=model, b=b, gm=gm, log_z=O.joint_solve_offsets(model, b)[3], fids=fids, beliefs=beliefs,
                     stats=LS.grouped_statistics(gm, fids, sets, 2, beliefs=beliefs))
-    return _ref(("readers", shape, d), build)
+    return O.ref(("readers", shape, d), build)
 
 
 READERS = [(shape, d, "tree") for shape in ("chain", "comb") for d in (5, 16, 17, 64)] + [("chain", 16, "chain-scan"), ("chain", 64, "chain-scan"),
@@ -375,7 +310,7 @@ def test_zero_offsets_equal_a_handle_that_never_called(hip_lib, monkeypatch, d, 
     for h in (zero, never):
         h.sweep(sweeps)
     assert np.array_equal(zero.get_marginals(model.x_ids), never.get_marginals(model.x_ids), equal_nan=True)
-    assert np.array_equal(_messages(zero, model), _messages(never, model), equal_nan=True)
+    assert np.array_equal(O.messages(zero, model), O.messages(never, model), equal_nan=True)
     if schedule != L.SCHED_FUSED:      # (after five fused sweeps some messages are still undefined: no evidence yet)
         assert zero.log_evidence_mfma()[0] == never.log_evidence_mfma()[0]
         fids = LS.pset_groups(model)[0]
@@ -404,13 +339,13 @@ def test_changes_after_the_offsets(hip_lib, monkeypatch, schedule, sweeps):
     model, b, ref = _chain_case(d, T)
     dev = _dev(model, schedule, b=b)
     dev.sweep(sweeps)
-    _check_marginals(dev, model, ref, tol, "offsets")
+    AN.check_marginals(dev, model, ref, tol, "offsets", close=assert_close)
     # new matrices under the same offsets: g and kappa follow (A, Q)
     A, Q = model.psets[0]
     dev.set_factor_matrices(0, 0.5 * A, 2.0 * Q)
     changed = dataclasses.replace(model, psets={**model.psets, 0: (0.5 * A, 2.0 * Q)})
     dev.sweep(sweeps)
-    _check_marginals(dev, changed, O.dense_posterior_offsets(changed, b), tol, "offsets, then new matrices")
+    AN.check_marginals(dev, changed, O.dense_posterior_offsets(changed, b), tol, "offsets, then new matrices", close=assert_close)
     want = O.joint_solve_offsets(changed, b)[3]
     got = dev.log_evidence_mfma()[0]
     print(f"evidence after new matrices: relative error {abs(got - want) / abs(want):.3e} (bound 1e-9)")
@@ -422,19 +357,19 @@ def test_changes_after_the_offsets(hip_lib, monkeypatch, schedule, sweeps):
         b2[f] = -2.0 * b[f]
     dev.set_factor_offsets_mfma(ids[::2], np.stack([b2[int(f)] for f in ids[::2]]))
     dev.sweep(sweeps)
-    _check_marginals(dev, changed, O.dense_posterior_offsets(changed, b2), tol, "some offsets replaced")
+    AN.check_marginals(dev, changed, O.dense_posterior_offsets(changed, b2), tol, "some offsets replaced", close=assert_close)
     # all offsets back to zero: a fresh handle without offsets, bit for bit, and the readers that refused work again
     calls = _refusing_calls(model, d)
     if schedule == L.SCHED_CHAIN_SCAN:
         for name, call in calls.items():
-            code, msg = _code(lambda: call(dev))
+            code, msg = code_of(lambda: call(dev))
             assert code == L.ERR_UNSUPPORTED and WHO in msg, (name, code, msg)
     dev.set_factor_offsets_mfma(ids, np.zeros_like(bb))
     dev.sweep(sweeps)
     fresh = _dev(changed, schedule)
     fresh.sweep(sweeps)
     assert np.array_equal(dev.get_marginals(model.x_ids), fresh.get_marginals(model.x_ids))
-    assert np.array_equal(_messages(dev, model), _messages(fresh, model), equal_nan=True)
+    assert np.array_equal(O.messages(dev, model), O.messages(fresh, model), equal_nan=True)
     if schedule == L.SCHED_CHAIN_SCAN:
         for name, call in calls.items():
             assert np.array_equal(call(dev), call(fresh)), name
@@ -456,7 +391,7 @@ def test_refusals(hip_lib):
     assert rc == L.ERR_UNSUPPORTED and WHO in nat2.lib.cx_last_error(nat2.h).decode()
     # no graph
     empty = cx.DeviceGraph(dim=d)
-    code, msg = _code(lambda: empty.set_factor_offsets_mfma([f0], one))
+    code, msg = code_of(lambda: empty.set_factor_offsets_mfma([f0], one))
     assert code == L.ERR_STATE and WHO in msg and "no graph" in msg
     # a factor of another kind, an unknown id, bad arguments
     top = int(max(model.edge_var.max(), model.edge_fac.max())) + 1
@@ -464,14 +399,14 @@ def test_refusals(hip_lib):
                                      edge_role=np.append(model.edge_role, L.ROLE_OUT).astype(np.int32), factor_ids=np.append(model.factor_ids, top),
                                      factor_kind=np.append(model.factor_kind, L.FACTOR_OPAQUE).astype(np.int32), factor_var=np.append(model.factor_var, 0.0))
     dev = _dev(with_prior)
-    code, msg = _code(lambda: dev.set_factor_offsets_mfma([top], one))
+    code, msg = code_of(lambda: dev.set_factor_offsets_mfma([top], one))
     assert code == L.ERR_UNSUPPORTED and WHO in msg and f"factor {top}" in msg
-    code, msg = _code(lambda: dev.set_factor_offsets_mfma([f0, 10 ** 9], np.ones((2, d))))
+    code, msg = code_of(lambda: dev.set_factor_offsets_mfma([f0, 10 ** 9], np.ones((2, d))))
     assert code == L.ERR_NOT_FOUND and WHO in msg and str(10 ** 9) in msg
     for bad in (np.nan, np.inf):
         row = np.zeros((1, d))
         row[0, d - 1] = bad
-        code, msg = _code(lambda: dev.set_factor_offsets_mfma([f0], row))
+        code, msg = code_of(lambda: dev.set_factor_offsets_mfma([f0], row))
         assert code == L.ERR_INVALID_ARGUMENT and WHO in msg
     ids = np.array([f0], np.int64)
     p64, pd = L.C.POINTER(L.C.c_int64), L.C.POINTER(L.C.c_double)
@@ -497,7 +432,7 @@ def test_refusals(hip_lib):
     # the readers that do not take offsets, with ONE non-zero offset
     dev.sweep(1)
     for name, call in _refusing_calls(with_prior, d).items():
-        code, msg = _code(lambda: call(dev))
+        code, msg = code_of(lambda: call(dev))
         assert code == L.ERR_UNSUPPORTED and WHO in msg and name in msg, (name, code, msg)
     # the dim 2 - 4 entry keeps refusing these dims, and em keeps refusing offsets there
     assert dev.lib.cx_set_factor_offsets(dev.h, 0, None, None) == L.ERR_UNSUPPORTED
@@ -505,20 +440,20 @@ def test_refusals(hip_lib):
         learn.em(dev, dict(model.psets), n_iter=1, offsets={0: np.zeros(d)})
     # the reference order
     ref = _dev(model, L.SCHED_REFERENCE)
-    code, msg = _code(lambda: ref.set_factor_offsets_mfma([f0], one))
+    code, msg = code_of(lambda: ref.set_factor_offsets_mfma([f0], one))
     assert code == L.ERR_UNSUPPORTED and WHO in msg and "CX_SCHED_REFERENCE" in msg
     # partitions, in either order
     halo = _dev(model)
     halo.halo_configure_state([], [], [], [])
-    code, msg = _code(lambda: halo.set_factor_offsets_mfma([f0], one))
+    code, msg = code_of(lambda: halo.set_factor_offsets_mfma([f0], one))
     assert code == L.ERR_UNSUPPORTED and WHO in msg and "partitioned" in msg
     for schedule, call in ((L.SCHED_FUSED, lambda h: h.halo_configure_state([], [], [], [])), (L.SCHED_CHAIN_SCAN, lambda h: h.halo_configure([], [], [], []))):
         h = _dev(model, schedule, b={f0: np.ones(d)})
-        code, msg = _code(lambda: call(h))
+        code, msg = code_of(lambda: call(h))
         assert code == L.ERR_UNSUPPORTED and "cx_set_factor_offsets" in msg
     m64 = AN.chain(3, 64)
     h = _dev(m64, L.SCHED_CHAIN_SCAN, b={int(O.linear_factors(m64)[0]): np.ones(64)})
-    code, msg = _code(lambda: h.chain_block_maps())
+    code, msg = code_of(lambda: h.chain_block_maps())
     assert code == L.ERR_UNSUPPORTED and "cx_set_factor_offsets" in msg
 
 
@@ -534,14 +469,14 @@ def test_checkpoint_carries_the_offsets_in_its_fingerprint(hip_lib):
     twin.import_state(blob)
     a.sweep(1)
     twin.sweep(1)
-    assert np.array_equal(_messages(a, model), _messages(twin, model), equal_nan=True)
+    assert np.array_equal(O.messages(a, model), O.messages(twin, model), equal_nan=True)
     assert np.array_equal(a.get_marginals(model.x_ids), twin.get_marginals(model.x_ids), equal_nan=True)
     for wrong in (_dev(model, b=other), _dev(model)):
-        code, msg = _code(lambda: wrong.import_state(blob))
+        code, msg = code_of(lambda: wrong.import_state(blob))
         assert code == L.ERR_INVALID_ARGUMENT and "different graph" in msg
     p = _dev(model, seed_variance=G.RING_SEED_VARIANCE)
     p.sweep(2)
-    assert _code(lambda: twin.import_state(p.export_state()))[0] == L.ERR_INVALID_ARGUMENT
+    assert code_of(lambda: twin.import_state(p.export_state()))[0] == L.ERR_INVALID_ARGUMENT
 
 
 # ---- 11. EM ------------------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,6 @@
 """-m gpu: cx_factor_beliefs / cx_factor_statistics and learn.em against the dense posterior, the RTS smoother,
 central differences of cx_log_evidence (Fisher's identity) and Shumway–Stoffer EM (tests/learning_support.py, pinned by
 tests/test_learning_checker.py)."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,24 +10,10 @@ from cortex.jl_amd import _lib as L
 from cortex.jl_amd import learn
 from tests import evidence_support as E
 from tests import learning_support as S
+from tests.gpu_support import code_of, iterative_device, run_demo
+from tests.learning_support import assert_rel_close as _close
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ITER = (L.SCHED_FUSED, L.SCHED_FLOODING)
-
-
-def _dev(model, schedule, iterative_sweeps=0):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule in ITER else None)
-    dev.sweep(iterative_sweeps if schedule in ITER else 1)
-    return dev
-
-
-def _close(got, want, rtol, what=""):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    scale = np.maximum(np.abs(want), 1.0)
-    err = float(np.max(np.abs(got - want) / scale)) if got.size else 0.0
-    assert err <= rtol, (what, err)
 
 
 def _pair_fids(gm):
@@ -59,7 +43,7 @@ def test_dim1_beliefs_match_the_dense_posterior(hip_lib, name, make, n_iter, cha
     gm = E.gmodel(model)
     assert set(gm.groups) == {2}
     for s in [L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED] + ([L.SCHED_CHAIN_SCAN] if chain else []):
-        dev = _dev(model, s, n_iter)
+        dev = iterative_device(model, s, n_iter)
         _check_beliefs(dev, gm, f"{name} schedule {s}")
         dev.close()
 
@@ -70,7 +54,7 @@ def test_dims_2_to_4_beliefs_match_the_dense_posterior(hip_lib, d):
     for name, model, chain in models:
         gm = E.gmodel(model)
         for s in [L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED] + ([L.SCHED_CHAIN_SCAN] if chain else []):
-            dev = _dev(model, s, 200)
+            dev = iterative_device(model, s, 200)
             _check_beliefs(dev, gm, f"d {d} {name} schedule {s}")
             dev.close()
 
@@ -88,7 +72,7 @@ def test_statistics_by_parameter_set_and_by_explicit_groups(hip_lib, d):
     gm = E.gmodel(model)
     fids, sets = S.pset_groups(model)
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE):
-        dev = _dev(model, s)
+        dev = iterative_device(model, s)
         got, cnt = dev.factor_statistics(n_groups=3)                         # set 2 unused: a zero row
         want = S.grouped_statistics(gm, fids, sets, 3)
         _check_stats(got, cnt, want, len(fids), 2, f"d {d} sets schedule {s}")
@@ -109,7 +93,7 @@ def test_dim1_statistics_with_explicit_groups(hip_lib):
     gm = E.gmodel(model)
     T = 60
     lik, tr = np.arange(2 * T + 1, 3 * T + 1), np.arange(3 * T + 1, 4 * T)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     # the likelihoods (ADDITIVE) share (kind, 1, 0); each transition has its own (a, b): one group each, a few skipped
     fids = np.concatenate([lik, tr])
     groups = np.concatenate([np.zeros(T, np.int64), 1 + np.arange(T - 1)])
@@ -187,7 +171,7 @@ def test_dim1_em_rebuilding_the_handle(hip_lib):
     trace = []
     for it in range(11):
         model.factor_var = np.concatenate([np.full(T, r), np.full(T - 1, q)])
-        dev = _dev(model, L.SCHED_CHAIN_SCAN)
+        dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
         trace.append(dev.log_evidence()[0])
         st, cnt = dev.factor_statistics(fids, groups)
         dev.close()
@@ -203,7 +187,7 @@ def test_dim1_em_rebuilding_the_handle(hip_lib):
 
 def test_determinism_and_no_side_effects(hip_lib):
     model = cx.synth.lgssm_chain(300, d=4, seed=280)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     before, _ = dev.log_evidence()
     blob = dev.export_state()
     a, ca = dev.factor_statistics(n_groups=2)
@@ -220,7 +204,7 @@ def test_determinism_and_no_side_effects(hip_lib):
     dev.close()
     # fused: the next sweeps are those of a twin handle that never called them
     model = cx.synth.tree_model(40, seed=281, k_choices=(1,), observe=0.2)
-    x, y = _dev(model, L.SCHED_FUSED, 5), _dev(model, L.SCHED_FUSED, 5)
+    x, y = iterative_device(model, L.SCHED_FUSED, 5), iterative_device(model, L.SCHED_FUSED, 5)
     fids = E.gmodel(model).groups[2]["fid"]
     x.factor_beliefs(fids)
     x.factor_statistics(fids, np.arange(len(fids)))                          # (dim 1: one group per factor shares its a trivially)
@@ -244,56 +228,50 @@ def test_undefined_states_are_nan(hip_lib):
     dev.close()
 
 
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
-
-
 def test_refusals(hip_lib):
     dev = cx.DeviceGraph(dim=2)
-    assert _code(dev.factor_statistics, n_groups=1)[0] == L.ERR_STATE                                # no graph
+    assert code_of(dev.factor_statistics, n_groups=1)[0] == L.ERR_STATE                                # no graph
     dev.close()
     dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    code, msg = _code(dev.factor_beliefs, [1])
+    code, msg = code_of(dev.factor_beliefs, [1])
     assert code == L.ERR_UNSUPPORTED and "Gaussian family" in msg
     dev.close()
     m16 = cx.synth.lgssm_chain(4, d=16, seed=291)
-    dev = _dev(m16, L.SCHED_FUSED, 2)
-    code, msg = _code(dev.factor_statistics, n_groups=2)
+    dev = iterative_device(m16, L.SCHED_FUSED, 2)
+    code, msg = code_of(dev.factor_statistics, n_groups=2)
     assert code == L.ERR_UNSUPPORTED and "dim 1, 2, 3 and 4" in msg
     dev.close()
     model = cx.synth.ssm_chain(20, seed=292)
-    dev = _dev(model, L.SCHED_FUSED, 5)
-    code, msg = _code(dev.factor_statistics, n_groups=2)                                            # dim 1 without groups
+    dev = iterative_device(model, L.SCHED_FUSED, 5)
+    code, msg = code_of(dev.factor_statistics, n_groups=2)                                            # dim 1 without groups
     assert code == L.ERR_INVALID_ARGUMENT and "name the factors" in msg
-    code, msg = _code(dev.factor_beliefs, [999])
+    code, msg = code_of(dev.factor_beliefs, [999])
     assert code == L.ERR_NOT_FOUND and "999" in msg
     dev.halo_configure([1], [2 * 20 + 1], [], [])                                                   # a partitioned handle
-    code, msg = _code(dev.factor_beliefs, [41])
+    code, msg = code_of(dev.factor_beliefs, [41])
     assert code == L.ERR_UNSUPPORTED and "partitioned" in msg
     dev.close()
     # a group whose factors do not share a
     model = cx.synth.ssm_chain_linear(20, seed=293)
-    dev = _dev(model, L.SCHED_TREE)
-    code, msg = _code(dev.factor_statistics, [61, 62], [0, 0], n_groups=1)
+    dev = iterative_device(model, L.SCHED_TREE)
+    code, msg = code_of(dev.factor_statistics, [61, 62], [0, 0], n_groups=1)
     assert code == L.ERR_INVALID_ARGUMENT and "61" in msg and "62" in msg
-    code, msg = _code(dev.factor_statistics, [61, 61], [0, 0], n_groups=1)
+    code, msg = code_of(dev.factor_statistics, [61, 61], [0, 0], n_groups=1)
     assert code == L.ERR_INVALID_ARGUMENT and "twice" in msg
-    code, msg = _code(dev.factor_statistics, [61], [1], n_groups=1)
+    code, msg = code_of(dev.factor_statistics, [61], [1], n_groups=1)
     assert code == L.ERR_INVALID_ARGUMENT
     dev.close()
     # zero noise
     model = cx.synth.ssm_chain(10, seed=294, q=0.0)
     dev = cx.DeviceGraph(schedule=L.SCHED_TREE)
     cx.synth.load_into_device(model, dev)
-    code, msg = _code(dev.factor_beliefs, [31])
+    code, msg = code_of(dev.factor_beliefs, [31])
     assert code == L.ERR_UNSUPPORTED and "factor 31" in msg and "zero noise" in msg
     dev.close()
     # dim 2: n_groups too small; a set shared with a factor of more than two variables; a k-ary factor named
     model = cx.synth.lgssm_chain(10, d=2, seed=295)
-    dev = _dev(model, L.SCHED_TREE)
-    code, msg = _code(dev.factor_statistics, n_groups=1)
+    dev = iterative_device(model, L.SCHED_TREE)
+    code, msg = code_of(dev.factor_statistics, n_groups=1)
     assert code == L.ERR_INVALID_ARGUMENT and "n_groups" in msg
     dev.close()
     # x_2 = A x_1 + w (set 0) next to x_3 = A x_1 + A x_2 + w (a CX_FACTOR_GAUSS_LINEAR_N factor reading set 0 too)
@@ -302,24 +280,18 @@ def test_refusals(hip_lib):
     dev.graph_create(np.array([1, 2, 3, 1, 2]), np.array([10, 10, 11, 11, 11]), np.array([10, 11]),
                      np.array([L.FACTOR_GAUSS_LINEAR, L.FACTOR_GAUSS_LINEAR_N], np.int32), np.array([0.0, 0.0]),
                      edge_role=np.array([L.ROLE_IN, L.ROLE_OUT, L.ROLE_OUT, L.ROLE_IN, L.ROLE_IN], np.int32))
-    code, msg = _code(dev.factor_statistics, n_groups=1)
+    code, msg = code_of(dev.factor_statistics, n_groups=1)
     assert code == L.ERR_UNSUPPORTED and "more than two variables" in msg
-    code, msg = _code(dev.factor_beliefs, [11])
+    code, msg = code_of(dev.factor_beliefs, [11])
     assert code == L.ERR_UNSUPPORTED and "factor 11" in msg
-    code, msg = _code(dev.factor_statistics, [11], [0], n_groups=1)
+    code, msg = code_of(dev.factor_statistics, [11], [0], n_groups=1)
     assert code == L.ERR_UNSUPPORTED and "factor 11" in msg
     dev.close()
 
 
 def test_cpp_host_class_factor_statistics(hip_lib, tmp_path):
-    exe = str(tmp_path / "learn_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "learn_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out.stdout.splitlines()}
+    out_lines = run_demo("learn_demo", tmp_path)
+    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out_lines}
     T = 50
     model = cx.synth.ssm_chain(T, seed=1)
     model.data_y = np.array([0.5 * t + (7 * t) % 5 for t in range(1, T + 1)], dtype=np.float64)

@@ -27,6 +27,8 @@ from tests import learn_mfma_support as LM
 from tests import learning_support as LS
 from tests import missing_data as MD
 from tests.helpers import assert_close
+from tests.learn_mfma_support import assert_within as _close
+from tests.learn_mfma_support import bound_of as _scale
 
 pytestmark = pytest.mark.gpu
 
@@ -46,18 +48,6 @@ def _dev(model, schedule, sweeps=None, opaque=None, missing=False):
         S.set_opaque(dev, opaque)
     dev.sweep(sweeps if sweeps is not None else (FUSED_SWEEPS if fused else 1))
     return dev
-
-
-def _close(got, want, tol, what):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    err = float(np.max(np.abs(got - want))) if want.size else 0.0
-    print(f"{what}: max abs error {err:.3e} (bound {tol:.3e})")
-    assert np.all(np.isfinite(got)), what
-    assert err <= tol, (what, err, tol)
-
-
-def _scale(want):
-    return 1e-9 * max(1.0, float(np.max(np.abs(want)))) if np.size(want) else 1e-9
 
 
 def _n_rule_factors(gm):

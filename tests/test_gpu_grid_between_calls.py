@@ -20,7 +20,7 @@ import pytest
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
 from tests.helpers import assert_close, flood_oracle_from_model
-from tests.sweep_graphs import GridIds, natural_form_sweeps, read_back, undefined_midcall_grid
+from tests.sweep_graphs import GridIds, assert_same, everything, fused_device, load_undefined_midcall, natural_form_sweeps, paired_launches, read_back, undefined_midcall_grid
 from tests.test_gpu_damping import _numpy_damped_sweeps
 from tests.test_gpu_scalar_parity import RTOL
 
@@ -35,33 +35,13 @@ GRID, SMALL = (9, 125), (20, 37)
 PRIOR_AT = {GRID: [(0, 0), (3, 61), (3, 62), (8, 124), (4, 30)], SMALL: [(0, 0), (6, 33), (6, 34), (19, 36), (4, 30)]}
 
 
-def _device(model, seed_variance=SEED_VARIANCE):
-    dev = cx.DeviceGraph(schedule=L.SCHED_FUSED)
-    cx.synth.load_into_device(model, dev, seed_variance)
-    return dev
-
-
-def _everything(dev, model):
-    f2v, marg = read_back(dev, model)
-    return f2v, marg, dev.get_messages(model.edge_var, model.edge_fac, L.TO_FACTOR, L.FORM_NATURAL)
-
-
-def _same(a, b, what):
-    for x, y, name in zip(a, b, ("messages to variables", "marginals", "messages to factors")):
-        assert np.array_equal(x, y, equal_nan=True), f"{what}: {name} differ"
-
-
-def _pairs(dev):
-    return dev.sweep_stats()["paired_launches"]
-
-
 class Trio:
     """`a`, `b` and `g` on one model, and the paired launches `a` must have run so far"""
 
     def __init__(self, shape, seed=7):
         self.model = cx.synth.gaussian_grid(*shape, seed=seed)
         self.ids = GridIds(*shape)
-        self.a, self.b = _device(self.model), _device(self.model)
+        self.a, self.b = fused_device(self.model), fused_device(self.model)
         self.g = flood_oracle_from_model(self.model, seed_variance=SEED_VARIANCE)
         self.g_marginals = None
         self.pairs = 0
@@ -92,11 +72,11 @@ class Trio:
         self.check(what, oracle)
 
     def check(self, what, oracle=True):
-        assert _pairs(self.a) == self.pairs, f"{what}: paired launches of a"
-        assert _pairs(self.b) == 0
+        assert paired_launches(self.a) == self.pairs, f"{what}: paired launches of a"
+        assert paired_launches(self.b) == 0
         assert self.a.stats()["sweeps_done"] == self.b.stats()["sweeps_done"]
-        ra = _everything(self.a, self.model)
-        _same(ra, _everything(self.b, self.model), what)
+        ra = everything(self.a, self.model)
+        assert_same(ra, everything(self.b, self.model), what)
         if not oracle:
             return
         g = self.g
@@ -184,7 +164,7 @@ def test_update_batch_between_two_calls(hip_lib, pairs_on):
     assert np.array_equal(ma, mb)
     assert_close(ma[:, 0], t.g_marginals[0][row - 1], RTOL, "batch: marginal means of the row")
     assert_close(ma[:, 1], t.g_marginals[1][row - 1], RTOL, "batch: marginal variances of the row")
-    _same(_everything(t.a, t.model), _everything(t.b, t.model), "after the batch")
+    assert_same(everything(t.a, t.model), everything(t.b, t.model), "after the batch")
     got = t.a.get_messages(t.g.edge_var, t.g.edge_fac, L.TO_VARIABLE)
     assert_close(got[:, 0], t.g.f2v_m, RTOL, "batch: message means")
     assert_close(got[:, 1], t.g.f2v_v, RTOL, "batch: message variances")
@@ -201,16 +181,16 @@ def test_state_import_continues_the_exporter(hip_lib, pairs_on, shape, at):
     if at == 6:
         t.sweep(1, 0, "one more")                # a call of fewer than three sweeps runs none
     blob = t.a.export_state()
-    imp = _device(t.model, 50.0)
+    imp = fused_device(t.model, 50.0)
     imp.sweep(2)
-    assert _pairs(imp) == 0
+    assert paired_launches(imp) == 0
     imp.import_state(blob)
-    _same(_everything(imp, t.model), _everything(t.a, t.model), "right after the import")
+    assert_same(everything(imp, t.model), everything(t.a, t.model), "right after the import")
     t.sweep(5, 2, "the exporter goes on")
     imp.sweep(5)
-    assert _pairs(imp) == 2                      # the importer's first call of >= 3 sweeps: checks the imported buffers, which a paired exporter left consistent
+    assert paired_launches(imp) == 2                      # the importer's first call of >= 3 sweeps: checks the imported buffers, which a paired exporter left consistent
     assert imp.stats()["sweeps_done"] == at + 5
-    _same(_everything(imp, t.model), _everything(t.a, t.model), "the importer against the exporter continuing")
+    assert_same(everything(imp, t.model), everything(t.a, t.model), "the importer against the exporter continuing")
     imp.close(); t.close()
 
 
@@ -218,14 +198,14 @@ def test_state_import_after_a_failed_check_brings_pairs_at_once(hip_lib, pairs_o
     """the importer was never seeded: its own check failed and it would look again once 16 sweeps are done; the imported state is defined"""
     t = Trio(GRID)
     t.sweep(5, 2, "before", oracle=False)
-    imp = _device(t.model, None)
+    imp = fused_device(t.model, None)
     imp.sweep(3)
-    assert _pairs(imp) == 0 and np.isnan(read_back(imp, t.model)[0]).any()
+    assert paired_launches(imp) == 0 and np.isnan(read_back(imp, t.model)[0]).any()
     imp.import_state(t.a.export_state())
     t.sweep(5, 2, "the exporter goes on", oracle=False)
     imp.sweep(5)
-    assert _pairs(imp) == 2                      # StateImported made the check due: 5 < 16 sweeps done does not matter
-    _same(_everything(imp, t.model), _everything(t.a, t.model), "the importer against the exporter continuing")
+    assert paired_launches(imp) == 2                      # StateImported made the check due: 5 < 16 sweeps done does not matter
+    assert_same(everything(imp, t.model), everything(t.a, t.model), "the importer against the exporter continuing")
     imp.close(); t.close()
 
 
@@ -271,16 +251,16 @@ def test_a_new_stream_between_two_calls(hip_lib, pairs_on):
 def test_sweep_until_with_and_without_pairs(hip_lib, monkeypatch, pairs_on):
     """the CPU checker's largest change of a message over five sweeps on this grid: 2.3e-3 after 20 sweeps, 3.2e-4 after 25"""
     model = cx.synth.gaussian_grid(*GRID, seed=7)
-    a = _device(model)
+    a = fused_device(model)
     na, ra = a.sweep_until(1e-3, 60, check_every=5)
     monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
-    c = _device(model)
+    c = fused_device(model)
     nc, rc = c.sweep_until(1e-3, 60, check_every=5)
     monkeypatch.delenv("CX_SWEEP_PAIRS")
     assert na == nc == 25
     assert ra == rc and 1e-4 < ra <= 1e-3
-    assert _pairs(a) == 2 * na // 5 and _pairs(c) == 0        # every round is a call of five sweeps: 2 each; cx_residual changes nothing
-    _same(_everything(a, model), _everything(c, model), "sweep_until")
+    assert paired_launches(a) == 2 * na // 5 and paired_launches(c) == 0        # every round is a call of five sweeps: 2 each; cx_residual changes nothing
+    assert_same(everything(a, model), everything(c, model), "sweep_until")
     g = flood_oracle_from_model(model, seed_variance=SEED_VARIANCE)
     g.sweep(na)
     got = a.get_messages(g.edge_var, g.edge_fac, L.TO_VARIABLE)
@@ -336,16 +316,16 @@ def test_readers_after_a_paired_call(hip_lib, monkeypatch, pairs_on):
         out["joint_marginals"] = _outcome(lambda: dev.get_joint_marginals(joint))
         out["products"] = _outcome(lambda: dev.get_products(row, np.full(len(row), 2), np.full(len(row), 4)))
         out["linear_moments"] = _outcome(lambda: dev.linear_moments([([int(row[0])], np.ones((1, 1)))]))
-        out["everything"] = ("ok", _everything(dev, model))
+        out["everything"] = ("ok", everything(dev, model))
         return out
 
-    a = _device(model)
+    a = fused_device(model)
     ra = run(a)
-    assert _pairs(a) == 2
+    assert paired_launches(a) == 2
     monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
-    c = _device(model)
+    c = fused_device(model)
     rc = run(c)
-    assert _pairs(c) == 0
+    assert paired_launches(c) == 0
     for name in ra:
         assert ra[name][0] == rc[name][0], f"{name}: {ra[name]} against {rc[name]}"
         if ra[name][0] == "refused":
@@ -367,20 +347,13 @@ def test_readers_after_a_paired_call(hip_lib, monkeypatch, pairs_on):
 
 
 # ---- 4. the refusal path ----------------------------------------------------------------------------------------------------------------------
-def _load_undefined_midcall():
-    model, sv, sf, payload = undefined_midcall_grid()
-    dev = _device(model)
-    dev.set_messages(sv, sf, L.TO_VARIABLE, L.FORM_NATURAL, payload)
-    return model, dev
-
-
 def test_a_launch_that_meets_an_undefined_message_is_reported_once(hip_lib, monkeypatch, pairs_on):
     """tests/sweep_graphs.py: undefined_midcall_grid — every input defined, so the check lets pairs start; sweep 1 divides by 1 + q w = 0, sweep 2
     stores undefined messages, and the second launch of sweep(7) (sweeps 3 and 4) reads them, as does the third.  The word a launch raises is
     found by whichever checked call comes first once the launch has run — cx_sweep's own last check, or the cx_sync behind it."""
     model, sv, sf, payload = undefined_midcall_grid()
     assert natural_form_sweeps(model, SEED_VARIANCE, sv, sf, payload, 3) == [(1, 0, 0), (0, 3, 0), (0, 0, 8)]
-    model, a = _load_undefined_midcall()
+    model, a = load_undefined_midcall()
     errors = []
     for call in (lambda: a.sweep(7), a.sync, a.sync, lambda: a.get_marginals(model.x_ids), a.sync):
         try:
@@ -390,23 +363,23 @@ def test_a_launch_that_meets_an_undefined_message_is_reported_once(hip_lib, monk
     assert len(errors) == 1, [str(e) for e in errors]
     assert errors[0].code == L.ERR_DEVICE and "CX_SWEEP_PAIRS=0" in str(errors[0]) and "undefined" in str(errors[0])
     assert a.stats()["sweeps_done"] == 7
-    ran = _pairs(a)
+    ran = paired_launches(a)
     assert ran == 3
     a.sweep(5)
     a.sync()
-    assert _pairs(a) == ran, "the handle sweeps plain from then on"
+    assert paired_launches(a) == ran, "the handle sweeps plain from then on"
     assert a.stats()["sweeps_done"] == 12
     a.close()
     # plain sweeps keep the older value of a slot whose input is undefined: the same inputs run to completion, one call or seven
     monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
-    _, c = _load_undefined_midcall()
-    _, b = _load_undefined_midcall()
+    _, c = load_undefined_midcall()
+    _, b = load_undefined_midcall()
     c.sweep(7)
     c.sync()
     for _ in range(7):
         b.sweep(1)
-    assert _pairs(c) == 0 and _pairs(b) == 0
-    _same(_everything(c, model), _everything(b, model), "CX_SWEEP_PAIRS=0: sweep(7) against 7 x sweep(1)")
+    assert paired_launches(c) == 0 and paired_launches(b) == 0
+    assert_same(everything(c, model), everything(b, model), "CX_SWEEP_PAIRS=0: sweep(7) against 7 x sweep(1)")
     c.close(); b.close()
 
 
@@ -426,8 +399,8 @@ def test_nontemporal_stores_in_a_process_of_their_own(hip_lib, tmp_path, pairs_o
     got = np.load(out)
     assert json.loads(str(got["info"])) == {"nt": "1", "paired_launches": 3, "sweeps_done": 8}
     model = cx.synth.gaussian_grid(*GRID, seed=7)
-    b = _device(model)
+    b = fused_device(model)
     for _ in range(8):
         b.sweep(1)
-    _same((got["f2v"], got["marg"], got["v2f"]), _everything(b, model), "CX_PAIR_NT=1 against plain sweeps")
+    assert_same((got["f2v"], got["marg"], got["v2f"]), everything(b, model), "CX_PAIR_NT=1 against plain sweeps")
     b.close()

@@ -5,8 +5,6 @@ Bounds: those of tests/test_gpu_factor_statistics.py for the same comparisons at
 1e-9 max(1, max|want|)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,28 +17,11 @@ from tests import evidence_support as E
 from tests import learn_mfma_support as M
 from tests import learning_support as S
 from tests import missing_data as MD
+from tests.gpu_support import HANDLE_CASES, STREAM_CASES, assert_reader_refusals, code_of, demo_chain, run_demo, swept_device, under_capture
+from tests.learn_mfma_support import assert_within as _close
+from tests.learn_mfma_support import bound_of as _scale
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _dev(model, schedule, fused_sweeps=60):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule == L.SCHED_FUSED else None)
-    dev.sweep(fused_sweeps if schedule == L.SCHED_FUSED else 1)      # (reference order: cx_sweep requests every variable)
-    return dev
-
-
-def _close(got, want, tol, what):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    err = float(np.max(np.abs(got - want))) if want.size else 0.0
-    print(f"{what}: max abs error {err:.3e} (bound {tol:.3e})")
-    assert np.all(np.isfinite(got)), what
-    assert err <= tol, (what, err, tol)
-
-
-def _scale(want):
-    return 1e-9 * max(1.0, float(np.max(np.abs(want)))) if np.size(want) else 1e-9
 
 
 def _check_beliefs(dev, gm, what, fids=None, want=None):
@@ -74,7 +55,7 @@ def test_beliefs_and_statistics_match_the_dense_posterior(hip_lib, d, shape):
     want_b = S.dense_factor_beliefs(gm, fids)
     want_s = S.grouped_statistics(gm, fids, groups, 3)
     for s in [L.SCHED_TREE, L.SCHED_REFERENCE] + ([L.SCHED_CHAIN_SCAN] if chain else []):
-        dev = _dev(model, s)
+        dev = swept_device(model, s)
         _check_beliefs(dev, gm, f"d {d} {name} schedule {s}", want=want_b)
         got, cnt = dev.factor_statistics_mfma(n_groups=3)                      # set 2 unused: a zero row
         _check_stats(got, cnt, want_s, len(fids), 2, f"d {d} {name} schedule {s}")
@@ -89,18 +70,12 @@ def test_beliefs_and_statistics_match_the_dense_posterior(hip_lib, d, shape):
 
 
 # ---- 3. explicit groups and every argument error ------------------------------------------------------------------------------------------
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
-
-
 def test_explicit_groups_and_argument_errors(hip_lib):
     d = 20
     model = cx.synth.lgssm_chain(9, d=d, seed=51)
     gm = E.gmodel(model)
     fids, sets = _set_groups(model, gm)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     # the transitions split into two groups by parity, a few factors skipped, the likelihoods in group 3; the caller's order is free
     rng = np.random.default_rng(d)
     groups = np.where(sets == 0, 1 + (np.arange(len(fids)) % 2), 3)
@@ -118,15 +93,15 @@ def test_explicit_groups_and_argument_errors(hip_lib):
     # errors
     tr, lik = fids[sets == 0], fids[sets == 1]
     who = "cx_factor_statistics_mfma"
-    code, msg = _code(dev.factor_statistics_mfma, [tr[0], lik[0]], [0, 0], n_groups=1)
+    code, msg = code_of(dev.factor_statistics_mfma, [tr[0], lik[0]], [0, 0], n_groups=1)
     assert code == L.ERR_INVALID_ARGUMENT and who in msg and "do not share" in msg
-    code, msg = _code(dev.factor_statistics_mfma, [tr[0], tr[0]], [0, 0], n_groups=1)
+    code, msg = code_of(dev.factor_statistics_mfma, [tr[0], tr[0]], [0, 0], n_groups=1)
     assert code == L.ERR_INVALID_ARGUMENT and "listed twice" in msg
-    code, msg = _code(dev.factor_statistics_mfma, [tr[0]], [3], n_groups=2)
+    code, msg = code_of(dev.factor_statistics_mfma, [tr[0]], [3], n_groups=2)
     assert code == L.ERR_INVALID_ARGUMENT and "not in -1" in msg
-    code, msg = _code(dev.factor_statistics_mfma, [10 ** 6], [0], n_groups=1)
+    code, msg = code_of(dev.factor_statistics_mfma, [10 ** 6], [0], n_groups=1)
     assert code == L.ERR_NOT_FOUND and who in msg
-    code, msg = _code(dev.factor_statistics_mfma, n_groups=1)
+    code, msg = code_of(dev.factor_statistics_mfma, n_groups=1)
     assert code == L.ERR_INVALID_ARGUMENT and "n_groups must exceed" in msg
     out, c4 = np.zeros(10 ** 4), (np.zeros(4, np.int64))
     assert dev.lib.cx_factor_statistics_mfma(dev.h, 0, None, None, 0, out.ctypes.data_as(C.POINTER(C.c_double)), c4.ctypes.data_as(C.POINTER(C.c_int64))) == L.ERR_INVALID_ARGUMENT
@@ -135,7 +110,7 @@ def test_explicit_groups_and_argument_errors(hip_lib):
     assert dev.lib.cx_factor_statistics_mfma(dev.h, 1, f1.ctypes.data_as(C.POINTER(C.c_int64)), None, 2, out.ctypes.data_as(C.POINTER(C.c_double)),
                                              c4.ctypes.data_as(C.POINTER(C.c_int64))) == L.ERR_INVALID_ARGUMENT
     assert b"go together" in dev.lib.cx_last_error(dev.h)
-    code, msg = _code(dev.factor_beliefs_mfma, [10 ** 6])
+    code, msg = code_of(dev.factor_beliefs_mfma, [10 ** 6])
     assert code == L.ERR_NOT_FOUND and "cx_factor_beliefs_mfma" in msg
     assert dev.lib.cx_factor_beliefs_mfma(dev.h, 1, None, None) == L.ERR_INVALID_ARGUMENT
     m, c = dev.factor_beliefs_mfma(np.zeros(0, np.int64))
@@ -147,9 +122,9 @@ def test_explicit_groups_and_argument_errors(hip_lib):
     cx.synth.load_into_device(model, dev)
     EM.set_opaque(dev, opq)
     dev.sweep(1)
-    code, msg = _code(dev.factor_beliefs_mfma, opq[1])
+    code, msg = code_of(dev.factor_beliefs_mfma, opq[1])
     assert code == L.ERR_UNSUPPORTED and str(int(opq[1][0])) in msg and "CX_FACTOR_GAUSS_LINEAR" in msg
-    code, msg = _code(dev.factor_statistics_mfma, opq[1], [0], n_groups=1)
+    code, msg = code_of(dev.factor_statistics_mfma, opq[1], [0], n_groups=1)
     assert code == L.ERR_UNSUPPORTED and str(int(opq[1][0])) in msg
     dev.close()
 
@@ -160,7 +135,7 @@ def test_observed_ends(hip_lib, d):
     model = EM.clamped_middle(d)      # a factor with both ends observed, one with its OUT end, one with its IN end observed
     gm = E.gmodel(model)
     fids, groups = _set_groups(model, gm)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     _, got_c = _check_beliefs(dev, gm, f"clamped middle d {d}")
     obs = gm.obs[gm.groups[2]["vars"]]
     for r in range(len(fids)):      # zero rows and columns on the observed ends, exactly
@@ -214,7 +189,7 @@ def test_opaque_prior(hip_lib, d):
 def test_loop_matches_the_restatement_on_the_device_messages(hip_lib, d):
     model = EM.ring(d)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_FUSED, EM.RING_SWEEPS)
+    dev = swept_device(model, L.SCHED_FUSED, EM.RING_SWEEPS)
     f2v, opq = E.device_messages(gm, dev)
     want_m, want_c, status = M.beliefs(gm, f2v, opq)
     assert np.all(status == M.OK)
@@ -299,13 +274,13 @@ def test_embedded_dims_give_the_real_models_values_at_any_tile_size(hip_lib, d, 
     gm = E.gmodel(model)
     fids, groups = _set_groups(model, gm)
     want = S.grouped_statistics(gm, fids, groups, 2)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     nat_b = _check_beliefs(dev, gm, f"d {d}, native tile")
     nat_s, cnt = dev.factor_statistics_mfma(n_groups=2)
     _check_stats(nat_s, cnt, want, len(fids), 2, f"d {d}, native tile")
     dev.close()
     monkeypatch.setenv("CX_MFMA_DIM", "64")
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     monkeypatch.delenv("CX_MFMA_DIM")
     for_b = _check_beliefs(dev, gm, f"d {d}, 4 x 4 tiles")
     for_s, cnt = dev.factor_statistics_mfma(n_groups=2)
@@ -319,7 +294,7 @@ def test_embedded_dims_give_the_real_models_values_at_any_tile_size(hip_lib, d, 
 @pytest.mark.parametrize("T,d", M.LONG)
 def test_long_chains_against_the_rts_smoother(hip_lib, T, d):
     model = cx.synth.lgssm_chain(T, d=d, seed=33)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = swept_device(model, L.SCHED_CHAIN_SCAN)
     got, cnt = dev.factor_statistics_mfma(n_groups=2)
     _check_stats(got, cnt, M.rts_statistics(model), 2 * T - 1, 2, f"d = {d}, T = {T}")
     again, _ = dev.factor_statistics_mfma(n_groups=2)
@@ -345,7 +320,7 @@ def test_more_partials_than_waves(hip_lib):
     groups, n_groups = M.many_groups(T)
     fids, sets = S.pset_groups(model)
     tr, lik = np.sort(fids[sets == 0]), np.sort(fids[sets == 1])      # ids ascend in time
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = swept_device(model, L.SCHED_CHAIN_SCAN)
     ids, grp = np.concatenate([tr, lik]), np.concatenate([groups[0], groups[1]])
     got, cnt = dev.factor_statistics_mfma(ids, grp, n_groups=n_groups)
     _check_stats(got, cnt, M.rts_statistics(model, groups, n_groups), 2 * T - 1, n_groups, f"d = {d}, T = {T}, {n_groups} groups")
@@ -367,7 +342,7 @@ def test_moves_nothing(hip_lib):
     model = cx.synth.lgssm_chain(8, d=16, seed=72)
     fids, _ = S.pset_groups(model)
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_REFERENCE, L.SCHED_TREE):
-        dev = _dev(model, s)
+        dev = swept_device(model, s)
         if s == L.SCHED_CHAIN_SCAN:      # (another reader first: every reader of the messages brings them to their slots)
             dev.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE)
         blob, marg = dev.export_state(), dev.get_marginals(model.x_ids)
@@ -384,7 +359,7 @@ def test_moves_nothing(hip_lib):
         assert sweeps == dev.stats()["sweeps_done"]
         dev.close()
     # fused: the next sweeps are those of a twin handle that never called them, bit for bit
-    a, b = _dev(model, L.SCHED_FUSED, 5), _dev(model, L.SCHED_FUSED, 5)
+    a, b = swept_device(model, L.SCHED_FUSED, 5), swept_device(model, L.SCHED_FUSED, 5)
     assert a.residual() == b.residual()
     a.factor_statistics_mfma(n_groups=2)
     a.factor_beliefs_mfma(fids)
@@ -424,105 +399,58 @@ def test_em_matches_shumway_stoffer(hip_lib, d):
 
 
 # ---- 14. refusals ---------------------------------------------------------------------------------------------------------------------
+P64, PD = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+
+
+def _raw_beliefs(dev, ids, bel):
+    return dev.lib.cx_factor_beliefs_mfma(dev.h, len(ids), ids.ctypes.data_as(P64), bel.ctypes.data_as(PD))
+
+
+def _raw_statistics(dev, st, c4):
+    return dev.lib.cx_factor_statistics_mfma(dev.h, 0, None, None, 2, st.ctypes.data_as(PD), c4.ctypes.data_as(P64))
+
+
+# what assert_reader_refusals asks of the two readers (factor 13: a likelihood of its dim 4 chain, the first transition of its dim 16 one)
+_COMMON = (dict(who="cx_factor_beliefs_mfma", small="cx_factor_beliefs", call=lambda dev: dev.factor_beliefs_mfma([13]),
+                small_call=lambda dev: dev.factor_beliefs([13]),
+                raw=lambda dev: _raw_beliefs(dev, np.array([13], np.int64), np.zeros((1, 2 * 16 + 4 * 256)))),
+           dict(who="cx_factor_statistics_mfma", small="cx_factor_statistics", call=lambda dev: dev.factor_statistics_mfma(n_groups=2),
+                small_call=lambda dev: dev.factor_statistics(n_groups=2),
+                raw=lambda dev: _raw_statistics(dev, np.zeros((2, 1 + 2 * 16 + 3 * 256)), np.zeros(4, np.int64))))
+
+
 def test_refusals(hip_lib):
-    calls = (("cx_factor_beliefs_mfma", "cx_factor_beliefs", lambda dev: dev.factor_beliefs_mfma([1])),
-             ("cx_factor_statistics_mfma", "cx_factor_statistics", lambda dev: dev.factor_statistics_mfma(n_groups=2)))
-    m4 = cx.synth.lgssm_chain(5, d=4, seed=91)
-    m16 = cx.synth.lgssm_chain(4, d=16, seed=92)
-    vm = cx.synth.vmp_ssm(8)
-    for who, small, call in calls:
-        dev = _dev(m4, L.SCHED_TREE)
-        code, msg = _code(call, dev)
-        assert code == L.ERR_UNSUPPORTED and msg.startswith(who) and small in msg.replace(who, "")      # names the call for dims 1 .. 4
-        dev.close()
-        dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-        code, msg = _code(call, dev)
-        assert code == L.ERR_UNSUPPORTED and msg.startswith(who) and "Gaussian family" in msg
-        dev.close()
-        dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
-        cx.synth.load_vmp_into_device(vm, dev)
-        code, msg = _code(call, dev)
-        assert code == L.ERR_UNSUPPORTED and "Gaussian family" in msg
-        dev.close()
-        dev = cx.DeviceGraph(dim=16)
-        code, msg = _code(call, dev)
-        assert code == L.ERR_STATE and msg.startswith(who) and "no graph" in msg
-        dev.close()
-        dev = _dev(m16, L.SCHED_FUSED, 2)
-        assert _code(dev.factor_beliefs, [1])[0] == L.ERR_UNSUPPORTED                  # the old calls keep refusing these dims
-        assert _code(dev.factor_statistics, n_groups=2)[0] == L.ERR_UNSUPPORTED
-        dev.halo_configure_state([m16.x_ids[0]], [3 * 4 + 1], [], [])      # a halo list: a partitioned handle
-        code, msg = _code(call, dev)
-        assert code == L.ERR_UNSUPPORTED and msg.startswith(who) and "partitioned handle" in msg
-        dev.close()
-        dev = _dev(m16, L.SCHED_CHAIN_SCAN)
-        dev.halo_configure([m16.x_ids[0]], [3 * 4 + 1], [], [])            # a chain's time block
-        code, msg = _code(call, dev)
-        assert code == L.ERR_UNSUPPORTED and "partitioned handle" in msg and "time block" in msg
-        dev.close()
-
-
-def _under_capture(dev, call):
-    """the status of `call` while the handle's stream is being captured (relaxed mode: the refusal's own runtime queries do not void
-    the capture); the handle is back on its own stream afterwards"""
-    hip = C.CDLL([ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0])
-    stream, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    dev.set_stream(stream.value)
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
-    rc = call()
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    dev.set_stream(None)
-    assert hip.hipStreamDestroy(stream) == 0
-    return rc, dev.lib.cx_last_error(dev.h).decode()
+    for reader in _COMMON:
+        assert_reader_refusals(**reader, cases=HANDLE_CASES)
 
 
 def test_refusals_of_a_captured_stream_and_of_parameter_sets_never_set(hip_lib):
+    for reader in _COMMON:
+        assert_reader_refusals(**reader, cases=STREAM_CASES)
     d = 16
     model = cx.synth.lgssm_chain(5, d=d, seed=93)
     fids, _ = S.pset_groups(model)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     want_s, _ = dev.factor_statistics_mfma(n_groups=2)
     want_b = dev.factor_beliefs_mfma(fids)
     ids = np.asarray(fids, np.int64)
     bel, st, c4 = np.zeros((len(ids), 2 * d + 4 * d * d)), np.zeros((2, 1 + 2 * d + 3 * d * d)), np.zeros(4, np.int64)
-    p64, pd = C.POINTER(C.c_int64), C.POINTER(C.c_double)
-    rc, msg = _under_capture(dev, lambda: dev.lib.cx_factor_beliefs_mfma(dev.h, len(ids), ids.ctypes.data_as(p64), bel.ctypes.data_as(pd)))
+    rc, msg = under_capture(dev, lambda: _raw_beliefs(dev, ids, bel))
     assert rc == L.ERR_STATE and msg.startswith("cx_factor_beliefs_mfma") and "captured" in msg, (rc, msg)
-    rc, msg = _under_capture(dev, lambda: dev.lib.cx_factor_statistics_mfma(dev.h, 0, None, None, 2, st.ctypes.data_as(pd), c4.ctypes.data_as(p64)))
+    rc, msg = under_capture(dev, lambda: _raw_statistics(dev, st, c4))
     assert rc == L.ERR_STATE and msg.startswith("cx_factor_statistics_mfma") and "captured" in msg, (rc, msg)
     assert not bel.any() and not st.any()                      # nothing was written
     got_s, _ = dev.factor_statistics_mfma(n_groups=2)          # and the handle works on, bit for bit
     got_b = dev.factor_beliefs_mfma(fids)
     assert all(np.array_equal(got_s[k], want_s[k]) for k in S.KEYS) and np.array_equal(got_b[0], want_b[0]) and np.array_equal(got_b[1], want_b[1])
     dev.close()
-    # Rule tables not on the device: behind a graph they are missing only while a parameter set that a factor names was never set, and
-    # that is refused first, under the call's own name (the guard behind it cannot be reached through the API)
-    dev = cx.DeviceGraph(dim=d, schedule=L.SCHED_TREE)
-    dev.set_factor_matrices(0, *model.psets[0])                # set 1, the likelihoods', is never set
-    dev.graph_create(model.edge_var, model.edge_fac, model.factor_ids, model.factor_kind, model.factor_var, edge_role=model.edge_role)
-    for who, call in (("cx_factor_beliefs_mfma", lambda: dev.factor_beliefs_mfma(fids)), ("cx_factor_statistics_mfma", lambda: dev.factor_statistics_mfma(n_groups=2))):
-        code, msg = _code(call)
-        assert code == L.ERR_STATE and msg.startswith(who) and "never set" in msg and "cx_set_factor_matrices" in msg, (code, msg)
-    dev.close()
 
 
 # ---- 15. the C++ host class -------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_factor_statistics_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "learn_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "learn_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: line.split()[1:] for line in out.stdout.splitlines()}
+    rows = {line.split()[0]: line.split()[1:] for line in run_demo("learn_mfma_demo", tmp_path)}
     T, d = 12, 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
-    Q, R = 0.5 * np.eye(d), np.eye(d)
-    y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
+    A, Q, R, y = demo_chain(T, d)
 
     class _Chain:      # what rts_statistics reads of a model
         dim, data_y, meta = d, y, {"T": T, "A": A, "Q": Q, "R": R}

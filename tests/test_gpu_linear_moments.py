@@ -2,8 +2,6 @@
 argument (the adjoint identity, independent of any solve), and against itself (determinism, independence of the other functionals and
 of the chunking).  Tolerance: tests/functional_support.REL_TOL, set by the restatement's own error (tests/test_functional_checker.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,10 +12,10 @@ from tests import evidence_support as E
 from tests import functional_support as F
 from tests import learning_support as LS
 from tests import sampling_support as SS
-from tests.test_gpu_posterior_samples import _code, _components, _dev
+from tests.test_gpu_posterior_samples import _components, _dev
+from tests.gpu_support import code_of, run_demo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = F.cases()
 
 
@@ -187,25 +185,25 @@ def test_undefined_component_is_nan(hip_lib):
 def test_refusals(hip_lib):
     one = [([1], [[1.0]])]
     dev = _dev(cx.synth.gaussian_grid(6, 5, seed=371), L.SCHED_FUSED, 5)                             # a loopy graph
-    code, msg = _code(dev.linear_moments, one)
+    code, msg = code_of(dev.linear_moments, one)
     assert code == L.ERR_UNSUPPORTED and "cx_linear_moments" in msg and "cycle" in msg and "variable" in msg, msg
     dev.close()
     dev = _dev(cx.synth.lgssm_chain(4, d=16, seed=370), L.SCHED_FUSED, 2)
-    code, msg = _code(dev.linear_moments, [([1], np.ones((1, 16)))])
+    code, msg = code_of(dev.linear_moments, [([1], np.ones((1, 16)))])
     assert code == L.ERR_UNSUPPORTED and "cx_linear_moments" in msg                                  # dim >= 5
     dev.close()
     vm = cx.synth.vmp_ssm(8)
     dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
     cx.synth.load_vmp_into_device(vm, dev)
-    assert _code(dev.linear_moments, one)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.linear_moments, one)[0] == L.ERR_UNSUPPORTED
     dev.close()
     model = cx.synth.ssm_chain(20, seed=372)
     dev = _dev(model, L.SCHED_TREE)
-    code, msg = _code(dev.linear_moments, [([99999], [[1.0]])])
+    code, msg = code_of(dev.linear_moments, [([99999], [[1.0]])])
     assert code == L.ERR_NOT_FOUND and "99999" in msg and "cx_linear_moments" in msg
     off, ids, w = np.array([0, 2, 1], np.int64), np.array([1, 2], np.int64), np.ones((2, 1))
-    assert _code(dev.linear_moments, (off, ids, w))[0] == L.ERR_INVALID_ARGUMENT                     # offsets decrease
-    assert _code(dev.linear_moments, (np.array([1, 2], np.int64), ids, w))[0] == L.ERR_INVALID_ARGUMENT      # do not start at 0
+    assert code_of(dev.linear_moments, (off, ids, w))[0] == L.ERR_INVALID_ARGUMENT                     # offsets decrease
+    assert code_of(dev.linear_moments, (np.array([1, 2], np.int64), ids, w))[0] == L.ERR_INVALID_ARGUMENT      # do not start at 0
     cnt = (C.c_int64 * 4)()
     off1 = np.array([0, 1], np.int64)
     po, pi, pw = off1.ctypes.data_as(C.POINTER(C.c_int64)), ids.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(C.POINTER(C.c_double))
@@ -217,12 +215,12 @@ def test_refusals(hip_lib):
     assert dev.lib.cx_linear_moments(dev.h, 1, po, pi, None, pm, None, cnt) == L.ERR_INVALID_ARGUMENT
     assert dev.lib.cx_linear_moments(dev.h, 1, po, pi, pw, pm, None, cnt) == L.OK
     dev.halo_configure([1], [2 * 20 + 1], [], [])                                                    # a partitioned handle
-    assert _code(dev.linear_moments, one)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.linear_moments, one)[0] == L.ERR_UNSUPPORTED
     dev.close()
     model = cx.synth.ssm_chain(10, seed=373, q=0.0)
     dev = cx.DeviceGraph(schedule=L.SCHED_TREE)
     cx.synth.load_into_device(model, dev)
-    code, msg = _code(dev.linear_moments, one)
+    code, msg = code_of(dev.linear_moments, one)
     assert code == L.ERR_UNSUPPORTED and "zero noise" in msg and "cx_linear_moments" in msg
     dev.close()
 
@@ -239,14 +237,8 @@ def test_sampler_is_unchanged_after_a_moments_call(hip_lib):
 
 
 def test_cpp_host_class_linear_moments(hip_lib, tmp_path):
-    exe = str(tmp_path / "functional_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "functional_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out.stdout.splitlines()}
+    out_lines = run_demo("functional_demo", tmp_path)
+    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out_lines}
     T = 50
     model = cx.synth.ssm_chain(T, seed=1)
     model.data_y = np.array([0.5 * t + (7 * t) % 5 for t in range(1, T + 1)], dtype=np.float64)

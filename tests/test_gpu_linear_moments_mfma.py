@@ -10,8 +10,6 @@ TOL = 1e-9 against the exact references, SAME = 1e-12 between tile sizes or path
 (tests/sample_mfma_support.py).  Every test prints its largest observed error."""
 import ctypes as C
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -27,25 +25,14 @@ from tests import missing_data as MD
 from tests import predictive_mfma_support as PM
 from tests import sample_mfma_support as SM
 from tests import sampling_support as SS
+from tests.gpu_support import assert_reader_refusals, code_of, demo_chain_model, run_demo, under_capture
+from tests.gpu_support import loaded_device as _load
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL, SAME = SM.TOL, SM.SAME
 WHO = "cx_linear_moments_mfma"
 MODELS = SM.models()
 _REFS = {}
-
-
-def _load(model, opaque=None, how="sweep", schedule=L.SCHED_TREE):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    if how == "flat":
-        MD.load(model, dev)                    # the flat message on the one edge of every latent leaf
-    else:
-        cx.synth.load_into_device(model, dev)
-    if how == "opaque":
-        S.set_opaque(dev, opaque)
-    dev.sweep(1)
-    return dev
 
 
 def _reference(model, opaque=None, key=None):
@@ -82,12 +69,6 @@ def _exact(dev, ref, what, components=1):
     assert cnt == {"components": components, "failed": 0, "nan_functionals": 0, "free": int((~gm.obs).sum())}, (what, cnt)
     _within(mean, cov, rm, rc, TOL, what)
     return mean, cov
-
-
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
 
 
 # ---- 1. exact after every schedule -----------------------------------------------------------------------------------------------------
@@ -342,48 +323,33 @@ def test_one_handle_with_the_sampler_follows_the_observed_flags(hip_lib):
 
 
 # ---- 12. refusals -----------------------------------------------------------------------------------------------------------------------------
-def _under_capture(dev, call):
-    """the status of `call` while the handle's stream is being captured (relaxed mode: the refusal's own runtime queries do not void
-    the capture); the handle is back on its own stream afterwards"""
-    hip = C.CDLL([ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0])
-    stream, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    dev.set_stream(stream.value)
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
-    rc = call()
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    dev.set_stream(None)
-    assert hip.hipStreamDestroy(stream) == 0
-    return rc, dev.lib.cx_last_error(dev.h).decode()
+def _one(dev):
+    """the cheapest functional: the sum of the entries of variable 1, at the handle's dim"""
+    return [([1], np.ones((1, dev.dim)))]
+
+
+def _raw_one(dev):
+    """_one(dev) through the C ABI; the status"""
+    off, ids, w = FS.as_csr(_one(dev), dev.dim)
+    p64, pd = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    mean, cov = np.zeros(1), np.zeros((1, 1))
+    return dev.lib.cx_linear_moments_mfma(dev.h, 1, off.ctypes.data_as(p64), ids.ctypes.data_as(p64), w.ctypes.data_as(pd),
+                                          mean.ctypes.data_as(pd), cov.ctypes.data_as(pd), (C.c_int64 * 4)())
 
 
 def test_refusals(hip_lib):
-    m4 = cx.synth.lgssm_chain(5, d=4, seed=91)
+    assert_reader_refusals(WHO, "cx_linear_moments", lambda dev: dev.linear_moments_mfma(_one(dev)), lambda dev: dev.linear_moments(_one(dev)), _raw_one)
     m16 = cx.synth.lgssm_chain(4, d=16, seed=92)
-    one4, one16 = [([int(m4.x_ids[0])], np.ones((1, 4)))], [([int(m16.x_ids[0])], np.ones((1, 16)))]
-    dev = _load(m4)
-    code, msg = _code(dev.linear_moments_mfma, one4)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "cx_linear_moments" in msg.replace(WHO, "")      # names the call for dims 1 .. 4
-    dev.close()
-    dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    code, msg = _code(dev.linear_moments_mfma, [([1], [[1.0]])])
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "Gaussian family" in msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16)
-    code, msg = _code(dev.linear_moments_mfma, one16)
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "no graph" in msg
-    dev.close()
+    one16 = [([int(m16.x_ids[0])], np.ones((1, 16)))]
     dev = cx.DeviceGraph(dim=16, schedule=L.SCHED_FUSED)      # a cycle among the non-observed variables
     ring = S.ring(16)
     cx.synth.load_into_device(ring, dev, seed_variance=1e6)
     dev.sweep(3)
-    code, msg = _code(dev.linear_moments_mfma, [([int(ring.x_ids[0])], np.ones((1, 16)))])
+    code, msg = code_of(dev.linear_moments_mfma, [([int(ring.x_ids[0])], np.ones((1, 16)))])
     assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "cycle" in msg and "variable" in msg, msg
     dev.close()
     dev = _load(m16)
-    code, msg = _code(dev.linear_moments, one16)
+    code, msg = code_of(dev.linear_moments, one16)
     assert code == L.ERR_UNSUPPORTED and "cx_linear_moments" in msg and WHO not in msg      # the old call keeps refusing these dims
     # the argument errors of cx_linear_moments, through the C ABI: a refused call writes nothing
     off, ids, w = FS.as_csr(one16, 16)
@@ -402,48 +368,24 @@ def test_refusals(hip_lib):
         assert call(dev.h, *args) == L.ERR_INVALID_ARGUMENT, args
         assert dev.lib.cx_last_error(dev.h).decode().startswith(WHO)
     assert mean[0] == 7.0 and cov[0, 0] == 7.0 and list(cnt) == [7, 7, 7, 7]
-    code, msg = _code(dev.linear_moments_mfma, [([int(m16.x_ids[0]), 10 ** 9], np.ones((2, 16)))])
+    code, msg = code_of(dev.linear_moments_mfma, [([int(m16.x_ids[0]), 10 ** 9], np.ones((2, 16)))])
     assert code == L.ERR_NOT_FOUND and msg.startswith(WHO) and str(10 ** 9) in msg
     want = dev.linear_moments_mfma(one16)      # and the handle works on
     assert call(dev.h, 1, po, pi, pw, pm, None, cnt) == L.OK and list(cnt) == [1, 0, 0, 4] and mean[0] == want[0][0] and cov[0, 0] == 7.0
     mean[:] = 7.0
-    rc, msg = _under_capture(dev, lambda: call(dev.h, 1, po, pi, pw, pm, pc, cnt))
+    rc, msg = under_capture(dev, lambda: call(dev.h, 1, po, pi, pw, pm, pc, cnt))
     assert rc == L.ERR_STATE and msg.startswith(WHO) and "captured" in msg, (rc, msg)
     assert mean[0] == 7.0 and cov[0, 0] == 7.0      # a refused call writes nothing
     again = dev.linear_moments_mfma(one16)
     assert np.array_equal(again[0], want[0]) and np.array_equal(again[1], want[1])
-    dev.halo_configure_state([m16.x_ids[0]], [3 * 4 + 1], [], [])      # a halo list: a partitioned handle
-    code, msg = _code(dev.linear_moments_mfma, one16)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "partitioned handle" in msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16, schedule=L.SCHED_TREE)
-    dev.set_factor_matrices(0, *m16.psets[0])                # set 1, the likelihoods', is never set
-    dev.graph_create(m16.edge_var, m16.edge_fac, m16.factor_ids, m16.factor_kind, m16.factor_var, edge_role=m16.edge_role)
-    code, msg = _code(dev.linear_moments_mfma, one16)
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "never set" in msg and "cx_set_factor_matrices" in msg, (code, msg)
     dev.close()
 
 
 # ---- 13. the C++ host class -------------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_linear_moments_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "linear_moments_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "linear_moments_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out.stdout.splitlines()}
+    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in run_demo("linear_moments_mfma_demo", tmp_path)}
     T, d = 12, 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
-    y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
-    base = cx.synth.lgssm_chain(T, d=d, seed=1)      # the demo's ids are lgssm_chain's; its connections in the demo's order
-    x, yv, lik, tr = base.x_ids, base.x_ids + T, base.x_ids + 2 * T, np.arange(3 * T + 1, 4 * T)
-    ev = np.concatenate([np.stack([yv, x], 1).ravel(), np.stack([x[:-1], x[1:]], 1).ravel()])
-    ef = np.concatenate([np.repeat(lik, 2), np.repeat(tr, 2)])
-    er = np.concatenate([np.tile([L.ROLE_OUT, L.ROLE_IN], T), np.tile([L.ROLE_IN, L.ROLE_OUT], T - 1)]).astype(np.int32)
-    model = dataclasses.replace(base, edge_var=ev, edge_fac=ef, edge_role=er, data_y=y, psets={0: (A, 0.5 * np.eye(d)), 1: (np.eye(d), np.eye(d))},
-                                meta={**base.meta, "A": A, "Q": 0.5 * np.eye(d), "R": np.eye(d)})
+    model = demo_chain_model(T, d)
     e0 = np.eye(d)[:1]
     fs = [(np.arange(3, 9), np.full((6, d), 1.0 / (6 * d))), ([2], e0), ([11], e0),
           ([1, 12, T + 5], np.concatenate([np.ones((1, d)), -np.ones((1, d)), 2.0 * np.ones((1, d))]))]

@@ -22,16 +22,13 @@ from tests import learning_support as LS
 from tests import missing_data as MD
 from tests import predictive_support as P
 from tests import sampling_support as SS
-from tests.helpers import assert_close as _assert_close
+from tests.helpers import assert_close_by_max as assert_close
+from tests.learning_support import assert_rel_close as _close
 
 pytestmark = pytest.mark.gpu
 
 CASES = {c[0]: c for c in MD.gpu_cases()}
 MODELS = MD.gpu_models()
-
-
-def assert_close(a, b, rtol, what=""):
-    return _assert_close(a, b, rtol, what, scale_by="max")
 
 
 def names(pred):
@@ -247,12 +244,6 @@ def reader_ref(name):
         r.update(log_z=E.dense_log_z(gm), kalman=k, causal=causal, n_rows=nr, loo=loo, loo_err=loo_err, beliefs=LS.dense_factor_beliefs(gm),
                  fids=fids, groups=groups, n_groups=n_groups, stats=LS.grouped_statistics(gm, fids, groups, n_groups), functionals=fs, moments=F.dense_moments(gm, fs))
     return r
-
-
-def _close(got, want, rtol, what=""):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    err = float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0))) if got.size else 0.0
-    assert err <= rtol, (what, err)
 
 
 def rows_subset(res, sel):

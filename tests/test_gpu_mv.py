@@ -11,12 +11,8 @@ import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
 from oracle import exact
 from oracle.mv import MvFlood
-from tests.helpers import assert_close as _assert_close
+from tests.helpers import assert_close_by_max as assert_close
 
-
-def assert_close(a, b, rtol, what=""):
-    # matrices carry numerically-zero entries: measure errors against the largest entry
-    return _assert_close(a, b, rtol, what, scale_by="max")
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-9

@@ -12,13 +12,9 @@ import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
 from oracle import exact
 from oracle.mv import MvFlood
-from tests.helpers import assert_close as _assert_close
+from tests.helpers import assert_close_by_max as assert_close
 
 pytestmark = pytest.mark.gpu
-
-
-def assert_close(a, b, rtol, what=""):
-    return _assert_close(a, b, rtol, what, scale_by="max")
 
 
 def _dev(model, schedule=L.SCHED_CHAIN_SCAN):

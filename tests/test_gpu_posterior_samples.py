@@ -3,8 +3,6 @@ restatement of the device generator and exact sampling distributions (tests/samp
 tests/test_sampling_checker.py)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +13,10 @@ from tests import evidence_support as E
 from tests import learning_support as LS
 from tests import sampling_support as SS
 from tests.test_gpu_kary_mv import _kary_tree, _load as _load_kary
+from tests.gpu_support import code_of, run_demo
+from tests.learning_support import assert_rel_close as _close
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _dev(model, schedule, sweeps=1):
@@ -25,19 +24,6 @@ def _dev(model, schedule, sweeps=1):
     cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule == L.SCHED_FUSED else None)
     dev.sweep(sweeps)
     return dev
-
-
-def _close(got, want, rtol, what=""):
-    got, want = np.asarray(got, float), np.asarray(want, float)
-    scale = np.maximum(np.abs(want), 1.0)
-    err = float(np.max(np.abs(got - want) / scale)) if got.size else 0.0
-    assert err <= rtol, (what, err)
-
-
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
 
 
 EXACT = [("ssm_chain", lambda: cx.synth.ssm_chain(60, seed=301), True),
@@ -230,27 +216,27 @@ def test_undefined_component_is_nan(hip_lib):
 
 def test_refusals(hip_lib):
     dev = cx.DeviceGraph()
-    assert _code(dev.sample_posterior, 1)[0] == L.ERR_STATE                                          # no graph
+    assert code_of(dev.sample_posterior, 1)[0] == L.ERR_STATE                                          # no graph
     dev.close()
     dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    assert _code(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED
     dev.close()
     vm = cx.synth.vmp_ssm(8)
     dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
     cx.synth.load_vmp_into_device(vm, dev)
-    assert _code(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED
     dev.close()
     dev = _dev(cx.synth.lgssm_chain(4, d=16, seed=370), L.SCHED_FUSED, 2)
-    assert _code(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED                                    # dim >= 5
+    assert code_of(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED                                    # dim >= 5
     dev.close()
     dev = _dev(cx.synth.gaussian_grid(6, 5, seed=371), L.SCHED_FUSED, 5)                             # a loopy graph
-    code, msg = _code(dev.sample_posterior, 1)
+    code, msg = code_of(dev.sample_posterior, 1)
     assert code == L.ERR_UNSUPPORTED and "cx_sample_posterior" in msg and "cycle" in msg and "variable" in msg, msg
     dev.close()
     model = cx.synth.ssm_chain(20, seed=372)
     dev = _dev(model, L.SCHED_TREE)
-    assert _code(dev.sample_posterior, 0)[0] == L.ERR_INVALID_ARGUMENT                               # n_samples < 1
-    code, msg = _code(dev.sample_posterior, 1, variable_ids=[99999])
+    assert code_of(dev.sample_posterior, 0)[0] == L.ERR_INVALID_ARGUMENT                               # n_samples < 1
+    code, msg = code_of(dev.sample_posterior, 1, variable_ids=[99999])
     assert code == L.ERR_NOT_FOUND and "99999" in msg
     ids = np.array([1, 2], np.int64)
     out = np.zeros(2)
@@ -259,25 +245,19 @@ def test_refusals(hip_lib):
     assert dev.lib.cx_sample_posterior(dev.h, 1, C.c_uint64(0), None, 2, pi, None, cnt) == L.ERR_INVALID_ARGUMENT      # no output
     assert dev.lib.cx_sample_posterior(dev.h, 1, C.c_uint64(0), None, -1, pi, po, cnt) == L.ERR_INVALID_ARGUMENT       # n < 0 with ids
     dev.halo_configure([1], [2 * 20 + 1], [], [])                                                    # a partitioned handle
-    assert _code(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.sample_posterior, 1)[0] == L.ERR_UNSUPPORTED
     dev.close()
     model = cx.synth.ssm_chain(10, seed=373, q=0.0)
     dev = cx.DeviceGraph(schedule=L.SCHED_TREE)
     cx.synth.load_into_device(model, dev)
-    code, msg = _code(dev.sample_posterior, 1)
+    code, msg = code_of(dev.sample_posterior, 1)
     assert code == L.ERR_UNSUPPORTED and "factor 31" in msg and "zero noise" in msg
     dev.close()
 
 
 def test_cpp_host_class_sample_posterior(hip_lib, tmp_path):
-    exe = str(tmp_path / "sample_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "sample_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out.stdout.splitlines()}
+    out_lines = run_demo("sample_demo", tmp_path)
+    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out_lines}
     T = 50
     model = cx.synth.ssm_chain(T, seed=1)
     model.data_y = np.array([0.5 * t + (7 * t) % 5 for t in range(1, T + 1)], dtype=np.float64)

@@ -2,8 +2,6 @@
 factor generates, from the stored messages — against the dense leave-one-out solve, the Kalman innovations and the numpy
 restatement of the formula (tests/predictive_support.py, pinned by tests/test_predictive_checker.py)."""
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,18 +13,10 @@ from tests import evidence_support as E
 from tests import predictive_support as P
 from tests.test_gpu_kary_mv import _kary_tree, _load as _load_kary
 from tests.test_host_mirror import make_ssm
+from tests.gpu_support import code_of, iterative_device, run_demo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ITER = (L.SCHED_FUSED, L.SCHED_FLOODING)
 EXACT, PARITY = 1e-9, 1e-10      # against exact solves (test_gpu_evidence.py: _exact); against the restatement on the device's messages
-
-
-def _dev(model, schedule, iterative_sweeps=0):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule in ITER else None)
-    dev.sweep(iterative_sweeps if schedule in ITER else 1)      # (reference order: cx_sweep requests every variable)
-    return dev
 
 
 def _kalman_rows(model, fids):
@@ -58,7 +48,7 @@ DIM1_CHAINS = [("ssm_chain", lambda: cx.synth.ssm_chain(200, seed=21, random_var
 def test_dim1_chains_after_every_schedule(hip_lib, name, make, n_iter):
     model = make()
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED, L.SCHED_FLOODING):
-        dev = _dev(model, s, n_iter)
+        dev = iterative_device(model, s, n_iter)
         _check_chain(model, dev, f"{name} schedule {s}")
         dev.close()
 
@@ -67,13 +57,13 @@ def test_dim1_chains_after_every_schedule(hip_lib, name, make, n_iter):
 def test_dims_2_to_4_chains_and_comb_after_every_schedule(hip_lib, d):
     model = cx.synth.lgssm_chain(60, d=d, seed=30 + d)
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED):
-        dev = _dev(model, s, 200)
+        dev = iterative_device(model, s, 200)
         _check_chain(model, dev, f"d {d} lgssm_chain schedule {s}")
         dev.close()
     model = cx.synth.lgssm_comb(15, d=d, teeth=1, seed=40 + d)
     want = P.dense_loo_all(E.gmodel(model))
     for s in (L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED):
-        dev = _dev(model, s, 200)
+        dev = iterative_device(model, s, 200)
         loo = dev.predictive("loo")
         assert loo["counts"] == {"rows": 30, "scored": 30, "undefined": 0, "improper": 0}
         print(d, s, "comb loo", P.assert_rows_close(loo, want, EXACT, f"d {d} lgssm_comb schedule {s}"))
@@ -87,7 +77,7 @@ def test_dim1_tree_with_kary_rows_after_every_schedule(hip_lib):
     assert sum(1 for r in rows if r[1] == 2) >= 2 and sum(1 for r in rows if r[1] > 2) >= 2
     want = P.dense_loo_all(gm)
     for s in (L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED, L.SCHED_FLOODING):
-        dev = _dev(model, s, 400)
+        dev = iterative_device(model, s, 400)
         loo = dev.predictive("loo")
         assert loo["counts"] == {"rows": len(rows), "scored": len(rows), "undefined": 0, "improper": 0}
         print(s, "tree loo", P.assert_rows_close(loo, want, EXACT, f"tree_model schedule {s}"))
@@ -100,7 +90,7 @@ def test_a_cavity_with_no_message_left_is_improper_by_structure(hip_lib, seed):
     model = cx.synth.ssm_chain_linear(6, seed=seed)
     want = E.kalman_of_chain(model)
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_TREE, L.SCHED_REFERENCE):
-        dev = _dev(model, s)
+        dev = iterative_device(model, s)
         cau = dev.predictive("causal")
         assert cau["counts"] == {"rows": 6, "scored": 5, "undefined": 0, "improper": 1}, (s, cau["counts"])
         assert np.isnan(cau["log_density"][0]) and abs(cau["total"] - want) <= EXACT * abs(want)
@@ -156,7 +146,7 @@ def test_formula_parity_off_a_fixed_point(hip_lib):
     model = cx.synth.kary_model(60, seed=24, tree=False, observe=0.5)
     gm = E.gmodel(model)
     assert len(P.rows_of(gm)) >= 2
-    dev = _dev(model, L.SCHED_FUSED, 6)
+    dev = iterative_device(model, L.SCHED_FUSED, 6)
     _parity(model, gm, dev, "kary_model(tree=False)")
     dev.close()
     # a loopy grid with an observed end hung on some of its variables (CX_FACTOR_GAUSS_ADDITIVE rows, the datum on the higher id)
@@ -173,13 +163,13 @@ def test_formula_parity_off_a_fixed_point(hip_lib):
                            prior_variance=grid.prior_variance, meta={"kind": "grid+obs"})
     gm = E.gmodel(model)
     assert len(P.rows_of(gm)) == len(xs)
-    dev = _dev(model, L.SCHED_FUSED, 5)
+    dev = iterative_device(model, L.SCHED_FUSED, 5)
     _parity(model, gm, dev, "grid with observed ends")
     dev.close()
     # on a forest the dense solve itself stays within the parity tolerance of the restatement on the device's messages
     model = cx.synth.lgssm_chain(30, d=3, seed=8)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     f2v, opq = _parity(model, gm, dev, "lgssm_chain d 3")
     print("dense vs restatement", P.assert_rows_close(P.dense_loo_all(gm), P.predictive_from_messages(gm, f2v, opq, P.LOO), PARITY, "dense vs restatement"))
     dev.close()
@@ -191,7 +181,7 @@ def _same_bits(a, b):
 
 def test_semantics(hip_lib):
     model = cx.synth.ssm_chain_linear(80, seed=41)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = iterative_device(model, L.SCHED_TREE)
     for mode in ("loo", "causal"):
         full = dev.predictive(mode)
         again = dev.predictive(mode)
@@ -217,7 +207,7 @@ def test_semantics(hip_lib):
 
 def test_no_side_effects(hip_lib):
     model = cx.synth.tree_model(60, seed=23, k_choices=(1, 2, 3), observe=0.25)
-    dev = _dev(model, L.SCHED_REFERENCE)
+    dev = iterative_device(model, L.SCHED_REFERENCE)
     blob, trace, health, stats = dev.export_state(), dev.ref_trace(), dev.message_health(), dev.ref_plan_stats()
     msgs, marg = dev.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE), dev.get_marginals(model.x_ids)
     stats = dev.ref_plan_stats()
@@ -228,7 +218,7 @@ def test_no_side_effects(hip_lib):
     assert np.array_equal(marg, dev.get_marginals(model.x_ids), equal_nan=True)
     dev.close()
     model = cx.synth.lgssm_chain(50, d=4, seed=72)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     dev.predictive("causal")                            # (the chain messages go to their slots on the first read-out)
     blob, health = dev.export_state(), dev.message_health()
     dev.predictive("causal"); dev.predictive("loo")
@@ -236,7 +226,7 @@ def test_no_side_effects(hip_lib):
     dev.close()
     # fused: the next sweeps are those of a twin handle that never called it, bit for bit
     model = cx.synth.ssm_chain(40, seed=73)
-    a, b = _dev(model, L.SCHED_FUSED, 5), _dev(model, L.SCHED_FUSED, 5)
+    a, b = iterative_device(model, L.SCHED_FUSED, 5), iterative_device(model, L.SCHED_FUSED, 5)
     a.predictive("loo"); a.predictive("causal")
     a.sweep(3); b.sweep(3)
     assert np.array_equal(a.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE), b.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE), equal_nan=True)
@@ -246,7 +236,7 @@ def test_no_side_effects(hip_lib):
 
 def test_new_parameters_are_read(hip_lib):
     model = cx.synth.lgssm_chain(200, d=2, seed=61)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     first = dev.predictive("causal")
     kal = E.kalman_of_chain(model)
     assert abs(first["total"] - kal) <= EXACT * abs(kal)
@@ -275,42 +265,36 @@ def test_undefined_rows_are_nan_and_counted_apart(hip_lib):
     assert dev.predictive("loo")["counts"]["scored"] == 50
     dev.close()
     one = cx.synth.ssm_chain(1, seed=82)                # one state and no prior: improper, not undefined
-    dev = _dev(one, L.SCHED_TREE)
+    dev = iterative_device(one, L.SCHED_TREE)
     assert dev.predictive("loo")["counts"] == {"rows": 1, "scored": 0, "undefined": 0, "improper": 1}
     dev.close()
 
 
-def _code(fn):
-    with pytest.raises(L.CortexHipError) as e:
-        fn()
-    return e.value.code, e.value.message
-
-
 def test_refusals(hip_lib):
     dev = cx.DeviceGraph()
-    assert _code(dev.predictive)[0] == L.ERR_STATE                            # no graph
+    assert code_of(dev.predictive)[0] == L.ERR_STATE                            # no graph
     dev.close()
     dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    assert _code(dev.predictive)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.predictive)[0] == L.ERR_UNSUPPORTED
     dev.close()
     vm = cx.synth.vmp_ssm(8)
     dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
     cx.synth.load_vmp_into_device(vm, dev)
-    assert _code(dev.predictive)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.predictive)[0] == L.ERR_UNSUPPORTED
     dev.close()
     m16 = cx.synth.lgssm_chain(4, d=16, seed=91)
-    dev = _dev(m16, L.SCHED_FUSED, 2)
-    assert _code(dev.predictive)[0] == L.ERR_UNSUPPORTED                      # dim >= 5
+    dev = iterative_device(m16, L.SCHED_FUSED, 2)
+    assert code_of(dev.predictive)[0] == L.ERR_UNSUPPORTED                      # dim >= 5
     dev.close()
     T = 20
     model = cx.synth.ssm_chain(T, seed=92)
-    dev = _dev(model, L.SCHED_FUSED, 5)
+    dev = iterative_device(model, L.SCHED_FUSED, 5)
     cnt = (L.C.c_int64 * 4)()
     assert dev.lib.cx_predictive(dev.h, L.PREDICT_LOO, 0, None, None, None, None) == L.ERR_INVALID_ARGUMENT      # NULL counts4
     assert dev.lib.cx_predictive(dev.h, 2, 0, None, None, None, cnt) == L.ERR_INVALID_ARGUMENT                   # unknown mode
-    code, msg = _code(lambda: dev.predictive("loo", factor_ids=[2 * T + 1, 999]))
+    code, msg = code_of(lambda: dev.predictive("loo", factor_ids=[2 * T + 1, 999]))
     assert code == L.ERR_NOT_FOUND and "999" in msg
-    code, msg = _code(lambda: dev.predictive("loo", factor_ids=[2 * T + 1, 3 * T + 1]))                          # a transition: no observed end
+    code, msg = code_of(lambda: dev.predictive("loo", factor_ids=[2 * T + 1, 3 * T + 1]))                          # a transition: no observed end
     assert code == L.ERR_UNSUPPORTED and f"factor {3 * T + 1}" in msg
     # a stream under capture (relaxed mode: the refusal's own runtime queries do not void the capture)
     hip = L.C.CDLL([ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0])      # the runtime the library itself loaded
@@ -327,12 +311,12 @@ def test_refusals(hip_lib):
     assert rc == L.ERR_STATE
     assert dev.predictive("loo")["counts"]["rows"] == T                       # and the handle works on
     dev.halo_configure([1], [2 * T + 1], [], [])                              # a halo list: a partitioned handle
-    assert _code(dev.predictive)[0] == L.ERR_UNSUPPORTED
+    assert code_of(dev.predictive)[0] == L.ERR_UNSUPPORTED
     dev.close()
     model = cx.synth.ssm_chain(10, seed=93, q=0.0)
     dev = cx.DeviceGraph(schedule=L.SCHED_TREE)
     cx.synth.load_into_device(model, dev)
-    code, msg = _code(dev.predictive)
+    code, msg = code_of(dev.predictive)
     assert code == L.ERR_UNSUPPORTED and "factor 31" in msg                   # zero noise: the first transition (ids 3T + 1 ..)
     dev.close()
     # a factor with two observed ends, and a CX_FACTOR_GAUSS_LINEAR whose IN end is the observed one
@@ -340,9 +324,9 @@ def test_refusals(hip_lib):
     dev = cx.DeviceGraph(schedule=L.SCHED_TREE)
     cx.synth.load_into_device(model, dev)
     dev.set_messages([1], [3 * 6 + 1], L.TO_FACTOR, L.FORM_POINT, [0.3])      # x_1 observed: likelihood 2T + 1 now has two observed ends
-    code, msg = _code(lambda: dev.predictive("loo", factor_ids=[2 * 6 + 1]))
+    code, msg = code_of(lambda: dev.predictive("loo", factor_ids=[2 * 6 + 1]))
     assert code == L.ERR_UNSUPPORTED and "factor 13" in msg
-    code, msg = _code(lambda: dev.predictive("loo", factor_ids=[3 * 6 + 1]))   # x_2 = a x_1 + b + noise with x_1 (IN) observed
+    code, msg = code_of(lambda: dev.predictive("loo", factor_ids=[3 * 6 + 1]))   # x_2 = a x_1 + b + noise with x_1 (IN) observed
     assert code == L.ERR_UNSUPPORTED and "factor 19" in msg
     assert list(dev.predictive_rows()) == list(range(2 * 6 + 2, 3 * 6 + 1))    # the other likelihoods
     dev.close()
@@ -372,18 +356,12 @@ def test_hip_processor_predictive(hip_lib):
 
 
 def test_cpp_host_class_predictive(hip_lib, tmp_path):
-    exe = str(tmp_path / "predictive_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "predictive_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    lines = [line.split() for line in out.stdout.splitlines()]
+    out_lines = run_demo("predictive_demo", tmp_path)
+    lines = [line.split() for line in out_lines]
     T = 50
     model = cx.synth.ssm_chain(T, seed=1)
     model.data_y = np.array([0.5 * t + (7 * t) % 5 for t in range(1, T + 1)], dtype=np.float64)
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = iterative_device(model, L.SCHED_CHAIN_SCAN)
     for mode in ("loo", "causal"):
         want = dev.predictive(mode)
         tot = [l for l in lines if l[0] == mode + "_total"][0]

@@ -3,10 +3,7 @@ against the dense leave-one-out solve, the Kalman innovations and the numpy rest
 messages (tests/predictive_support.py; the models are those of tests/predictive_mfma_support.py, pinned on the CPU by
 tests/test_predictive_mfma_checker.py).  Rows are held to predictive_support.assert_rows_close(..., 1e-9), totals to 1e-9 relative."""
 import ctypes as C
-import dataclasses
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,27 +12,13 @@ import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
 from tests import evidence_mfma_support as S
 from tests import evidence_support as E
-from tests import missing_data as MD
 from tests import predictive_mfma_support as PM
 from tests import predictive_support as P
+from tests.gpu_support import (HANDLE_CASES, STREAM_CASES, assert_reader_refusals, code_of, demo_chain, missing_data_device, run_demo,
+                               swept_device, under_capture, with_sets)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-9
-
-
-def _dev(model, schedule, fused_sweeps=60):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    cx.synth.load_into_device(model, dev, seed_variance=1e6 if schedule == L.SCHED_FUSED else None)
-    dev.sweep(fused_sweeps if schedule == L.SCHED_FUSED else 1)      # (reference order: cx_sweep requests every variable)
-    return dev
-
-
-def _md_dev(model):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=L.SCHED_TREE)
-    MD.load(model, dev)                    # the flat message on the one edge of every latent leaf
-    dev.sweep(1)
-    return dev
 
 
 def _close(got, want, what):
@@ -68,7 +51,7 @@ def test_rows_after_every_schedule(hip_lib, d, shape):
     n = len(dense["factor_ids"])
     for s in [L.SCHED_TREE, L.SCHED_REFERENCE, L.SCHED_FUSED] + ([L.SCHED_CHAIN_SCAN] if shape == "chain" else []):
         what = f"d {d} {shape} schedule {s}"
-        dev = _dev(model, s)      # (fused: seed variance 1e6 and 60 sweeps, the diameter is under 20)
+        dev = swept_device(model, s)      # (fused: seed variance 1e6 and 60 sweeps, the diameter is under 20)
         assert np.array_equal(dev.predictive_rows_mfma(), dense["factor_ids"])
         loo, cau = dev.predictive_mfma("loo"), dev.predictive_mfma("causal")
         _close(loo, dense, what + " loo vs dense")
@@ -89,7 +72,7 @@ def test_general_matrices_gaps_and_a_forecast_tail(hip_lib, d):
     model = PM.gen(d)
     gm = E.gmodel(model)
     want, log_first = PM.kalman_rows(model)
-    dev = _md_dev(model)
+    dev = missing_data_device(model)
     cau, loo = dev.predictive_mfma("causal"), dev.predictive_mfma("loo")
     assert np.array_equal(cau["factor_ids"], np.sort(model.data_fac)) and np.array_equal(loo["factor_ids"], cau["factor_ids"])      # the observed steps
     _close(cau, want, f"gen d {d} causal vs kalman_missing")
@@ -120,7 +103,7 @@ def _pivots(A):
 def test_a_leading_gap_is_improper_by_the_flat_pivot_rule(hip_lib, d):
     model = PM.leading_gap(d)
     gm = E.gmodel(model)
-    dev = _md_dev(model)
+    dev = missing_data_device(model)
     cau, loo = dev.predictive_mfma("causal"), dev.predictive_mfma("loo")
     # the measurement the rule's constant rests on: row 0's causal cavity is the one message of the first transition into x_2, whose
     # information is flat — its pivots against the diagonal of the sum of all messages into x_2, from the device's own messages
@@ -173,7 +156,7 @@ def test_a_clamped_state_in_the_middle(hip_lib, d):
     ev, ef, er = np.asarray(model.edge_var), np.asarray(model.edge_fac), np.asarray(model.edge_role)
     into = int(ef[(ev == x) & (er == L.ROLE_OUT)][0])                          # the transition into x: x is its OUT end
     lik = int(np.asarray(model.data_fac)[model.meta["clamped_state"]])         # x's likelihood: both ends observed
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     rows = dev.predictive_rows_mfma()
     assert len(rows) == 5 and into in rows.tolist() and lik not in rows.tolist()
     with pytest.raises(L.CortexHipError) as e:
@@ -191,7 +174,7 @@ def test_a_clamped_state_in_the_middle(hip_lib, d):
 def test_a_loop_matches_the_formula_on_the_device_messages(hip_lib, d):
     model = S.ring(d)
     gm = E.gmodel(model)
-    dev = _dev(model, L.SCHED_FUSED, S.RING_SWEEPS)
+    dev = swept_device(model, L.SCHED_FUSED, S.RING_SWEEPS)
     for name, mode in (("loo", P.LOO), ("causal", P.CAUSAL)):
         got, again = dev.predictive_mfma(name), dev.predictive_mfma(name)
         _close(got, _on_device_messages(gm, dev, mode), f"ring d {d} {name}")
@@ -206,11 +189,11 @@ def test_a_loop_matches_the_formula_on_the_device_messages(hip_lib, d):
 @pytest.mark.parametrize("d", [8, 20])
 def test_embedded_dims_give_the_real_models_rows_at_any_tile_size(hip_lib, d, monkeypatch):
     model = cx.synth.lgssm_chain(5, d=d, seed=90 + d)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     native = {m: dev.predictive_mfma(m) for m in ("loo", "causal")}
     dev.close()
     monkeypatch.setenv("CX_MFMA_DIM", "64")
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     monkeypatch.delenv("CX_MFMA_DIM")
     for m in ("loo", "causal"):
         forced = dev.predictive_mfma(m)
@@ -222,12 +205,6 @@ def test_embedded_dims_give_the_real_models_rows_at_any_tile_size(hip_lib, d, mo
 
 
 # ---- 8. undefined inputs; new parameters -----------------------------------------------------------------------------------------------
-def _with_sets(model, psets):
-    A, Q = psets[0]
-    _, R = psets[1]
-    return dataclasses.replace(model, meta={**model.meta, "A": np.asarray(A), "Q": np.asarray(Q), "R": np.asarray(R)})
-
-
 @pytest.mark.parametrize("d", [8, 32])
 def test_undefined_then_exact_then_new_parameters(hip_lib, d):
     model = cx.synth.lgssm_chain(7, d=d, seed=81 + d)
@@ -248,7 +225,7 @@ def test_undefined_then_exact_then_new_parameters(hip_lib, d):
             dev.set_factor_matrices(1, *psets[1])
         dev.sweep(1)
         cau, loo = dev.predictive_mfma("causal"), dev.predictive_mfma("loo")
-        _close(cau, PM.innovations_rows(_with_sets(model, psets)), f"d {d} {step} causal vs the Kalman innovations")      # the [A' | Q] table followed
+        _close(cau, PM.innovations_rows(with_sets(model, psets)), f"d {d} {step} causal vs the Kalman innovations")      # the [A' | Q] table followed
         _close(loo, P.dense_loo_all(E.gmodel(model, psets=psets)), f"d {d} {step} loo vs dense")
         if first is None:
             first = cau
@@ -263,7 +240,7 @@ def test_undefined_then_exact_then_new_parameters(hip_lib, d):
 # ---- 9. named rows -----------------------------------------------------------------------------------------------------------------------
 def test_named_rows_in_the_callers_order(hip_lib):
     model = cx.synth.lgssm_chain(9, d=16, seed=83)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     for m in ("loo", "causal"):
         full = dev.predictive_mfma(m)
         ids = full["factor_ids"]
@@ -288,7 +265,7 @@ def test_named_rows_in_the_callers_order(hip_lib):
 def test_long_chains_against_the_kalman_innovations(hip_lib, T, d):
     model = cx.synth.lgssm_chain(T, d=d, seed=33)
     assert T * (d + d * d + 2) * 8 > 32 << 20      # more than one chunk of the payload
-    dev = _dev(model, L.SCHED_CHAIN_SCAN)
+    dev = swept_device(model, L.SCHED_CHAIN_SCAN)
     cau = dev.predictive_mfma("causal")
     _close(cau, PM.innovations_rows(model), f"d = {d}, T = {T}, chain scan, causal vs the Kalman innovations")
     assert cau["counts"] == _counts(T, improper=1), cau["counts"]
@@ -304,7 +281,7 @@ def test_long_chains_against_the_kalman_innovations(hip_lib, T, d):
 def test_moves_nothing(hip_lib):
     model = cx.synth.lgssm_chain(8, d=16, seed=72)
     for s in (L.SCHED_CHAIN_SCAN, L.SCHED_REFERENCE, L.SCHED_TREE):
-        dev = _dev(model, s)
+        dev = swept_device(model, s)
         if s == L.SCHED_CHAIN_SCAN:      # (another reader first: every reader of the messages brings them to their slots)
             dev.get_messages(model.edge_var, model.edge_fac, L.TO_VARIABLE)
         blob, marg = dev.export_state(), dev.get_marginals(model.x_ids)
@@ -315,7 +292,7 @@ def test_moves_nothing(hip_lib):
         assert np.array_equal(blob, dev.export_state())
         dev.close()
     # fused: the next sweeps are those of a twin handle that never called it, bit for bit
-    a, b = _dev(model, L.SCHED_FUSED, 5), _dev(model, L.SCHED_FUSED, 5)
+    a, b = swept_device(model, L.SCHED_FUSED, 5), swept_device(model, L.SCHED_FUSED, 5)
     assert a.residual() == b.residual()      # (the first call takes the snapshot the next one measures against)
     a.predictive_mfma("causal"); a.predictive_mfma("loo")
     a.sweep(3); b.sweep(3)
@@ -328,112 +305,64 @@ def test_moves_nothing(hip_lib):
 
 
 # ---- 12. refusals ------------------------------------------------------------------------------------------------------------------------
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
+WHO = "cx_predictive_mfma"
+
+
+def _raw_causal(dev, out):
+    """every causal row through the C ABI, into out [rows, d + d d + 2]; the status"""
+    return dev.lib.cx_predictive_mfma(dev.h, L.PREDICT_CAUSAL, 0, None, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(C.c_double()), (C.c_int64 * 4)())
+
+
+# what assert_reader_refusals asks of this reader (rows=False: the call itself; with rows the row list, cx_predictive_rows_mfma, is asked
+# first; raw: its dim 16 chain has 4 rows)
+_COMMON = dict(who=WHO, small="cx_predictive", call=lambda dev: dev.predictive_mfma(rows=False), small_call=lambda dev: dev.predictive(),
+               raw=lambda dev: _raw_causal(dev, np.zeros((4, 16 + 256 + 2))))
 
 
 def test_refusals(hip_lib):
-    who = "cx_predictive_mfma"      # (rows=False: the call itself; with rows the row list, cx_predictive_rows_mfma, is asked first)
+    who = WHO
+    assert_reader_refusals(**_COMMON, cases=HANDLE_CASES)
     m4 = cx.synth.lgssm_chain(5, d=4, seed=91)
     m16 = cx.synth.lgssm_chain(4, d=16, seed=92)
-    dev = _dev(m4, L.SCHED_TREE)
-    code, msg = _code(dev.predictive_mfma, rows=False)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(who) and "cx_predictive" in msg.replace(who, "")      # names the call for dims 1 .. 4
-    code, msg = _code(dev.predictive_rows_mfma)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith("cx_predictive_rows_mfma")
+    dev = swept_device(m4, L.SCHED_TREE)
+    code, msg = code_of(dev.predictive_rows_mfma)
+    assert code == L.ERR_UNSUPPORTED and msg.startswith("cx_predictive_rows_mfma")      # the row list refuses under its own name
     dev.close()
-    dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    code, msg = _code(dev.predictive_mfma, rows=False)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(who) and "Gaussian family" in msg
-    dev.close()
-    vm = cx.synth.vmp_ssm(8)
-    dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
-    cx.synth.load_vmp_into_device(vm, dev)
-    code, msg = _code(dev.predictive_mfma, rows=False)
-    assert code == L.ERR_UNSUPPORTED and "Gaussian family" in msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16)
-    code, msg = _code(dev.predictive_mfma, rows=False)
-    assert code == L.ERR_STATE and msg.startswith(who) and "no graph" in msg
-    dev.close()
-    dev = _dev(m16, L.SCHED_FUSED, 2)
-    assert _code(dev.predictive)[0] == L.ERR_UNSUPPORTED and _code(dev.predictive_rows)[0] == L.ERR_UNSUPPORTED      # the old calls keep refusing these dims
+    dev = swept_device(m16, L.SCHED_FUSED, 2)
+    assert code_of(dev.predictive_rows)[0] == L.ERR_UNSUPPORTED      # the old row list keeps refusing these dims too
     tot, c4 = C.c_double(), (C.c_int64 * 4)()
     ids = (C.c_int64 * 1)(int(m16.data_fac[0]))
     for args, text in (((7, 0, None, None, C.byref(tot), c4), "mode is"), ((L.PREDICT_LOO, 0, None, None, C.byref(tot), None), "counts4 is null"),
                        ((L.PREDICT_LOO, -1, ids, None, C.byref(tot), c4), "negative count")):
         assert dev.lib.cx_predictive_mfma(dev.h, *args) == L.ERR_INVALID_ARGUMENT
         assert dev.lib.cx_last_error(dev.h).decode().startswith(who) and text in dev.lib.cx_last_error(dev.h).decode()
-    dev.halo_configure_state([m16.x_ids[0]], [3 * 4 + 1], [], [])      # a halo list: a partitioned handle
-    code, msg = _code(dev.predictive_mfma, rows=False)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(who) and "partitioned handle" in msg
     dev.close()
-    dev = _dev(m16, L.SCHED_CHAIN_SCAN)
-    dev.predictive_mfma()
-    dev.halo_configure([m16.x_ids[0]], [3 * 4 + 1], [], [])            # a chain's time block
-    code, msg = _code(dev.predictive_mfma, rows=False)
-    assert code == L.ERR_UNSUPPORTED and "partitioned handle" in msg and "time block" in msg
-    dev.close()
-
-
-def _under_capture(dev, call):
-    """the status of `call` while the handle's stream is being captured (relaxed mode: the refusal's own runtime queries do not void
-    the capture); the handle is back on its own stream afterwards"""
-    hip = C.CDLL([ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0])
-    stream, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    dev.set_stream(stream.value)
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
-    rc = call()
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    dev.set_stream(None)
-    assert hip.hipStreamDestroy(stream) == 0
-    return rc, dev.lib.cx_last_error(dev.h).decode()
 
 
 def test_refusals_of_a_captured_stream_and_of_parameter_sets_never_set(hip_lib):
+    assert_reader_refusals(**_COMMON, cases=STREAM_CASES)
     d = 16
     model = cx.synth.lgssm_chain(5, d=d, seed=93)
-    dev = _dev(model, L.SCHED_TREE)
+    dev = swept_device(model, L.SCHED_TREE)
     want = dev.predictive_mfma("causal")
-    out, tot, c4 = np.zeros((5, d + d * d + 2)), C.c_double(), (C.c_int64 * 4)()
-    rc, msg = _under_capture(dev, lambda: dev.lib.cx_predictive_mfma(dev.h, L.PREDICT_CAUSAL, 0, None, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(tot), c4))
+    out = np.zeros((5, d + d * d + 2))
+    rc, msg = under_capture(dev, lambda: _raw_causal(dev, out))
     assert rc == L.ERR_STATE and msg.startswith("cx_predictive_mfma") and "captured" in msg, (rc, msg)
     assert not out.any()                                       # nothing was written
     got = dev.predictive_mfma("causal")                        # and the handle works on, bit for bit
     assert all(got[k].tobytes() == want[k].tobytes() for k in ("mean", "cov", "log_density", "mahalanobis")) and got["total"] == want["total"]
     dev.close()
-    # Rule tables not on the device: behind a graph they are missing only while a parameter set that a factor names was never set, and
-    # that is refused first, under the call's own name (the guard behind it cannot be reached through the API)
-    dev = cx.DeviceGraph(dim=d, schedule=L.SCHED_TREE)
-    dev.set_factor_matrices(0, *model.psets[0])                # set 1, the likelihoods', is never set
-    dev.graph_create(model.edge_var, model.edge_fac, model.factor_ids, model.factor_kind, model.factor_var, edge_role=model.edge_role)
-    code, msg = _code(dev.predictive_mfma, rows=False)
-    assert code == L.ERR_STATE and msg.startswith("cx_predictive_mfma") and "never set" in msg and "cx_set_factor_matrices" in msg, (code, msg)
-    dev.close()
 
 
 # ---- 13. the C++ host class --------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_predictive_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "predictive_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "predictive_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    lines = [line.split() for line in out.stdout.splitlines()]
+    lines = [line.split() for line in run_demo("predictive_mfma_demo", tmp_path)]
     head = {ln[0]: ln[1:] for ln in lines if ln[0] != "row"}
     rows = [ln[1:] for ln in lines if ln[0] == "row"]
     T, d = 12, 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
-    y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
-    yh, Sm, term, maha = P.kalman_innovations(np.broadcast_to(A, (T - 1, d, d)), np.zeros((T - 1, d)), np.broadcast_to(0.5 * np.eye(d), (T - 1, d, d)),
-                                              np.broadcast_to(np.eye(d), (T, d, d)), y)
+    A, Q, R, y = demo_chain(T, d)
+    yh, Sm, term, maha = P.kalman_innovations(np.broadcast_to(A, (T - 1, d, d)), np.zeros((T - 1, d)), np.broadcast_to(Q, (T - 1, d, d)),
+                                              np.broadcast_to(R, (T, d, d)), y)
     assert float(head["before"][0]) == 0.0 and head["before"][1:] == [str(T), "0", str(T), "0"]
     want_total = float(np.sum(term[1:]))
     assert abs(float(head["causal"][0]) - want_total) <= TOL * abs(want_total) and head["causal"][1:] == [str(T), str(T - 1), "0", "1"]

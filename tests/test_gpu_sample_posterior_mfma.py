@@ -9,8 +9,6 @@ map x = mean + B ε (tests 1 - 5) and the device's ε are the restated Philox no
 pins on the CPU: there is no Monte-Carlo test."""
 import ctypes as C
 import dataclasses
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,24 +23,13 @@ from tests import missing_data as MD
 from tests import predictive_mfma_support as PM
 from tests import sample_mfma_support as SM
 from tests import sampling_support as SS
+from tests.gpu_support import assert_reader_refusals, code_of, demo_chain_model, run_demo, under_capture
+from tests.gpu_support import loaded_device as _load
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL, SAME = SM.TOL, SM.SAME
 WHO = "cx_sample_posterior_mfma"
 MODELS = SM.models()
-
-
-def _load(model, opaque=None, how="sweep", schedule=L.SCHED_TREE):
-    dev = cx.DeviceGraph(dim=model.dim, schedule=schedule)
-    if how == "flat":
-        MD.load(model, dev)                    # the flat message on the one edge of every latent leaf
-    else:
-        cx.synth.load_into_device(model, dev)
-    if how == "opaque":
-        S.set_opaque(dev, opaque)
-    dev.sweep(1)
-    return dev
 
 
 def _close(got, want, rtol, what=""):
@@ -76,12 +63,6 @@ def _exact(dev, ref, what, components=1):
     assert err <= TOL, (what + " B B'", err)
     assert np.array_equal(x[:, gm.obs], np.broadcast_to(gm.y[gm.obs], x[:, gm.obs].shape)), what + " data"
     return x
-
-
-def _code(fn, *a, **k):
-    with pytest.raises(L.CortexHipError) as e:
-        fn(*a, **k)
-    return e.value.code, e.value.message
 
 
 # ---- 1. exact mean and covariance after every schedule ---------------------------------------------------------------------------------
@@ -290,52 +271,23 @@ def test_one_handle_follows_the_observed_flags(hip_lib):
 
 
 # ---- 9. refusals -------------------------------------------------------------------------------------------------------------------------
-def _under_capture(dev, call):
-    """the status of `call` while the handle's stream is being captured (relaxed mode: the refusal's own runtime queries do not void
-    the capture); the handle is back on its own stream afterwards"""
-    hip = C.CDLL([ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln][0])
-    stream, graph = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    dev.set_stream(stream.value)
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
-    rc = call()
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    if graph.value:
-        hip.hipGraphDestroy(graph)
-    dev.set_stream(None)
-    assert hip.hipStreamDestroy(stream) == 0
-    return rc, dev.lib.cx_last_error(dev.h).decode()
+def _raw_one(dev):
+    """one sample of every variable of a dim 16 handle of 8 variables through the C ABI; the status"""
+    out = np.zeros((1, 8, 16))
+    return dev.lib.cx_sample_posterior_mfma(dev.h, 1, C.c_uint64(0), None, 0, None, out.ctypes.data_as(C.POINTER(C.c_double)), (C.c_int64 * 4)())
 
 
 def test_refusals(hip_lib):
-    m4 = cx.synth.lgssm_chain(5, d=4, seed=91)
+    assert_reader_refusals(WHO, "cx_sample_posterior", lambda dev: dev.sample_posterior_mfma(1), lambda dev: dev.sample_posterior(1), _raw_one)
     m16 = cx.synth.lgssm_chain(4, d=16, seed=92)
-    dev = _load(m4)
-    code, msg = _code(dev.sample_posterior_mfma, 1)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "cx_sample_posterior" in msg.replace(WHO, "")      # names the call for dims 1 .. 4
-    dev.close()
-    dev = cx.DeviceGraph(family=L.FAMILY_NATURAL2)
-    code, msg = _code(dev.sample_posterior_mfma, 1)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "Gaussian family" in msg
-    dev.close()
-    vm = cx.synth.vmp_ssm(8)
-    dev = cx.DeviceGraph(schedule=L.SCHED_CHAIN_SCAN, family=L.FAMILY_VMP_STRUCTURED)
-    cx.synth.load_vmp_into_device(vm, dev)
-    code, msg = _code(dev.sample_posterior_mfma, 1)
-    assert code == L.ERR_UNSUPPORTED and "Gaussian family" in msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16)
-    code, msg = _code(dev.sample_posterior_mfma, 1)
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "no graph" in msg
-    dev.close()
     dev = cx.DeviceGraph(dim=16, schedule=L.SCHED_FUSED)      # a cycle among the non-observed variables
     cx.synth.load_into_device(S.ring(16), dev, seed_variance=1e6)
     dev.sweep(3)
-    code, msg = _code(dev.sample_posterior_mfma, 1)
+    code, msg = code_of(dev.sample_posterior_mfma, 1)
     assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "cycle" in msg and "variable" in msg, msg
     dev.close()
     dev = _load(m16)
-    code, msg = _code(dev.sample_posterior, 1)
+    code, msg = code_of(dev.sample_posterior, 1)
     assert code == L.ERR_UNSUPPORTED and "cx_sample_posterior" in msg and WHO not in msg      # the old call keeps refusing these dims
     n = 8
     out, c4 = np.zeros((2, n, 16)), (C.c_int64 * 4)()
@@ -347,23 +299,14 @@ def test_refusals(hip_lib):
                  (1, C.c_uint64(0), None, -1, ids, po, c4)):
         assert call(dev.h, *args) == L.ERR_INVALID_ARGUMENT, args
         assert dev.lib.cx_last_error(dev.h).decode().startswith(WHO)
-    code, msg = _code(dev.sample_posterior_mfma, 1, variable_ids=[int(m16.x_ids[0]), 10 ** 9])
+    code, msg = code_of(dev.sample_posterior_mfma, 1, variable_ids=[int(m16.x_ids[0]), 10 ** 9])
     assert code == L.ERR_NOT_FOUND and msg.startswith(WHO) and str(10 ** 9) in msg
     want = dev.sample_posterior_mfma(3, seed=4)[0]      # and the handle works on
     out3 = np.zeros((3, n, 16))
-    rc, msg = _under_capture(dev, lambda: call(dev.h, 3, C.c_uint64(4), None, 0, None, out3.ctypes.data_as(C.POINTER(C.c_double)), c4))
+    rc, msg = under_capture(dev, lambda: call(dev.h, 3, C.c_uint64(4), None, 0, None, out3.ctypes.data_as(C.POINTER(C.c_double)), c4))
     assert rc == L.ERR_STATE and msg.startswith(WHO) and "captured" in msg, (rc, msg)
     assert not out3.any()                                # a refused call writes nothing
     assert np.array_equal(dev.sample_posterior_mfma(3, seed=4)[0], want)
-    dev.halo_configure_state([m16.x_ids[0]], [3 * 4 + 1], [], [])      # a halo list: a partitioned handle
-    code, msg = _code(dev.sample_posterior_mfma, 1)
-    assert code == L.ERR_UNSUPPORTED and msg.startswith(WHO) and "partitioned handle" in msg
-    dev.close()
-    dev = cx.DeviceGraph(dim=16, schedule=L.SCHED_TREE)
-    dev.set_factor_matrices(0, *m16.psets[0])                # set 1, the likelihoods', is never set
-    dev.graph_create(m16.edge_var, m16.edge_fac, m16.factor_ids, m16.factor_kind, m16.factor_var, edge_role=m16.edge_role)
-    code, msg = _code(dev.sample_posterior_mfma, 1)
-    assert code == L.ERR_STATE and msg.startswith(WHO) and "never set" in msg and "cx_set_factor_matrices" in msg, (code, msg)
     dev.close()
     # (a factor of another kind: cx_graph_create admits none at these dims — tests/test_gpu_causal_marginals_mfma.py shows it — so the
     # refusal of mfr::checked_pairs under this call's name is a guard that no graph reaches through the API)
@@ -371,23 +314,10 @@ def test_refusals(hip_lib):
 
 # ---- 10. the C++ host class --------------------------------------------------------------------------------------------------------------
 def test_cpp_host_class_sample_posterior_mfma(hip_lib, tmp_path):
-    exe = str(tmp_path / "sample_mfma_demo")
-    libdir = os.path.join(ROOT, "cortex.jl_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "sample_mfma_demo.cpp"), "-o", exe, "-L" + libdir, "-lcortex_hip",
-                           "-Wl,-rpath," + libdir])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in out.stdout.splitlines()}
+    rows = {line.split()[0]: [float(v) for v in line.split()[1:]] for line in run_demo("sample_mfma_demo", tmp_path)}
     T, d = 12, 16
-    A = np.array([[0.9 if i == j else (0.05 if j == (i + 1) % d else 0.0) for j in range(d)] for i in range(d)])
-    y = np.array([[0.25 * t + ((3 * t + k) % 7) - 3.0 for k in range(d)] for t in range(1, T + 1)], dtype=np.float64)
-    base = cx.synth.lgssm_chain(T, d=d, seed=1)      # the demo's ids are lgssm_chain's; its connections in the demo's order
-    x, yv, lik, tr = base.x_ids, base.x_ids + T, base.x_ids + 2 * T, np.arange(3 * T + 1, 4 * T)
-    ev = np.concatenate([np.stack([yv, x], 1).ravel(), np.stack([x[:-1], x[1:]], 1).ravel()])
-    ef = np.concatenate([np.repeat(lik, 2), np.repeat(tr, 2)])
-    er = np.concatenate([np.tile([L.ROLE_OUT, L.ROLE_IN], T), np.tile([L.ROLE_IN, L.ROLE_OUT], T - 1)]).astype(np.int32)
-    model = dataclasses.replace(base, edge_var=ev, edge_fac=ef, edge_role=er, data_y=y, psets={0: (A, 0.5 * np.eye(d)), 1: (np.eye(d), np.eye(d))}, meta={**base.meta, "A": A, "Q": 0.5 * np.eye(d), "R": np.eye(d)})
+    model = demo_chain_model(T, d)
+    y = model.data_y
     gm, mean, _Sig, _eps = _reference(model)
     xs = np.searchsorted(gm.var_ids, model.x_ids)
     assert rows["counts"] == [T, 1, 0, 0] and rows["sizes"] == [T * d, 3 * T * d, 2 * T * d]

@@ -7,7 +7,7 @@ import pytest
 
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
-from tests.sweep_graphs import grid_with_star, random_sparse, read_back, undefined_midcall_grid
+from tests.sweep_graphs import assert_same, clean_env, everything, fused_device, grid_with_star, launches, load_undefined_midcall, model_of, random_sparse
 
 pytestmark = pytest.mark.gpu
 
@@ -18,30 +18,6 @@ WIDTHS = {3: (59, 60, 61, 120, 121, 240, 241), 4: (57, 58, 59, 116, 117, 232, 23
 # grids smaller than the pipeline (fewer rows or columns than levels, one lane with both neighbours or none); C4's own width
 SMALL = [(2, 2), (3, 3), (2, 300), (40, 2), (300, 3), (24, 1415)]
 ROWS_CASES = [(s, r) for s in ((20, 37), (9, 125)) for r in (1, 2, 3, 7, 64)]
-SEED = 1e6
-
-
-def _device(model, seed_variance=SEED):
-    dev = cx.DeviceGraph(schedule=L.SCHED_FUSED)
-    cx.synth.load_into_device(model, dev, seed_variance)
-    return dev
-
-
-def _everything(dev, model):
-    """factor→variable messages, marginals, and the variable→factor messages (formed on demand from the last sweep's input)"""
-    f2v, marg = read_back(dev, model)
-    return f2v, marg, dev.get_messages(model.edge_var, model.edge_fac, L.TO_FACTOR, L.FORM_NATURAL)
-
-
-def _same(a, b, what):
-    for x, y, name in zip(a, b, ("messages to variables", "marginals", "messages to factors")):
-        assert np.array_equal(x, y, equal_nan=True), f"{what}: {name} differ"
-
-
-def _launches(dev):
-    """(launches of two sweeps, of three, of four)"""
-    d = dev.sweep_deep_stats()
-    return dev.sweep_stats()["paired_launches"], d["depth3_launches"], d["depth4_launches"]
 
 
 def greedy(n, depth):
@@ -63,36 +39,23 @@ def test_the_decomposition_this_file_expects():
     assert greedy(8, 4) == (3, 0, 0) and greedy(17, 2) == (8, 0, 0)
 
 
-_models, _singles = {}, {}
-
-
-def model_of(shape, seed=7):
-    if (shape, seed) not in _models:
-        _models[(shape, seed)] = cx.synth.gaussian_grid(*shape, seed=seed)
-    return _models[(shape, seed)]
+_singles = {}
 
 
 def singles(shape, seed=7):
     """the read-backs after n = 16 .. 19 calls of sweep(1), computed once per grid and shared by every depth and rows case"""
     if (shape, seed) not in _singles:
         model = model_of(shape, seed)
-        b = _device(model)
+        b = fused_device(model)
         out = {}
         for n in range(1, max(NS) + 1):
             b.sweep(1)
             if n in NS:
-                out[n] = _everything(b, model)
-        assert _launches(b) == (0, 0, 0)
+                out[n] = everything(b, model)
+        assert launches(b) == (0, 0, 0)
         b.close()
         _singles[(shape, seed)] = out
     return _singles[(shape, seed)]
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for name in ("CX_SWEEP_PAIRS", "CX_SWEEP_DEPTH", "CX_PAIR_ROWS", "CX_DEEP_ROWS", "CX_MARG_EVERY_SWEEP"):
-        monkeypatch.delenv(name, raising=False)
-    return monkeypatch
 
 
 def _check_shape(monkeypatch, shape, depth, rows=None, seed=7):
@@ -102,22 +65,22 @@ def _check_shape(monkeypatch, shape, depth, rows=None, seed=7):
         monkeypatch.setenv("CX_SWEEP_DEPTH", str(depth))
         if rows:
             monkeypatch.setenv("CX_DEEP_ROWS", str(rows))
-        a = _device(model)
+        a = fused_device(model)
         a.sweep(n)
         monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
-        c = _device(model)
+        c = fused_device(model)
         c.sweep(n)
         monkeypatch.delenv("CX_SWEEP_PAIRS")
-        assert _launches(a) == greedy(n, depth), what
-        assert _launches(c) == (0, 0, 0), what
+        assert launches(a) == greedy(n, depth), what
+        assert launches(c) == (0, 0, 0), what
         d = a.sweep_deep_stats()
         assert d["depth"] == depth and (d["rows"] == rows if rows else d["rows"] >= 4 * (depth - 1)), (what, d)
         assert a.stats()["sweeps_done"] == c.stats()["sweeps_done"] == n, what
         assert a.sweep_stats()["sweeps_without_marginals"] == c.sweep_stats()["sweeps_without_marginals"] == n - 1, what
-        ra = _everything(a, model)
+        ra = everything(a, model)
         assert np.all(np.isfinite(ra[0])), "a seeded grid: every message defined"
-        _same(ra, ref[n], f"{what} against {n} x sweep(1)")
-        _same(ra, _everything(c, model), f"{what} against CX_SWEEP_PAIRS=0")
+        assert_same(ra, ref[n], f"{what} against {n} x sweep(1)")
+        assert_same(ra, everything(c, model), f"{what} against CX_SWEEP_PAIRS=0")
         a.close(); c.close()
 
 
@@ -145,26 +108,26 @@ def test_any_rows_per_segment(hip_lib, clean_env, depth, shape, rows):
 def test_two_consecutive_calls(hip_lib, clean_env, depth):
     model = model_of((20, 37))
     clean_env.setenv("CX_SWEEP_DEPTH", str(depth))
-    a, b = _device(model), _device(model)
+    a, b = fused_device(model), fused_device(model)
     a.sweep(17)
     a.sweep(16)
     for _ in range(33):
         b.sweep(1)
-    assert _launches(a) == tuple(x + y for x, y in zip(greedy(17, depth), greedy(16, depth)))
+    assert launches(a) == tuple(x + y for x, y in zip(greedy(17, depth), greedy(16, depth)))
     assert a.stats()["sweeps_done"] == 33
-    _same(_everything(a, model), _everything(b, model), "sweep(17) then sweep(16) against 33 x sweep(1)")
+    assert_same(everything(a, model), everything(b, model), "sweep(17) then sweep(16) against 33 x sweep(1)")
     a.close(); b.close()
 
 
 def test_a_short_call_runs_pairs_only(hip_lib, clean_env):
     model = model_of((20, 37))
-    a, b = _device(model), _device(model)
+    a, b = fused_device(model), fused_device(model)
     a.sweep(8)
     for _ in range(8):
         b.sweep(1)
-    assert _launches(a) == (3, 0, 0)
+    assert launches(a) == (3, 0, 0)
     assert a.sweep_deep_stats()["depth"] == 2
-    _same(_everything(a, model), _everything(b, model), "sweep(8), no depth forced")
+    assert_same(everything(a, model), everything(b, model), "sweep(8), no depth forced")
     a.close(); b.close()
 
 
@@ -176,22 +139,15 @@ def test_refused_graphs_and_handles_sweep_plain(hip_lib, clean_env, depth, name)
     clean_env.setenv("CX_SWEEP_DEPTH", str(depth))
     if name == "every_sweep_marginals":
         clean_env.setenv("CX_MARG_EVERY_SWEEP", "1")
-    a, b = _device(model, 50.0), _device(model, 50.0)
+    a, b = fused_device(model, 50.0), fused_device(model, 50.0)
     if name == "damped":
         a.set_damping(0.25); b.set_damping(0.25)
     a.sweep(17)
     for _ in range(17):
         b.sweep(1)
-    assert _launches(a) == (0, 0, 0)
-    _same(_everything(a, model), _everything(b, model), name)
+    assert launches(a) == (0, 0, 0)
+    assert_same(everything(a, model), everything(b, model), name)
     a.close(); b.close()
-
-
-def _load_undefined_midcall():
-    model, sv, sf, payload = undefined_midcall_grid()
-    dev = _device(model)
-    dev.set_messages(sv, sf, L.TO_VARIABLE, L.FORM_NATURAL, payload)
-    return model, dev
 
 
 @pytest.mark.parametrize("depth", DEPTHS)
@@ -200,7 +156,7 @@ def test_a_deep_launch_that_meets_an_undefined_message_is_reported_once(hip_lib,
     sweep 2 stores undefined messages and sweep 3 — level 3 of the first launch — reads them: the NaN path, no fault.  The word is found by
     whichever checked call comes first once the launch has run, and the later launches of the call, which raise it again, are not reported."""
     clean_env.setenv("CX_SWEEP_DEPTH", str(depth))
-    model, a = _load_undefined_midcall()
+    model, a = load_undefined_midcall()
     errors = []
     for call in (lambda: a.sweep(17), a.sync, a.sync, lambda: a.get_marginals(model.x_ids), a.sync):
         try:
@@ -210,21 +166,21 @@ def test_a_deep_launch_that_meets_an_undefined_message_is_reported_once(hip_lib,
     assert len(errors) == 1, [str(e) for e in errors]
     assert errors[0].code == L.ERR_DEVICE and "CX_SWEEP_PAIRS=0" in str(errors[0]) and "undefined" in str(errors[0])
     assert a.stats()["sweeps_done"] == 17
-    ran = _launches(a)
+    ran = launches(a)
     assert ran == greedy(17, depth)
     a.sweep(17)
     a.sync()
-    assert _launches(a) == ran, "the handle sweeps plain from then on"
+    assert launches(a) == ran, "the handle sweeps plain from then on"
     assert a.stats()["sweeps_done"] == 34
     a.close()
     # plain sweeps keep the older value of a slot whose input is undefined: the same inputs run to completion, one call or seventeen
     clean_env.setenv("CX_SWEEP_PAIRS", "0")
-    _, c = _load_undefined_midcall()
-    _, b = _load_undefined_midcall()
+    _, c = load_undefined_midcall()
+    _, b = load_undefined_midcall()
     c.sweep(17)
     c.sync()
     for _ in range(17):
         b.sweep(1)
-    assert _launches(c) == (0, 0, 0) and _launches(b) == (0, 0, 0)
-    _same(_everything(c, model), _everything(b, model), "CX_SWEEP_PAIRS=0: sweep(17) against 17 x sweep(1)")
+    assert launches(c) == (0, 0, 0) and launches(b) == (0, 0, 0)
+    assert_same(everything(c, model), everything(b, model), "CX_SWEEP_PAIRS=0: sweep(17) against 17 x sweep(1)")
     c.close(); b.close()

@@ -9,7 +9,7 @@ import pytest
 
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
-from tests.sweep_graphs import read_back, undefined_midcall_grid
+from tests.sweep_graphs import assert_same, clean_env, fused_device, model_of, read_back, undefined_midcall_grid
 from tests.test_lattice_deep_classes import COLUMN_EDGE, GENERAL, INTERIOR, classes
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +19,6 @@ DEFAULT_DEPTH = 5          # cx_api_sweep.hip: kDeepDefault (profiles/deep_sweep
 N = 17
 ROWS_CASES = (1, 3, 7)     # 7: a short last segment at every height below (2 = 2, 4 = 4, 5 = 5, 9 = 7 + 2, 11 = 7 + 4, 20 = 7 + 7 + 6)
 REMAINDER_NS = range(16, 23)
-SEED = 1e6
 
 
 def widths(K):
@@ -50,31 +49,14 @@ def test_the_decomposition_this_file_expects():
     assert greedy(8, 6) == (0, 0, 3, 0, 0, 0, 0) and all(g[0] == g[1] == 0 for g in (greedy(n, d) for n in REMAINDER_NS for d in DEPTHS))
 
 
-_models, _plain, _singles = {}, {}, {}
-
-
-def model_of(shape):
-    if shape not in _models:
-        _models[shape] = cx.synth.gaussian_grid(*shape, seed=7)
-    return _models[shape]
-
-
-def _device(model):
-    dev = cx.DeviceGraph(schedule=L.SCHED_FUSED)
-    cx.synth.load_into_device(model, dev, SEED)
-    return dev
-
-
-def _same(got, want, what):
-    for x, y, name in zip(got, want, ("messages to variables", "marginals")):
-        assert np.array_equal(x, y, equal_nan=True), f"{what}: {name} differ"
+_plain, _singles = {}, {}
 
 
 def plain(monkeypatch, shape, calls=(N,)):
     """(messages to variables, marginals) after the calls under CX_SWEEP_PAIRS=0: computed once per grid, shared by both depths and every rows case"""
     if (shape, calls) not in _plain:
         monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
-        c = _device(model_of(shape))
+        c = fused_device(model_of(shape))
         for n in calls:
             c.sweep(n)
         monkeypatch.delenv("CX_SWEEP_PAIRS")
@@ -87,7 +69,7 @@ def plain(monkeypatch, shape, calls=(N,)):
 def singles(shape):
     """the read-backs after n = 16 .. 22 calls of sweep(1), computed once"""
     if shape not in _singles:
-        b = _device(model_of(shape))
+        b = fused_device(model_of(shape))
         out = {}
         for n in range(1, max(REMAINDER_NS) + 1):
             b.sweep(1)
@@ -99,20 +81,13 @@ def singles(shape):
     return _singles[shape]
 
 
-@pytest.fixture
-def clean_env(monkeypatch):
-    for name in ("CX_SWEEP_PAIRS", "CX_SWEEP_DEPTH", "CX_PAIR_ROWS", "CX_DEEP_ROWS", "CX_MARG_EVERY_SWEEP"):
-        monkeypatch.delenv(name, raising=False)
-    return monkeypatch
-
-
 def _run(env, shape, depth, rows, want, calls=(N,)):
     """the calls at `depth` and `rows` rows per segment (None: chosen) on a fresh handle, compared with `want`; returns the handle's launch counts"""
     what = f"{shape}, depth {depth}, {rows or 'chosen'} rows per segment: sweep{calls}"
     env.setenv("CX_SWEEP_DEPTH", str(depth))
     if rows:
         env.setenv("CX_DEEP_ROWS", str(rows))
-    a = _device(model_of(shape))
+    a = fused_device(model_of(shape))
     for n in calls:
         a.sweep(n)
     ran = a.sweep_deep_launches()
@@ -122,7 +97,7 @@ def _run(env, shape, depth, rows, want, calls=(N,)):
     got = read_back(a, model_of(shape))
     a.close()
     assert np.all(np.isfinite(got[0])), f"{what}: a seeded grid, every message defined"
-    _same(got, want, what)
+    assert_same(got, want, what)
     return ran
 
 
@@ -165,10 +140,10 @@ def test_the_default_depth(hip_lib, clean_env):
     """no variable set: a long call runs at kDeepDefault, at the rows per segment chosen by occupancy; 40 x 180 has interior waves there"""
     shape = (40, 180)
     want = plain(clean_env, shape)
-    a = _device(model_of(shape))
+    a = fused_device(model_of(shape))
     a.sweep(N)
     assert a.sweep_deep_stats()["depth"] == DEFAULT_DEPTH and a.sweep_deep_launches() == greedy(N, DEFAULT_DEPTH)
-    _same(read_back(a, model_of(shape)), want, f"{shape} at the default depth")
+    assert_same(read_back(a, model_of(shape)), want, f"{shape} at the default depth")
     a.close()
 
 
@@ -177,7 +152,7 @@ def test_a_launch_that_meets_an_undefined_message_is_reported_once(hip_lib, clea
     """tests/sweep_graphs.py: undefined_midcall_grid — sweep 3, level 3 of the first launch, reads an undefined message: the NaN path, no fault"""
     clean_env.setenv("CX_SWEEP_DEPTH", str(depth))
     model, sv, sf, payload = undefined_midcall_grid()
-    a = _device(model)
+    a = fused_device(model)
     a.set_messages(sv, sf, L.TO_VARIABLE, L.FORM_NATURAL, payload)
     errors = []
     for call in (lambda: a.sweep(N), a.sync, a.sync, lambda: a.get_marginals(model.x_ids), a.sync):

@@ -11,7 +11,7 @@ import pytest
 
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
-from tests.sweep_graphs import GridIds, read_back
+from tests.sweep_graphs import GridIds, clean_env, fused_device, launches, model_of, read_back, rows_cases
 from tests.test_gpu_sweep_deep import greedy
 from tests.test_lattice_deep_classes import COLUMN_EDGE, GENERAL, classes
 
@@ -20,7 +20,6 @@ pytestmark = pytest.mark.gpu
 DEPTHS = (3, 4)
 HEIGHTS = (20, 40)
 N = 17
-SEED = 1e6
 
 
 def widths(K):
@@ -28,49 +27,21 @@ def widths(K):
     return (2, 3, 57, sc, sc + 1, 2 * sc, 4 * sc + 1, 5 * sc + 1)
 
 
-def rows_cases(K):
-    return (1, 3, 4 * (K - 1))
-
-
-_models, _plain = {}, {}
-
-
-def model_of(shape):
-    if shape not in _models:
-        _models[shape] = cx.synth.gaussian_grid(*shape, seed=7)
-    return _models[shape]
-
-
-def _device(model):
-    dev = cx.DeviceGraph(schedule=L.SCHED_FUSED)
-    cx.synth.load_into_device(model, dev, SEED)
-    return dev
-
-
-def _launches(dev):
-    d = dev.sweep_deep_stats()
-    return dev.sweep_stats()["paired_launches"], d["depth3_launches"], d["depth4_launches"]
+_plain = {}
 
 
 def plain(monkeypatch, shape, calls=(N,)):
     """(messages to variables, marginals) after the calls under CX_SWEEP_PAIRS=0: computed once per grid, shared by every depth and rows case"""
     if (shape, calls) not in _plain:
         monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
-        c = _device(model_of(shape))
+        c = fused_device(model_of(shape))
         for n in calls:
             c.sweep(n)
         monkeypatch.delenv("CX_SWEEP_PAIRS")
-        assert _launches(c) == (0, 0, 0), shape
+        assert launches(c) == (0, 0, 0), shape
         _plain[(shape, calls)] = read_back(c, model_of(shape))
         c.close()
     return _plain[(shape, calls)]
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for name in ("CX_SWEEP_PAIRS", "CX_SWEEP_DEPTH", "CX_PAIR_ROWS", "CX_DEEP_ROWS", "CX_MARG_EVERY_SWEEP"):
-        monkeypatch.delenv(name, raising=False)
-    return monkeypatch
 
 
 def column_edge_waves(depth, shape, rows):
@@ -98,9 +69,9 @@ def test_column_edge_waves_leave_every_bit_as_it_was(hip_lib, clean_env, depth, 
             if W == 4 * sc + 1 and rows == 3 and height == 40:      # the packed workgroup of segments 0 .. 3 of strip 4 mixes general and column-edge waves
                 assert edge.shape[0] == 5 and not edge[4, 0] and edge[4, 3], what
             clean_env.setenv("CX_DEEP_ROWS", str(rows))
-            a = _device(model)
+            a = fused_device(model)
             a.sweep(N)
-            assert _launches(a) == greedy(N, depth), what
+            assert launches(a) == greedy(N, depth), what
             d = a.sweep_deep_stats()
             assert d["depth"] == depth and d["rows"] == rows, (what, d)
             got = read_back(a, model)
@@ -118,10 +89,10 @@ def test_a_second_call_starts_from_what_the_first_call_stored(hip_lib, clean_env
     shape = (40, 4 * sc + 1)
     model, want = model_of(shape), plain(clean_env, shape, (16, 17))
     clean_env.setenv("CX_SWEEP_DEPTH", str(depth))
-    a = _device(model)
+    a = fused_device(model)
     a.sweep(16)
     a.sweep(17)
-    assert _launches(a) == tuple(x + y for x, y in zip(greedy(16, depth), greedy(17, depth)))
+    assert launches(a) == tuple(x + y for x, y in zip(greedy(16, depth), greedy(17, depth)))
     edge = column_edge_waves(depth, shape, a.sweep_deep_stats()["rows"])
     assert edge[0].any() and edge[-1].any()
     assert a.stats()["sweeps_done"] == 33
@@ -165,7 +136,7 @@ def test_an_undefined_message_born_on_an_edge_column_is_reported_once(hip_lib, c
     clean_env.setenv("CX_SWEEP_DEPTH", str(depth))
     clean_env.setenv("CX_DEEP_ROWS", str(UNDEF_ROWS))
     model, sv, sf, payload = _undefined_model(col)
-    a = _device(model)
+    a = fused_device(model)
     a.set_messages(sv, sf, L.TO_VARIABLE, L.FORM_NATURAL, payload)
     errors = []
     for call in (lambda: a.sweep(17), a.sync, a.sync, lambda: a.get_marginals(model.x_ids), a.sync):
@@ -176,10 +147,10 @@ def test_an_undefined_message_born_on_an_edge_column_is_reported_once(hip_lib, c
     assert len(errors) == 1, [str(e) for e in errors]
     assert errors[0].code == L.ERR_DEVICE and "CX_SWEEP_PAIRS=0" in str(errors[0]) and "undefined" in str(errors[0])
     assert a.stats()["sweeps_done"] == 17
-    ran = _launches(a)
+    ran = launches(a)
     assert ran == greedy(17, depth)
     a.sweep(17)
     a.sync()
-    assert _launches(a) == ran, "the handle sweeps plain from then on"
+    assert launches(a) == ran, "the handle sweeps plain from then on"
     assert a.stats()["sweeps_done"] == 34
     a.close()

@@ -10,7 +10,7 @@ import pytest
 
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
-from tests.sweep_graphs import GridIds, natural_form_sweeps, read_back
+from tests.sweep_graphs import GridIds, clean_env, fused_device, launches, model_of, natural_form_sweeps, read_back
 
 pytestmark = pytest.mark.gpu
 
@@ -18,31 +18,7 @@ DEPTHS = (3, 4)
 SEED = 1e6
 STRIP_COLS = {3: 60, 4: 58}
 
-_models, _plain = {}, {}
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for name in ("CX_SWEEP_PAIRS", "CX_SWEEP_DEPTH", "CX_PAIR_ROWS", "CX_DEEP_ROWS", "CX_MARG_EVERY_SWEEP"):
-        monkeypatch.delenv(name, raising=False)
-    return monkeypatch
-
-
-def model_of(shape):
-    if shape not in _models:
-        _models[shape] = cx.synth.gaussian_grid(*shape, seed=7)
-    return _models[shape]
-
-
-def _device(model):
-    dev = cx.DeviceGraph(schedule=L.SCHED_FUSED)
-    cx.synth.load_into_device(model, dev, SEED)
-    return dev
-
-
-def _launches(dev):
-    d = dev.sweep_deep_stats()
-    return dev.sweep_stats()["paired_launches"], d["depth3_launches"], d["depth4_launches"]
+_plain = {}
 
 
 def greedy(n, depth):
@@ -62,10 +38,10 @@ def plain(monkeypatch, shape, calls):
     if (shape, calls) not in _plain:
         monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
         model = model_of(shape)
-        dev = _device(model)
+        dev = fused_device(model)
         for n in calls:
             dev.sweep(n)
-        assert _launches(dev) == (0, 0, 0)
+        assert launches(dev) == (0, 0, 0)
         _plain[(shape, calls)] = read_back(dev, model)
         dev.close()
         monkeypatch.delenv("CX_SWEEP_PAIRS")
@@ -79,11 +55,11 @@ def _check(monkeypatch, shape, depth, rows, calls):
     if rows:
         monkeypatch.setenv("CX_DEEP_ROWS", str(rows))
     model = model_of(shape)
-    dev = _device(model)
+    dev = fused_device(model)
     for n in calls:
         dev.sweep(n)
     expect = tuple(sum(x) for x in zip(*(greedy(n, depth) for n in calls)))
-    assert _launches(dev) == expect and expect[depth - 2] > 0, (what, _launches(dev), expect)
+    assert launches(dev) == expect and expect[depth - 2] > 0, (what, launches(dev), expect)
     d = dev.sweep_deep_stats()
     assert d["depth"] == depth and (d["rows"] == rows if rows else d["rows"] >= 4 * (depth - 1)), (what, d)
     got = read_back(dev, model)
@@ -171,7 +147,7 @@ def _undefined_model():
 
 def _load_undefined():
     model, sv, sf, payload = _undefined_model()
-    dev = _device(model)
+    dev = fused_device(model)
     dev.set_messages(sv, sf, L.TO_VARIABLE, L.FORM_NATURAL, payload)
     return model, dev
 
@@ -205,11 +181,11 @@ def test_an_undefined_message_met_by_an_interior_wave_is_reported_once(hip_lib, 
     assert len(errors) == 1, [str(e) for e in errors]
     assert errors[0].code == L.ERR_DEVICE and "CX_SWEEP_PAIRS=0" in str(errors[0]) and "undefined" in str(errors[0])
     assert a.stats()["sweeps_done"] == 17
-    ran = _launches(a)
+    ran = launches(a)
     assert ran == greedy(17, depth)
     a.sweep(17)
     a.sync()
-    assert _launches(a) == ran, "the handle sweeps plain from then on"
+    assert launches(a) == ran, "the handle sweeps plain from then on"
     a.close()
     # under CX_SWEEP_PAIRS=0 the plain sweeps carry on: one call or seventeen
     clean_env.setenv("CX_SWEEP_PAIRS", "0")
@@ -219,7 +195,7 @@ def test_an_undefined_message_met_by_an_interior_wave_is_reported_once(hip_lib, 
     c.sync()
     for _ in range(17):
         b.sweep(1)
-    assert _launches(c) == (0, 0, 0) and _launches(b) == (0, 0, 0)
+    assert launches(c) == (0, 0, 0) and launches(b) == (0, 0, 0)
     for x, y in zip(read_back(c, model), read_back(b, model)):
         assert np.array_equal(x, y, equal_nan=True)
     c.close(); b.close()

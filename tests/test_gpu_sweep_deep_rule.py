@@ -14,7 +14,7 @@ import pytest
 
 import cortex.jl_amd as cx
 from cortex.jl_amd import _lib as L
-from tests.sweep_graphs import GridIds, read_back
+from tests.sweep_graphs import GridIds, clean_env, read_back
 
 pytestmark = pytest.mark.gpu
 
@@ -60,13 +60,6 @@ def _device(shape, extreme):
     payload = np.array([(0.25 * (k + 1) * (-1) ** k, np.inf) for k in range(len(pm))] + [(0.5, 0.0), (-1.5, 0.0)][:len(z)])
     dev.set_messages([ids.var(r, c) for r, c in cells], [ids.unary(r, c) for r, c in cells], L.TO_VARIABLE, L.FORM_NATURAL, payload)
     return dev
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for name in ("CX_SWEEP_PAIRS", "CX_SWEEP_DEPTH", "CX_PAIR_ROWS", "CX_DEEP_ROWS", "CX_MARG_EVERY_SWEEP"):
-        monkeypatch.delenv(name, raising=False)
-    return monkeypatch
 
 
 def plain(env, shape, extreme):

@@ -8,9 +8,7 @@ profiles/deep_sweep_stores.md.  The shapes are what such a change has to pass.)"
 import numpy as np
 import pytest
 
-import cortex.jl_amd as cx
-from cortex.jl_amd import _lib as L
-from tests.sweep_graphs import read_back
+from tests.sweep_graphs import clean_env, fused_device, launches, model_of, read_back, rows_cases
 from tests.test_gpu_sweep_deep import greedy
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +16,6 @@ pytestmark = pytest.mark.gpu
 DEPTHS = (3, 4)
 HEIGHTS = (5, 9, 20)
 N = 17
-SEED = 1e6
 
 
 def widths(K):
@@ -27,48 +24,20 @@ def widths(K):
     return (4 * sc + 1, 5 * sc + 1, 6 * sc + 1, 4 * sc, 57, 2, 3)
 
 
-def rows_cases(K):
-    return (1, 3, 4 * (K - 1))
-
-
-_models, _plain = {}, {}
-
-
-def model_of(shape):
-    if shape not in _models:
-        _models[shape] = cx.synth.gaussian_grid(*shape, seed=7)
-    return _models[shape]
-
-
-def _device(model):
-    dev = cx.DeviceGraph(schedule=L.SCHED_FUSED)
-    cx.synth.load_into_device(model, dev, SEED)
-    return dev
-
-
-def _launches(dev):
-    d = dev.sweep_deep_stats()
-    return dev.sweep_stats()["paired_launches"], d["depth3_launches"], d["depth4_launches"]
+_plain = {}
 
 
 def plain(monkeypatch, shape):
     """(messages to variables, marginals) after sweep(17) under CX_SWEEP_PAIRS=0: computed once per grid, shared by every depth and rows case"""
     if shape not in _plain:
         monkeypatch.setenv("CX_SWEEP_PAIRS", "0")
-        c = _device(model_of(shape))
+        c = fused_device(model_of(shape))
         c.sweep(N)
         monkeypatch.delenv("CX_SWEEP_PAIRS")
-        assert _launches(c) == (0, 0, 0), shape
+        assert launches(c) == (0, 0, 0), shape
         _plain[shape] = read_back(c, model_of(shape))
         c.close()
     return _plain[shape]
-
-
-@pytest.fixture
-def clean_env(monkeypatch):
-    for name in ("CX_SWEEP_PAIRS", "CX_SWEEP_DEPTH", "CX_PAIR_ROWS", "CX_DEEP_ROWS", "CX_MARG_EVERY_SWEEP"):
-        monkeypatch.delenv(name, raising=False)
-    return monkeypatch
 
 
 @pytest.mark.parametrize("height", HEIGHTS)
@@ -81,9 +50,9 @@ def test_strip_edges_and_packed_columns_leave_every_bit_as_it_was(hip_lib, clean
         for rows in rows_cases(depth):
             what = f"{shape}, depth {depth}, {rows} rows per segment: sweep({N})"
             clean_env.setenv("CX_DEEP_ROWS", str(rows))
-            a = _device(model)
+            a = fused_device(model)
             a.sweep(N)
-            assert _launches(a) == greedy(N, depth), what
+            assert launches(a) == greedy(N, depth), what
             d = a.sweep_deep_stats()
             assert d["depth"] == depth and d["rows"] == rows, (what, d)
             got = read_back(a, model)
@@ -100,15 +69,15 @@ def test_a_second_call_starts_from_what_the_first_call_stored(hip_lib, clean_env
     sc = 64 - 2 * (depth - 1)
     model = model_of((20, 4 * sc + 1))
     clean_env.setenv("CX_SWEEP_DEPTH", str(depth))
-    a = _device(model)
+    a = fused_device(model)
     a.sweep(16)
     a.sweep(17)
     clean_env.setenv("CX_SWEEP_PAIRS", "0")
-    c = _device(model)
+    c = fused_device(model)
     c.sweep(16)
     c.sweep(17)
-    assert _launches(a) == tuple(x + y for x, y in zip(greedy(16, depth), greedy(17, depth)))
-    assert _launches(c) == (0, 0, 0)
+    assert launches(a) == tuple(x + y for x, y in zip(greedy(16, depth), greedy(17, depth)))
+    assert launches(c) == (0, 0, 0)
     assert a.stats()["sweeps_done"] == c.stats()["sweeps_done"] == 33
     for x, y, name in zip(read_back(a, model), read_back(c, model), ("messages to variables", "marginals")):
         assert np.array_equal(x, y, equal_nan=True), f"depth {depth}: {name} differ from CX_SWEEP_PAIRS=0"
